@@ -2,7 +2,13 @@
 """Benchmark of the north-star path: verify_blob_kzg_proof_batch on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|configs1|config5] [--blobs n] [--group G] [--inflight 4]
-                    [--force-collectives] [--no-shard-leg] [--no-configs] [--no-concurrent] [--no-latency] [--no-self-check] [--no-cpu-baseline]
+                    [--force-collectives] [--dump-outputs DIR]
+                    [--full [--no-shard-leg] [--no-configs] [--no-concurrent] [--no-latency] [--no-self-check] [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times `--steps` launch groups and prints ONE JSON line: `value` (blobs/s), `ms_per_step` and the
+run's `config` / `preflight`.  `--dump-outputs DIR` writes what the timed path returned for its last step (the verdict of every
+batch of that launch group) to DIR/verdicts.npy; the inputs are seeded, so two builds can be compared output for output.
+Everything else below is measured only with `--full`.
 
 One "step" = one LAUNCH GROUP: `--group` (256) independent verify_blob_kzg_proof_batch calls
 (src/kzg_proof.rs:472-525) of `--blobs` (1 024, BASELINE.json configs[1]) synthetic blobs each, all already resident
@@ -10,7 +16,7 @@ in HBM - 262 144 blobs, 32 GiB of blob bytes per step and GPU.  Every batch of t
 verification (its own transcript, challenge r, MSMs and pairing; its own boolean).  At n = 1 024 each phase of ONE
 batch is a latency-bound serial chain that occupies a sliver of the chip, so the batch dimension lives inside every
 kernel, and `--inflight` groups are kept in flight by a fixed-order software pipeline on one host thread.
-The latency of ONE batch at a time (the reference's call shape) is measured too and reported as `single_batch`
+With `--full` the latency of ONE batch at a time (the reference's call shape) is measured too and reported as `single_batch`
 (device-resident) and `end_to_end` (host `Vec<Blob>` layout through kzg_verify_blob_kzg_proof_batch, PCIe included).
 
 With N > 1 (launched by torch.distributed.run, one rank per GPU over RCCL) the default workload is BASELINE.json
@@ -24,7 +30,7 @@ Rank 0 prints ONE JSON line.
 `python3 bench.py --gpus N` from a bare command (no WORLD_SIZE in the environment) starts the N ranks itself, as child
 processes, BEFORE anything in this process has touched the GPU, and exits with their worst return code.
 
-The default one-GPU run also measures BASELINE configs[4]'s SHARD SHAPE on that one GPU (`configs.config5_shard`: 8 batches x 32 768 blobs
+The `--full` one-GPU run also measures BASELINE configs[4]'s SHARD SHAPE on that one GPU (`configs.config5_shard`: 8 batches x 32 768 blobs
 per step through the very code path `--gpus N` runs - `--workload config5 --force-collectives` in a child process, a world of one rank over
 RCCL - with its stage split and a poisoned batch), so that a later `--gpus N` curve has a like-for-like N = 1 point
 (`multi_gpu.efficiency_vs`); a pre-flight sizes the variants against free HBM and shrinks the launch group instead of dying.  `configs.config3`
@@ -32,7 +38,7 @@ RCCL - with its stage split and a poisoned batch), so that a later `--gpus N` cu
 `end_to_end.large_calls`: ONE call with a Vec<Blob> of 8 192 / 32 768 blobs.  The `roofline` / `path` / `valu` blocks are assembled by
 kzg_rs_amd/benchline.py (its docstring states the rules; `roofline.inputs` carries the measurement they follow from).
 
-Also in the line: `self_check` (the negative control THROUGH THE BENCHMARKED ENTRY POINT: five launch groups of the full
+Also in the `--full` line: `self_check` (the negative control THROUGH THE BENCHMARKED ENTRY POINT: five launch groups of the full
 shape through kzg_verify_blob_kzg_proof_batch_groups_device with the benchmark's groups in flight, a wrong proof, a field
 element equal to r and a commitment outside G1 poisoned into batches of DIFFERENT groups and lanes - the call must say
 false / Err / Err for exactly those), `roofline.standalone_ms` (the dominant kernel alone on the chip: one launch group on a
@@ -213,7 +219,7 @@ def concurrent_callers(settings, blobs, cs, ps, synth, qc, qz, qy, qp, no_cpu=Fa
 
 
 def config_legs(settings, torch, dev, no_cpu=False):
-    """BASELINE.json configs[2] and configs[3] as measured legs of the default run (they are parity-tested at full size in
+    """BASELINE.json configs[2] and configs[3] as measured legs of the --full run (they are parity-tested at full size in
     tests/test_gpu_baseline_sizes.py; here they get a number the driver's line carries), each with a result check.
       config3: evaluate_polynomial_in_evaluation_form only (src/kzg_proof.rs:94-133), 16 384 device-resident blobs (2 GiB) through
                kzg_evaluate_polynomials_device.  Check: z = a root of unity for 32 of the blobs -> y must be the blob's own element
@@ -526,7 +532,7 @@ def main():
     ap.add_argument("--no-concurrent", action="store_true", help="skip the concurrent_callers block (T threads on one shared handle)")
     ap.add_argument("--force-collectives", action="store_true",
                     help="run the one-process-per-GPU path (PipelinedVerifier: kzg_shard_* phases + torch.distributed exchanges) even in a world of ONE rank - "
-                         "what the default run's configs.config5_shard leg does in a child process, so that the 1-GPU figure of the sharded shape comes from the "
+                         "what the --full run's configs.config5_shard leg does in a child process, so that the 1-GPU figure of the sharded shape comes from the "
                          "same code path --gpus N runs")
     ap.add_argument("--no-shard-leg", action="store_true", help="skip configs.config5_shard (BASELINE configs[4]'s shard shape on one GPU, in a child process)")
     ap.add_argument("--precall-single", action="store_true",
@@ -534,7 +540,17 @@ def main():
                          "two more users of the 8 hardware queues the pipeline's lanes share)")
     ap.add_argument("--single-process-devices", default=None, metavar="0,1,...",
                     help="only the single-process multi-device leg: one handle over these devices, --blobs per device (default 32768)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (latency legs, self checks, concurrent callers, BASELINE config legs, the "
+                         "shard-shape leg, the CPU baseline, the pipeline's negative control, roofline / per-kernel blocks); the --no-* "
+                         "options trim this set.  Without it a run sets up, warms up, times --steps launch groups and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned for its last step (one verdict per batch) to DIR/verdicts.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_latency = args.no_self_check = args.no_configs = args.no_concurrent = args.no_shard_leg = args.no_cpu_baseline = True
 
     if args.single_process_devices:
         return single_process_leg(args.single_process_devices, args.blobs or 32768, max(args.steps, 1) if args.steps != 20 else 5, args.warmup if args.warmup != 5 else 2)
@@ -601,7 +617,7 @@ def main():
         G = max(1, G // 2)
     preflight = {"free_hbm_GiB": round(free_b / 2**30, 1), "variants": n_var, "needed_GiB": round(_need(G) / 2**30, 1), "batches_per_step": G,
                  "batches_per_step_asked": G_asked, "shrunk": G != G_asked}
-    n_src = min(n, 1024) if args.force_collectives and world == 1 else n   # (the shard leg of the default run: 1 024 valid blobs, tiled)
+    n_src = min(n, 1024) if args.force_collectives and world == 1 else n   # (the shard leg of the --full run: 1 024 valid blobs, tiled)
     blobs, cs, ps, settings = synth.make_valid_batch(n_src, seed=1000 + rank, chunk=1024)
     if n_src != n:
         reps = (n + n_src - 1) // n_src
@@ -659,7 +675,7 @@ def main():
             res = pipe.run(groups)
         if not all(all(r) for r in res):
             raise SystemExit("verification of a valid synthetic batch returned false")
-        return groups
+        return res
 
     def timed(fn):
         if dist:
@@ -696,7 +712,9 @@ def main():
         ws, wc, _ = h.kernel_stamp_totals(reset=True)
         other_stamps = {k: other_stamps.get(k, 0.0) + v for k, v in ws.items()}
         other_stamp_cnt += wc
-    elapsed, _ = timed(lambda: run_groups(K))
+    elapsed, res_timed = timed(lambda: run_groups(K))
+    last_step = res_timed[-1]   # what a caller of the timed path receives for the last step: one verdict per batch
+    del res_timed
     clk_cycles = clk_ticks = 0.0
     for h in handles:  # the clock the SIMDs ran at during the timed region (every wave of the challenge kernel stamps it)
         a, b = h.shader_clock(reset=True)
@@ -958,7 +976,7 @@ def main():
                 configs = config_legs(settings, torch, dev, no_cpu=args.no_cpu_baseline)
     backend_name = dist.get_backend() if dist else None
     pipe_check = rank_stats = None
-    if pipe is not None:
+    if pipe is not None and args.full:
         # the negative control THROUGH THE PIPELINED PATH: one group of the timed shape with one proof swapped for another blob's in
         # batch G // 2 - that batch false on every rank, every other batch true (src/kzg_proof.rs:436-444)
         v0 = variants[0]
@@ -990,28 +1008,6 @@ def main():
         dist.destroy_process_group()
     if rank != 0:
         return
-    # ---- roofline / path / valu: assembled by kzg_rs_amd/benchline.py (a pure function of this measurement and the PMC profile under
-    # profiles/; its docstring states the dominance rule and what every column means; tests/test_benchline.py checks its arithmetic)
-    from kzg_rs_amd import benchline
-    from kzg_rs_amd import build as kbuild
-    pmc_file, pmc = benchline.load_pmc(ROOT)
-    try:
-        kkey = kbuild.kernel_key()
-    except BaseException:
-        kkey = None
-    n_chal = cnt + warm_cnt + solo_cnt + sc_cnt
-    measurement = {
-        "n": n, "G": G, "K": K, "F": F, "world": world, "elapsed_s": elapsed, "shader_mhz": shader_mhz,
-        "in_flight_ms": {k: v for k, v in in_flight.items() if v}, "stamp_cnt": stamp_cnt, "stamp_sum_ms": stamp_sum,
-        "other_stamp_sum_ms": other_stamps, "other_stamp_cnt": other_stamp_cnt,
-        "solo_stamps_ms": {k: v for k, v in (solo_stamps or {}).items() if v} or None,
-        "standalone_event_ms": standalone,
-        "challenge_event_population": {"all_launches_ms": (sums[5] + warm_sum5 + solo_sums[5] + sc_sums[5]) / n_chal if n_chal and kernels["k_blob_challenge"] > 0 else None,
-                                       "launches": n_chal if kernels["k_blob_challenge"] > 0 else None,
-                                       "incl_warmup_ms": (sums[5] + warm_sum5) / max(cnt + warm_cnt, 1) if kernels["k_blob_challenge"] > 0 else None},
-    }
-    blocks = benchline.assemble(measurement, pmc_file, pmc, kkey)
-    clock_hz = (shader_mhz or 2400.0) * 1e6
     out = {
         "metric": "blobs/sec verify_blob_kzg_proof_batch",
         "value": round(n * world * G * K / elapsed, 2),
@@ -1036,21 +1032,46 @@ def main():
                                   "inside the library" % (K, F) if not use_pipe else
                                   "kzg_shard_*_launch/_wait phases driven by kzg_rs_amd.distributed.PipelinedVerifier, one process per GPU%s"
                                   % (" (a world of ONE rank: --force-collectives)" if world == 1 else "")},
-        "roofline": blocks["roofline"],
-        "path": blocks["path"],
-        "valu": blocks["valu"],
-        "kernel_ms_standalone": blocks["kernel_ms_standalone"],
-        "kernel_ms_in_flight": blocks["kernel_ms_in_flight"],
-        "self_check": self_check,
-        "single_batch": single,
-        "end_to_end": end2end,
-        "verify_kzg_proof_ms": proof_ms,
-        "verify_blob_kzg_proof_ms": blob_ms,
-        "verify_blob_kzg_proof_batch_6_host_blobs_ms": small_ms,
-        "verify_kzg_proofs_independent_per_s": proofs_per_s,
-        "concurrent_callers": concurrent,
-        "configs": configs,
     }
+    if args.full:
+        # ---- roofline / path / valu: assembled by kzg_rs_amd/benchline.py (a pure function of this measurement and the PMC profile under
+        # profiles/; its docstring states the dominance rule and what every column means; tests/test_benchline.py checks its arithmetic)
+        from kzg_rs_amd import benchline
+        from kzg_rs_amd import build as kbuild
+        pmc_file, pmc = benchline.load_pmc(ROOT)
+        try:
+            kkey = kbuild.kernel_key()
+        except BaseException:
+            kkey = None
+        n_chal = cnt + warm_cnt + solo_cnt + sc_cnt
+        measurement = {
+            "n": n, "G": G, "K": K, "F": F, "world": world, "elapsed_s": elapsed, "shader_mhz": shader_mhz,
+            "in_flight_ms": {k: v for k, v in in_flight.items() if v}, "stamp_cnt": stamp_cnt, "stamp_sum_ms": stamp_sum,
+            "other_stamp_sum_ms": other_stamps, "other_stamp_cnt": other_stamp_cnt,
+            "solo_stamps_ms": {k: v for k, v in (solo_stamps or {}).items() if v} or None,
+            "standalone_event_ms": standalone,
+            "challenge_event_population": {"all_launches_ms": (sums[5] + warm_sum5 + solo_sums[5] + sc_sums[5]) / n_chal if n_chal and kernels["k_blob_challenge"] > 0 else None,
+                                           "launches": n_chal if kernels["k_blob_challenge"] > 0 else None,
+                                           "incl_warmup_ms": (sums[5] + warm_sum5) / max(cnt + warm_cnt, 1) if kernels["k_blob_challenge"] > 0 else None},
+        }
+        blocks = benchline.assemble(measurement, pmc_file, pmc, kkey)
+        clock_hz = (shader_mhz or 2400.0) * 1e6
+        out.update({
+            "roofline": blocks["roofline"],
+            "path": blocks["path"],
+            "valu": blocks["valu"],
+            "kernel_ms_standalone": blocks["kernel_ms_standalone"],
+            "kernel_ms_in_flight": blocks["kernel_ms_in_flight"],
+            "self_check": self_check,
+            "single_batch": single,
+            "end_to_end": end2end,
+            "verify_kzg_proof_ms": proof_ms,
+            "verify_blob_kzg_proof_ms": blob_ms,
+            "verify_blob_kzg_proof_batch_6_host_blobs_ms": small_ms,
+            "verify_kzg_proofs_independent_per_s": proofs_per_s,
+            "concurrent_callers": concurrent,
+            "configs": configs,
+        })
     if configs:   # cycles per VALU instruction of the two config kernels: this run's time x the measured clock / the instruction counts of the committed PMC profile
         try:
             cfile = "r6_config_pmc.json"
@@ -1074,7 +1095,7 @@ def main():
         except Exception:
             pass
     out["preflight"] = preflight
-    if use_pipe:
+    if use_pipe and args.full:
         g = max(pipe.stats["groups"], 1)  # warm-up groups included; per-step averages of THIS rank's host time
         bulk_once = G % world == 0
         shard_1gpu = None
@@ -1125,6 +1146,11 @@ def main():
         out["configs"]["config5_shard"] = run_shard_leg_child(args.steps, args.warmup)
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(blobs, cs, ps, synth.synthetic_setup()[1], args.cpu_sample)
+    if args.dump_outputs:
+        # the last timed step's verdicts, one per batch of the launch group in order: 1 = true, 0 = false, NaN = Err
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "verdicts.npy"),
+                np.array([np.nan if r is None else float(r) for r in last_step], dtype=np.float32))
     print(json.dumps(out))
 
 
@@ -1134,7 +1160,7 @@ def run_shard_leg_child(steps, warmup, timeout=420):
     288-byte partial sums: a world of one rank over RCCL), i.e. the N = 1 point of the curve `--gpus N` draws."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", "config5", "--force-collectives", "--steps", str(steps), "--warmup", str(warmup),
-           "--no-latency", "--no-self-check", "--no-cpu-baseline", "--no-configs", "--no-concurrent"]
+           "--full", "--no-latency", "--no-self-check", "--no-cpu-baseline", "--no-configs", "--no-concurrent"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)

@@ -44,3 +44,9 @@ def test_launched_rank_keeps_the_torchrun_contract():
              "--gpus", "2")
     assert r.returncode == 0
     assert json.loads(r.stdout.strip())["RANK"] == "1"
+
+
+def test_zero_steps_is_an_argument_error():
+    # ms_per_step divides by the step count: a run with no timed step must be refused before anything starts
+    r = _run({"KZG_BENCH_DRY_SPAWN": "1"}, "--gpus", "1", "--steps", "0")
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -150,7 +150,7 @@ def test_bench_script_two_ranks_shared_gpu():
     env = dict(os.environ, KZG_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--group", "16", "--no-cpu-baseline", "--workload", "configs1"]
+           "--group", "16", "--full", "--no-cpu-baseline", "--workload", "configs1"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -168,7 +168,7 @@ def test_bench_script_two_ranks_shared_gpu():
 
 
 def test_bench_shard_leg_world_of_one():
-    """`bench.py --workload config5 --force-collectives` on ONE GPU (what the default run's configs.config5_shard leg starts as a child):
+    """`bench.py --workload config5 --force-collectives` on ONE GPU (what the --full run's configs.config5_shard leg starts as a child):
     BASELINE configs[4]'s shard shape through PipelinedVerifier with the exchanges of a world of one rank over RCCL - here at a reduced
     size (2 048-blob shards, 4 batches per step) - prints the standard line with the stage split, the exchange that ran and the
     poisoned batch's false."""
@@ -176,7 +176,7 @@ def test_bench_shard_leg_world_of_one():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "config5", "--force-collectives", "--steps", "3", "--warmup", "1",
-           "--blobs", "2048", "--group", "4", "--no-latency", "--no-self-check", "--no-cpu-baseline", "--no-configs", "--no-concurrent"]
+           "--blobs", "2048", "--group", "4", "--full", "--no-latency", "--no-self-check", "--no-cpu-baseline", "--no-configs", "--no-concurrent"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -186,6 +186,29 @@ def test_bench_shard_leg_world_of_one():
     assert mg["backend"] == "nccl" and mg["exchange_ran"]["world_of_one"] is True and "RCCL" in mg["exchange_ran"]["transport"]
     assert mg["pipe_check"]["passed"] is True and mg["pipe_check"]["results"] == [True, True, False, True]
     assert mg["per_rank_stage_ms_per_step"][0]["r_hash_ms"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain one-GPU `bench.py` (no --full) at a reduced size: exactly --steps timed launch groups, the contract's fields, none of
+    the --full legs, and --dump-outputs writes the last step's verdicts (one per batch of the launch group) as float32."""
+    import json
+    import subprocess
+
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--blobs", "1024", "--group", "16",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "blobs/sec verify_blob_kzg_proof_batch" and d["unit"] == "blobs/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["blobs_per_step"] == 16 * 1024
+    assert abs(d["value"] - 16 * 1024 / (d["ms_per_step"] / 1e3)) <= 1e-3 * d["value"]
+    assert not {"roofline", "self_check", "single_batch", "configs", "cpu_baseline", "multi_gpu"} & set(d)
+    v = np.load(tmp_path / "out" / "verdicts.npy")
+    assert v.dtype == np.float32 and v.shape == (16,) and (v == 1).all()
 
 
 def test_bench_script_bare_command_starts_its_own_ranks():
@@ -198,7 +221,7 @@ def test_bench_script_bare_command_starts_its_own_ranks():
     env["KZG_BENCH_SHARE_GPU"] = "1"
     env["KZG_BENCH_SINGLE_PROCESS"] = "force"  # also the one-process leg (a child process over the device list "0,0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--group", "4", "--blobs", "256",
-           "--no-cpu-baseline", "--no-latency", "--workload", "configs1"]
+           "--full", "--no-cpu-baseline", "--no-latency", "--workload", "configs1"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

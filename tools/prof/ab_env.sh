@@ -5,7 +5,7 @@
 for rep in 1 2; do
   for setting in "$@"; do
     [ "$setting" = "-" ] && setting=""
-    line=$(env $setting python3 bench.py --steps 12 --warmup 4 --no-latency --no-cpu-baseline 2>/dev/null | tail -1)
+    line=$(env $setting python3 bench.py --steps 12 --warmup 4 --full --no-latency --no-cpu-baseline 2>/dev/null | tail -1)
     python3 - "$setting" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])
