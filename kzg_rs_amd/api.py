@@ -18,8 +18,9 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KZG_LIB_OVERRIDE") or os.path.join(HERE, "libkzg_rs_amd.so")
-# the A/B build (python -m kzg_rs_amd.build): the product plus the alternative kernel forms kept for measurement and for the
-# differential fuzz; a process selects it with KZG_LIB_OVERRIDE=LIB_AB_PATH and a form with KZG_OPTIONS (options_string)
+# the A/B build (python -m kzg_rs_amd.build): the product's kernels with the measurement and test switches of KZG_OPTIONS
+# (options_string) read at run time, so that tests reach forms the dispatch does not pick at a given size; a process selects
+# it with KZG_LIB_OVERRIDE=LIB_AB_PATH
 LIB_AB_PATH = os.path.join(HERE, "libkzg_rs_amd_ab.so")
 TRUSTED_SETUP_PATH = os.path.join(HERE, "data", "trusted_setup.txt")
 

@@ -2,11 +2,12 @@
 
     python -m kzg_rs_amd.build          # regenerates constants / SLP programs, then compiles
 
-Two libraries come out of the one source tree:
-    libkzg_rs_amd.so      the PRODUCT: -DKZG_AB_VARIANTS=0, only the kernel forms the dispatch by launch size selects
-    libkzg_rs_amd_ab.so   the A/B build: -DKZG_AB_VARIANTS=1 adds the alternative forms kept for measurement and for the
-                          differential fuzz (12x32-limb point kernels, the 8x32 evaluation, the 16-chunk proofs layout),
-                          selected through KZG_OPTIONS (csrc/capi_host_util.hpp); tests load it through KZG_LIB_OVERRIDE
+Two libraries come out of the one source tree, both linked against ONE gfx950 code object (the device pass):
+    libkzg_rs_amd.so      the PRODUCT: host code with -DKZG_AB_VARIANTS=0, its measurement switches fixed at compile time
+    libkzg_rs_amd_ab.so   the A/B build: host code with -DKZG_AB_VARIANTS=1, which reads those switches from KZG_OPTIONS
+                          (csrc/capi_host_util.hpp ab_flag / ab_int) so that tests and measurements reach forms the dispatch
+                          does not pick at a given size; tests load it through KZG_LIB_OVERRIDE
+KZG_AB_VARIANTS may appear in host-only files alone (_device_key refuses it elsewhere), so both builds hold the same kernels.
 hipcc cross-compiles without a GPU; the resulting .so files travel with the repo snapshot.
 """
 import os
@@ -44,19 +45,14 @@ def build(force=False, verbose=False, variants=(0, 1)):
     fb_gen = os.path.join(ROOT, "tools", "gen_fixed_base.py")
     if force or _newer(os.path.join(data, "fixed_base.bin"), [fb_gen, os.path.join(ROOT, "tools", "bls_params.py")]):
         subprocess.check_call([sys.executable, fb_gen])
-    # 2. the libraries (the two device passes side by side: each is one hipcc process)
+    # 2. the libraries
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(data, "slp_prep.bin"),
                                                                os.path.join(data, "slp_verify.bin"), os.path.join(data, "slp_verify2.bin"),
                                                                os.path.join(data, "slp_scalars.bin"), os.path.join(data, "slp_verify3.bin"), os.path.join(data, "fixed_base.bin"),
                                                                os.path.join(ROOT, "include", "kzg_rs_amd.h")]
     todo = [v for v in variants if force or _newer(LIB_AB if v else LIB, deps)]
-    if len(todo) > 1:
-        import concurrent.futures
-        with concurrent.futures.ThreadPoolExecutor(len(todo)) as ex:
-            for f in [ex.submit(_compile, csrc, data, force, verbose, v) for v in todo]:
-                f.result()
-    elif todo:
-        _compile(csrc, data, force, verbose, todo[0])
+    if todo:
+        _compile(csrc, data, force, verbose, todo)
     return LIB
 
 
@@ -66,6 +62,7 @@ def build(force=False, verbose=False, variants=(0, 1)):
 # see of the host files: the kernels and launch helpers they name (with their template arguments), their preprocessor
 # lines and constants.  The key is a heuristic, so the link step CHECKS it: every kernel the host object launches (its
 # __device_stub__ symbols) must be defined in the cached code object, else the device pass runs again.
+# The device pass is shared by the product and the A/B build, so a device-side file may not name KZG_AB_VARIANTS.
 # `--force` (and any cold build) runs every step.
 HOST_ONLY = ("capi_host_util.hpp", "capi_pieces.hpp", "capi_prover.hpp", "capi_settings.hpp", "capi_verify.hpp",
              "capi_multi.hpp", "capi_coalesce.hpp", "small_queue.hpp", "dyn_lds.hpp", "capi_pipeline.hpp", "host_only.hpp", "kzg_capi.hip")
@@ -84,15 +81,17 @@ def _device_key(csrc, flags):
             seen = re.findall(rb"\b(?:k_[A-Za-z0-9_]+|msm_window_launch|launch_program2|run_program2?)\s*(?:<[^;(]*?>)?", body)
             seen += re.findall(rb"constexpr[^;]*;", body) + re.findall(rb"(?m)^\s*#\s*(?:if|ifdef|ifndef|elif|else|endif|define|undef)\b[^\n]*", body)
             body = b"\n".join(sorted(set(seen)))
+        elif b"KZG_AB_VARIANTS" in body:
+            raise SystemExit("build.py: %s holds device code and names KZG_AB_VARIANTS: both libraries share one device pass" % f)
         h.update(f.encode() + b"\0" + body + b"\0")
     return h.hexdigest()[:24]
 
 
-def kernel_key(variant=0):
+def kernel_key():
     """What identifies the KERNELS of a build, wherever the tree lies: the device-side sources in full plus what the device pass sees
     of the host-only files (_device_key), without the absolute paths of the compile flags.  PMC profiles under profiles/ are stamped
     with it (tools/prof/pmc_to_json.py) and bench.py flags a profile whose stamp differs from the tree it runs in."""
-    return _device_key(os.path.join(HERE, "csrc"), ["kernel-key", "-DKZG_AB_VARIANTS=%d" % variant])
+    return _device_key(os.path.join(HERE, "csrc"), ["kernel-key"])
 
 
 def _kernel_names(obj, stubs):
@@ -128,40 +127,43 @@ def _device_pass(flags, dev, fb, verbose):
     os.remove(dev)
 
 
-def _compile(csrc, data, force, verbose, variant=0):
+def _compile(csrc, data, force, verbose, variants):
     cache = os.path.join(ROOT, "build", "devcache")
     os.makedirs(cache, exist_ok=True)
-    lib = LIB_AB if variant else LIB
-    tag = "ab%d-" % variant
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-pthread", "-Wno-unused-result",
-             "-DKZG_AB_VARIANTS=%d" % variant, '-DKZG_DATA_DIR="%s"' % data, "-I", csrc]
+             '-DKZG_DATA_DIR="%s"' % data, "-I", csrc]
     key = _device_key(csrc, flags)
-    fb = os.path.join(cache, tag + key + ".hipfb")
-    dev = os.path.join(cache, tag + key + ".out")
+    fb = os.path.join(cache, key + ".hipfb")
+    dev = os.path.join(cache, key + ".out")
     fresh = force or not (os.path.exists(fb) and os.path.exists(fb + ".syms"))
     if fresh:
         _device_pass(flags, dev, fb, verbose)
-    host = os.path.join(cache, tag + "host.o")
 
-    def host_pass():
-        subprocess.check_call(["hipcc"] + flags + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", fb,
-                                                   "-c", "-o", host, SRC])
+    def host_pass(variant):
+        host = os.path.join(cache, "host%d.o" % variant)
+        subprocess.check_call(["hipcc"] + flags + ["-DKZG_AB_VARIANTS=%d" % variant, "--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary",
+                                                   "-Xclang", fb, "-c", "-o", host, SRC])
         return _kernel_names(host, stubs=True) - set(open(fb + ".syms").read().splitlines())
 
-    missing = host_pass()
+    def host_passes():  # side by side: each is one hipcc process
+        import concurrent.futures
+        with concurrent.futures.ThreadPoolExecutor(len(variants)) as ex:
+            return set().union(*ex.map(host_pass, variants))
+
+    missing = host_passes()
     if missing and not fresh:  # the key missed a new instantiation: the cached code object lacks kernels the host launches
         print("build.py: cached device code lacks %d kernel(s) (%s ...): running the device pass" % (len(missing), sorted(missing)[0]))
         _device_pass(flags, dev, fb, verbose)
-        missing = host_pass()
+        missing = host_passes()
     if missing:
         raise SystemExit("build.py: the device code object does not define: %s" % ", ".join(sorted(missing)))
-    subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", lib + ".tmp", host, "-ldl"])
-    os.replace(lib + ".tmp", lib)
-    os.remove(host)
-    for old in os.listdir(cache):  # one entry per variant is enough
-        if old.startswith(tag) and not old.startswith(tag + key):
-            os.remove(os.path.join(cache, old))
-        elif not old.startswith("ab"):
+    for v in variants:
+        lib, host = LIB_AB if v else LIB, os.path.join(cache, "host%d.o" % v)
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", lib + ".tmp", host, "-ldl"])
+        os.replace(lib + ".tmp", lib)
+        os.remove(host)
+    for old in os.listdir(cache):  # one device code object is enough
+        if not old.startswith(key):
             os.remove(os.path.join(cache, old))
 
 

@@ -15,9 +15,9 @@ extern "C" const char* kzg_last_error(void) { return g_err.c_str(); }
 // ONE environment variable, KZG_OPTIONS = "key=value;key=value;..." (';' or blanks between entries), carries every tuning
 // and test switch of the library; a switch is named by its key in the comment beside the code that reads it, and
 // INTEGRATION.md lists them.  The string is parsed when it is first needed and again whenever its value has changed
-// (tests change it between handles); most switches are latched by their reader on first use.  Switches that select a kernel
-// variant compiled only into the A/B build (KZG_AB_VARIANTS=1: fp29=0, evaluate_kernel=32, proofs_chunks=16) are ignored by
-// the product build - ab_variants_built() tells which one is loaded.
+// (tests change it between handles); most switches are latched by their reader on first use.  The A/B build (KZG_AB_VARIANTS=1)
+// reads the measurement switches of ab_flag / ab_int below, which the product build ignores - kzg_debug_option() tells which
+// one is loaded.  Both builds hold the same kernels: KZG_AB_VARIANTS appears in host code only.
 // The device list of an UNCHANGED caller is the one deployment knob with a variable of its own: KZG_DEVICES.
 //
 // The library does not touch the process environment (rounds 1-3 set GPU_MAX_HW_QUEUES from a load-time constructor): the
@@ -117,20 +117,10 @@ struct DevTmp {
     T* as() const { return static_cast<T*>(p); }
 };
 
-// Point arithmetic of the decode and MSM kernels: the radix-2^29 field (fp29.hpp) unless the A/B build's option fp29=0 selects the 12x32
-// field (measurement, cross-check).  Decides the table format (G1Jac29Mem / G1Jac) for the whole process.
-static bool fp29_enabled() {
-#if KZG_AB_VARIANTS
-    static const bool v = opt_flag("fp29", true);
-    return v;
-#else
-    return true;
-#endif
-}
 // Throughput layout of the verification MSM (MSM_CHUNKS tables) with AFFINE entries and mixed additions (msm.hpp
-// k_mult_to_affine29); option msm_affine=0 keeps Jacobian entries (A/B measurement).  Radix-2^29 field only.
+// k_mult_to_affine29); option msm_affine=0 keeps Jacobian entries (A/B measurement).
 static bool msm_affine_enabled() {
-    static const bool v = fp29_enabled() && ab_flag("msm_affine", true);
+    static const bool v = ab_flag("msm_affine", true);
     return v;
 }
-constexpr size_t MULT_ENTRY_BYTES = sizeof(G1Jac29Mem) > sizeof(G1Jac) ? sizeof(G1Jac29Mem) : sizeof(G1Jac);
+constexpr size_t MULT_ENTRY_BYTES = sizeof(G1Jac29Mem);  // a table entry of either form (G1Aff29Mem is the smaller)

@@ -183,7 +183,7 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
     const int fold_per = std::max(fold_per_opt, (int)((gz + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS));
     int fold_gp = 0;
     (void)msm_large_tail_groups(gz, fold_per, &fold_gp);
-    const bool large_tail = fp29_enabled() && gz >= 16 && ab_flag("g1_msm_large_tail", true) &&
+    const bool large_tail = gz >= 16 && ab_flag("g1_msm_large_tail", true) &&
                             w.cap_msm_save >= msm_save_layer_bytes(W, 1, MSM_SAVE2_WORDS) * gz;
     // scratch: window sums [gz_pad][W] | fold level A [gz_pad / 2][W] | fold level B [gz_pad / 4][W] | the large tail's
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -222,10 +222,7 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
     d.chunks_per_block = MSM_CHUNKS;  // one workgroup per (window, slice): the four chunks' entries in one sorted list
     d.flags = (gz & 7) == 0 ? MSM_FLAG_XCD : 0;
     if (tb.affine) msm_window_launch<Curve29Aff, true>(d, W, 1, gz, w.d_msm_save, w.cap_msm_save, s->s1, !large_tail);
-    else if (fp29_enabled()) msm_window_launch<Curve29, true>(d, W, 1, gz, w.d_msm_save, w.cap_msm_save, s->s1, !large_tail);
-#if KZG_AB_VARIANTS
-    else msm_window_launch<Curve32, true>(d, W, 1, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-#endif
+    else msm_window_launch<Curve29, true>(d, W, 1, gz, w.d_msm_save, w.cap_msm_save, s->s1, !large_tail);
     if (large_tail) HIPCHK(msm_large_tail(w.d_msm_save, W, gz, fold_per, t_tail, t_ws, s->s1));
     // window sums [2 S (padded to whole groups of 64 with identities)][W] -> [1][W]: trees over up to 64 slices at a time.  A level
     // with more than 64 inputs reads them in whole groups of 64: the tail of the last group is zeroed here when the level below
@@ -245,8 +242,7 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
         left = groups;
     }
     // 8 windows of one output: the Horner chain with four lanes per doubling / addition (0.8 -> ~0.2 ms of a 2^20-term call)
-    if (fp29_enabled()) hipLaunchKernelGGL(k_msm_combine_quad, dim3(1), dim3(64), 0, s->s1, cur, w.d_ab, (int)W);
-    else hipLaunchKernelGGL(k_msm_combine, dim3(1), dim3(64), 0, s->s1, cur, w.d_ab, 1, (int)W);
+    hipLaunchKernelGGL(k_msm_combine_quad, dim3(1), dim3(64), 0, s->s1, cur, w.d_ab, (int)W);
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
     hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, w.d_ab, w.d_bytes, 1);
     HIPCHK(hipGetLastError());
@@ -289,15 +285,10 @@ extern "C" KzgRet kzg_g1_msm(uint8_t out[48], const uint8_t* points48, const uin
                                w.d_bytes, (int)n, w.d_points, w.d_pflag, w.d_mult, w.d_jtmp, (int)n, np);
             const unsigned conv_blocks = (unsigned)((n + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
             hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp, w.d_pflag, (G1Aff29Mem*)w.d_mult, (int)n, np);
-        } else if (fp29_enabled()) {
+        } else {
             hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1,
                                w.d_bytes, w.d_bytes, (int)n, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, (int)n, np);
         }
-#if KZG_AB_VARIANTS
-        else
-            hipLaunchKernelGGL(k_g1_decode_multiples<MSM_CHUNKS>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->s1, w.d_bytes, w.d_bytes, (int)n, w.d_points,
-                               w.d_pflag, (G1Jac*)w.d_mult, (int)n, np);
-#endif
         HIPCHK(hipGetLastError());
         // (a point outside G1 has the digit 0 in every window - the kernel reads its flag - so the verdict on the inputs is
         // looked at after the sum: one wait at the end)

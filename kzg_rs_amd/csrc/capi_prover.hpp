@@ -117,11 +117,7 @@ static KzgRet setup_msm(const KzgSettings* s, ProverBufs& b, size_t m) {
     const unsigned slots = MSM_CHUNKS / d.chunks_per_block;
     KzgRet rc_save = msm_save_reserve(s, 8, slots, (unsigned)m);
     if (rc_save != KZG_OK) return rc_save;
-#if KZG_AB_VARIANTS
-    if (!fp29_enabled()) msm_window_launch<Curve32, false>(d, 8, slots, (unsigned)m, s->ws.d_msm_save, s->ws.cap_msm_save, s->s1);
-    else
-#endif
-        if (aff) msm_window_launch<Curve29Aff, true>(d, 8, slots, (unsigned)m, s->ws.d_msm_save, s->ws.cap_msm_save, s->s1);
+    if (aff) msm_window_launch<Curve29Aff, true>(d, 8, slots, (unsigned)m, s->ws.d_msm_save, s->ws.cap_msm_save, s->s1);
     else msm_window_launch<Curve29, false>(d, 8, slots, (unsigned)m, s->ws.d_msm_save, s->ws.cap_msm_save, s->s1);
     hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)m), dim3(64), 0, s->s1, b.d_win, b.d_res, (int)slots, 8);
     hipLaunchKernelGGL(k_jac_compress_n, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, b.d_res, b.d_out, (int)m);
@@ -202,7 +198,7 @@ static KzgRet compute_proofs(uint8_t* proofs48, uint8_t* ys32, const uint8_t* bl
             // the commitments' validity (decompression + subgroup test): EIGHT lanes per point where every workgroup of eight points can
             // have a CU to itself (msm.hpp k_g1_decode_multiples29_quads: 1.2 ms instead of the one-lane kernel's 2.5 - the longest chain of
             // a one-blob proof call); its table multiples are a by-product nobody reads
-            static const bool dec_quads = fp29_enabled() && ab_flag("decode_quads", true);
+            static const bool dec_quads = ab_flag("decode_quads", true);
             const unsigned qblocks = (unsigned)((m + DECQ_POINTS_PER_BLOCK - 1) / DECQ_POINTS_PER_BLOCK);
             if (dec_quads && (int)qblocks <= s->n_cus && DYN_LDS(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, DECQ_LDS_BYTES) == hipSuccess)
                 hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, dim3(qblocks), dim3(64), DECQ_LDS_BYTES, dec, (const uint8_t*)b.d_cm, (const uint8_t*)b.d_cm, (int)m,
@@ -259,7 +255,7 @@ extern "C" KzgRet kzg_compute_blob_kzg_proof(uint8_t* proofs48, const uint8_t* b
 //           the window form at 1 / 1 024 / 4 096 / 32 768 / 65 536 / 2^20 terms: 0.39 / 0.69 / 0.77 / 1.04 / 1.30 / 5.2 ms against
 //           1.14 / 1.19 / 1.63 / 1.50 / 1.83 / 8.1 ms
 //   window  the verification path's window kernel (GLV, 8-bit windows) over the setup's affine table rows: the fallback when the
-//           fixed-base form's bucket sums would pass 2 GiB (above ~2^24.6 terms) or the handle has no affine rows (A/B build, fp29=0)
+//           fixed-base form's bucket sums would pass 2 GiB (above ~2^24.6 terms) or the handle has no affine rows (A/B build, msm_affine=0)
 // option g1_msm_setup_form = window | fixed forces one (tests, A/B).  timings: [2] the MSM, [6] = 0 (no decode, no tables).
 constexpr size_t FBM_MIN_TERMS = 1;
 static KzgRet fb_rows_ready(const KzgSettings* s) {

@@ -36,7 +36,7 @@ struct Workspace {
     G1Jac* d_send = nullptr;  // a shard's contribution to the RCCL all-gather of partial sums: up to MAX_WORLD pieces x (A, B) (capi_multi.hpp)
     uint32_t* d_msm_save = nullptr;  // the window kernel's bucket sums between its row and column trees (msm.hpp MsmDesc::save)
     size_t cap_msm_save = 0;         // bytes
-    void* d_mult = nullptr;  // MSM tables: G1Jac29Mem / G1Aff29Mem / G1Jac entries (fp29_enabled(), msm_affine_enabled())
+    void* d_mult = nullptr;  // MSM tables: G1Jac29Mem / G1Aff29Mem entries (msm_affine_enabled())
     // in-kernel stamps of the last launch group (field.hpp kstamp_in / kstamp_out): 16 words - [0, 4) the throughput-form
     // challenge kernel (its interval and its clock, fr_kernels.hpp), [4, 6) k_blob_evaluate, [6, 8) the decode pass, [8, 10) the
     // MSM window kernel
@@ -69,7 +69,7 @@ struct KzgSettings {
     uint32_t* d_eval_c = nullptr;
     Fp* d_tau4 = nullptr;   // [tau]G2 affine (x.c0 x.c1 y.c0 y.c1), Montgomery
     Fp* d_prep = nullptr;   // prepared lines: [tau]G2 then generator (2 * 408 Fp)
-    void* d_gen_mult = nullptr;   // the generator's MSM tables: [0, 4) the default layout, [4, 36) the latency layout, [36, 52) the proofs layout (msm.hpp)
+    void* d_gen_mult = nullptr;   // the generator's MSM tables (G1Jac29Mem): [0, 4) the default layout, [4, 36) the latency layout (msm.hpp)
     G1Aff29Mem* d_gen_mult_aff = nullptr;  // [0, 4) as affine entries
     // full trusted setup (kzg_settings_load_trusted_setup only; not needed by verification):
     G1Aff* d_g1 = nullptr;            // g1_points, bit-reversal permuted (build.rs:79,89-105), 4096 entries
@@ -358,7 +358,7 @@ static KzgRet settings_build(KzgSettings* s, const uint8_t tau_g2[96]) {
         DevTmp t_g, t_gf, t_gm;
         HIPCHK(hipMalloc(&t_g.p, sizeof(G1Aff)));
         HIPCHK(hipMalloc(&t_gf.p, 4));
-        constexpr int NG = MSM_CHUNKS + MSM_CHUNKS_LATENCY + MSM_CHUNKS_PROOFS;
+        constexpr int NG = MSM_CHUNKS + MSM_CHUNKS_LATENCY;
         HIPCHK(hipMalloc(&t_gm.p, sizeof(G1Jac) * NG));
         G1Aff* d_g = t_g.as<G1Aff>();
         uint32_t* d_gf = t_gf.as<uint32_t>();
@@ -366,16 +366,10 @@ static KzgRet settings_build(KzgSettings* s, const uint8_t tau_g2[96]) {
         hipLaunchKernelGGL(k_set_generator, dim3(1), dim3(64), 0, s->s1, d_g, d_gf, 0);
         hipLaunchKernelGGL(k_g1_multiples, dim3(1), dim3(64), 0, s->s1, d_g, d_gf, d_gm, 1, 1, MSM_CHUNKS);
         hipLaunchKernelGGL(k_g1_multiples, dim3(1), dim3(64), 0, s->s1, d_g, d_gf, d_gm + MSM_CHUNKS, 1, 1, MSM_CHUNKS_LATENCY);
-        hipLaunchKernelGGL(k_g1_multiples, dim3(1), dim3(64), 0, s->s1, d_g, d_gf, d_gm + MSM_CHUNKS + MSM_CHUNKS_LATENCY, 1, 1, MSM_CHUNKS_PROOFS);
-        if (fp29_enabled()) {
-            HIPCHK(hipMalloc(&s->d_gen_mult, sizeof(G1Jac29Mem) * NG));
-            hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(64), 0, s->s1, d_gm, (G1Jac29Mem*)s->d_gen_mult, NG);
-            HIPCHK(hipMalloc(&s->d_gen_mult_aff, sizeof(G1Aff29Mem) * MSM_CHUNKS));
-            hipLaunchKernelGGL(k_jac29_to_aff29, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)s->d_gen_mult, s->d_gen_mult_aff, MSM_CHUNKS);
-        } else {
-            s->d_gen_mult = d_gm;  // the handle owns it from here
-            t_gm.p = nullptr;
-        }
+        HIPCHK(hipMalloc(&s->d_gen_mult, sizeof(G1Jac29Mem) * NG));
+        hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(64), 0, s->s1, d_gm, (G1Jac29Mem*)s->d_gen_mult, NG);
+        HIPCHK(hipMalloc(&s->d_gen_mult_aff, sizeof(G1Aff29Mem) * MSM_CHUNKS));
+        hipLaunchKernelGGL(k_jac29_to_aff29, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)s->d_gen_mult, s->d_gen_mult_aff, MSM_CHUNKS);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s->s1));  // before the temporaries of this scope are released
     }
@@ -407,14 +401,8 @@ static KzgRet settings_load_points(KzgSettings* s, const std::vector<uint8_t>& g
     HIPCHK(hipMalloc(&s->d_g1_mult, MULT_ENTRY_BYTES * MSM_CHUNKS * (size_t)N));
     HIPCHK(hipMemcpyAsync(d_bytes, g1b.data(), g1b.size(), hipMemcpyHostToDevice, s->s1));
     hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s->s1, d_bytes, d_bytes, N, s->d_g1, s->d_g1_flag, N, 0);
-#if KZG_AB_VARIANTS
-    if (!fp29_enabled())
-        hipLaunchKernelGGL(k_g1_decode_multiples<MSM_CHUNKS>, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s->s1, d_bytes, d_bytes, N, d_tmp,
-                           d_flag2, (G1Jac*)s->d_g1_mult, N, N);
-    else
-#endif
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((N + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, d_bytes, d_bytes, N, d_tmp,
-                           d_flag2, s->d_g1_mult, (G1Jac29Mem*)nullptr, N, N);
+    hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((N + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, d_bytes, d_bytes, N, d_tmp,
+                       d_flag2, s->d_g1_mult, (G1Jac29Mem*)nullptr, N, N);
     HIPCHK(hipGetLastError());
     s->n_g1 = N;
     DevTmp t_jtmp, t_aff_pts;

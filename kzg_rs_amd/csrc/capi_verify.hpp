@@ -1,20 +1,12 @@
 // capi_verify.hpp - the verification path: kernel selection, workspace, MSM tail, the three phases as launch + wait, and the entry points.
 // Part of the single translation unit kzg_capi.hip; not a stand-alone header.
 
-// The evaluation kernel over T blobs on stream s1 (radix-2^29 form; option evaluate_kernel=32 of the A/B build selects the 8x32
-// form, kept for measurement and as a cross-check).
+// The evaluation kernel over T blobs on stream s1 (radix-2^29 form).
 // alone: the evaluation is the whole call (kzg_evaluate_polynomials*, BASELINE configs[2]) - nothing else wants the CUs.
 // stamp: the kernel records its own execution interval in the workspace's stamp words (phase 1 has zeroed them)
 static KzgRet launch_evaluate(const KzgSettings* s, const void* d_blobs, const Fr* d_z, Fr* d_y, uint32_t* d_status, size_t T, bool alone = false,
                               bool stamp = false) {
     unsigned long long* const kt = stamp && s->ws.d_ktime ? s->ws.d_ktime + 4 : nullptr;
-#if KZG_AB_VARIANTS
-    static const bool use32 = opt_is("evaluate_kernel", "32");
-    if (use32) {
-        hipLaunchKernelGGL(k_blob_evaluate32, dim3((unsigned)T), dim3(64), 0, s->s1, (const uint8_t*)d_blobs, d_z, s->d_M, s->d_DM, d_y, d_status);
-        return KZG_OK;
-    }
-#endif
     if (T > s->eval_scratch_cap) {  // 576 bytes per blob between the three kernels (fr_kernels.hpp); callers hold the handle's lock
         if (s->d_eval_scratch) HIPCHK(hipFree(s->d_eval_scratch));  // waits for the kernels that may still read it
         s->d_eval_scratch = nullptr;
@@ -38,25 +30,12 @@ static KzgRet launch_evaluate(const KzgSettings* s, const void* d_blobs, const F
     // (the attribute is a per-kernel maximum that dyn_lds_ensure only raises: concurrent launches with different paddings cannot
     // fail each other; a launch whose request could not be raised goes without its padding - slower placement, same result)
     size_t spread_lds = eval_blocks <= (unsigned)s->n_cus ? (size_t)EVAL_SPREAD_LDS : lds_pad;
-    if (spread_lds) {
-        bool attr_ok = DYN_LDS(k_blob_evaluate_t<true>, spread_lds) == hipSuccess;
-#if KZG_AB_VARIANTS
-        attr_ok = DYN_LDS(k_blob_evaluate_t<false>, spread_lds) == hipSuccess && attr_ok;
-#endif
-        if (!attr_ok) {
-            (void)hipGetLastError();  // nothing sticky is left for the callers' checks
-            spread_lds = 0;
-        }
+    if (spread_lds && DYN_LDS(k_blob_evaluate_t<true>, spread_lds) != hipSuccess) {
+        (void)hipGetLastError();  // nothing sticky is left for the callers' checks
+        spread_lds = 0;
     }
-#if KZG_AB_VARIANTS
-    static const bool eval_r3 = opt_is("evaluate_kernel", "r3");  // round 3's kernel: 192 VGPRs, two wavefronts per SIMD (A/B measurement)
-    if (eval_r3)
-        hipLaunchKernelGGL(k_blob_evaluate_t<false>, dim3(eval_blocks), dim3(64 * EVAL_BLOBS_PER_BLOCK), spread_lds, s->s1,
-                           (const uint8_t*)d_blobs, EvalTables{s->d_eval_a, s->d_eval_b, s->d_eval_c}, s->d_eval_scratch, d_status, (int)T, kt);
-    else
-#endif
-        hipLaunchKernelGGL(k_blob_evaluate_t<true>, dim3(eval_blocks), dim3(64 * EVAL_BLOBS_PER_BLOCK), spread_lds, s->s1,
-                           (const uint8_t*)d_blobs, EvalTables{s->d_eval_a, s->d_eval_b, s->d_eval_c}, s->d_eval_scratch, d_status, (int)T, kt);
+    hipLaunchKernelGGL(k_blob_evaluate_t<true>, dim3(eval_blocks), dim3(64 * EVAL_BLOBS_PER_BLOCK), spread_lds, s->s1,
+                       (const uint8_t*)d_blobs, EvalTables{s->d_eval_a, s->d_eval_b, s->d_eval_c}, s->d_eval_scratch, d_status, (int)T, kt);
     hipLaunchKernelGGL(k_eval_finish, dim3(per_lane), dim3(64), 0, s->s1, s->d_eval_scratch, d_y, (int)T);
     return KZG_OK;
 }
@@ -84,13 +63,7 @@ static KzgRet launch_challenge(const KzgSettings* s, const void* d_blobs, const 
         // 4 wavefronts per SIMD (114 VGPRs; the compiler's own choice was 146 = 3): the whole launch is resident at once.
         // Measured and not taken: 5 wavefronts (spills: -2.3 %), the launch as 2 / 4 back-to-back halves / quarters
         // so that the chain's waves leave registers for the other kernels of the pipeline (-2.6 % / -3.5 %).
-#if KZG_AB_VARIANTS
-        static const long occ = opt_int("challenge_occ", 4);
-        if (occ == 3) hipLaunchKernelGGL(k_blob_challenge_t<3>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, bl, cm, d_z, (int)T, kt);
-        else if (occ == 5) hipLaunchKernelGGL(k_blob_challenge_t<5>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, bl, cm, d_z, (int)T, kt);
-        else
-#endif
-            hipLaunchKernelGGL(k_blob_challenge_t<4>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, bl, cm, d_z, (int)T, kt);
+        hipLaunchKernelGGL(k_blob_challenge_t<4>, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, bl, cm, d_z, (int)T, kt);
     } else if (form == 2) {
         hipLaunchKernelGGL(k_blob_challenge_split, dim3((unsigned)((T + 63) / 64)), dim3(128), 0, st, bl, cm, d_z, (int)T);
     } else {
@@ -190,7 +163,7 @@ static int msm_chunks_per_block(size_t B) {
 // is launched in z-pieces by msm_window_launch.
 static KzgRet msm_save_reserve(const KzgSettings* s, unsigned gx, unsigned gy, unsigned gz) {
     Workspace& w = s->ws;
-    const size_t layer = msm_save_layer_bytes(gx, gy, fp29_enabled() ? MSM_SAVE2_WORDS : Curve32::WORDS);  // (the larger of the forms' point sizes)
+    const size_t layer = msm_save_layer_bytes(gx, gy, MSM_SAVE2_WORDS);  // (the larger of the forms' point sizes)
     const size_t want = std::max(layer, std::min(layer * gz, (size_t)512 << 20));
     if (want > w.cap_msm_save) {
         if (w.d_msm_save) (void)hipFree(w.d_msm_save);
@@ -242,11 +215,7 @@ static KzgRet run_msm(const KzgSettings* s, size_t n, size_t B) {
     if (d.chunks != MSM_CHUNKS && S == 1 && n >= 256 && B <= 4) S = latency_slices;
     // ... and until a block's sorted term list fits in LDS (msm.hpp LDSSORT): the global list costs a line of HBM write
     // traffic per 4-byte entry once the launch outgrows the L2
-#if KZG_AB_VARIANTS
-    const size_t lds_cap = fp29_enabled() ? msm_lds_sort_capacity<Curve29>() : msm_lds_sort_capacity<Curve32>();
-#else
     const size_t lds_cap = msm_lds_sort_capacity<Curve29>();
-#endif
     auto slice_terms = [&](unsigned S_) { return ((size_t)mt + S_ - 1) / S_ * (size_t)d.chunks_per_block; };
     while (S < MSM_MAX_SLICES && slice_terms(S) > lds_cap && n / (2 * S) >= 1024 && 2 * S * B <= 128) S *= 2;  // (d_window_sl holds S B <= 128 slice sets)
     const bool lds_sort = slice_terms(S) + 1 <= lds_cap;  // (+1: slice boundaries round either way)
@@ -261,7 +230,7 @@ static KzgRet run_msm(const KzgSettings* s, size_t n, size_t B) {
     if (w.mult_affine) {
         if (lds_sort) msm_window_launch<Curve29Aff, true>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
         else msm_window_launch<Curve29Aff, false>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-    } else if (fp29_enabled()) {
+    } else {
         // the latency layout's few workgroups run their reduction trees with four lanes per addition (option msm_tree_quads=0: A/B)
         static const bool tree_quads = ab_flag("msm_tree_quads", true);
         if (tree_quads && d.chunks != MSM_CHUNKS && B <= 4) {
@@ -270,16 +239,10 @@ static KzgRet run_msm(const KzgSettings* s, size_t n, size_t B) {
         } else if (lds_sort) msm_window_launch<Curve29, true>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
         else msm_window_launch<Curve29, false>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
     }
-#if KZG_AB_VARIANTS
-    else {
-        if (lds_sort) msm_window_launch<Curve32, true>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-        else msm_window_launch<Curve32, false>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-    }
-#endif
     // the latency layout (one window per chunk) of a few batches: every output is the plain sum of its slots x slices window
     // sums - one workgroup per output, four lanes per addition (option msm_sum_quads=0: the fold + combine kernels, A/B)
     static const bool sum_quads = ab_flag("msm_sum_quads", true);
-    if (sum_quads && W == 1 && fp29_enabled() && slots * S >= 2 && slots * S <= (unsigned)SUMQ_MAX_POINTS && 2 * B < 64) {
+    if (sum_quads && W == 1 && slots * S >= 2 && slots * S <= (unsigned)SUMQ_MAX_POINTS && 2 * B < 64) {
         HIPCHK(DYN_LDS(k_msm_sum_quads, SUMQ_LDS_BYTES));
         hipLaunchKernelGGL(k_msm_sum_quads, dim3((unsigned)(2 * B)), dim3(256), SUMQ_LDS_BYTES, s->s1, d.window_sums, w.d_ab, (int)(slots * S));
         HIPCHK(hipGetLastError());
@@ -304,15 +267,10 @@ static KzgRet launch_decode(const KzgSettings* s, const void* d_commitments, con
     const int np = (int)(2 * T + 1);
     unsigned blocks = (unsigned)((2 * T + 63) / 64);
     static const bool no_latency_layout = !ab_flag("msm_latency_layout", true);
-#if KZG_AB_VARIANTS
-    static const bool proofs_16 = opt_int("proofs_chunks", 0) == 16;  // (A/B measurement: round 1's sixteen 16-bit chunks for the proof-tuple entries)
-#else
-    constexpr bool proofs_16 = false;
-#endif
-    w.chunks = (T <= LATENCY_MAX_BLOBS && !no_latency_layout) ? ((behind_sha || !proofs_16) ? MSM_CHUNKS_LATENCY : MSM_CHUNKS_PROOFS) : MSM_CHUNKS;
+    w.chunks = (T <= LATENCY_MAX_BLOBS && !no_latency_layout) ? MSM_CHUNKS_LATENCY : MSM_CHUNKS;
     const uint8_t *c = (const uint8_t*)d_commitments, *p = (const uint8_t*)d_proofs;
     const int n2 = (int)(2 * T);
-    const size_t gen_off = w.chunks == MSM_CHUNKS ? 0 : w.chunks == MSM_CHUNKS_LATENCY ? MSM_CHUNKS : MSM_CHUNKS + MSM_CHUNKS_LATENCY;
+    const size_t gen_off = w.chunks == MSM_CHUNKS ? 0 : MSM_CHUNKS;
     w.mult_affine = msm_affine_enabled() && w.chunks == MSM_CHUNKS;
     if (w.mult_affine) {
         // affine tables: rows 0 and 2 straight from the decode pass, rows 1 and 3 from 2^64 P through one inversion per 16 points
@@ -325,7 +283,7 @@ static KzgRet launch_decode(const KzgSettings* s, const void* d_commitments, con
         HIPCHK(hipEventRecord(s->ev[10], s->s2));
         hipLaunchKernelGGL(k_set_generator_multiples<G1Aff29Mem>, dim3(1), dim3(64), 0, s->s2, w.d_points, w.d_pflag, mult,
                            (const G1Aff29Mem*)s->d_gen_mult_aff, n2, np, w.chunks);
-    } else if (fp29_enabled()) {
+    } else {
         G1Jac29Mem* mult = (G1Jac29Mem*)w.d_mult;
         // (the generator's rows first: behind the decode kernel they would sit on the critical path of a proof-tuple call)
         hipLaunchKernelGGL(k_set_generator_multiples<G1Jac29Mem>, dim3(1), dim3(64), 0, s->s2, w.d_points, w.d_pflag, mult,
@@ -336,40 +294,14 @@ static KzgRet launch_decode(const KzgSettings* s, const void* d_commitments, con
         // chain anyway and has only half the CUs)
         if (dec_quads && w.chunks != MSM_CHUNKS && !behind_sha && (2 * T + DECQ_POINTS_PER_BLOCK - 1) / DECQ_POINTS_PER_BLOCK <= (size_t)s->n_cus) {
             blocks = (unsigned)((2 * T + DECQ_POINTS_PER_BLOCK - 1) / DECQ_POINTS_PER_BLOCK);
-#if KZG_AB_VARIANTS
-            if (w.chunks != MSM_CHUNKS_LATENCY) {
-                HIPCHK(DYN_LDS(k_g1_decode_multiples29_quads<MSM_CHUNKS_PROOFS>, DECQ_LDS_BYTES));
-                hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_PROOFS>, dim3(blocks), dim3(64), DECQ_LDS_BYTES, s->s2, c, p, (int)T, w.d_points, w.d_pflag, mult, n2, np);
-            } else
-#endif
-            {
-                HIPCHK(DYN_LDS(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, DECQ_LDS_BYTES));
-                hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, dim3(blocks), dim3(64), DECQ_LDS_BYTES, s->s2, c, p, (int)T, w.d_points, w.d_pflag, mult, n2, np);
-            }
+            HIPCHK(DYN_LDS(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, DECQ_LDS_BYTES));
+            hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, dim3(blocks), dim3(64), DECQ_LDS_BYTES, s->s2, c, p, (int)T, w.d_points, w.d_pflag, mult, n2, np);
         } else if (w.chunks == MSM_CHUNKS_LATENCY)
             hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS_LATENCY, false>), dim3(blocks), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, n2, np);
-#if KZG_AB_VARIANTS
-        else if (w.chunks == MSM_CHUNKS_PROOFS)
-            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS_PROOFS, false>), dim3(blocks), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, n2, np);
-#endif
         else
             hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3(blocks), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, n2, np);
         HIPCHK(hipEventRecord(s->ev[10], s->s2));
     }
-#if KZG_AB_VARIANTS
-    else {
-        G1Jac* mult = (G1Jac*)w.d_mult;
-        if (w.chunks == MSM_CHUNKS_LATENCY)
-            hipLaunchKernelGGL(k_g1_decode_multiples<MSM_CHUNKS_LATENCY>, dim3(blocks), dim3(64), 0, s->s2, c, p, (int)T, w.d_points, w.d_pflag, mult, n2, np);
-        else if (w.chunks == MSM_CHUNKS_PROOFS)
-            hipLaunchKernelGGL(k_g1_decode_multiples<MSM_CHUNKS_PROOFS>, dim3(blocks), dim3(64), 0, s->s2, c, p, (int)T, w.d_points, w.d_pflag, mult, n2, np);
-        else
-            hipLaunchKernelGGL(k_g1_decode_multiples<MSM_CHUNKS>, dim3(blocks), dim3(64), 0, s->s2, c, p, (int)T, w.d_points, w.d_pflag, mult, n2, np);
-        HIPCHK(hipEventRecord(s->ev[10], s->s2));
-        hipLaunchKernelGGL(k_set_generator_multiples<G1Jac>, dim3(1), dim3(64), 0, s->s2, w.d_points, w.d_pflag, mult,
-                           (const G1Jac*)s->d_gen_mult + gen_off, n2, np, w.chunks);
-    }
-#endif
     HIPCHK(hipGetLastError());
     return KZG_OK;
 }

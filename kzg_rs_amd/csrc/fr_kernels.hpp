@@ -32,9 +32,6 @@
 
 namespace kzg {
 
-#ifndef KZG_AB_VARIANTS
-#define KZG_AB_VARIANTS 0
-#endif
 constexpr int FE_PER_BLOB = 4096;
 constexpr int BLOB_BYTES = 131072;
 
@@ -99,10 +96,12 @@ __device__ __forceinline__ void bswap4(uint32_t* w, const uint4& q) {
 // own execution interval, which a HIP-event pair around the launch cannot give while other launch groups share the chip
 // (the events also time the wait for free CUs); { sum of shader cycles (s_memtime), sum of reference ticks } over the waves in
 // ktime[2..3]: the shader clock the kernel ran at while the other kernels of the pipeline shared the chip.  Zeroed by the host
-// before the launch.
+// before the launch.  WAVES = 4 is the only form (launch_challenge); the parameter keeps the kernel's name that profiles and
+// tests look up.
 template <int WAVES>
 __global__ __launch_bounds__(256, WAVES) void k_blob_challenge_t(const uint8_t* __restrict__ blobs, const uint8_t* __restrict__ commitments,
                                                                 Fr* __restrict__ z_out, int n, unsigned long long* __restrict__ ktime) {
+    static_assert(WAVES == 4, "k_blob_challenge_t has one form");
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const bool stamp = ktime && (threadIdx.x & 63) == 0;
@@ -443,95 +442,10 @@ __device__ __forceinline__ Fr fr_shfl_xor(const Fr& a, int mask) {
     return r;
 }
 
-#if KZG_AB_VARIANTS  // (the 8x32 form of the evaluation: A/B build only, option evaluate_kernel=32)
-
-// z_in: plain little-endian limbs (any value < 2^256; reduced mod r here, like scalar_from_bytes_unchecked)
-// y_out: plain little-endian canonical limbs.  status[b] |= 1 when a blob element is >= r
-// (src/kzg_proof.rs:36-41 -> KzgError::BadArgs).
-__global__ __launch_bounds__(64, 4) void k_blob_evaluate32(const uint8_t* __restrict__ blobs, const Fr* __restrict__ z_in,
-                                                      const Fr* __restrict__ M, const Fr* __restrict__ DM,
-                                                      Fr* __restrict__ y_out, uint32_t* __restrict__ status) {
-    const int blob_idx = blockIdx.x;
-    const int lane = threadIdx.x;
-    __shared__ Fr Z[14];              // Z[L] = z^(2^L), Montgomery; Z[13] = z R^2 (takes plain operands)
-    __shared__ uint4 stack[6][2][64]; // levels 1..6, two 16-byte halves, lane-major: conflict-free b128
-    if (lane == 0) {
-        Fr z = FrF::to_mont(z_in[blob_idx]);
-        Fr r2;
-#pragma unroll
-        for (int i = 0; i < 8; i++) r2.l[i] = consts::FR_R2[i];
-        Z[0] = z;
-        Z[13] = FrF::mul(z, r2);
-        for (int l = 1; l <= 12; l++) {
-            z = FrF::sqr(z);
-            Z[l] = z;
-        }
-    }
-    __syncthreads();
-    const uint4* src = reinterpret_cast<const uint4*>(blobs + (size_t)blob_idx * BLOB_BYTES) + (size_t)lane * 128;
-    const Fr zd = Z[13];
-    bool bad = false;
-    Fr n, psum = FrF::zero();  // psum: this lane's share of S = sum_i p_i (plain)
-    for (int q = 0; q < 32; q++) {
-        uint4 a_hi = src[4 * q], a_lo = src[4 * q + 1], b_hi = src[4 * q + 2], b_lo = src[4 * q + 3];
-        Fr pa = fr_from_be_words(a_hi, a_lo), pb = fr_from_be_words(b_hi, b_lo);
-        bad |= FrF::geq_mod(pa) | FrF::geq_mod(pb);
-        Fr u = FrF::sub(pa, pb), s = FrF::add(pa, pb);
-        int k = 32 * lane + q;  // level-1 node index
-        psum = FrF::add(psum, s);
-        n = FrF::add(FrF::mul(zd, s), FrF::mul(DM[2 * k], u));  // z s + roots[2k] u, Montgomery
-        int level = 1;
-        for (int qq = q; qq & 1; qq >>= 1) {
-            Fr na;
-            uint4 h0 = stack[level - 1][0][lane], h1 = stack[level - 1][1][lane];
-            na.l[0] = h0.x; na.l[1] = h0.y; na.l[2] = h0.z; na.l[3] = h0.w;
-            na.l[4] = h1.x; na.l[5] = h1.y; na.l[6] = h1.z; na.l[7] = h1.w;
-            Fr sum = FrF::add(na, n), dif = FrF::sub(na, n);
-            n = FrF::add(FrF::mul(Z[level], sum), FrF::mul(M[k & ~1], dif));
-            k >>= 1;
-            level++;
-        }
-        if (level <= 6 && q != 31) {
-            stack[level - 1][0][lane] = make_uint4(n.l[0], n.l[1], n.l[2], n.l[3]);
-            stack[level - 1][1][lane] = make_uint4(n.l[4], n.l[5], n.l[6], n.l[7]);
-        }
-    }
-    // n = N_{6,lane}; fold across lanes
-    for (int L = 6; L < 12; L++) {
-        int sh = L - 6;
-        Fr other = fr_shfl_xor(n, 1 << sh);
-        int j = lane >> sh;  // node index at level L
-        bool left = (j & 1) == 0;
-        Fr na, nb;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            na.l[i] = left ? n.l[i] : other.l[i];
-            nb.l[i] = left ? other.l[i] : n.l[i];
-        }
-        Fr sum = FrF::add(na, nb), dif = FrF::sub(na, nb);
-        n = FrF::add(FrF::mul(Z[L], sum), FrF::mul(M[j & ~1], dif));
-    }
-    for (int sh = 1; sh < 64; sh <<= 1) psum = FrF::add(psum, fr_shfl_xor(psum, sh));
-    unsigned long long any_bad = __ballot(bad);
-    if (lane == 0) {
-        Fr inv;
-#pragma unroll
-        for (int i = 0; i < 8; i++) inv.l[i] = consts::FR_INV4096_PLAIN[i];
-        // N = z N0 - (z^4096 - 1) S;  mul(Z[13], S) = z S R, so (z^4096 - 1) S R = Z_12 S R - S R with S R = to_mont(S)
-        Fr sm = FrF::to_mont(psum);
-        Fr nn = FrF::sub(FrF::mul(n, Z[0]), FrF::sub(FrF::mul(Z[12], sm), sm));
-        y_out[blob_idx] = FrF::mul(nn, inv);  // (N R)(1/4096) R^-1 = N/4096, plain
-        if (any_bad) atomicOr(&status[blob_idx], 1u);
-    }
-}
-
-#endif  // KZG_AB_VARIANTS
-
 // ---------------------------------------------------------------- evaluation in radix 2^29 (fr29.hpp)
-// The same tree as k_blob_evaluate32 with every field element in 9 x 29-bit limbs: products accumulate a whole
-// column in one 64-bit register without carry instructions, additions are limb-wise and nothing is reduced inside
-// the tree (value and limb bounds: fr29.hpp), and the two products of a merge share one Montgomery reduction.
-// ~0.45x the VALU cycles of the 8x32 form.
+// The tree of the header comment with every field element in 9 x 29-bit limbs: products accumulate a whole column in one 64-bit register
+// without carry instructions, additions are limb-wise and nothing is reduced inside the tree (value and limb bounds:
+// fr29.hpp), and the two products of a merge share one Montgomery reduction.  ~0.45x the VALU cycles of an 8x32 form.
 struct alignas(16) Fr29Mem {  // table entry: 9 limbs padded to 48 bytes (two b128 loads + one b32)
     uint32_t l[12];
 };
@@ -660,13 +574,14 @@ __global__ __launch_bounds__(64) void k_eval_finish(const uint32_t* __restrict__
 // wait counters turn the prefetches into stalls - three waves per SIMD were 2 % slower than two with working prefetches.
 constexpr int EVAL_BLOBS_PER_BLOCK = 4;
 constexpr int EVAL_SPREAD_LDS = 96 * 1024;  // dynamic LDS nobody touches: with it a CU holds ONE workgroup (launch_evaluate)
-// SPLIT = true (round 4, the product's form): three wavefronts per SIMD - 166 VGPRs, no scratch - by (i) buffer descriptors
-// instead of 64-bit address pairs, (ii) a line that is live once instead of twice (see the loop).  SPLIT = false is round 3's
-// kernel (192 VGPRs, two wavefronts per SIMD), kept in the A/B build (option evaluate_kernel=r3) for measurement.
+// Round 4's form: three wavefronts per SIMD - 166 VGPRs, no scratch - by (i) buffer descriptors instead of 64-bit address
+// pairs, (ii) a line that is live once instead of twice (see the loop).  (Round 3's kernel took 192 VGPRs, two wavefronts
+// per SIMD.)  SPLIT = true is the only form; the parameter keeps the kernel's name that profiles and tests look up.
 template <bool SPLIT>
-__global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_blob_evaluate_t(const uint8_t* __restrict__ blobs, const EvalTables tab,
+__global__ __launch_bounds__(256, 3) void k_blob_evaluate_t(const uint8_t* __restrict__ blobs, const EvalTables tab,
                                                        uint32_t* __restrict__ scratch, uint32_t* __restrict__ status, int T,
                                                        unsigned long long* __restrict__ ktime) {
+    static_assert(SPLIT, "k_blob_evaluate_t has one form");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int blob_idx = blockIdx.x * EVAL_BLOBS_PER_BLOCK + wave;
     const bool active = blob_idx < T;
@@ -680,10 +595,9 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_blob_evaluate_t(const ui
     kstamp_in(ktime);
     // (the wavefront's blob index is uniform, but derived from threadIdx: readfirstlane makes that provable - the blob's
     // addresses then live in scalar registers, and a buffer operation is not wrapped in a waterfall loop)
-    const int blob_u = SPLIT ? __builtin_amdgcn_readfirstlane(blob_idx) : blob_idx;
+    const int blob_u = __builtin_amdgcn_readfirstlane(blob_idx);
     uint32_t* const my = scratch + (size_t)blob_u * EVAL_SCRATCH_WORDS;
     for (int i = lane; i < 14 * 9; i += 64) reinterpret_cast<uint32_t*>(Z)[i] = my[i];
-    const uint4* src = reinterpret_cast<const uint4*>(blobs + (size_t)blob_idx * BLOB_BYTES) + (size_t)lane * 128;
     const Fr29 zd = Z[13];
     bool bad = false;
     Fr29 n, psum;  // psum: this lane's share of S = sum_i p_i (plain integer, < 64 r)
@@ -695,7 +609,6 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_blob_evaluate_t(const ui
     // the root entry of the next merge are requested one product ahead of their use (three waves per SIMD do not hide an
     // L2 / HBM round trip by themselves).
     uint4 cur[8];
-    if constexpr (SPLIT) {
     const __amdgpu_buffer_rsrc_t rs_blob = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(blobs) + (size_t)blob_u * BLOB_BYTES, 0, BLOB_BYTES, 0x00020000);
     EvalRsrc rs;
     rs.a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(tab.a), 0, EVAL_SLOTS * 64 * 16, 0x00020000);
@@ -769,60 +682,6 @@ __global__ __launch_bounds__(256, SPLIT ? 3 : 2) void k_blob_evaluate_t(const ui
             stack_b[level - 2][lane] = make_uint4(n.l[4], n.l[5], n.l[6], n.l[7]);
             stack_c[level - 2][lane] = n.l[8];
         }
-    }
-    } else {
-#pragma unroll
-    for (int i = 0; i < 8; i++) cur[i] = src[i];
-    Fr29 leaf0 = eval_table_load(tab, 0, lane), leaf1 = eval_table_load(tab, 1, lane);
-    auto leaf_pair = [&](const uint4& a_hi, const uint4& a_lo, const uint4& b_hi, const uint4& b_lo, const Fr29& w) {
-        Fr wa = fr_from_be_words(a_hi, a_lo), wb = fr_from_be_words(b_hi, b_lo);
-        // canonical check (>= r -> BadArgs): the full 8-limb compare only when some lane's top word reaches r's
-        if (__any((wa.l[7] >= consts::FR_MOD[7]) | (wb.l[7] >= consts::FR_MOD[7]))) bad |= FrF::geq_mod(wa) | FrF::geq_mod(wb);
-        const Fr29 pa = fr29_from_words(wa.l), pb = fr29_from_words(wb.l);
-        const Fr29 s = fr29_add(pa, pb), u = fr29_sub_biased4(pa, pb);
-        psum = fr29_add(psum, s);
-        return fr29_mul2(s, zd, u, w);  // z s + roots[2k] u, k = 32 lane + q: ONE reduction (fr29.hpp)
-    };
-    for (int j = 0; j < 16; j++) {  // pairs q = 2j, 2j + 1
-        const int jn = j < 15 ? j + 1 : 15;
-        // Loads complete in issue order (one vmcnt counter): what this iteration needs is requested first, what the next
-        // one needs last, and no load sits in a branch (a control-flow merge makes the wait counters conservative).
-        Fr29 root = eval_table_load(tab, 32 + j, lane);             // the level-1 merge of the two pairs
-        Fr29 root_next = eval_table_load(tab, 48 + (j >> 1), lane);  // the level-2 merge that follows when j is odd
-        __builtin_amdgcn_sched_barrier(0x7);
-        uint4 nxt[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) nxt[i] = src[8 * jn + i];
-        const Fr29 leaf0_next = eval_table_load(tab, 2 * jn, lane), leaf1_next = eval_table_load(tab, 2 * jn + 1, lane);
-        __builtin_amdgcn_sched_barrier(0x7);
-        const Fr29 n0 = leaf_pair(cur[0], cur[1], cur[2], cur[3], leaf0);
-        const Fr29 n1 = leaf_pair(cur[4], cur[5], cur[6], cur[7], leaf1);
-        psum = fr29_normalize(psum);  // limbs: 2^29 + 2 * 2^30 < 2^32 between normalisations
-        n = fr29_mul2(fr29_add(n0, n1), Z[1], fr29_sub_biased4(n0, n1), root);
-        root = root_next;
-        int level = 2;  // level of the merge that may follow: node index at level L is (32 lane + 2j + 1) >> L
-        for (int jj = j; jj & 1; jj >>= 1) {
-            Fr29 na;
-            const uint4 h0 = stack_a[level - 2][lane], h1 = stack_b[level - 2][lane];
-            na.l[0] = h0.x; na.l[1] = h0.y; na.l[2] = h0.z; na.l[3] = h0.w;
-            na.l[4] = h1.x; na.l[5] = h1.y; na.l[6] = h1.z; na.l[7] = h1.w;
-            na.l[8] = stack_c[level - 2][lane];
-            root_next = eval_table_load(tab, 64 - (32 >> level) + (j >> level), lane);  // for the merge one level up, if it follows (always a valid slot)
-            const Fr29 sum = fr29_add(na, n), dif = fr29_sub_biased4(na, n);
-            n = fr29_mul2(sum, Z[level], dif, root);
-            root = root_next;
-            level++;
-        }
-        if (j != 15) {  // level <= 5 here
-            stack_a[level - 2][lane] = make_uint4(n.l[0], n.l[1], n.l[2], n.l[3]);
-            stack_b[level - 2][lane] = make_uint4(n.l[4], n.l[5], n.l[6], n.l[7]);
-            stack_c[level - 2][lane] = n.l[8];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) cur[i] = nxt[i];
-        leaf0 = leaf0_next;
-        leaf1 = leaf1_next;
-    }
     }
     // n = N0_{6,lane}; fold across lanes
     for (int L = 6; L < 12; L++) {

@@ -89,7 +89,7 @@ __global__ void k_finish_g(const Fr* __restrict__ partial, int nparts, Fr* __res
 //     k P = k1_lo P + k1_hi (2^64 P) + k2_lo (-phi P) + k2_hi (-phi(2^64 P)).
 // mult[0..3][p] = P, 2^64 P, -phi(P), -phi(2^64 P) (Jacobian): 64 doublings + 2 multiplications per point, which
 // depend only on the INPUT points.  On the verification path they come out of the decode pass for free
-// (k_g1_decode_multiples below shares the doubling chain with the subgroup test, beside the SHA-256 challenge chain);
+// (k_g1_decode_multiples29 below shares the doubling chain with the subgroup test, beside the SHA-256 challenge chain);
 // k_g1_multiples is the stand-alone form for points that are already decoded (the generator, kzg_g1_msm).
 // Points must lie in G1 (all callers decode with the subgroup check).
 //
@@ -102,8 +102,6 @@ __global__ void k_finish_g(const Fr* __restrict__ partial, int nparts, Fr* __res
 // the combine, ~0.1 ms of a single batch.)
 constexpr int MSM_CHUNKS = 4;
 constexpr int MSM_CHUNKS_LATENCY = 32;
-constexpr int MSM_CHUNKS_PROOFS = 16;  // the proof-tuple entry points have no SHA-256 chain to hide the decode pass behind: 16-bit
-                                       // chunks (two windows each, 8 doublings in the combine) keep that pass 0.6 ms shorter
 constexpr int MSM_ENTRY_CHUNK_SHIFT = 27;  // a sorted-list entry: chunk << 27 | point index
 constexpr uint32_t MSM_ENTRY_POINT_MASK = (1u << MSM_ENTRY_CHUNK_SHIFT) - 1;
 __device__ __forceinline__ G1Jac g1_neg_phi(const G1Jac& p) {
@@ -128,47 +126,16 @@ __global__ __launch_bounds__(64, 4) void k_g1_multiples(const G1Aff* __restrict_
     }
 }
 
-// Decode + subgroup check + multiples in one pass: the subgroup test's first scalar multiplication walks the same
-// doubling chain that produces 2^64 P (g1.hpp g1_in_subgroup_with_multiple), which saves the 64 doublings of a
-// separate k_g1_multiples pass.  bytes0 holds points [0, n0), bytes1 points [n0, n).
-template <int CHUNKS>
-__global__ __launch_bounds__(64, 2) void k_g1_decode_multiples(const uint8_t* __restrict__ bytes0, const uint8_t* __restrict__ bytes1,
-                                                               int n0, G1Aff* __restrict__ points, uint32_t* __restrict__ pflag,
-                                                               G1Jac* __restrict__ mult, int n, int stride) {
-    constexpr int HALF = CHUNKS / 2, STEP = 256 / CHUNKS;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint8_t* src = i < n0 ? bytes0 + (size_t)i * 48 : bytes1 + (size_t)(i - n0) * 48;
-    G1Aff a;
-    uint32_t st = g1_decompress(a, src, false);
-    if (st == G1_OK) {
-        const G1Jac p = g1_from_affine(a);
-        mult[i] = p;
-        mult[(size_t)HALF * stride + i] = g1_neg_phi(p);
-        const bool in = g1_in_subgroup_with_multiples<STEP>(a, [&](int k, const G1Jac& m) {
-            mult[(size_t)k * stride + i] = m;
-            mult[(size_t)(HALF + k) * stride + i] = g1_neg_phi(m);
-        });
-        if (!in) st = G1_INVALID;
-    }
-    if (st != G1_OK) {
-        a.x = FpF::zero();
-        a.y = FpF::zero();
-        const G1Jac id = g1_identity();
-        for (int k = 0; k < CHUNKS; k++) mult[(size_t)k * stride + i] = id;
-    }
-    points[i] = a;
-    pflag[i] = st;
-}
-
 // diagnostic (tools/prof/decode_placement.py): where the first wavefront of the last latency decode ran, and for how long
 __device__ unsigned long long g_decode_dbg[4];  // HW_ID | XCC_ID | shader cycles | wall-clock ticks (100 MHz)
 
 #ifndef KZG_DECODE_OCC
 #define KZG_DECODE_OCC 2
 #endif
-// The same pass in the radix-2^29 field (fp29.hpp, g1_29.hpp): tables written as G1Jac29Mem (lazy values), the affine
-// point as a canonical 12x32 element like the kernel above.
+// Decode + subgroup check + multiples in one pass, in the radix-2^29 field (fp29.hpp, g1_29.hpp): the subgroup test's first
+// scalar multiplication walks the same doubling chain that produces the multiples, which saves the doublings of a separate
+// k_g1_multiples pass.  bytes0 holds points [0, n0), bytes1 points [n0, n).  Tables are written as G1Jac29Mem (lazy values),
+// the affine point as a canonical 12x32 element.
 // AFF (CHUNKS = 4 only): the AFFINE table layout of the throughput path.  P and -phi(P) are affine as they are; the one
 // Jacobian multiple 2^64 P goes to jtmp[i] and k_mult_to_affine29 below turns it into table rows 1 and 3, so that the
 // window kernel's bucket additions are mixed additions (8M + 3S instead of 12M + 4S).
@@ -349,7 +316,7 @@ __global__ __launch_bounds__(256) void k_glv_split(Fr* __restrict__ scalars, int
 //   term_point[o][t], term_scalar[o][t]  (indices into points[] / scalars[]); nterms[o].
 // pflag[p] != 0 marks the identity / an invalid point (skipped).
 struct MsmDesc {
-    const void* mult;             // [chunks][stride] precomputed multiples: G1Jac (Curve32) or G1Jac29Mem (Curve29)
+    const void* mult;             // [chunks][stride] precomputed multiples: G1Jac29Mem (Curve29) or G1Aff29Mem (Curve29Aff)
     const uint32_t* pflag;
     const Fr* scalars;            // plain little-endian limbs
     const uint32_t* term_point;   // [2][max_terms]
@@ -740,31 +707,13 @@ __device__ __forceinline__ G1Jac29 lds_load_jac29(const uint32_t* base, int slot
     return p;
 }
 
-// The window kernel is written once over a curve policy: Curve29 (radix-2^29 field, lazy reduction: the default) or
-// Curve32 (the 12x32 field of field.hpp; KZG_FP29=0, kept for A/B measurement and as a cross-check).
-struct Curve32 {
-    using Pt = G1Jac;
-    using Mem = G1Jac;
-    using Entry = G1Jac;
-    static constexpr int WORDS = 36;
-    static constexpr bool SPLIT = false;  // the 12x32 A/B variant keeps the complete formulas in its loops
-    static constexpr bool QUADS = false;
-    __device__ static __forceinline__ Pt add_entry(const Pt& a, const Entry& b) { return g1_add(a, b); }
-    __device__ static __forceinline__ Pt identity() { return g1_identity(); }
-    __device__ static __forceinline__ Pt add(const Pt& a, const Pt& b) { return g1_add(a, b); }
-    __device__ static __forceinline__ Pt dbl(const Pt& a) { return g1_dbl(a); }
-    __device__ static __forceinline__ Pt load(const Mem& m) { return m; }
-    __device__ static __forceinline__ void lds_store(uint32_t* b, int s, const Pt& p) { lds_store_jac(b, s, p); }
-    __device__ static __forceinline__ Pt lds_load(const uint32_t* b, int s) { return lds_load_jac(b, s); }
-    __device__ static __forceinline__ G1Jac to_std(const Pt& p) { return p; }
-};
+// The window kernel is written once over a curve policy: Curve29 (radix-2^29 field, lazy reduction) and its variants below.
+// The additions of its loops run in two halves (g1_29_formulas.hpp): entry_special(head) -> the pair needs the complete formula.
 struct Curve29 {
     using Pt = G1Jac29;
     using Mem = G1Jac29Mem;
     using Entry = G1Jac29;
     static constexpr int WORDS = 42;
-    // the additions of the loops in two halves (g1_29_formulas.hpp): special(h) -> the pair needs the complete formula
-    static constexpr bool SPLIT = true;
     static constexpr bool QUADS = false;  // reduction trees with four lanes per addition (Curve29Quads)
     using EntryHead = G1AddHead;
     // (accumulator and table entries are finite in the bucket loop; an accumulator that a P - P turned into the identity
@@ -844,14 +793,14 @@ __device__ __forceinline__ G1Jac29 g1j29_add_fast(const G1Jac29& x, const G1Jac2
         return g1j29_add_tail(h);
     }
 }
-// TWO PASSES (round 3; the radix-2^29 throughput variants - every CV with SPLIT and without QUADS): the window kernel ends
+// TWO PASSES (round 3; the throughput variants - every CV without QUADS): the window kernel ends
 // with the bucket sums, written to the save area, and k_msm_reduce turns them into the window sum.  In one kernel the 16
 // levels of the reduction ran on one or two of a block's four wavefronts while the block held its 43 KB of LDS - a third
 // of a block's life at a quarter of its lanes (SIMD utilisation of the kernel 58 %: profiles/r2_pmc.json, 7.4 cycles per
 // instruction against 4.3); as a kernel of its own the reduction needs no LDS and no barrier, half the additions, and the
 // bucket kernel's blocks leave as soon as their longest bucket is done.
 template <class CV>
-constexpr bool msm_two_pass() { return CV::SPLIT && !CV::QUADS; }
+constexpr bool msm_two_pass() { return !CV::QUADS; }
 template <class CV, bool LDSSORT = false>
 __global__ __launch_bounds__(256, CV::QUADS ? 1 : KZG_MSM_OCC) void k_msm_window(MsmDesc d) {  // (the latency variant has a CU to itself)
     using Pt = typename CV::Pt;
@@ -1001,7 +950,7 @@ __global__ __launch_bounds__(256, CV::QUADS ? 1 : KZG_MSM_OCC) void k_msm_window
         put(bucket, accumulate(bucket > 0 ? off[bucket] : 0u, bucket > 0 ? off[bucket + 1] : 0u));
         kstamp_out(d.ktime);
         return;
-    } else if constexpr (CV::SPLIT) {
+    } else {
         // (the latency variant: Curve29Quads) the same loop with the long buckets' tails left to the quads
         uint32_t k = bucket > 0 ? off[bucket] : 0u, w = k;
         const uint32_t kend_all = bucket > 0 ? off[bucket + 1] : 0u;
@@ -1031,11 +980,6 @@ __global__ __launch_bounds__(256, CV::QUADS ? 1 : KZG_MSM_OCC) void k_msm_window
                     for (uint32_t j = kend; j < kend_all; j++) sorted_global[j] = lst[j];
                 long_buckets[atomicAdd(&n_long, 1u)] = (uint32_t)bucket;
             }
-        }
-    } else if (bucket > 0) {
-        for (uint32_t k = off[bucket]; k < off[bucket + 1]; k++) {
-            const uint32_t e = sorted_at(k);
-            acc = CV::add_entry(acc, CV::load(mult[(size_t)(e >> MSM_ENTRY_CHUNK_SHIFT) * d.stride + (e & MSM_ENTRY_POINT_MASK)]));
         }
     }
     // 3. sum_b b*B_b with b = 16 hi + lo:   16 * sum_hi hi*R_hi + sum_lo lo*C_lo,
@@ -1155,22 +1099,18 @@ __global__ __launch_bounds__(256, CV::QUADS ? 1 : KZG_MSM_OCC) void k_msm_window
             y = CV::lds_load(arr, src);
         }
         __syncthreads();  // scan levels read a slot that its owner rewrites in the same level
-        if constexpr (CV::SPLIT) {
-            // every path ends in its own store: no point value is merged across the paths (see the bucket loop)
-            if (active) {
-                Fp29 Z1Z1, Z2Z2;
-                bool p_inf, q_inf;
-                g1j29_inf_flags(x, y, Z1Z1, Z2Z2, p_inf, q_inf);
-                if (p_inf | q_inf) {
-                    CV::lds_store(arr, dst, p_inf ? y : x);  // empty buckets: common in small batches
-                } else {
-                    const G1AddHead h = g1j29_add_head(x, y, Z1Z1, Z2Z2);  // x and y are dead from here
-                    if (g1j29_add_same_x(h)) CV::lds_store(arr, dst, g1j29_add_same_x_result(h));
-                    else CV::lds_store(arr, dst, g1j29_add_tail(h));
-                }
+        // every path ends in its own store: no point value is merged across the paths (see the bucket loop)
+        if (active) {
+            Fp29 Z1Z1, Z2Z2;
+            bool p_inf, q_inf;
+            g1j29_inf_flags(x, y, Z1Z1, Z2Z2, p_inf, q_inf);
+            if (p_inf | q_inf) {
+                CV::lds_store(arr, dst, p_inf ? y : x);  // empty buckets: common in small batches
+            } else {
+                const G1AddHead h = g1j29_add_head(x, y, Z1Z1, Z2Z2);  // x and y are dead from here
+                if (g1j29_add_same_x(h)) CV::lds_store(arr, dst, g1j29_add_same_x_result(h));
+                else CV::lds_store(arr, dst, g1j29_add_tail(h));
             }
-        } else {
-            if (active) CV::lds_store(arr, dst, CV::add(x, y));
         }
         __syncthreads();
     }

@@ -362,15 +362,12 @@ def test_challenge_kernel_forms(form):
 
 @pytest.mark.parametrize("opts", [
     "msm_latency_layout=0",               # small batches through the throughput layout: affine tables, mixed additions
-    "msm_latency_layout=0;msm_affine=0",  # ... with Jacobian tables in the radix-2^29 field
-    "fp29=0",                             # point kernels in the 12x32 field            (A/B build only)
-    "evaluate_kernel=32",                 # evaluation in the 8x32 field                (A/B build only)
-    "proofs_chunks=16",                   # sixteen 16-bit chunks for the proof tuples  (A/B build only)
-], ids=["affine-tables", "jacobian29-tables", "fp-12x32", "fr-8x32", "proofs-16"])
+    "msm_latency_layout=0;msm_affine=0",  # ... with Jacobian tables
+], ids=["affine-tables", "jacobian29-tables"])
 def test_kernel_variants_differential_fuzz(opts):
-    """The alternative forms of the point and evaluation kernels (each selected for a whole process through KZG_OPTIONS, in
-    the A/B build of the library - libkzg_rs_amd_ab.so, the product plus the variants; the shipped library holds only the
-    default forms) through 12 s of tools/fuzz_campaign.py: mutated c-kzg vectors with duplicates, points at infinity, points
+    """The throughput layout's table forms of the point kernels (each selected for a whole process through KZG_OPTIONS, which
+    the A/B build of the library - libkzg_rs_amd_ab.so, the product's kernels with its measurement switches read at run
+    time - honours) through 12 s of tools/fuzz_campaign.py: mutated c-kzg vectors with duplicates, points at infinity, points
     off the curve or outside G1 and non-canonical scalars, three entry points, every outcome equal to the oracle's.
     The default process takes the latency layout for batches this small, so this is also what runs the throughput
     layout's mixed-addition special cases (P + P, P - P, first addition into an empty bucket) against the oracle."""
