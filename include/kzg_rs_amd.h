@@ -49,6 +49,11 @@ extern "C" {
 #define KZG_BYTES_PER_COMMITMENT 48         /* src/consts.rs:9  */
 #define KZG_BYTES_PER_PROOF 48              /* src/consts.rs:10 */
 #define KZG_BYTES_PER_G2 96                 /* src/consts.rs:2  */
+/* EIP-7594 (PeerDAS) cells; not in the reference (c-kzg-4844) */
+#define KZG_FIELD_ELEMENTS_PER_CELL 64
+#define KZG_BYTES_PER_CELL 2048
+#define KZG_CELLS_PER_EXT_BLOB 128
+#define KZG_FIELD_ELEMENTS_PER_EXT_BLOB 8192
 
 typedef enum {
     KZG_OK = 0,
@@ -285,6 +290,34 @@ KzgRet kzg_compute_kzg_proof(uint8_t *proofs_out, uint8_t *ys_out, const uint8_t
                              const KzgSettings *s);
 KzgRet kzg_compute_blob_kzg_proof(uint8_t *proofs_out, const uint8_t *blobs, const uint8_t *commitments, size_t n,
                                   const KzgSettings *s);
+
+/* EIP-7594 cell proofs (not in the reference: c-kzg-4844's verify_cell_kzg_proof_batch, the consensus spec's
+ * verify_cell_kzg_proof_batch_impl).  Cell k of the batch is (commitment k, cell index k, 64 big-endian field elements - the
+ * evaluations of the extended blob at brp_roots_8192[64 c .. 64 c + 63] - and proof k); one random linear combination of all n
+ * checks with r = SHA-256("RCKZGCBATCH__V1_" || u64be(4096) || u64be(64) || u64be(m) || u64be(n) || the m distinct commitments in
+ * first-seen order || per cell: u64be(commitment index) || u64be(cell index) || cell || proof) mod r, and ONE pairing:
+ *     e(sum r^k pi_k, [tau^64]G2) == e(sum w_i C_i - [I(tau)]G1 + sum r^k h_(c_k)^64 pi_k, G2)
+ * Inputs are host arrays: commitments n * 48, cell_indices n, cells n * 2048, proofs n * 48 bytes; n <= 2^20.
+ * Errors, in this order, each KZG_BADARGS with *ok untouched: null pointers; settings without G1 points (kzg_settings_from_tau_g2)
+ * or with fewer than 65 G2 points; a cell index >= 128; a field element >= r; a commitment or proof that is not a G1 point
+ * (decompression, on the curve, in the r-torsion subgroup; the identity is allowed).  n == 0: *ok = true.
+ * The setup needs nothing new: [tau^i]G1 for i < 64 are the commitments of the 64 "blobs" (w_j^i)_j over the handle's Lagrange
+ * points and [tau^64]G2 is g2_points[64].  The first cell call on a handle makes them (64 commitments on the prover's MSM path
+ * and the lines of g2_points[64]; a few ms) and keeps them with ~5 KB per cell of grow-only buffers.  Cost of a call: the
+ * transcript hash runs on a host thread (SHA-NI: ~1 ms per 1 000 cells) while the points and cells are copied,
+ * decoded and checked on the device; then column sums and 64-point inverse DFTs, two MSMs (n terms; n + m + 64 terms) and one
+ * pairing.  Multi-device handles run it on their first device.  kzg_last_timings afterwards: [0] the call (host wall clock),
+ * [1] the transcript hash (host), [2] the two MSMs, [3] the pairing, [4] the kernels between r and the MSMs, [6] the copies and
+ * decode of the points and cells. */
+KzgRet kzg_verify_cell_kzg_proof_batch(bool *ok, const uint8_t *commitments, const uint64_t *cell_indices,
+                                       const uint8_t *cells, const uint8_t *proofs, size_t n, const KzgSettings *s);
+/* The batch challenge r of the above alone, as 32 big-endian bytes: host code, no device and no settings needed; inputs are
+ * hashed as given (nothing is validated). */
+KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t *commitments, const uint64_t *cell_indices,
+                                const uint8_t *cells, const uint8_t *proofs, size_t n);
+/* [tau^i]G1, i < 64, compressed: derived from the handle's Lagrange points by the first cell call or the first call of this
+ * accessor.  KZG_BADARGS for i >= 64 and for the settings the cell verifier refuses. */
+KzgRet kzg_settings_g1_monomial_point(const KzgSettings *s, size_t i, uint8_t out[48]);
 
 /* ---- pieces of the path, exposed for parity tests and the per-kernel benchmarks ---- */
 /* compute_challenge (src/kzg_proof.rs:46-72) for n blobs: z_out = n * 32 bytes, big-endian canonical.

@@ -27,6 +27,10 @@ TRUSTED_SETUP_PATH = os.path.join(HERE, "data", "trusted_setup.txt")
 BYTES_PER_FIELD_ELEMENT = 32
 FIELD_ELEMENTS_PER_BLOB = 4096
 BYTES_PER_BLOB = 131072
+# EIP-7594 cells (not in the reference; c-kzg-4844)
+FIELD_ELEMENTS_PER_CELL = 64
+BYTES_PER_CELL = 2048
+CELLS_PER_EXT_BLOB = 128
 BYTES_PER_COMMITMENT = 48
 BYTES_PER_PROOF = 48
 
@@ -120,6 +124,9 @@ def lib():
         L.kzg_blob_to_kzg_commitment.argtypes = [u8, u8, sz, vp]
         L.kzg_compute_kzg_proof.argtypes = [u8, u8, u8, u8, sz, vp]
         L.kzg_compute_blob_kzg_proof.argtypes = [u8, u8, u8, sz, vp]
+        L.kzg_verify_cell_kzg_proof_batch.argtypes = [bp, u8, C.POINTER(C.c_uint64), u8, u8, sz, vp]
+        L.kzg_cell_batch_challenge.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz]
+        L.kzg_settings_g1_monomial_point.argtypes = [vp, sz, u8]
         L.kzg_verify_kzg_proof.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_verify_kzg_proof_batch.argtypes = [bp, u8, u8, u8, u8, sz, vp]
         L.kzg_verify_kzg_proofs.argtypes = [bp, u8, u8, u8, u8, u8, sz, vp]
@@ -213,6 +220,11 @@ class Bytes48(_BytesN):
 
 class Blob(_BytesN):
     SIZE = BYTES_PER_BLOB
+
+
+class Cell(_BytesN):
+    """EIP-7594 cell: 64 big-endian field elements (not in the reference; c-kzg-4844's Cell)."""
+    SIZE = BYTES_PER_CELL
 
 
 class KzgSettings:
@@ -310,6 +322,12 @@ class KzgSettings:
         """g1_points[i] (bit-reversal permuted, build.rs:79) as 48 compressed bytes."""
         out = C.create_string_buffer(48)
         _chk(lib().kzg_settings_g1_point(self._h, i, out))
+        return out.raw
+
+    def g1_monomial_point(self, i):
+        """[tau^i]G1 for i < 64 as 48 compressed bytes, derived from the Lagrange points on first use (the cell verifier's setup)."""
+        out = C.create_string_buffer(48)
+        _chk(lib().kzg_settings_g1_monomial_point(self._h, i, out))
         return out.raw
 
     def g2_point(self, i):
@@ -433,12 +451,45 @@ class KzgProof:
         return bool(ok.value)
 
     @staticmethod
+    def verify_cell_kzg_proof_batch(commitments, cell_indices, cells, proofs, kzg_settings):
+        """c-kzg-4844's verify_cell_kzg_proof_batch (EIP-7594; not in the reference): lists of Bytes48 commitments, int cell
+        indices, Cell cells and Bytes48 proofs, one entry per cell.  Lists of unequal length or items of the wrong size raise
+        InvalidBytesLength; a cell index >= 128, a non-canonical field element or a non-G1 point raise BadArgs."""
+        args = _cell_args(commitments, cell_indices, cells, proofs)
+        ok = C.c_bool(False)
+        _chk(lib().kzg_verify_cell_kzg_proof_batch(C.byref(ok), *args, kzg_settings._h))
+        return bool(ok.value)
+
+    @staticmethod
     def verify_blob_kzg_proof_batch_device(d_blobs, d_commitments, d_proofs, n, kzg_settings):
         """Device-resident form: arguments are device pointers (ints), e.g. torch tensor .data_ptr()."""
         ok = C.c_bool(False)
         _chk(lib().kzg_verify_blob_kzg_proof_batch_device(C.byref(ok), d_blobs, d_commitments, d_proofs, n,
                                                           kzg_settings._h))
         return bool(ok.value)
+
+
+def _cell_args(commitments, cell_indices, cells, proofs):
+    n = len(cells)
+    if len(commitments) != n or len(cell_indices) != n or len(proofs) != n:
+        raise InvalidBytesLength("commitments, cell_indices, cells and proofs must have the same length")
+    raw = lambda x: x.data if isinstance(x, _BytesN) else bytes(x)
+    cm, ce, pr = (b"".join(raw(x) for x in xs) for xs in (commitments, cells, proofs))
+    if len(cm) != 48 * n or len(pr) != 48 * n:
+        raise InvalidBytesLength("commitments and proofs are 48 bytes each")
+    if len(ce) != BYTES_PER_CELL * n:
+        raise InvalidBytesLength("cells are %d bytes each" % BYTES_PER_CELL)
+    if any(not 0 <= int(c) < 2 ** 64 for c in cell_indices):
+        raise BadArgs("cell index out of range")
+    idx = (C.c_uint64 * max(n, 1))(*[int(c) for c in cell_indices])
+    return cm, idx, ce, pr, n
+
+
+def cell_batch_challenge(commitments, cell_indices, cells, proofs):
+    """The batch challenge r of verify_cell_kzg_proof_batch (host code, no device): 32 big-endian bytes."""
+    out = C.create_string_buffer(32)
+    _chk(lib().kzg_cell_batch_challenge(out, *_cell_args(commitments, cell_indices, cells, proofs)))
+    return out.raw
 
 
 def verify_kzg_proofs(commitments, zs, ys, proofs, kzg_settings):

@@ -1,0 +1,346 @@
+// capi_cells.hpp - EIP-7594 cell proofs (c-kzg-4844 verify_cell_kzg_proof_batch; not in the reference): the entry points.
+// Part of the single translation unit kzg_capi.hip; not a stand-alone header.  Device side: cell_kernels.hpp.
+//
+// The check is the consensus spec's verify_cell_kzg_proof_batch_impl: for cells k (commitment C_k, cell index c_k, 64 evaluations
+// over the coset h_c <w64>, proof pi_k) and r = SHA-256(transcript) mod r,
+//     e(sum_k r^k pi_k, [tau^64]G2) == e(sum_i w_i U_i - [I(tau)]G1 + sum_k r^k h_(c_k)^64 pi_k, G2)
+// with U_i the distinct commitments, w_i the sum of r^k over the cells of U_i and I the sum over the columns of the
+// interpolants of the r-weighted column sums.  Data flow of one call:
+//   host    argument and cell-index checks, dedup of the commitments, counting sorts by column and by commitment
+//   host    the transcript hash (one serial SHA-256 chain of ~2.1 KB per cell) on a thread of its own, WHILE
+//   device  the points [proofs | unique commitments | [tau^i]G1] are decoded with their subgroup test and table rows, and the
+//           cells are decoded with their canonical check - none of that needs r
+//   device  r^k, the column sums, the 64-point inverse DFTs, the MSM scalars (cell_kernels.hpp)
+//   device  two sums over the one set of decoded tables (g1_msm_core): LL over the proofs, RL over all N = n + m + 64 points
+//   device  one pairing against the prepared lines of (g2_points[64], G2), made with the monomial table and kept on the handle
+// The hash stays on the host: a GPU lane runs SHA-256 at ~1.4 us per 64-byte block, a SHA-NI core at ~1.5 GB/s, and the chain
+// has no parallelism to give the GPU.  A multi-device handle runs on its first device, as the prover entry points do.
+
+constexpr size_t CELL_BYTES = (size_t)CELL_FE * 32;   // BYTES_PER_CELL
+constexpr size_t CELL_MAX_CELLS = (size_t)1 << 20;    // 8 192 blobs x 128 cells per call
+
+// ---------------------------------------------------------------- host: dedup and the batch challenge
+static void cell_u64be(uint8_t o[8], uint64_t v) {
+    for (int i = 0; i < 8; i++) o[i] = (uint8_t)(v >> (56 - 8 * i));
+}
+// ci[k] = index of commitment k among the distinct commitments (compared as bytes), numbered in first-seen order; uniq[i] = the
+// first k that holds distinct commitment i
+static void cell_dedup(const uint8_t* commitments, size_t n, std::vector<uint32_t>& ci, std::vector<uint32_t>& uniq) {
+    std::unordered_map<std::string, uint32_t> seen;
+    seen.reserve(n);
+    ci.resize(n);
+    uniq.clear();
+    for (size_t k = 0; k < n; k++) {
+        auto it = seen.emplace(std::string(reinterpret_cast<const char*>(commitments + 48 * k), 48), (uint32_t)uniq.size());
+        if (it.second) uniq.push_back((uint32_t)k);
+        ci[k] = it.first->second;
+    }
+}
+// compute_verify_cell_kzg_proof_batch_challenge: SHA-256("RCKZGCBATCH__V1_" || u64be(4096) || u64be(64) || u64be(m) || u64be(n) ||
+// unique commitments || per cell: u64be(commitment index) || u64be(cell index) || cell || proof), read big-endian, mod r
+static void cell_challenge(uint8_t r_be[32], const uint8_t* commitments, const std::vector<uint32_t>& ci, const std::vector<uint32_t>& uniq,
+                           const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n) {
+    hostsha::Stream h;
+    uint8_t hdr[48];
+    memcpy(hdr, "RCKZGCBATCH__V1_", 16);
+    cell_u64be(hdr + 16, (uint64_t)FE_PER_BLOB);
+    cell_u64be(hdr + 24, (uint64_t)CELL_FE);
+    cell_u64be(hdr + 32, (uint64_t)uniq.size());
+    cell_u64be(hdr + 40, (uint64_t)n);
+    h.update(hdr, 48);
+    for (uint32_t k : uniq) h.update(commitments + 48 * (size_t)k, 48);
+    for (size_t k = 0; k < n; k++) {
+        uint8_t ix[16];
+        cell_u64be(ix, ci[k]);
+        cell_u64be(ix + 8, cell_indices[k]);
+        h.update(ix, 16);
+        h.update(cells + CELL_BYTES * k, CELL_BYTES);
+        h.update(proofs + 48 * k, 48);
+    }
+    h.finish(r_be);
+    while (be_geq_r(r_be)) be_sub_r(r_be);
+}
+extern "C" KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                                           const uint8_t* proofs, size_t n) try {
+    if (!r_out || (n && (!commitments || !cell_indices || !cells || !proofs))) return fail(KZG_BADARGS, "null argument");
+    std::vector<uint32_t> ci, uniq;
+    cell_dedup(commitments, n, ci, uniq);
+    cell_challenge(r_out, commitments, ci, uniq, cell_indices, cells, proofs, n);
+    return KZG_OK;
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");
+}
+
+// ---------------------------------------------------------------- the handle's cell state
+// Made by the first cell call (or monomial-point accessor) under the handle's lock, like the prover's buffers, and released with
+// the handle: the w8192 power table, [tau^i]G1 for i < 64, the prepared lines of (g2_points[64], G2), and grow-only call buffers.
+struct CellState {
+    Fr* d_T = nullptr;                          // w8192^e, e < 8192, Montgomery
+    uint8_t mono[CELL_FE * 48] = {};            // [tau^i]G1, compressed
+    Fp* d_lines = nullptr;                      // prepared lines of g2_points[64] then G2, 8x32 Montgomery (VERIFY)
+    uint32_t* d_lines29 = nullptr;              // the same in the latency program's format (VERIFY2)
+    size_t cap = 0;                             // cells the call buffers hold
+    uint8_t* d_cells = nullptr;                 // [cap] x 2048 bytes as given
+    Fr *d_vals = nullptr, *d_rM = nullptr, *d_sc_ll = nullptr, *d_sc_rl = nullptr, *d_coef = nullptr, *d_r = nullptr;
+    uint32_t *d_bad = nullptr, *d_idx = nullptr;
+    void free_calls() {
+        void* ptrs[] = {d_cells, d_vals, d_rM, d_sc_ll, d_sc_rl, d_bad, d_idx};
+        for (void* q : ptrs)
+            if (q) (void)hipFree(q);
+        d_cells = nullptr, d_vals = d_rM = d_sc_ll = d_sc_rl = nullptr, d_bad = d_idx = nullptr;
+        cap = 0;
+    }
+    ~CellState() {
+        free_calls();
+        void* ptrs[] = {d_T, d_lines, d_lines29, d_coef, d_r};
+        for (void* q : ptrs)
+            if (q) (void)hipFree(q);
+    }
+    static size_t idx_words(size_t n) { return 4 * n + 2 * CELLS_PER_EXT_BLOB + 4; }  // see kzg_verify_cell_kzg_proof_batch
+    KzgRet reserve(size_t n) {
+        if (n <= cap) return KZG_OK;
+        free_calls();
+        const size_t c = std::max<size_t>(n, 64);
+        HIPCHK(hipMalloc(&d_cells, CELL_BYTES * c));
+        HIPCHK(hipMalloc(&d_vals, sizeof(Fr) * CELL_FE * c));
+        HIPCHK(hipMalloc(&d_rM, sizeof(Fr) * c));
+        HIPCHK(hipMalloc(&d_sc_ll, sizeof(Fr) * c));
+        HIPCHK(hipMalloc(&d_sc_rl, sizeof(Fr) * (2 * c + CELL_FE)));
+        HIPCHK(hipMalloc(&d_bad, 4 * c));
+        HIPCHK(hipMalloc(&d_idx, 4 * idx_words(c)));
+        cap = c;
+        return KZG_OK;
+    }
+};
+static void cells_release(const KzgSettings* s) {
+    delete s->cells;
+    s->cells = nullptr;
+}
+static KzgRet cells_ready(const KzgSettings* s) {
+    if (!s->d_g1) return fail(KZG_BADARGS, "cell proofs need the G1 points of a trusted-setup file; these settings hold [tau]G2 alone");
+    if (s->n_g2 < (size_t)CELL_FE + 1) return fail(KZG_BADARGS, "cell proofs need g2_points[64]; these settings hold fewer than 65 G2 points");
+    return prover_ready(s);
+}
+// the caller holds the handle's lock and has selected the plain stream pair
+static KzgRet cells_state(const KzgSettings* s, CellState** out) {
+    if (s->cells) {
+        *out = s->cells;
+        return KZG_OK;
+    }
+    std::unique_ptr<CellState> c(new CellState());
+    StreamDrain drain{s->s1};
+    HIPCHK(hipMalloc(&c->d_T, sizeof(Fr) * EXT_FE));
+    HIPCHK(hipMalloc(&c->d_coef, sizeof(Fr) * CELL_FE * CELLS_PER_EXT_BLOB));
+    HIPCHK(hipMalloc(&c->d_r, sizeof(Fr)));
+    hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T);
+    // [tau^i]G1 = sum_j w_j^i g1_points[j]: the commitments of 64 "blobs" over the Lagrange points, on the prover's MSM path
+    ProverBufs* bp = nullptr;
+    KzgRet rc = prover_bufs(s, &bp);
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_cell_monomial_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->d_M, bp->d_sc);
+    HIPCHK(hipGetLastError());
+    if ((rc = setup_msm(s, *bp, CELL_FE)) != KZG_OK) return rc;
+    HIPCHK(hipMemcpyAsync(c->mono, bp->d_out, sizeof c->mono, hipMemcpyDeviceToHost, s->s1));
+    // the lines of (g2_points[64], G2): the PREP program on two instances, as kzg_pairings_verify runs it per call
+    const size_t n_lines = (size_t)2 * s->prep.p.n_out;
+    DevTmp t_q;
+    HIPCHK(hipMalloc(&t_q.p, sizeof(Fp) * 8));
+    HIPCHK(hipMalloc(&c->d_lines, sizeof(Fp) * n_lines));
+    HIPCHK(hipMalloc(&c->d_lines29, (size_t)64 * n_lines));
+    HIPCHK(hipMemcpyAsync(t_q.p, s->d_g2 + 4 * CELL_FE, sizeof(Fp) * 4, hipMemcpyDeviceToDevice, s->s1));
+    hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, t_q.as<Fp>() + 4);
+    HIPCHK(hipGetLastError());
+    if ((rc = run_program(s->prep, t_q.as<Fp>(), nullptr, c->d_lines, 2, s->s1)) != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s->s1, (const Fp*)c->d_lines, c->d_lines29, (int)n_lines);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s->s1));
+    s->cells = c.release();
+    *out = s->cells;
+    return KZG_OK;
+}
+
+// e(LL, g2_points[64]) == e(RL, G2) on the cached lines: kzg_pairings_verify's VERIFY step without its per-call PREP
+static KzgRet cells_pairing(const KzgSettings* s, const CellState& c, const uint8_t ll[48], const uint8_t rl[48], bool* ok) {
+    Workspace& w = s->ws;
+    uint8_t* h = w.h_buf;  // pinned: [LL | RL] in, then flags and the program's output
+    memcpy(h, ll, 48);
+    memcpy(h + 48, rl, 48);
+    HIPCHK(hipMemcpyAsync(w.d_bytes, h, 96, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g1_decode, dim3(1), dim3(64), 0, s->s1, w.d_bytes, w.d_bytes, 2, w.d_points, w.d_pflag, 2, 0);
+    hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points, w.d_pflag, w.d_slp_in);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[3], s->s1));
+    KzgRet rc = pairing_latency_form(1) ? run_program2(s->verify2, w.d_slp_in, c.d_lines29, w.d_slp_out, 1, s->s1)
+                                        : run_program(s->verify, w.d_slp_in, c.d_lines, w.d_slp_out, 1, s->s1);
+    if (rc != KZG_OK) return rc;
+    HIPCHK(hipEventRecord(s->ev[4], s->s1));
+    uint32_t* hf = reinterpret_cast<uint32_t*>(h + 128);  // [g1 flags 2 | out 72]
+    HIPCHK(hipMemcpyAsync(hf, w.d_pflag, 8, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(hf + 2, w.d_slp_out, sizeof(Fp) * 6, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipStreamSynchronize(s->s1));
+    elapsed(&s->timings[3], s->ev[3], s->ev[4]);
+    if (hf[0] == G1_INVALID || hf[1] == G1_INVALID) return fail(KZG_ERROR, "cell batch: an MSM result did not decode");
+    uint32_t any = 0;
+    for (int i = 0; i < 72; i++) any |= hf[2 + i];
+    *ok = any == 0;
+    return KZG_OK;
+}
+
+// ---------------------------------------------------------------- entry points
+extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                                                  const uint8_t* proofs, size_t n, const KzgSettings* s) try {
+    if (!ok || !s || (n && (!commitments || !cell_indices || !cells || !proofs))) return fail(KZG_BADARGS, "null argument");
+    KzgRet rc = cells_ready(s);
+    if (rc != KZG_OK) return rc;
+    if (n > CELL_MAX_CELLS) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batch: more than 2^20 cells");
+    for (size_t k = 0; k < n; k++)
+        if (cell_indices[k] >= (uint64_t)CELLS_PER_EXT_BLOB) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
+    if (n == 0) {
+        *ok = true;
+        return KZG_OK;
+    }
+    const auto t_call = std::chrono::steady_clock::now();
+    // r-independent host work: the distinct commitments, the cells by column and by commitment (stable counting sorts: every
+    // device sum runs in ascending k).  idx: [cell index n | order by column n | column starts U + 1 | columns U | order by
+    // commitment n | commitment starts m + 1] at the fixed offsets below
+    std::vector<uint32_t> ci, uniq;
+    cell_dedup(commitments, n, ci, uniq);
+    const size_t m = uniq.size(), N = n + m + CELL_FE;
+    std::vector<uint32_t> idx(CellState::idx_words(n), 0u);
+    uint32_t *h_cidx = idx.data(), *h_order = h_cidx + n, *h_start = h_order + n, *h_cols = h_start + CELLS_PER_EXT_BLOB + 1,
+             *h_wlist = h_cols + CELLS_PER_EXT_BLOB, *h_wstart = h_wlist + n;
+    uint32_t cnt[CELLS_PER_EXT_BLOB + 1] = {};
+    for (size_t k = 0; k < n; k++) cnt[(h_cidx[k] = (uint32_t)cell_indices[k]) + 1]++;
+    for (int c = 0; c < CELLS_PER_EXT_BLOB; c++) cnt[c + 1] += cnt[c];
+    int U = 0;
+    for (int c = 0; c < CELLS_PER_EXT_BLOB; c++)
+        if (cnt[c + 1] > cnt[c]) {
+            h_start[U] = cnt[c];
+            h_cols[U++] = (uint32_t)c;
+        }
+    h_start[U] = (uint32_t)n;
+    for (size_t k = 0; k < n; k++) h_order[cnt[h_cidx[k]]++] = (uint32_t)k;
+    for (size_t k = 0; k < n; k++) h_wstart[ci[k] + 1]++;
+    for (size_t i = 0; i < m; i++) h_wstart[i + 1] += h_wstart[i];
+    {
+        std::vector<uint32_t> pos(h_wstart, h_wstart + m);
+        for (size_t k = 0; k < n; k++) h_wlist[pos[ci[k]]++] = (uint32_t)k;
+    }
+
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
+    CellState* cs = nullptr;
+    if ((rc = cells_state(s, &cs)) != KZG_OK || (rc = cs->reserve(n)) != KZG_OK || (rc = ws_reserve(s, (N + 1) / 2 + 1, 1, STAGE_NONE)) != KZG_OK)
+        return rc;
+    Workspace& w = s->ws;
+    std::vector<uint32_t> h_bad(n), h_pflag(N);
+    StreamDrain drain{s->s1};  // (declared after the host buffers the copies write: destroyed - and the stream drained - first)
+
+    // the transcript hash on a host thread of its own; the inputs cross to the device and are decoded meanwhile
+    uint8_t r_be[32];
+    double hash_ms = 0.0;
+    auto hash = [&] {
+        const auto t0 = std::chrono::steady_clock::now();
+        cell_challenge(r_be, commitments, ci, uniq, cell_indices, cells, proofs, n);
+        hash_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    std::thread hasher;
+    struct Join {
+        std::thread& t;
+        ~Join() {
+            if (t.joinable()) t.join();
+        }
+    } join{hasher};
+    try {
+        hasher = std::thread(hash);
+    } catch (const std::system_error&) {
+        hash();  // (no thread to be had: hash first)
+    }
+    // points [proofs | distinct commitments | [tau^i]G1] -> decoded, subgroup-tested, table rows (kzg_g1_msm's decode)
+    uint8_t* hp = w.h_buf;  // pinned, at least 128 N bytes (ws_reserve)
+    memcpy(hp, proofs, 48 * n);
+    for (size_t i = 0; i < m; i++) memcpy(hp + 48 * (n + i), commitments + 48 * (size_t)uniq[i], 48);
+    memcpy(hp + 48 * (n + m), cs->mono, sizeof cs->mono);
+    HIPCHK(hipEventRecord(s->ev[5], s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_bytes, hp, 48 * N, hipMemcpyHostToDevice, s->s1));
+    const bool aff = msm_affine_enabled();
+    const unsigned blocks256 = (unsigned)((N + 255) / 256);
+    if (aff) {
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3(blocks256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, w.d_bytes,
+                           w.d_bytes, (int)N, w.d_points, w.d_pflag, w.d_mult, w.d_jtmp, (int)N, (int)N);
+        const unsigned conv_blocks = (unsigned)((N + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
+        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp, w.d_pflag, (G1Aff29Mem*)w.d_mult, (int)N, (int)N);
+    } else {
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((N + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1,
+                           w.d_bytes, w.d_bytes, (int)N, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, (int)N, (int)N);
+    }
+    HIPCHK(hipGetLastError());
+    // the cells -> plain limbs with their canonical flags, and the index arrays
+    uint32_t* const d_cidx = cs->d_idx;
+    const size_t o_order = n, o_start = 2 * n, o_cols = o_start + CELLS_PER_EXT_BLOB + 1, o_wlist = o_cols + CELLS_PER_EXT_BLOB, o_wstart = o_wlist + n;
+    HIPCHK(hipMemcpyAsync(cs->d_idx, idx.data(), 4 * (o_wstart + m + 1), hipMemcpyHostToDevice, s->s1));
+    HIPCHK(hipMemsetAsync(cs->d_bad, 0, 4 * n, s->s1));
+    HIPCHK(hipMemcpyAsync(cs->d_cells, cells, CELL_BYTES * n, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * n + 255) / 256)), dim3(256), 0, s->s1, (const uint8_t*)cs->d_cells, cs->d_vals, cs->d_bad,
+                       (int)(CELL_FE * n));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_bad.data(), cs->d_bad, 4 * n, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(h_pflag.data(), w.d_pflag, 4 * N, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipEventRecord(s->ev[6], s->s1));
+    if (hasher.joinable()) hasher.join();
+    HIPCHK(hipStreamSynchronize(s->s1));
+    for (size_t k = 0; k < n; k++)
+        if (h_bad[k]) return fail(KZG_BADARGS, "a cell holds a field element >= r");
+    for (size_t i = 0; i < n + m; i++)
+        if (h_pflag[i] == G1_INVALID) return fail(KZG_BADARGS, i < n ? "invalid proof (not a G1 point)" : "invalid commitment (not a G1 point)");
+    for (size_t i = n + m; i < N; i++)
+        if (h_pflag[i] == G1_INVALID) return fail(KZG_BAD_SETUP, "a monomial setup point is outside G1");
+
+    // r -> the scalars: [r^k | -] for LL, [r^k h^64 | w_i | -I_i] for RL
+    uint8_t r_le[32];
+    reverse32(r_le, r_be);
+    HIPCHK(hipEventRecord(s->ev[7], s->s1));
+    HIPCHK(hipMemcpyAsync(cs->d_r, r_le, 32, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_cell_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, (const Fr*)cs->d_r, (const uint32_t*)d_cidx, (const Fr*)cs->d_T, cs->d_rM,
+                       cs->d_sc_ll, cs->d_sc_rl, (int)n);
+    hipLaunchKernelGGL(k_cell_commitment_weights, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const Fr*)cs->d_rM, (const uint32_t*)(d_cidx + o_wlist),
+                       (const uint32_t*)(d_cidx + o_wstart), cs->d_sc_rl + n, (int)m);
+    hipLaunchKernelGGL(k_cell_column_ifft, dim3((unsigned)U), dim3(64), 0, s->s1, (const Fr*)cs->d_vals, (const Fr*)cs->d_rM, (const uint32_t*)(d_cidx + o_order),
+                       (const uint32_t*)(d_cidx + o_start), (const uint32_t*)(d_cidx + o_cols), (const Fr*)cs->d_T, cs->d_coef);
+    hipLaunchKernelGGL(k_cell_interp_sum, dim3(1), dim3(64), 0, s->s1, (const Fr*)cs->d_coef, U, cs->d_sc_rl + n + m);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[8], s->s1));
+    // the two sums over the one set of tables (each decoded proof serves both); g1_msm_core splits its scalars in place
+    const G1MsmTables tb{w.d_mult, w.d_pflag, (int)N, aff, false};
+    uint8_t ll[48], rl[48];
+    HIPCHK(hipMemcpyAsync(w.d_scalars, cs->d_sc_ll, sizeof(Fr) * n, hipMemcpyDeviceToDevice, s->s1));
+    if ((rc = g1_msm_core(s, n, tb, ll)) != KZG_OK) return rc;
+    const float msm_ll = s->timings[2];
+    elapsed(&s->timings[6], s->ev[5], s->ev[6]);
+    elapsed(&s->timings[4], s->ev[7], s->ev[8]);
+    HIPCHK(hipMemcpyAsync(w.d_scalars, cs->d_sc_rl, sizeof(Fr) * N, hipMemcpyDeviceToDevice, s->s1));
+    if ((rc = g1_msm_core(s, N, tb, rl)) != KZG_OK) return rc;
+    s->timings[2] += msm_ll;
+    if ((rc = cells_pairing(s, *cs, ll, rl, ok)) != KZG_OK) return rc;
+    s->timings[0] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    s->timings[1] = (float)hash_ms;
+    s->timings[5] = s->timings[7] = 0.0f;
+    return KZG_OK;
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
+}
+
+extern "C" KzgRet kzg_settings_g1_monomial_point(const KzgSettings* s, size_t i, uint8_t out[48]) {
+    if (!s || !out) return fail(KZG_BADARGS, "null argument");
+    if (i >= (size_t)CELL_FE) return fail(KZG_BADARGS, "monomial point index out of range (>= 64)");
+    KzgRet rc = cells_ready(s);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);
+    CellState* cs = nullptr;
+    if ((rc = cells_state(s, &cs)) != KZG_OK) return rc;
+    memcpy(out, cs->mono + 48 * i, 48);
+    return KZG_OK;
+}

@@ -11,9 +11,11 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/kzg_rs_amd.h"
@@ -24,6 +26,7 @@
 #include "slp.hpp"
 #include "slp2.hpp"
 #include "proof_kernels.hpp"
+#include "cell_kernels.hpp"
 
 using namespace kzg;
 
@@ -60,4 +63,5 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_pipeline.hpp"
 #include "capi_pieces.hpp"
 #include "capi_prover.hpp"
+#include "capi_cells.hpp"
 #include "capi_debug.hpp"

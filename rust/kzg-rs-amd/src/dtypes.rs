@@ -1,5 +1,6 @@
-//! The three byte newtypes of the API - `Bytes32` (a field element), `Bytes48` (a compressed G1 point), `Blob` (4096 field
-//! elements) - with the constructors, conversions and optional `serde` / `rkyv` derives of kzg-rs `src/dtypes.rs:7-57`.
+//! The byte newtypes of the API - `Bytes32` (a field element), `Bytes48` (a compressed G1 point), `Blob` (4096 field
+//! elements), `Cell` (64 field elements; EIP-7594, not in kzg-rs) - with the constructors, conversions and optional `serde` /
+//! `rkyv` derives of kzg-rs `src/dtypes.rs:7-57`.
 //! `#[repr(transparent)]` is added: a `Vec<Blob>` is then provably one contiguous `n * 131072`-byte region, which is what
 //! the library's batch entry point takes as it lies in memory (no per-blob copy).
 use crate::enums::KzgError;
@@ -62,6 +63,13 @@ byte_newtype!(
 byte_newtype!(
     /// 131 072 bytes: 4096 field elements of 32 big-endian bytes each.
     Blob[BYTES_PER_BLOB]
+);
+
+/// Bytes of an EIP-7594 cell (c-kzg-4844's `BYTES_PER_CELL`; not in kzg-rs).
+pub const BYTES_PER_CELL: usize = 2048;
+byte_newtype!(
+    /// 2 048 bytes: one EIP-7594 cell, 64 field elements of 32 big-endian bytes each (not in kzg-rs; c-kzg-4844's `Cell`).
+    Cell[BYTES_PER_CELL]
 );
 
 impl Blob {

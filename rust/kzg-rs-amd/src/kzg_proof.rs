@@ -1,6 +1,6 @@
 //! `KzgProof` of kzg-rs `src/kzg_proof.rs:350-526`: the four verification functions with their signatures, early
 //! returns and error variants; each forwards to one entry point of the library.
-use crate::dtypes::{Blob, Bytes32, Bytes48};
+use crate::dtypes::{Blob, Bytes32, Bytes48, Cell};
 use crate::enums::KzgError;
 use crate::ffi;
 use crate::trusted_setup::KzgSettings;
@@ -121,6 +121,36 @@ impl KzgProof {
                 commitments_bytes.as_ptr().cast::<u8>(),
                 proofs_bytes.as_ptr().cast::<u8>(),
                 blobs.len(),
+                kzg_settings.raw(),
+            )
+        })?;
+        Ok(ok)
+    }
+
+    /// c-kzg-4844's `verify_cell_kzg_proof_batch` (EIP-7594; not in kzg-rs): one entry per cell - its blob's commitment, its
+    /// cell index (< 128), the cell and its proof - checked with one random linear combination and one pairing
+    /// (include/kzg_rs_amd.h).  Slices of unequal length are `InvalidBytesLength`; a cell index >= 128, a non-canonical field
+    /// element or a point outside G1 is `BadArgs`; an empty batch is `Ok(true)`.
+    pub fn verify_cell_kzg_proof_batch(
+        commitments: &[Bytes48],
+        cell_indices: &[u64],
+        cells: &[Cell],
+        proofs: &[Bytes48],
+        kzg_settings: &KzgSettings,
+    ) -> Result<bool, KzgError> {
+        let n = cells.len();
+        if commitments.len() != n || cell_indices.len() != n || proofs.len() != n {
+            return Err(KzgError::InvalidBytesLength("commitments, cell indices, cells and proofs differ in length".to_string()));
+        }
+        let mut ok = false;
+        ffi::check(unsafe {
+            ffi::kzg_verify_cell_kzg_proof_batch(
+                &mut ok,
+                commitments.as_ptr().cast::<u8>(),
+                cell_indices.as_ptr(),
+                cells.as_ptr().cast::<u8>(),
+                proofs.as_ptr().cast::<u8>(),
+                n,
                 kzg_settings.raw(),
             )
         })?;
