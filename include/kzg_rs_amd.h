@@ -291,6 +291,22 @@ KzgRet kzg_compute_kzg_proof(uint8_t *proofs_out, uint8_t *ys_out, const uint8_t
 KzgRet kzg_compute_blob_kzg_proof(uint8_t *proofs_out, const uint8_t *blobs, const uint8_t *commitments, size_t n,
                                   const KzgSettings *s);
 
+/* EIP-7594 cell prover (not in the reference: c-kzg-4844's compute_cells and compute_cells_and_kzg_proofs).  blobs: n * 131072
+ * bytes (host).  cells_out: n * 128 cells of 2048 bytes, cell c of blob b at cells_out + (b * 128 + c) * 2048: cells 0..63 are the
+ * blob's own bytes, cells 64..127 the blob polynomial on the coset w8192 <w4096>, bit-reversal permuted (two 4 096-point field
+ * transforms per blob on the device).  proofs_out: n * 128 proofs of 48 bytes, by FK20 (c-kzg-4844's compute_fk20_cell_proofs):
+ * 128 sums of 64 terms over a table derived from the Lagrange points, then the inverse DFT - truncate - DFT of the 128 results
+ * as one circulant product (128 sums of 65 terms).  Blobs are processed 64 per launch.  The identity proof is 0xC0 00 .. 00.
+ * KZG_BADARGS for a field element >= r (no output is promised) or settings without G1 points, KZG_BAD_SETUP for an off-subgroup
+ * set-up point; n == 0 is KZG_OK.  No G2 point is read.  The handle's lock is taken; a multi-device handle runs the call on its
+ * first device.  The FIRST proof call on a handle derives the FK20 table: 8 192 points x 32 rows = 48 MB kept on the handle, built
+ * by 128 launches of the 64-blob commitment path: that call takes 1.24 s - MORE THAN A SECOND - against 6.2 ms for one blob, 9.7 ms
+ * for six and 62 ms for 64 afterwards; kzg_compute_cells alone needs a 384 KB twiddle table only (0.24 ms a blob).  The call buffers (up to ~100 MB for 64 blobs with proofs) stay on the handle. */
+KzgRet kzg_compute_cells(uint8_t *cells_out, const uint8_t *blobs, size_t n, const KzgSettings *s);
+/* the same cells (cells_out may be NULL) and the n * 128 proofs */
+KzgRet kzg_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint8_t *blobs, size_t n,
+                                        const KzgSettings *s);
+
 /* EIP-7594 cell proofs (not in the reference: c-kzg-4844's verify_cell_kzg_proof_batch, the consensus spec's
  * verify_cell_kzg_proof_batch_impl).  Cell k of the batch is (commitment k, cell index k, 64 big-endian field elements - the
  * evaluations of the extended blob at brp_roots_8192[64 c .. 64 c + 63] - and proof k); one random linear combination of all n

@@ -125,6 +125,8 @@ def lib():
         L.kzg_compute_kzg_proof.argtypes = [u8, u8, u8, u8, sz, vp]
         L.kzg_compute_blob_kzg_proof.argtypes = [u8, u8, u8, sz, vp]
         L.kzg_verify_cell_kzg_proof_batch.argtypes = [bp, u8, C.POINTER(C.c_uint64), u8, u8, sz, vp]
+        L.kzg_compute_cells.argtypes = [u8, u8, sz, vp]
+        L.kzg_compute_cells_and_kzg_proofs.argtypes = [u8, u8, u8, sz, vp]
         L.kzg_cell_batch_challenge.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz]
         L.kzg_settings_g1_monomial_point.argtypes = [vp, sz, u8]
         L.kzg_verify_kzg_proof.argtypes = [bp, u8, u8, u8, u8, vp]
@@ -680,6 +682,46 @@ def compute_blob_kzg_proof(blobs, commitments, kzg_settings):
     pr = C.create_string_buffer(48 * max(n, 1))
     _chk(lib().kzg_compute_blob_kzg_proof(pr, b"".join(blobs), b"".join(commitments), n, kzg_settings._h))
     return [pr.raw[48 * i: 48 * i + 48] for i in range(n)]
+
+
+def _cell_prover_blobs(blobs):
+    data = [b.data if isinstance(b, Blob) else bytes(b) for b in blobs]
+    for b in data:
+        if len(b) != BYTES_PER_BLOB:
+            raise InvalidBytesLength("Invalid blob length: %d bytes, expected %d" % (len(b), BYTES_PER_BLOB))
+    return data
+
+
+def _cells_of(buf, n):
+    per = CELLS_PER_EXT_BLOB * BYTES_PER_CELL
+    raw = buf.raw
+    return [[Cell(raw[per * b + BYTES_PER_CELL * c: per * b + BYTES_PER_CELL * (c + 1)]) for c in range(CELLS_PER_EXT_BLOB)]
+            for b in range(n)]
+
+
+def compute_cells(blobs, kzg_settings):
+    """c-kzg-4844's compute_cells (EIP-7594; not in the reference) for a list of blobs (Blob or bytes): -> per blob the list
+    of its 128 Cells.  A wrong blob length raises InvalidBytesLength before any device call; a field element >= r raises
+    BadArgs."""
+    data = _cell_prover_blobs(blobs)
+    n = len(data)
+    out = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * max(n, 1))
+    _chk(lib().kzg_compute_cells(out, b"".join(data), n, kzg_settings._h))
+    return _cells_of(out, n)
+
+
+def compute_cells_and_kzg_proofs(blobs, kzg_settings):
+    """c-kzg-4844's compute_cells_and_kzg_proofs: -> (cells, proofs), per blob its 128 Cells and its 128 proofs (48-byte
+    strings), the proofs by FK20 on the device.  Errors as compute_cells."""
+    data = _cell_prover_blobs(blobs)
+    n = len(data)
+    out = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * max(n, 1))
+    pr = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(n, 1))
+    _chk(lib().kzg_compute_cells_and_kzg_proofs(out, pr, b"".join(data), n, kzg_settings._h))
+    raw = pr.raw
+    proofs = [[raw[48 * (CELLS_PER_EXT_BLOB * b + c): 48 * (CELLS_PER_EXT_BLOB * b + c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
+              for b in range(n)]
+    return _cells_of(out, n), proofs
 
 
 def g1_mul_generator(scalars, kzg_settings):

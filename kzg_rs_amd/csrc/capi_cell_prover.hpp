@@ -1,0 +1,161 @@
+// capi_cell_prover.hpp - EIP-7594 cell prover (c-kzg-4844 compute_cells / compute_cells_and_kzg_proofs; not in the reference):
+// the entry points.  Part of the single translation unit kzg_capi.hip; not a stand-alone header.  Device side and the algorithm:
+// fk20_kernels.hpp, cell_ntt.hpp.
+//
+// Data flow of one call, PROVER_CHUNK blobs per launch of every kernel (the blob is a grid dimension):
+//   copy     the blobs to the device; cells 0..63 of a blob are its own bytes and never leave the host
+//   cells    k_cell_ntt: canonical check, inverse transform (coefficients, kept on the device), twist, forward transform:
+//            cells 64..127
+//   proofs   k_fk20_tvec_dft -> k_fk20_msm<Fixed> over the handle's FK20 table -> k_fk20_rows -> k_fk20_msm<Variable> ->
+//            k_fk20_compress
+// The FK20 table (8 192 points x 32 rows of 192 bytes = 48 MB on the handle) is made by the first proof call: 128 launches of the
+// prover's 64-blob commitment path over the Lagrange points, one per column k (see kzg_rs_amd.h for the measured time).  A call
+// that wants cells alone makes only the twiddle table (8 192 x 48 bytes).  Neither call reads a G2 point.
+
+struct CellProverState {
+    Fr* d_T = nullptr;             // w8192^e, 8x32 Montgomery (k_cell_roots)
+    Fr29Mem* d_W = nullptr;        // the same as twiddle entries of cell_ntt.hpp
+    G1Jac29Mem* d_X = nullptr;     // FK20 table: rows 2^(8c) X[i][k] at ((k * 64 + i) * 32 + c); nullptr until a proof call
+    Fr* d_circ = nullptr;          // the circulant's 65 scalars
+    size_t cap = 0;                // blobs the call buffers hold
+    bool cap_proofs = false;       // ... with the proof path's buffers
+    uint8_t *d_blobs = nullptr, *d_ext = nullptr, *d_out = nullptr;
+    Fr *d_coef = nullptr, *d_sc = nullptr;
+    G1Jac29Mem *d_H = nullptr, *d_Hrows = nullptr, *d_P = nullptr;
+    uint32_t* d_status = nullptr;
+    void free_calls() {
+        void* ptrs[] = {d_blobs, d_ext, d_out, d_coef, d_sc, d_H, d_Hrows, d_P, d_status};
+        for (void* q : ptrs)
+            if (q) (void)hipFree(q);
+        d_blobs = d_ext = d_out = nullptr, d_coef = d_sc = nullptr, d_H = d_Hrows = d_P = nullptr, d_status = nullptr;
+        cap = 0;
+        cap_proofs = false;
+    }
+    ~CellProverState() {
+        free_calls();
+        void* ptrs[] = {d_T, d_W, d_X, d_circ};
+        for (void* q : ptrs)
+            if (q) (void)hipFree(q);
+    }
+    KzgRet reserve(size_t m, bool proofs) {
+        if (m <= cap && (cap_proofs || !proofs)) return KZG_OK;
+        const size_t c = std::max(m, cap);
+        const bool pr = proofs || cap_proofs;
+        free_calls();
+        HIPCHK(hipMalloc(&d_blobs, (size_t)BLOB_BYTES * c));
+        HIPCHK(hipMalloc(&d_ext, (size_t)BLOB_BYTES * c));
+        HIPCHK(hipMalloc(&d_coef, sizeof(Fr) * FE_PER_BLOB * c));
+        HIPCHK(hipMalloc(&d_status, 4 * c));
+        if (pr) {
+            HIPCHK(hipMalloc(&d_sc, sizeof(Fr) * FK20_K2 * 64 * c));
+            HIPCHK(hipMalloc(&d_H, sizeof(G1Jac29Mem) * FK20_K2 * c));
+            HIPCHK(hipMalloc(&d_Hrows, sizeof(G1Jac29Mem) * FK20_K2 * FK20_ROWS * c));
+            HIPCHK(hipMalloc(&d_P, sizeof(G1Jac29Mem) * FK20_K2 * c));
+            HIPCHK(hipMalloc(&d_out, (size_t)48 * FK20_K2 * c));
+        }
+        cap = c;
+        cap_proofs = pr;
+        return KZG_OK;
+    }
+};
+static void cell_prover_release(const KzgSettings* s) {
+    delete s->cell_prover;
+    s->cell_prover = nullptr;
+}
+// the caller holds the handle's lock and has selected the plain stream pair
+static KzgRet cell_prover_state(const KzgSettings* s, CellProverState** out) {
+    if (!s->cell_prover) {
+        std::unique_ptr<CellProverState> c(new CellProverState());
+        StreamDrain drain{s->s1};
+        HIPCHK(hipMalloc(&c->d_T, sizeof(Fr) * EXT_FE));
+        HIPCHK(hipMalloc(&c->d_W, sizeof(Fr29Mem) * NTT_ROOTS));
+        hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T);
+        hipLaunchKernelGGL(k_fk20_twiddles, dim3(NTT_ROOTS / 256), dim3(256), 0, s->s1, (const Fr*)c->d_T, c->d_W);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s->s1));
+        s->cell_prover = c.release();
+    }
+    *out = s->cell_prover;
+    return KZG_OK;
+}
+// the FK20 table, column by column: X[.][k] = the commitments of the 64 "blobs" of k_fk20_setup_scalars
+static KzgRet cell_prover_tables(const KzgSettings* s, CellProverState& c) {
+    if (c.d_X) return KZG_OK;
+    ProverBufs* bp = nullptr;
+    KzgRet rc = prover_bufs(s, &bp);
+    if (rc != KZG_OK) return rc;
+    StreamDrain drain{s->s1};
+    DevTmp t_jac, t_X;
+    HIPCHK(hipMalloc(&t_jac.p, sizeof(G1Jac29Mem) * CELL_FE));
+    HIPCHK(hipMalloc(&t_X.p, sizeof(G1Jac29Mem) * (size_t)CELL_FE * FK20_K2 * FK20_ROWS));
+    if (!c.d_circ) HIPCHK(hipMalloc(&c.d_circ, sizeof(Fr) * FK20_CIRC_TERMS));
+    hipLaunchKernelGGL(k_fk20_circulant, dim3(1), dim3(128), 0, s->s1, (const Fr*)c.d_T, c.d_circ);
+    for (int k = 0; k < FK20_K2; k++) {
+        hipLaunchKernelGGL(k_fk20_setup_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->d_M, (const Fr*)c.d_T, k, bp->d_sc);
+        HIPCHK(hipGetLastError());
+        if ((rc = setup_msm(s, *bp, CELL_FE)) != KZG_OK) return rc;
+        hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(CELL_FE), 0, s->s1, (const G1Jac*)bp->d_res, t_jac.as<G1Jac29Mem>(), CELL_FE);
+        hipLaunchKernelGGL(k_fk20_rows, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.as<G1Jac29Mem>(),
+                           t_X.as<G1Jac29Mem>() + (size_t)k * CELL_FE * FK20_ROWS, CELL_FE);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(s->s1));
+    c.d_X = t_X.as<G1Jac29Mem>();
+    t_X.p = nullptr;
+    return KZG_OK;
+}
+
+static KzgRet cell_prover_run(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n, const KzgSettings* s) {
+    KzgRet rc = prover_ready(s);
+    if (rc != KZG_OK || n == 0) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
+    CellProverState* cp = nullptr;
+    if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cp->reserve(std::min(n, PROVER_CHUNK), proofs_out != nullptr)) != KZG_OK) return rc;
+    if (proofs_out && (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
+    CellProverState& c = *cp;
+    if (DYN_LDS(k_cell_ntt, CELL_NTT_LDS) != hipSuccess) return fail(KZG_ERROR, "k_cell_ntt: the device refuses 144 KB of LDS per workgroup");
+    std::vector<uint32_t> st(PROVER_CHUNK);
+    StreamDrain drain{s->s1};  // (declared after the host buffer the copies write)
+    constexpr size_t EXT_BYTES = (size_t)BLOB_BYTES, CELLS_BYTES = 2 * EXT_BYTES, PROOFS_BYTES = (size_t)48 * FK20_K2;
+    for (size_t lo = 0; lo < n; lo += PROVER_CHUNK) {
+        const size_t m = std::min(PROVER_CHUNK, n - lo);
+        HIPCHK(hipMemcpyAsync(c.d_blobs, blobs + EXT_BYTES * lo, EXT_BYTES * m, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemsetAsync(c.d_status, 0, 4 * m, s->s1));
+        hipLaunchKernelGGL(k_cell_ntt, dim3((unsigned)m), dim3(CELL_NTT_THREADS), CELL_NTT_LDS, s->s1, (const uint8_t*)c.d_blobs, (const Fr29Mem*)c.d_W, c.d_coef, c.d_ext,
+                           c.d_status);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(st.data(), c.d_status, 4 * m, hipMemcpyDeviceToHost, s->s1));
+        if (cells_out)
+            HIPCHK(hipMemcpy2DAsync(cells_out + CELLS_BYTES * lo + EXT_BYTES, CELLS_BYTES, c.d_ext, EXT_BYTES, EXT_BYTES, m, hipMemcpyDeviceToHost, s->s1));
+        if (proofs_out) {
+            hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, (unsigned)m), dim3(64), 0, s->s1, (const Fr*)c.d_coef, (const Fr29Mem*)c.d_W, c.d_sc);
+            hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X, (const Fr*)c.d_sc, c.d_H);
+            hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H, c.d_Hrows, (int)(m * FK20_K2));
+            hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows, (const Fr*)c.d_circ, c.d_P);
+            hipLaunchKernelGGL(k_fk20_compress, dim3((unsigned)m), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P, c.d_out);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(proofs_out + PROOFS_BYTES * lo, c.d_out, PROOFS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
+        }
+        if (cells_out)  // cells 0..63 of a blob are the blob (the host copies them while the device works)
+            for (size_t b = 0; b < m; b++) memcpy(cells_out + CELLS_BYTES * (lo + b), blobs + EXT_BYTES * (lo + b), EXT_BYTES);
+        HIPCHK(hipStreamSynchronize(s->s1));
+        for (size_t b = 0; b < m; b++)
+            if (st[b]) return fail(KZG_BADARGS, "a blob holds a field element >= r");
+    }
+    return KZG_OK;
+}
+
+extern "C" KzgRet kzg_compute_cells(uint8_t* cells_out, const uint8_t* blobs, size_t n, const KzgSettings* s) try {
+    if (!s || (n && (!cells_out || !blobs))) return fail(KZG_BADARGS, "null argument");
+    return cell_prover_run(cells_out, nullptr, blobs, n, s);
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");
+}
+extern "C" KzgRet kzg_compute_cells_and_kzg_proofs(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n, const KzgSettings* s) try {
+    if (!s || (n && (!proofs_out || !blobs))) return fail(KZG_BADARGS, "null argument");
+    return cell_prover_run(cells_out, proofs_out, blobs, n, s);
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");
+}

@@ -116,6 +116,7 @@ struct KzgSettings {
     mutable uint64_t tcount = 0;
     mutable struct ProverBufs* prover = nullptr;  // the prover-side entry points' buffers, made by the first of those calls (capi_prover.hpp)
     mutable struct CellState* cells = nullptr;    // the cell-proof entry points' tables and buffers, made by the first of those calls (capi_cells.hpp)
+    mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the
     // last launch group, and summed over the groups finished since the last reset (kzg_kernel_stamp_totals)
@@ -574,6 +575,7 @@ static void ws_free(Workspace& w) {
 
 static void prover_release(const KzgSettings* s);  // (capi_prover.hpp)
 static void cells_release(const KzgSettings* s);   // (capi_cells.hpp)
+static void cell_prover_release(const KzgSettings* s);  // (capi_cell_prover.hpp)
 extern "C" void kzg_settings_free(KzgSettings* s) {
     if (!s) return;
     int prev = -1;
@@ -591,6 +593,7 @@ extern "C" void kzg_settings_free(KzgSettings* s) {
     if (s->h_proofs) (void)hipHostFree(s->h_proofs);
     prover_release(s);
     cells_release(s);
+    cell_prover_release(s);
     if (!s->borrowed) {  // (a lane reads its parent's tables)
         void* ptrs[] = {s->d_g1, s->d_g1_flag, s->d_g1_mult, s->d_g1_mult_aff, s->d_g1_fb_rows, s->d_fb_plan, s->d_g2, s->d_M, s->d_DM, s->d_M29, s->d_DM29, s->d_eval_a, s->d_eval_b, s->d_eval_c, s->d_tau4, s->d_prep, s->d_gen_mult, s->d_gen_mult_aff, s->prep.blob, s->verify.blob, s->verify2.blob, s->d_prep29, s->scalars.blob, s->verify3.blob, s->d_fixed_base};
         for (void* p : ptrs)

@@ -27,6 +27,7 @@
 #include "slp2.hpp"
 #include "proof_kernels.hpp"
 #include "cell_kernels.hpp"
+#include "fk20_kernels.hpp"
 
 using namespace kzg;
 
@@ -64,4 +65,5 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_pieces.hpp"
 #include "capi_prover.hpp"
 #include "capi_cells.hpp"
+#include "capi_cell_prover.hpp"
 #include "capi_debug.hpp"

@@ -156,4 +156,26 @@ impl KzgProof {
         })?;
         Ok(ok)
     }
+
+    /// c-kzg-4844's `compute_cells` (EIP-7594; not in kzg-rs): the 128 cells of every blob, blob after blob
+    /// (include/kzg_rs_amd.h).  A field element >= r is `BadArgs`.
+    pub fn compute_cells(blobs: &[Blob], kzg_settings: &KzgSettings) -> Result<Vec<Cell>, KzgError> {
+        let n = blobs.len();
+        let mut cells: Vec<u8> = alloc::vec![0u8; n * 128 * crate::dtypes::BYTES_PER_CELL];
+        ffi::check(unsafe { ffi::kzg_compute_cells(cells.as_mut_ptr(), blobs.as_ptr().cast::<u8>(), n, kzg_settings.raw()) })?;
+        cells.chunks_exact(crate::dtypes::BYTES_PER_CELL).map(Cell::from_slice).collect()
+    }
+
+    /// c-kzg-4844's `compute_cells_and_kzg_proofs`: the same cells and the 128 proofs of every blob (FK20 on the device).
+    pub fn compute_cells_and_kzg_proofs(blobs: &[Blob], kzg_settings: &KzgSettings) -> Result<(Vec<Cell>, Vec<Bytes48>), KzgError> {
+        let n = blobs.len();
+        let mut cells: Vec<u8> = alloc::vec![0u8; n * 128 * crate::dtypes::BYTES_PER_CELL];
+        let mut proofs: Vec<u8> = alloc::vec![0u8; n * 128 * 48];
+        ffi::check(unsafe {
+            ffi::kzg_compute_cells_and_kzg_proofs(cells.as_mut_ptr(), proofs.as_mut_ptr(), blobs.as_ptr().cast::<u8>(), n, kzg_settings.raw())
+        })?;
+        let cells: Result<Vec<Cell>, KzgError> = cells.chunks_exact(crate::dtypes::BYTES_PER_CELL).map(Cell::from_slice).collect();
+        let proofs: Result<Vec<Bytes48>, KzgError> = proofs.chunks_exact(48).map(Bytes48::from_slice).collect();
+        Ok((cells?, proofs?))
+    }
 }
