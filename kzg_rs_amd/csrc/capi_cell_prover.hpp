@@ -12,46 +12,35 @@
 // prover's 64-blob commitment path over the Lagrange points, one per column k (see kzg_rs_amd.h for the measured time).  A call
 // that wants cells alone makes only the twiddle table (8 192 x 48 bytes).  Neither call reads a G2 point.
 
-struct CellProverState {
-    Fr* d_T = nullptr;             // w8192^e, 8x32 Montgomery (k_cell_roots)
-    Fr29Mem* d_W = nullptr;        // the same as twiddle entries of cell_ntt.hpp
-    G1Jac29Mem* d_X = nullptr;     // FK20 table: rows 2^(8c) X[i][k] at ((k * 64 + i) * 32 + c); nullptr until a proof call
-    Fr* d_circ = nullptr;          // the circulant's 65 scalars
+struct CellProverCallBufs {  // what CellProverState::reserve rebuilds as a whole
     size_t cap = 0;                // blobs the call buffers hold
     bool cap_proofs = false;       // ... with the proof path's buffers
-    uint8_t *d_blobs = nullptr, *d_ext = nullptr, *d_out = nullptr;
-    Fr *d_coef = nullptr, *d_sc = nullptr;
-    G1Jac29Mem *d_H = nullptr, *d_Hrows = nullptr, *d_P = nullptr;
-    uint32_t* d_status = nullptr;
-    void free_calls() {
-        void* ptrs[] = {d_blobs, d_ext, d_out, d_coef, d_sc, d_H, d_Hrows, d_P, d_status};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-        d_blobs = d_ext = d_out = nullptr, d_coef = d_sc = nullptr, d_H = d_Hrows = d_P = nullptr, d_status = nullptr;
-        cap = 0;
-        cap_proofs = false;
-    }
-    ~CellProverState() {
-        free_calls();
-        void* ptrs[] = {d_T, d_W, d_X, d_circ};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-    }
+    DevBuf<uint8_t> d_blobs, d_ext, d_out;
+    DevBuf<Fr> d_coef, d_sc;
+    DevBuf<G1Jac29Mem> d_H, d_Hrows, d_P;
+    DevBuf<uint32_t> d_status;
+    void reset() { *this = CellProverCallBufs(); }
+};
+struct CellProverState : CellProverCallBufs {
+    DevBuf<Fr> d_T;             // w8192^e, 8x32 Montgomery (k_cell_roots)
+    DevBuf<Fr29Mem> d_W;        // the same as twiddle entries of cell_ntt.hpp
+    DevBuf<G1Jac29Mem> d_X;     // FK20 table: rows 2^(8c) X[i][k] at ((k * 64 + i) * 32 + c); empty until a proof call
+    DevBuf<Fr> d_circ;          // the circulant's 65 scalars
     KzgRet reserve(size_t m, bool proofs) {
         if (m <= cap && (cap_proofs || !proofs)) return KZG_OK;
         const size_t c = std::max(m, cap);
         const bool pr = proofs || cap_proofs;
-        free_calls();
-        HIPCHK(hipMalloc(&d_blobs, (size_t)BLOB_BYTES * c));
-        HIPCHK(hipMalloc(&d_ext, (size_t)BLOB_BYTES * c));
-        HIPCHK(hipMalloc(&d_coef, sizeof(Fr) * FE_PER_BLOB * c));
-        HIPCHK(hipMalloc(&d_status, 4 * c));
+        CellProverCallBufs::reset();
+        HIPCHK(d_blobs.alloc((size_t)BLOB_BYTES * c));
+        HIPCHK(d_ext.alloc((size_t)BLOB_BYTES * c));
+        HIPCHK(d_coef.alloc(FE_PER_BLOB * c));
+        HIPCHK(d_status.alloc(c));
         if (pr) {
-            HIPCHK(hipMalloc(&d_sc, sizeof(Fr) * FK20_K2 * 64 * c));
-            HIPCHK(hipMalloc(&d_H, sizeof(G1Jac29Mem) * FK20_K2 * c));
-            HIPCHK(hipMalloc(&d_Hrows, sizeof(G1Jac29Mem) * FK20_K2 * FK20_ROWS * c));
-            HIPCHK(hipMalloc(&d_P, sizeof(G1Jac29Mem) * FK20_K2 * c));
-            HIPCHK(hipMalloc(&d_out, (size_t)48 * FK20_K2 * c));
+            HIPCHK(d_sc.alloc(FK20_K2 * 64 * c));
+            HIPCHK(d_H.alloc(FK20_K2 * c));
+            HIPCHK(d_Hrows.alloc(FK20_K2 * FK20_ROWS * c));
+            HIPCHK(d_P.alloc(FK20_K2 * c));
+            HIPCHK(d_out.alloc((size_t)48 * FK20_K2 * c));
         }
         cap = c;
         cap_proofs = pr;
@@ -67,10 +56,10 @@ static KzgRet cell_prover_state(const KzgSettings* s, CellProverState** out) {
     if (!s->cell_prover) {
         std::unique_ptr<CellProverState> c(new CellProverState());
         StreamDrain drain{s->s1};
-        HIPCHK(hipMalloc(&c->d_T, sizeof(Fr) * EXT_FE));
-        HIPCHK(hipMalloc(&c->d_W, sizeof(Fr29Mem) * NTT_ROOTS));
-        hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T);
-        hipLaunchKernelGGL(k_fk20_twiddles, dim3(NTT_ROOTS / 256), dim3(256), 0, s->s1, (const Fr*)c->d_T, c->d_W);
+        HIPCHK(c->d_T.alloc(EXT_FE));
+        HIPCHK(c->d_W.alloc(NTT_ROOTS));
+        hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T.p);
+        hipLaunchKernelGGL(k_fk20_twiddles, dim3(NTT_ROOTS / 256), dim3(256), 0, s->s1, (const Fr*)c->d_T.p, c->d_W.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s->s1));
         s->cell_prover = c.release();
@@ -80,28 +69,27 @@ static KzgRet cell_prover_state(const KzgSettings* s, CellProverState** out) {
 }
 // the FK20 table, column by column: X[.][k] = the commitments of the 64 "blobs" of k_fk20_setup_scalars
 static KzgRet cell_prover_tables(const KzgSettings* s, CellProverState& c) {
-    if (c.d_X) return KZG_OK;
+    if (c.d_X.p) return KZG_OK;
     ProverBufs* bp = nullptr;
     KzgRet rc = prover_bufs(s, &bp);
     if (rc != KZG_OK) return rc;
     StreamDrain drain{s->s1};
-    DevTmp t_jac, t_X;
-    HIPCHK(hipMalloc(&t_jac.p, sizeof(G1Jac29Mem) * CELL_FE));
-    HIPCHK(hipMalloc(&t_X.p, sizeof(G1Jac29Mem) * (size_t)CELL_FE * FK20_K2 * FK20_ROWS));
-    if (!c.d_circ) HIPCHK(hipMalloc(&c.d_circ, sizeof(Fr) * FK20_CIRC_TERMS));
-    hipLaunchKernelGGL(k_fk20_circulant, dim3(1), dim3(128), 0, s->s1, (const Fr*)c.d_T, c.d_circ);
+    DevBuf<G1Jac29Mem> t_jac, t_X;
+    HIPCHK(t_jac.alloc(CELL_FE));
+    HIPCHK(t_X.alloc((size_t)CELL_FE * FK20_K2 * FK20_ROWS));
+    HIPCHK(c.d_circ.grow(FK20_CIRC_TERMS));
+    hipLaunchKernelGGL(k_fk20_circulant, dim3(1), dim3(128), 0, s->s1, (const Fr*)c.d_T.p, c.d_circ.p);
     for (int k = 0; k < FK20_K2; k++) {
-        hipLaunchKernelGGL(k_fk20_setup_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->d_M, (const Fr*)c.d_T, k, bp->d_sc);
+        hipLaunchKernelGGL(k_fk20_setup_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->t->d_M.p, (const Fr*)c.d_T.p, k, bp->d_sc.p);
         HIPCHK(hipGetLastError());
         if ((rc = setup_msm(s, *bp, CELL_FE)) != KZG_OK) return rc;
-        hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(CELL_FE), 0, s->s1, (const G1Jac*)bp->d_res, t_jac.as<G1Jac29Mem>(), CELL_FE);
-        hipLaunchKernelGGL(k_fk20_rows, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.as<G1Jac29Mem>(),
-                           t_X.as<G1Jac29Mem>() + (size_t)k * CELL_FE * FK20_ROWS, CELL_FE);
+        hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(CELL_FE), 0, s->s1, (const G1Jac*)bp->d_res.p, t_jac.p, CELL_FE);
+        hipLaunchKernelGGL(k_fk20_rows, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.p,
+                           t_X.p + (size_t)k * CELL_FE * FK20_ROWS, CELL_FE);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(s->s1));
-    c.d_X = t_X.as<G1Jac29Mem>();
-    t_X.p = nullptr;
+    c.d_X = std::move(t_X);
     return KZG_OK;
 }
 
@@ -121,22 +109,22 @@ static KzgRet cell_prover_run(uint8_t* cells_out, uint8_t* proofs_out, const uin
     constexpr size_t EXT_BYTES = (size_t)BLOB_BYTES, CELLS_BYTES = 2 * EXT_BYTES, PROOFS_BYTES = (size_t)48 * FK20_K2;
     for (size_t lo = 0; lo < n; lo += PROVER_CHUNK) {
         const size_t m = std::min(PROVER_CHUNK, n - lo);
-        HIPCHK(hipMemcpyAsync(c.d_blobs, blobs + EXT_BYTES * lo, EXT_BYTES * m, hipMemcpyHostToDevice, s->s1));
-        HIPCHK(hipMemsetAsync(c.d_status, 0, 4 * m, s->s1));
-        hipLaunchKernelGGL(k_cell_ntt, dim3((unsigned)m), dim3(CELL_NTT_THREADS), CELL_NTT_LDS, s->s1, (const uint8_t*)c.d_blobs, (const Fr29Mem*)c.d_W, c.d_coef, c.d_ext,
-                           c.d_status);
+        HIPCHK(hipMemcpyAsync(c.d_blobs.p, blobs + EXT_BYTES * lo, EXT_BYTES * m, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemsetAsync(c.d_status.p, 0, 4 * m, s->s1));
+        hipLaunchKernelGGL(k_cell_ntt, dim3((unsigned)m), dim3(CELL_NTT_THREADS), CELL_NTT_LDS, s->s1, (const uint8_t*)c.d_blobs.p, (const Fr29Mem*)c.d_W.p, c.d_coef.p, c.d_ext.p,
+                           c.d_status.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(st.data(), c.d_status, 4 * m, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(st.data(), c.d_status.p, 4 * m, hipMemcpyDeviceToHost, s->s1));
         if (cells_out)
-            HIPCHK(hipMemcpy2DAsync(cells_out + CELLS_BYTES * lo + EXT_BYTES, CELLS_BYTES, c.d_ext, EXT_BYTES, EXT_BYTES, m, hipMemcpyDeviceToHost, s->s1));
+            HIPCHK(hipMemcpy2DAsync(cells_out + CELLS_BYTES * lo + EXT_BYTES, CELLS_BYTES, c.d_ext.p, EXT_BYTES, EXT_BYTES, m, hipMemcpyDeviceToHost, s->s1));
         if (proofs_out) {
-            hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, (unsigned)m), dim3(64), 0, s->s1, (const Fr*)c.d_coef, (const Fr29Mem*)c.d_W, c.d_sc);
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X, (const Fr*)c.d_sc, c.d_H);
-            hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H, c.d_Hrows, (int)(m * FK20_K2));
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows, (const Fr*)c.d_circ, c.d_P);
-            hipLaunchKernelGGL(k_fk20_compress, dim3((unsigned)m), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P, c.d_out);
+            hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, (unsigned)m), dim3(64), 0, s->s1, (const Fr*)c.d_coef.p, (const Fr29Mem*)c.d_W.p, c.d_sc.p);
+            hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X.p, (const Fr*)c.d_sc.p, c.d_H.p);
+            hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)(m * FK20_K2));
+            hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_circ.p, c.d_P.p);
+            hipLaunchKernelGGL(k_fk20_compress, dim3((unsigned)m), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(proofs_out + PROOFS_BYTES * lo, c.d_out, PROOFS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
+            HIPCHK(hipMemcpyAsync(proofs_out + PROOFS_BYTES * lo, c.d_out.p, PROOFS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
         }
         if (cells_out)  // cells 0..63 of a blob are the blob (the host copies them while the device works)
             for (size_t b = 0; b < m; b++) memcpy(cells_out + CELLS_BYTES * (lo + b), blobs + EXT_BYTES * (lo + b), EXT_BYTES);

@@ -74,40 +74,31 @@ extern "C" KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t* com
 // ---------------------------------------------------------------- the handle's cell state
 // Made by the first cell call (or monomial-point accessor) under the handle's lock, like the prover's buffers, and released with
 // the handle: the w8192 power table, [tau^i]G1 for i < 64, the prepared lines of (g2_points[64], G2), and grow-only call buffers.
-struct CellState {
-    Fr* d_T = nullptr;                          // w8192^e, e < 8192, Montgomery
-    uint8_t mono[CELL_FE * 48] = {};            // [tau^i]G1, compressed
-    Fp* d_lines = nullptr;                      // prepared lines of g2_points[64] then G2, 8x32 Montgomery (VERIFY)
-    uint32_t* d_lines29 = nullptr;              // the same in the latency program's format (VERIFY2)
+struct CellCallBufs {  // what CellState::reserve rebuilds as a whole
     size_t cap = 0;                             // cells the call buffers hold
-    uint8_t* d_cells = nullptr;                 // [cap] x 2048 bytes as given
-    Fr *d_vals = nullptr, *d_rM = nullptr, *d_sc_ll = nullptr, *d_sc_rl = nullptr, *d_coef = nullptr, *d_r = nullptr;
-    uint32_t *d_bad = nullptr, *d_idx = nullptr;
-    void free_calls() {
-        void* ptrs[] = {d_cells, d_vals, d_rM, d_sc_ll, d_sc_rl, d_bad, d_idx};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-        d_cells = nullptr, d_vals = d_rM = d_sc_ll = d_sc_rl = nullptr, d_bad = d_idx = nullptr;
-        cap = 0;
-    }
-    ~CellState() {
-        free_calls();
-        void* ptrs[] = {d_T, d_lines, d_lines29, d_coef, d_r};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-    }
+    DevBuf<uint8_t> d_cells;                    // [cap] x 2048 bytes as given
+    DevBuf<Fr> d_vals, d_rM, d_sc_ll, d_sc_rl;
+    DevBuf<uint32_t> d_bad, d_idx;
+    void reset() { *this = CellCallBufs(); }
+};
+struct CellState : CellCallBufs {
+    DevBuf<Fr> d_T;                             // w8192^e, e < 8192, Montgomery
+    uint8_t mono[CELL_FE * 48] = {};            // [tau^i]G1, compressed
+    DevBuf<Fp> d_lines;                         // prepared lines of g2_points[64] then G2, 8x32 Montgomery (VERIFY)
+    DevBuf<uint32_t> d_lines29;                 // the same in the latency program's format (VERIFY2)
+    DevBuf<Fr> d_coef, d_r;
     static size_t idx_words(size_t n) { return 4 * n + 2 * CELLS_PER_EXT_BLOB + 4; }  // see kzg_verify_cell_kzg_proof_batch
     KzgRet reserve(size_t n) {
         if (n <= cap) return KZG_OK;
-        free_calls();
+        CellCallBufs::reset();
         const size_t c = std::max<size_t>(n, 64);
-        HIPCHK(hipMalloc(&d_cells, CELL_BYTES * c));
-        HIPCHK(hipMalloc(&d_vals, sizeof(Fr) * CELL_FE * c));
-        HIPCHK(hipMalloc(&d_rM, sizeof(Fr) * c));
-        HIPCHK(hipMalloc(&d_sc_ll, sizeof(Fr) * c));
-        HIPCHK(hipMalloc(&d_sc_rl, sizeof(Fr) * (2 * c + CELL_FE)));
-        HIPCHK(hipMalloc(&d_bad, 4 * c));
-        HIPCHK(hipMalloc(&d_idx, 4 * idx_words(c)));
+        HIPCHK(d_cells.alloc(CELL_BYTES * c));
+        HIPCHK(d_vals.alloc(CELL_FE * c));
+        HIPCHK(d_rM.alloc(c));
+        HIPCHK(d_sc_ll.alloc(c));
+        HIPCHK(d_sc_rl.alloc(2 * c + CELL_FE));
+        HIPCHK(d_bad.alloc(c));
+        HIPCHK(d_idx.alloc(idx_words(c)));
         cap = c;
         return KZG_OK;
     }
@@ -117,7 +108,7 @@ static void cells_release(const KzgSettings* s) {
     s->cells = nullptr;
 }
 static KzgRet cells_ready(const KzgSettings* s) {
-    if (!s->d_g1) return fail(KZG_BADARGS, "cell proofs need the G1 points of a trusted-setup file; these settings hold [tau]G2 alone");
+    if (!s->t->d_g1.p) return fail(KZG_BADARGS, "cell proofs need the G1 points of a trusted-setup file; these settings hold [tau]G2 alone");
     if (s->n_g2 < (size_t)CELL_FE + 1) return fail(KZG_BADARGS, "cell proofs need g2_points[64]; these settings hold fewer than 65 G2 points");
     return prover_ready(s);
 }
@@ -129,29 +120,29 @@ static KzgRet cells_state(const KzgSettings* s, CellState** out) {
     }
     std::unique_ptr<CellState> c(new CellState());
     StreamDrain drain{s->s1};
-    HIPCHK(hipMalloc(&c->d_T, sizeof(Fr) * EXT_FE));
-    HIPCHK(hipMalloc(&c->d_coef, sizeof(Fr) * CELL_FE * CELLS_PER_EXT_BLOB));
-    HIPCHK(hipMalloc(&c->d_r, sizeof(Fr)));
-    hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T);
+    HIPCHK(c->d_T.alloc(EXT_FE));
+    HIPCHK(c->d_coef.alloc(CELL_FE * CELLS_PER_EXT_BLOB));
+    HIPCHK(c->d_r.alloc(1));
+    hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T.p);
     // [tau^i]G1 = sum_j w_j^i g1_points[j]: the commitments of 64 "blobs" over the Lagrange points, on the prover's MSM path
     ProverBufs* bp = nullptr;
     KzgRet rc = prover_bufs(s, &bp);
     if (rc != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_cell_monomial_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->d_M, bp->d_sc);
+    hipLaunchKernelGGL(k_cell_monomial_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->t->d_M.p, bp->d_sc.p);
     HIPCHK(hipGetLastError());
     if ((rc = setup_msm(s, *bp, CELL_FE)) != KZG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(c->mono, bp->d_out, sizeof c->mono, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(c->mono, bp->d_out.p, sizeof c->mono, hipMemcpyDeviceToHost, s->s1));
     // the lines of (g2_points[64], G2): the PREP program on two instances, as kzg_pairings_verify runs it per call
-    const size_t n_lines = (size_t)2 * s->prep.p.n_out;
-    DevTmp t_q;
-    HIPCHK(hipMalloc(&t_q.p, sizeof(Fp) * 8));
-    HIPCHK(hipMalloc(&c->d_lines, sizeof(Fp) * n_lines));
-    HIPCHK(hipMalloc(&c->d_lines29, (size_t)64 * n_lines));
-    HIPCHK(hipMemcpyAsync(t_q.p, s->d_g2 + 4 * CELL_FE, sizeof(Fp) * 4, hipMemcpyDeviceToDevice, s->s1));
-    hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, t_q.as<Fp>() + 4);
+    const size_t n_lines = (size_t)2 * s->t->prep.p.n_out;
+    DevBuf<Fp> t_q;
+    HIPCHK(t_q.alloc(8));
+    HIPCHK(c->d_lines.alloc(n_lines));
+    HIPCHK(c->d_lines29.alloc(16 * n_lines));
+    HIPCHK(hipMemcpyAsync(t_q.p, s->t->d_g2.p + 4 * CELL_FE, sizeof(Fp) * 4, hipMemcpyDeviceToDevice, s->s1));
+    hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, t_q.p + 4);
     HIPCHK(hipGetLastError());
-    if ((rc = run_program(s->prep, t_q.as<Fp>(), nullptr, c->d_lines, 2, s->s1)) != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s->s1, (const Fp*)c->d_lines, c->d_lines29, (int)n_lines);
+    if ((rc = run_program(s->t->prep, t_q.p, nullptr, c->d_lines.p, 2, s->s1)) != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s->s1, (const Fp*)c->d_lines.p, c->d_lines29.p, (int)n_lines);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->s1));
     s->cells = c.release();
@@ -162,21 +153,21 @@ static KzgRet cells_state(const KzgSettings* s, CellState** out) {
 // e(LL, g2_points[64]) == e(RL, G2) on the cached lines: kzg_pairings_verify's VERIFY step without its per-call PREP
 static KzgRet cells_pairing(const KzgSettings* s, const CellState& c, const uint8_t ll[48], const uint8_t rl[48], bool* ok) {
     Workspace& w = s->ws;
-    uint8_t* h = w.h_buf;  // pinned: [LL | RL] in, then flags and the program's output
+    uint8_t* h = w.h_buf.p;  // pinned: [LL | RL] in, then flags and the program's output
     memcpy(h, ll, 48);
     memcpy(h + 48, rl, 48);
-    HIPCHK(hipMemcpyAsync(w.d_bytes, h, 96, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g1_decode, dim3(1), dim3(64), 0, s->s1, w.d_bytes, w.d_bytes, 2, w.d_points, w.d_pflag, 2, 0);
-    hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points, w.d_pflag, w.d_slp_in);
+    HIPCHK(hipMemcpyAsync(w.d_bytes.p, h, 96, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g1_decode, dim3(1), dim3(64), 0, s->s1, w.d_bytes.p, w.d_bytes.p, 2, w.d_points.p, w.d_pflag.p, 2, 0);
+    hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points.p, w.d_pflag.p, w.d_slp_in.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
-    KzgRet rc = pairing_latency_form(1) ? run_program2(s->verify2, w.d_slp_in, c.d_lines29, w.d_slp_out, 1, s->s1)
-                                        : run_program(s->verify, w.d_slp_in, c.d_lines, w.d_slp_out, 1, s->s1);
+    KzgRet rc = pairing_latency_form(1) ? run_program2(s->t->verify2, w.d_slp_in.p, c.d_lines29.p, w.d_slp_out.p, 1, s->s1)
+                                        : run_program(s->t->verify, w.d_slp_in.p, c.d_lines.p, w.d_slp_out.p, 1, s->s1);
     if (rc != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[4], s->s1));
     uint32_t* hf = reinterpret_cast<uint32_t*>(h + 128);  // [g1 flags 2 | out 72]
-    HIPCHK(hipMemcpyAsync(hf, w.d_pflag, 8, hipMemcpyDeviceToHost, s->s1));
-    HIPCHK(hipMemcpyAsync(hf + 2, w.d_slp_out, sizeof(Fp) * 6, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(hf, w.d_pflag.p, 8, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(hf + 2, w.d_slp_out.p, sizeof(Fp) * 6, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     elapsed(&s->timings[3], s->ev[3], s->ev[4]);
     if (hf[0] == G1_INVALID || hf[1] == G1_INVALID) return fail(KZG_ERROR, "cell batch: an MSM result did not decode");
@@ -258,35 +249,35 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
         hash();  // (no thread to be had: hash first)
     }
     // points [proofs | distinct commitments | [tau^i]G1] -> decoded, subgroup-tested, table rows (kzg_g1_msm's decode)
-    uint8_t* hp = w.h_buf;  // pinned, at least 128 N bytes (ws_reserve)
+    uint8_t* hp = w.h_buf.p;  // pinned, at least 128 N bytes (ws_reserve)
     memcpy(hp, proofs, 48 * n);
     for (size_t i = 0; i < m; i++) memcpy(hp + 48 * (n + i), commitments + 48 * (size_t)uniq[i], 48);
     memcpy(hp + 48 * (n + m), cs->mono, sizeof cs->mono);
     HIPCHK(hipEventRecord(s->ev[5], s->s1));
-    HIPCHK(hipMemcpyAsync(w.d_bytes, hp, 48 * N, hipMemcpyHostToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_bytes.p, hp, 48 * N, hipMemcpyHostToDevice, s->s1));
     const bool aff = msm_affine_enabled();
     const unsigned blocks256 = (unsigned)((N + 255) / 256);
     if (aff) {
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3(blocks256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, w.d_bytes,
-                           w.d_bytes, (int)N, w.d_points, w.d_pflag, w.d_mult, w.d_jtmp, (int)N, (int)N);
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3(blocks256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, w.d_bytes.p,
+                           w.d_bytes.p, (int)N, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, (int)N, (int)N);
         const unsigned conv_blocks = (unsigned)((N + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
-        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp, w.d_pflag, (G1Aff29Mem*)w.d_mult, (int)N, (int)N);
+        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp.p, w.d_pflag.p, (G1Aff29Mem*)w.d_mult.p, (int)N, (int)N);
     } else {
         hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((N + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1,
-                           w.d_bytes, w.d_bytes, (int)N, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, (int)N, (int)N);
+                           w.d_bytes.p, w.d_bytes.p, (int)N, w.d_points.p, w.d_pflag.p, w.d_mult.p, (G1Jac29Mem*)nullptr, (int)N, (int)N);
     }
     HIPCHK(hipGetLastError());
     // the cells -> plain limbs with their canonical flags, and the index arrays
-    uint32_t* const d_cidx = cs->d_idx;
+    uint32_t* const d_cidx = cs->d_idx.p;
     const size_t o_order = n, o_start = 2 * n, o_cols = o_start + CELLS_PER_EXT_BLOB + 1, o_wlist = o_cols + CELLS_PER_EXT_BLOB, o_wstart = o_wlist + n;
-    HIPCHK(hipMemcpyAsync(cs->d_idx, idx.data(), 4 * (o_wstart + m + 1), hipMemcpyHostToDevice, s->s1));
-    HIPCHK(hipMemsetAsync(cs->d_bad, 0, 4 * n, s->s1));
-    HIPCHK(hipMemcpyAsync(cs->d_cells, cells, CELL_BYTES * n, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * n + 255) / 256)), dim3(256), 0, s->s1, (const uint8_t*)cs->d_cells, cs->d_vals, cs->d_bad,
+    HIPCHK(hipMemcpyAsync(cs->d_idx.p, idx.data(), 4 * (o_wstart + m + 1), hipMemcpyHostToDevice, s->s1));
+    HIPCHK(hipMemsetAsync(cs->d_bad.p, 0, 4 * n, s->s1));
+    HIPCHK(hipMemcpyAsync(cs->d_cells.p, cells, CELL_BYTES * n, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * n + 255) / 256)), dim3(256), 0, s->s1, (const uint8_t*)cs->d_cells.p, cs->d_vals.p, cs->d_bad.p,
                        (int)(CELL_FE * n));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_bad.data(), cs->d_bad, 4 * n, hipMemcpyDeviceToHost, s->s1));
-    HIPCHK(hipMemcpyAsync(h_pflag.data(), w.d_pflag, 4 * N, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(h_bad.data(), cs->d_bad.p, 4 * n, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(h_pflag.data(), w.d_pflag.p, 4 * N, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipEventRecord(s->ev[6], s->s1));
     if (hasher.joinable()) hasher.join();
     HIPCHK(hipStreamSynchronize(s->s1));
@@ -301,25 +292,25 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     uint8_t r_le[32];
     reverse32(r_le, r_be);
     HIPCHK(hipEventRecord(s->ev[7], s->s1));
-    HIPCHK(hipMemcpyAsync(cs->d_r, r_le, 32, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_cell_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, (const Fr*)cs->d_r, (const uint32_t*)d_cidx, (const Fr*)cs->d_T, cs->d_rM,
-                       cs->d_sc_ll, cs->d_sc_rl, (int)n);
-    hipLaunchKernelGGL(k_cell_commitment_weights, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const Fr*)cs->d_rM, (const uint32_t*)(d_cidx + o_wlist),
-                       (const uint32_t*)(d_cidx + o_wstart), cs->d_sc_rl + n, (int)m);
-    hipLaunchKernelGGL(k_cell_column_ifft, dim3((unsigned)U), dim3(64), 0, s->s1, (const Fr*)cs->d_vals, (const Fr*)cs->d_rM, (const uint32_t*)(d_cidx + o_order),
-                       (const uint32_t*)(d_cidx + o_start), (const uint32_t*)(d_cidx + o_cols), (const Fr*)cs->d_T, cs->d_coef);
-    hipLaunchKernelGGL(k_cell_interp_sum, dim3(1), dim3(64), 0, s->s1, (const Fr*)cs->d_coef, U, cs->d_sc_rl + n + m);
+    HIPCHK(hipMemcpyAsync(cs->d_r.p, r_le, 32, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_cell_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, (const Fr*)cs->d_r.p, (const uint32_t*)d_cidx, (const Fr*)cs->d_T.p, cs->d_rM.p,
+                       cs->d_sc_ll.p, cs->d_sc_rl.p, (int)n);
+    hipLaunchKernelGGL(k_cell_commitment_weights, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const Fr*)cs->d_rM.p, (const uint32_t*)(d_cidx + o_wlist),
+                       (const uint32_t*)(d_cidx + o_wstart), cs->d_sc_rl.p + n, (int)m);
+    hipLaunchKernelGGL(k_cell_column_ifft, dim3((unsigned)U), dim3(64), 0, s->s1, (const Fr*)cs->d_vals.p, (const Fr*)cs->d_rM.p, (const uint32_t*)(d_cidx + o_order),
+                       (const uint32_t*)(d_cidx + o_start), (const uint32_t*)(d_cidx + o_cols), (const Fr*)cs->d_T.p, cs->d_coef.p);
+    hipLaunchKernelGGL(k_cell_interp_sum, dim3(1), dim3(64), 0, s->s1, (const Fr*)cs->d_coef.p, U, cs->d_sc_rl.p + n + m);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[8], s->s1));
     // the two sums over the one set of tables (each decoded proof serves both); g1_msm_core splits its scalars in place
-    const G1MsmTables tb{w.d_mult, w.d_pflag, (int)N, aff, false};
+    const G1MsmTables tb{w.d_mult.p, w.d_pflag.p, (int)N, aff, false};
     uint8_t ll[48], rl[48];
-    HIPCHK(hipMemcpyAsync(w.d_scalars, cs->d_sc_ll, sizeof(Fr) * n, hipMemcpyDeviceToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_scalars.p, cs->d_sc_ll.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, s->s1));
     if ((rc = g1_msm_core(s, n, tb, ll)) != KZG_OK) return rc;
     const float msm_ll = s->timings[2];
     elapsed(&s->timings[6], s->ev[5], s->ev[6]);
     elapsed(&s->timings[4], s->ev[7], s->ev[8]);
-    HIPCHK(hipMemcpyAsync(w.d_scalars, cs->d_sc_rl, sizeof(Fr) * N, hipMemcpyDeviceToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_scalars.p, cs->d_sc_rl.p, sizeof(Fr) * N, hipMemcpyDeviceToDevice, s->s1));
     if ((rc = g1_msm_core(s, N, tb, rl)) != KZG_OK) return rc;
     s->timings[2] += msm_ll;
     if ((rc = cells_pairing(s, *cs, ll, rl, ok)) != KZG_OK) return rc;

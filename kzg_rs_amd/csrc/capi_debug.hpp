@@ -32,19 +32,20 @@ extern "C" KzgRet kzg_debug_slp_bench(float* ms_out, float* mhz_out, int instanc
     if (!s || !ms_out || instances < 1) return fail(KZG_BADARGS, "bad argument");
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
-    DevTmp t_in, t_out, t_clk;
-    HIPCHK(hipMalloc(&t_in.p, sizeof(Fp) * 6 * instances));
-    HIPCHK(hipMalloc(&t_out.p, sizeof(Fp) * 6 * instances));
-    HIPCHK(hipMalloc(&t_clk.p, 16));
-    Fp *d_in = t_in.as<Fp>(), *d_out = t_out.as<Fp>();
-    unsigned long long* d_clk = t_clk.as<unsigned long long>();
+    DevBuf<Fp> t_in, t_out;
+    DevBuf<unsigned long long> t_clk;
+    HIPCHK(t_in.alloc((size_t)6 * instances));
+    HIPCHK(t_out.alloc((size_t)6 * instances));
+    HIPCHK(t_clk.alloc(2));
+    Fp *d_in = t_in.p, *d_out = t_out.p;
+    unsigned long long* d_clk = t_clk.p;
     HIPCHK(hipMemset(d_in, 0, sizeof(Fp) * 6 * instances));
-    KzgRet rc = run_program(s->verify, d_in, s->d_prep, d_out, instances, s->s1);
+    KzgRet rc = run_program(s->t->verify, d_in, s->t->d_prep.p, d_out, instances, s->s1);
     if (rc != KZG_OK) return rc;
     HIPCHK(hipStreamSynchronize(s->s1));
     HIPCHK(hipEventRecord(s->ev[2], s->s1));
     for (int i = 0; i < reps; i++)
-        if ((rc = run_program(s->verify, d_in, s->d_prep, d_out, instances, s->s1)) != KZG_OK) return rc;
+        if ((rc = run_program(s->t->verify, d_in, s->t->d_prep.p, d_out, instances, s->s1)) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
     HIPCHK(hipEventSynchronize(s->ev[3]));
     float ms = 0;
@@ -65,12 +66,12 @@ extern "C" KzgRet kzg_debug_msm_sum_quads(uint8_t out[144], const uint8_t* point
     if (!s || !out || !points || npts < 2 || npts > SUMQ_MAX_POINTS || (npts & (npts - 1))) return fail(KZG_BADARGS, "bad argument");
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
-    DevTmp t_in, t_out;
-    HIPCHK(hipMalloc(&t_in.p, sizeof(G1Jac) * npts));
-    HIPCHK(hipMalloc(&t_out.p, sizeof(G1Jac)));
+    DevBuf<G1Jac> t_in, t_out;
+    HIPCHK(t_in.alloc((size_t)npts));
+    HIPCHK(t_out.alloc(1));
     HIPCHK(hipMemcpy(t_in.p, points, sizeof(G1Jac) * npts, hipMemcpyHostToDevice));
     HIPCHK(DYN_LDS(k_msm_sum_quads, SUMQ_LDS_BYTES));
-    hipLaunchKernelGGL(k_msm_sum_quads, dim3(1), dim3(256), SUMQ_LDS_BYTES, s->s1, t_in.as<G1Jac>(), t_out.as<G1Jac>(), npts);
+    hipLaunchKernelGGL(k_msm_sum_quads, dim3(1), dim3(256), SUMQ_LDS_BYTES, s->s1, t_in.p, t_out.p, npts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->s1));
     HIPCHK(hipMemcpy(out, t_out.p, sizeof(G1Jac), hipMemcpyDeviceToHost));

@@ -103,19 +103,9 @@ static void elapsed(float* out, hipEvent_t a, hipEvent_t b) {
     }
 }
 
-// a scratch device allocation of one call: released on every path out of the function (hipFree waits for the work that
-// may still use it)
-struct DevTmp {
-    void* p = nullptr;
-    DevTmp() = default;
-    DevTmp(const DevTmp&) = delete;
-    DevTmp& operator=(const DevTmp&) = delete;
-    ~DevTmp() {
-        if (p) (void)hipFree(p);
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
+// DevBuf<T> / PinnedBuf<T>: the owners of every device and pinned-host allocation.  A DevBuf local is the scratch allocation
+// of one call: released on every path out of its scope (hipFree waits for the work that may still use it).
+#include "dev_buf.hpp"
 
 // Throughput layout of the verification MSM (MSM_CHUNKS tables) with AFFINE entries and mixed additions (msm.hpp
 // k_mult_to_affine29); option msm_affine=0 keeps Jacobian entries (A/B measurement).

@@ -118,7 +118,7 @@ static KzgRet multi_allgather_partials(const KzgSettings* s, const std::vector<c
             first = "HIP: hipSetDevice inside the RCCL group";
             break;
         }
-        r = api->AllGather(h[k]->ws.d_send, h[k]->ws.d_parts, 288 * count, ncclUint8, m->comms[k], h[k]->s1);
+        r = api->AllGather(h[k]->ws.d_send.p, h[k]->ws.d_parts.p, 288 * count, ncclUint8, m->comms[k], h[k]->s1);
         if (r != ncclSuccess) first = std::string("RCCL: ") + api->GetErrorString(r) + " at ncclAllGather";
     }
     r = api->GroupEnd();  // always: an open group would swallow every later collective of the process
@@ -205,7 +205,7 @@ static KzgRet multi_build(KzgSettings* s, const uint8_t tau_g2[96], const std::v
                 for (size_t k = 0; k < D; k++) {
                     h[k] = shard_of(s, k);
                     HIPCHK(hipSetDevice(h[k]->device));
-                    HIPCHK(hipMemsetAsync(h[k]->ws.d_send, 0, 288, h[k]->s1));
+                    HIPCHK(hipMemsetAsync(h[k]->ws.d_send.p, 0, 288, h[k]->s1));
                 }
                 rc = multi_allgather_partials(s, h, 1);
                 for (size_t k = 0; k < D && rc == KZG_OK; k++) {
@@ -327,13 +327,13 @@ static KzgRet multi_pieces_locked(bool* ok, std::vector<Piece>& pieces, size_t n
         const HostBatch hb{pc.blobs, pc.c, pc.p};
         if (copy) {
             if (kind == MultiSrc::OneDevice) {  // resident on one device: the piece crosses xGMI (a caller that can should hand over per-device shards)
-                HIPCHK(hipMemcpyPeerAsync(w.d_stage_cp, c->device, pc.c, src_dev, 48 * pc.n, c->s1));
-                HIPCHK(hipMemcpyPeerAsync(w.d_stage_cp + 48 * pc.n, c->device, pc.p, src_dev, 48 * pc.n, c->s1));
-                HIPCHK(hipMemcpyPeerAsync(w.d_stage_blobs, c->device, pc.blobs, src_dev, (size_t)BLOB_BYTES * pc.n, c->s1));
+                HIPCHK(hipMemcpyPeerAsync(w.d_stage_cp.p, c->device, pc.c, src_dev, 48 * pc.n, c->s1));
+                HIPCHK(hipMemcpyPeerAsync(w.d_stage_cp.p + 48 * pc.n, c->device, pc.p, src_dev, 48 * pc.n, c->s1));
+                HIPCHK(hipMemcpyPeerAsync(w.d_stage_blobs.p, c->device, pc.blobs, src_dev, (size_t)BLOB_BYTES * pc.n, c->s1));
             }  // (a host piece: phase 1 brings it over itself, in slices across its blobs - capi_verify.hpp host_slices)
-            db = w.d_stage_blobs;
-            dc = w.d_stage_cp;
-            dp = w.d_stage_cp + 48 * pc.n;
+            db = w.d_stage_blobs.p;
+            dc = w.d_stage_cp.p;
+            dp = w.d_stage_cp.p + 48 * pc.n;
         }
         ran[i] = 1;  // (from here on the handle may have work in flight)
         return phase1_launch_locked(db, dc, dp, pc.n, 1, c, kind == MultiSrc::Host ? &hb : nullptr);
@@ -488,14 +488,14 @@ static KzgRet multi_pieces_locked(bool* ok, std::vector<Piece>& pieces, size_t n
         for (size_t k = 0; k < D; k++) h[k] = lane_of(shard_of(s, k), lane0);
         for (size_t k = 0; k < D; k++) {
             if (hipSetDevice(h[k]->device) != hipSuccess) return drain_all(fail(KZG_ERROR, "HIP: hipSetDevice"));
-            if (hipMemsetAsync(h[k]->ws.d_send, 0, 288 * cnt, h[k]->s1) != hipSuccess) return drain_all(fail(KZG_ERROR, "HIP: hipMemsetAsync"));
+            if (hipMemsetAsync(h[k]->ws.d_send.p, 0, 288 * cnt, h[k]->s1) != hipSuccess) return drain_all(fail(KZG_ERROR, "HIP: hipMemsetAsync"));
             for (size_t j = 0; j < of_shard[k].size(); j++) {
                 const KzgSettings* ph = pieces[of_shard[k][j]].h;
                 if (ph != h[k]) {  // the piece's MSM runs on its own stream: the collective's stream waits for it
                     if (hipEventRecord(ph->ev[3], ph->s1) != hipSuccess || hipStreamWaitEvent(h[k]->s1, ph->ev[3], 0) != hipSuccess)
                         return drain_all(fail(KZG_ERROR, "HIP: event between a piece and the collective"));
                 }
-                if (hipMemcpyAsync((uint8_t*)h[k]->ws.d_send + 288 * j, ph->ws.d_ab, 288, hipMemcpyDeviceToDevice, h[k]->s1) != hipSuccess)
+                if (hipMemcpyAsync((uint8_t*)h[k]->ws.d_send.p + 288 * j, ph->ws.d_ab.p, 288, hipMemcpyDeviceToDevice, h[k]->s1) != hipSuccess)
                     return drain_all(fail(KZG_ERROR, "HIP: hipMemcpyAsync"));
             }
         }
@@ -504,7 +504,7 @@ static KzgRet multi_pieces_locked(bool* ok, std::vector<Piece>& pieces, size_t n
         std::vector<uint8_t>* const cap = both ? tm.capture_rccl : tm.capture;
         if (cap) {  // (behind the collective on the fold's stream; read after finish_wait_locked has waited for that stream)
             cap->assign(288 * D * cnt, 0);
-            if (hipMemcpyAsync(cap->data(), fold->ws.d_parts, 288 * D * cnt, hipMemcpyDeviceToHost, fold->s1) != hipSuccess)
+            if (hipMemcpyAsync(cap->data(), fold->ws.d_parts.p, 288 * D * cnt, hipMemcpyDeviceToHost, fold->s1) != hipSuccess)
                 return drain_all(fail(KZG_ERROR, "HIP: hipMemcpyAsync"));
         }
         tm.ms[4] = (float)ms_since(t0);
@@ -609,7 +609,8 @@ static KzgRet multi_exchange_selftest(KzgSettings* s, bool& equal, std::string& 
     const auto t_start = std::chrono::steady_clock::now();
     KzgRet rc = multi_ensure_lanes(s, 1);
     if (rc != KZG_OK) return rc;
-    std::vector<DevTmp> d_blobs(D), d_cp(D), d_sc(D);
+    std::vector<DevBuf<uint8_t>> d_blobs(D), d_cp(D);
+    std::vector<DevBuf<Fr>> d_sc(D);
     std::vector<uint8_t> hb(nb * (size_t)BLOB_BYTES), hs(64 * nb);
     std::vector<ShardIn> in(D);
     const int saved_exchange = m->exchange;
@@ -620,11 +621,11 @@ static KzgRet multi_exchange_selftest(KzgSettings* s, bool& equal, std::string& 
             const KzgSettings* c = shard_of(s, k);
             HIPCHK(hipSetDevice(c->device));
             if (!d_blobs[k].p) {
-                HIPCHK(hipMalloc(&d_blobs[k].p, nb * (size_t)BLOB_BYTES));
-                HIPCHK(hipMalloc(&d_cp[k].p, 96 * nb));
-                HIPCHK(hipMalloc(&d_sc[k].p, 64 * nb));
+                HIPCHK(d_blobs[k].alloc(nb * (size_t)BLOB_BYTES));
+                HIPCHK(d_cp[k].alloc(96 * nb));
+                HIPCHK(d_sc[k].alloc(2 * nb));
             }
-            uint8_t* cp = d_cp[k].as<uint8_t>();
+            uint8_t* cp = d_cp[k].p;
             if (batch == 0) {
                 uint64_t x = 0x9E3779B97F4A7C15ull * (k + 1) + 0x1234567ull;  // xorshift64*: reproducible, different per shard
                 uint64_t* w = reinterpret_cast<uint64_t*>(hb.data());
@@ -641,7 +642,7 @@ static KzgRet multi_exchange_selftest(KzgSettings* s, bool& equal, std::string& 
                 }
                 HIPCHK(hipMemcpyAsync(d_blobs[k].p, hb.data(), hb.size(), hipMemcpyHostToDevice, c->s1));
                 HIPCHK(hipMemcpyAsync(d_sc[k].p, hs.data(), hs.size(), hipMemcpyHostToDevice, c->s1));
-                hipLaunchKernelGGL(k_g1_mul_generator, dim3((unsigned)((2 * nb + 63) / 64)), dim3(64), 0, c->s1, d_sc[k].as<Fr>(), cp, (int)(2 * nb));
+                hipLaunchKernelGGL(k_g1_mul_generator, dim3((unsigned)((2 * nb + 63) / 64)), dim3(64), 0, c->s1, d_sc[k].p, cp, (int)(2 * nb));
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(c->s1));  // (hb / hs are refilled for the next shard)
             } else {
@@ -651,7 +652,7 @@ static KzgRet multi_exchange_selftest(KzgSettings* s, bool& equal, std::string& 
                 HIPCHK(hipMemcpyAsync(cp, inf.data(), inf.size(), hipMemcpyHostToDevice, c->s1));
                 HIPCHK(hipStreamSynchronize(c->s1));
             }
-            in[k] = ShardIn{d_blobs[k].as<uint8_t>(), cp, cp + 48 * nb, nb};
+            in[k] = ShardIn{d_blobs[k].p, cp, cp + 48 * nb, nb};
         }
         if (rc == KZG_OK) {  // ONE run: the same partial sums through both exchanges, folded and paired once from each
             m->exchange = MULTI_EXCHANGE_BOTH;

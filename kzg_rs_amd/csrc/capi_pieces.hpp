@@ -17,8 +17,8 @@ extern "C" KzgRet kzg_compute_challenges(uint8_t* z_out, const uint8_t* blobs, c
     if (S > 1) {  // the same sliced hand-over as the batch entry point (capi_verify.hpp): segments of the chain behind the slices
         const HostBatch host{blobs, commitments, nullptr};
         HIPCHK(hipEventRecord(s->ev[0], s->s1));
-        if ((rc = sliced_points_copy(s, host, w.d_stage_cp, nullptr, n, s->ev[0])) != KZG_OK ||
-            (rc = sliced_segments(s, host, w.d_stage_blobs, w.d_stage_cp, w.d_z, n, S, s->s1)) != KZG_OK) {
+        if ((rc = sliced_points_copy(s, host, w.d_stage_cp.p, nullptr, n, s->ev[0])) != KZG_OK ||
+            (rc = sliced_segments(s, host, w.d_stage_blobs.p, w.d_stage_cp.p, w.d_z.p, n, S, s->s1)) != KZG_OK) {
             const std::string msg = g_err;
             (void)hipStreamSynchronize(s->s_copy);
             (void)hipStreamSynchronize(s->s1);
@@ -27,27 +27,27 @@ extern "C" KzgRet kzg_compute_challenges(uint8_t* z_out, const uint8_t* blobs, c
             return rc;
         }
     } else {
-        HIPCHK(hipMemcpyAsync(w.d_stage_blobs, blobs, (size_t)BLOB_BYTES * n, hipMemcpyHostToDevice, s->s1));
-        HIPCHK(hipMemcpyAsync(w.d_stage_cp, commitments, 48 * n, hipMemcpyHostToDevice, s->s1));
-        if ((rc = launch_challenge(s, w.d_stage_blobs, w.d_stage_cp, w.d_z, n)) != KZG_OK) return rc;
+        HIPCHK(hipMemcpyAsync(w.d_stage_blobs.p, blobs, (size_t)BLOB_BYTES * n, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemcpyAsync(w.d_stage_cp.p, commitments, 48 * n, hipMemcpyHostToDevice, s->s1));
+        if ((rc = launch_challenge(s, w.d_stage_blobs.p, w.d_stage_cp.p, w.d_z.p, n)) != KZG_OK) return rc;
     }
-    HIPCHK(hipMemcpyAsync(w.h_buf, w.d_z, 32 * n, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(w.h_buf.p, w.d_z.p, 32 * n, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
-    for (size_t i = 0; i < n; i++) reverse32(z_out + 32 * i, w.h_buf + 32 * i);
+    for (size_t i = 0; i < n; i++) reverse32(z_out + 32 * i, w.h_buf.p + 32 * i);
     return KZG_OK;
 }
 
 static KzgRet evaluate_device_locked(void* d_y, const void* d_blobs, const void* d_z, size_t n, const KzgSettings* s,
                                      bool* any_bad) {
     Workspace& w = s->ws;
-    HIPCHK(hipMemsetAsync(w.d_status, 0, 4 * n, s->s1));
+    HIPCHK(hipMemsetAsync(w.d_status.p, 0, 4 * n, s->s1));
     HIPCHK(hipEventRecord(s->ev[7], s->s1));
-    KzgRet rc = launch_evaluate(s, d_blobs, (const Fr*)d_z, (Fr*)d_y, w.d_status, n, /*alone=*/true);
+    KzgRet rc = launch_evaluate(s, d_blobs, (const Fr*)d_z, (Fr*)d_y, w.d_status.p, n, /*alone=*/true);
     if (rc != KZG_OK) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[8], s->s1));
-    uint32_t* h_status = reinterpret_cast<uint32_t*>(w.h_buf + 64 * n);
-    HIPCHK(hipMemcpyAsync(h_status, w.d_status, 4 * n, hipMemcpyDeviceToHost, s->s1));
+    uint32_t* h_status = reinterpret_cast<uint32_t*>(w.h_buf.p + 64 * n);
+    HIPCHK(hipMemcpyAsync(h_status, w.d_status.p, 4 * n, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     elapsed(&s->timings[4], s->ev[7], s->ev[8]);
     *any_bad = false;
@@ -77,15 +77,15 @@ extern "C" KzgRet kzg_evaluate_polynomials(uint8_t* ys_out, const uint8_t* blobs
     KzgRet rc = ws_reserve(s, n, 1, STAGE_BLOBS);
     if (rc != KZG_OK) return rc;
     Workspace& w = s->ws;
-    for (size_t i = 0; i < n; i++) reverse32(w.h_buf + 32 * i, zs + 32 * i);
-    HIPCHK(hipMemcpyAsync(w.d_stage_blobs, blobs, (size_t)BLOB_BYTES * n, hipMemcpyHostToDevice, s->s1));
-    HIPCHK(hipMemcpyAsync(w.d_z, w.h_buf, 32 * n, hipMemcpyHostToDevice, s->s1));
+    for (size_t i = 0; i < n; i++) reverse32(w.h_buf.p + 32 * i, zs + 32 * i);
+    HIPCHK(hipMemcpyAsync(w.d_stage_blobs.p, blobs, (size_t)BLOB_BYTES * n, hipMemcpyHostToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_z.p, w.h_buf.p, 32 * n, hipMemcpyHostToDevice, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     bool bad = false;
-    if ((rc = evaluate_device_locked(w.d_y, w.d_stage_blobs, w.d_z, n, s, &bad)) != KZG_OK) return rc;
+    if ((rc = evaluate_device_locked(w.d_y.p, w.d_stage_blobs.p, w.d_z.p, n, s, &bad)) != KZG_OK) return rc;
     if (bad) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
-    HIPCHK(hipMemcpy(w.h_buf, w.d_y, 32 * n, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++) reverse32(ys_out + 32 * i, w.h_buf + 32 * i);
+    HIPCHK(hipMemcpy(w.h_buf.p, w.d_y.p, 32 * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) reverse32(ys_out + 32 * i, w.h_buf.p + 32 * i);
     return KZG_OK;
 }
 
@@ -98,17 +98,17 @@ extern "C" KzgRet kzg_g1_decompress(uint8_t* status_out, uint8_t* xy_out, const 
     KzgRet rc = ws_reserve(s, (n + 1) / 2 + 1, 1, STAGE_NONE);
     if (rc != KZG_OK) return rc;
     Workspace& w = s->ws;
-    HIPCHK(hipMemcpyAsync(w.d_bytes, points48, 48 * n, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->s1, w.d_bytes, w.d_bytes, (int)n, w.d_points, w.d_pflag, (int)n, 1);
+    HIPCHK(hipMemcpyAsync(w.d_bytes.p, points48, 48 * n, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->s1, w.d_bytes.p, w.d_bytes.p, (int)n, w.d_points.p, w.d_pflag.p, (int)n, 1);
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> st(n);
-    HIPCHK(hipMemcpyAsync(st.data(), w.d_pflag, 4 * n, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(st.data(), w.d_pflag.p, 4 * n, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     for (size_t i = 0; i < n; i++) status_out[i] = (uint8_t)st[i];
     if (xy_out) {
-        DevTmp xy;
-        HIPCHK(hipMalloc(&xy.p, 96 * n));
-        hipLaunchKernelGGL(k_aff_to_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->s1, w.d_points, xy.as<uint8_t>(), (int)n);
+        DevBuf<uint8_t> xy;
+        HIPCHK(xy.alloc(96 * n));
+        hipLaunchKernelGGL(k_aff_to_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->s1, w.d_points.p, xy.p, (int)n);
         HIPCHK(hipMemcpyAsync(xy_out, xy.p, 96 * n, hipMemcpyDeviceToHost, s->s1));
         HIPCHK(hipStreamSynchronize(s->s1));
     }
@@ -141,15 +141,8 @@ struct StreamDrain {
 // the family's device scratch lives on the handle, grow-only (three or four hipMalloc + hipFree per call stalled every small-call
 // lane of the device: hipFree waits for the whole device)
 static KzgRet g1msm_scratch(const KzgSettings* s, size_t bytes, uint8_t** out) {
-    Workspace& w = s->ws;
-    if (bytes > w.cap_g1msm) {
-        if (w.d_g1msm) (void)hipFree(w.d_g1msm);
-        w.d_g1msm = nullptr;
-        w.cap_g1msm = 0;
-        HIPCHK(hipMalloc(&w.d_g1msm, bytes));
-        w.cap_g1msm = bytes;
-    }
-    *out = w.d_g1msm;
+    HIPCHK(s->ws.d_g1msm.grow(bytes));
+    *out = s->ws.d_g1msm.p;
     return KZG_OK;
 }
 struct G1MsmTables {
@@ -184,7 +177,7 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
     int fold_gp = 0;
     (void)msm_large_tail_groups(gz, fold_per, &fold_gp);
     const bool large_tail = gz >= 16 && ab_flag("g1_msm_large_tail", true) &&
-                            w.cap_msm_save >= msm_save_layer_bytes(W, 1, MSM_SAVE2_WORDS) * gz;
+                            msm_save_bytes(w) >= msm_save_layer_bytes(W, 1, MSM_SAVE2_WORDS) * gz;
     // scratch: window sums [gz_pad][W] | fold level A [gz_pad / 2][W] | fold level B [gz_pad / 4][W] | the large tail's
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_ws = up(sizeof(G1Jac) * (size_t)gz_pad * W), b_f0 = up(sizeof(G1Jac) * (size_t)std::max(1u, gz_pad / 2) * W),
@@ -199,19 +192,19 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
         HIPCHK(hipMemsetAsync(t_ws + (size_t)gz * W, 0, sizeof(G1Jac) * (size_t)(gz_pad - gz) * W, s->s1));
     HIPCHK(hipEventRecord(s->ev[2], s->s1));
     if (n) {
-        hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, w.d_scalars, (int)n);
+        hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, w.d_scalars.p, (int)n);
         if (tb.periodic && (size_t)tb.stride == (size_t)FE_PER_BLOB)
-            hipLaunchKernelGGL(k_commit_terms, dim3((unsigned)((2 * h + 255) / 256)), dim3(256), 0, s->s1, w.d_term_point, w.d_term_scalar, (int)(2 * h));
+            hipLaunchKernelGGL(k_commit_terms, dim3((unsigned)((2 * h + 255) / 256)), dim3(256), 0, s->s1, w.d_term_point.p, w.d_term_scalar.p, (int)(2 * h));
         else
-            hipLaunchKernelGGL(k_plain_terms, dim3((unsigned)((2 * h + 255) / 256)), dim3(256), 0, s->s1, w.d_term_point, w.d_term_scalar, (int)(2 * h));
+            hipLaunchKernelGGL(k_plain_terms, dim3((unsigned)((2 * h + 255) / 256)), dim3(256), 0, s->s1, w.d_term_point.p, w.d_term_scalar.p, (int)(2 * h));
     }
     MsmDesc d{};
     d.mult = const_cast<void*>(tb.mult);
     d.pflag = const_cast<uint32_t*>(tb.pflag);
-    d.scalars = w.d_scalars;
-    d.term_point = w.d_term_point;  // output 1's list starts at entry max_terms = h: term_point[i] = i (or i mod 4096) serves both
-    d.term_scalar = w.d_term_scalar;
-    d.sorted = w.d_sorted;
+    d.scalars = w.d_scalars.p;
+    d.term_point = w.d_term_point.p;  // output 1's list starts at entry max_terms = h: term_point[i] = i (or i mod 4096) serves both
+    d.term_scalar = w.d_term_scalar.p;
+    d.sorted = w.d_sorted.p;
     d.window_sums = t_ws;
     d.nterms[0] = (int)h;
     d.nterms[1] = (int)(n - h);
@@ -221,9 +214,9 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
     d.chunks = MSM_CHUNKS;
     d.chunks_per_block = MSM_CHUNKS;  // one workgroup per (window, slice): the four chunks' entries in one sorted list
     d.flags = (gz & 7) == 0 ? MSM_FLAG_XCD : 0;
-    if (tb.affine) msm_window_launch<Curve29Aff, true>(d, W, 1, gz, w.d_msm_save, w.cap_msm_save, s->s1, !large_tail);
-    else msm_window_launch<Curve29, true>(d, W, 1, gz, w.d_msm_save, w.cap_msm_save, s->s1, !large_tail);
-    if (large_tail) HIPCHK(msm_large_tail(w.d_msm_save, W, gz, fold_per, t_tail, t_ws, s->s1));
+    if (tb.affine) msm_window_launch<Curve29Aff, true>(d, W, 1, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1, !large_tail);
+    else msm_window_launch<Curve29, true>(d, W, 1, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1, !large_tail);
+    if (large_tail) HIPCHK(msm_large_tail(w.d_msm_save.p, W, gz, fold_per, t_tail, t_ws, s->s1));
     // window sums [2 S (padded to whole groups of 64 with identities)][W] -> [1][W]: trees over up to 64 slices at a time.  A level
     // with more than 64 inputs reads them in whole groups of 64: the tail of the last group is zeroed here when the level below
     // wrote a count that is not a multiple of 64 (gz = 4 160 -> 65 partial sums: round 5 read 63 uninitialised points there)
@@ -242,11 +235,11 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
         left = groups;
     }
     // 8 windows of one output: the Horner chain with four lanes per doubling / addition (0.8 -> ~0.2 ms of a 2^20-term call)
-    hipLaunchKernelGGL(k_msm_combine_quad, dim3(1), dim3(64), 0, s->s1, cur, w.d_ab, (int)W);
+    hipLaunchKernelGGL(k_msm_combine_quad, dim3(1), dim3(64), 0, s->s1, cur, w.d_ab.p, (int)W);
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
-    hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, w.d_ab, w.d_bytes, 1);
+    hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, w.d_ab.p, w.d_bytes.p, 1);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, w.d_bytes, 48, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(out, w.d_bytes.p, 48, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     elapsed(&s->timings[2], s->ev[2], s->ev[3]);
     return KZG_OK;
@@ -255,9 +248,9 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
 // reversed them on the host: 10 ms of a 2^20-term call); staged behind `skip` bytes of ws.d_bytes
 static KzgRet g1_msm_scalars_in(const KzgSettings* s, const uint8_t* scalars, size_t n, size_t skip) {
     Workspace& w = s->ws;
-    uint8_t* const stage = w.d_bytes + ((skip + 15) & ~(size_t)15);
+    uint8_t* const stage = w.d_bytes.p + ((skip + 15) & ~(size_t)15);
     HIPCHK(hipMemcpyAsync(stage, scalars, 32 * n, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_scalars_reduce_be, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, stage, w.d_scalars, (int)n);
+    hipLaunchKernelGGL(k_scalars_reduce_be, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, stage, w.d_scalars.p, (int)n);
     HIPCHK(hipGetLastError());
     return KZG_OK;
 }
@@ -276,26 +269,26 @@ extern "C" KzgRet kzg_g1_msm(uint8_t out[48], const uint8_t* points48, const uin
     StreamDrain drain{s->s1};  // (declared after `st`: destroyed - and the stream drained - before it)
     HIPCHK(hipEventRecord(s->ev[5], s->s1));
     if (n) {
-        HIPCHK(hipMemcpyAsync(w.d_bytes, points48, 48 * n, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemcpyAsync(w.d_bytes.p, points48, 48 * n, hipMemcpyHostToDevice, s->s1));
         if ((rc = g1_msm_scalars_in(s, scalars, n, 48 * n)) != KZG_OK) return rc;
         HIPCHK(hipEventRecord(s->ev[5], s->s1));
         const unsigned blocks256 = (unsigned)((n + 255) / 256);
         if (aff) {
-            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3(blocks256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, w.d_bytes,
-                               w.d_bytes, (int)n, w.d_points, w.d_pflag, w.d_mult, w.d_jtmp, (int)n, np);
+            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3(blocks256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, w.d_bytes.p,
+                               w.d_bytes.p, (int)n, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, (int)n, np);
             const unsigned conv_blocks = (unsigned)((n + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
-            hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp, w.d_pflag, (G1Aff29Mem*)w.d_mult, (int)n, np);
+            hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp.p, w.d_pflag.p, (G1Aff29Mem*)w.d_mult.p, (int)n, np);
         } else {
             hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1,
-                               w.d_bytes, w.d_bytes, (int)n, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, (int)n, np);
+                               w.d_bytes.p, w.d_bytes.p, (int)n, w.d_points.p, w.d_pflag.p, w.d_mult.p, (G1Jac29Mem*)nullptr, (int)n, np);
         }
         HIPCHK(hipGetLastError());
         // (a point outside G1 has the digit 0 in every window - the kernel reads its flag - so the verdict on the inputs is
         // looked at after the sum: one wait at the end)
-        HIPCHK(hipMemcpyAsync(st.data(), w.d_pflag, 4 * n, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(st.data(), w.d_pflag.p, 4 * n, hipMemcpyDeviceToHost, s->s1));
     }
     HIPCHK(hipEventRecord(s->ev[6], s->s1));
-    const G1MsmTables tb{w.d_mult, w.d_pflag, np, aff, false};
+    const G1MsmTables tb{w.d_mult.p, w.d_pflag.p, np, aff, false};
     if ((rc = g1_msm_core(s, n, tb, out)) != KZG_OK) return rc;
     elapsed(&s->timings[6], s->ev[5], s->ev[6]);
     for (size_t i = 0; i < n; i++)
@@ -318,15 +311,14 @@ extern "C" KzgRet kzg_g1_mul_generator(uint8_t* out48, const uint8_t* scalars, s
         while (be_geq_r(t)) be_sub_r(t);
         reverse32(le.data() + 32 * i, t);
     }
-    DevTmp ts, to;
-    HIPCHK(hipMalloc(&ts.p, 32 * n));
-    HIPCHK(hipMalloc(&to.p, 48 * n));
-    Fr* d_s = ts.as<Fr>();
-    uint8_t* d_o = to.as<uint8_t>();
-    HIPCHK(hipMemcpyAsync(d_s, le.data(), 32 * n, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g1_mul_generator, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->s1, d_s, d_o, (int)n);
+    DevBuf<Fr> d_s;
+    DevBuf<uint8_t> d_o;
+    HIPCHK(d_s.alloc(n));
+    HIPCHK(d_o.alloc(48 * n));
+    HIPCHK(hipMemcpyAsync(d_s.p, le.data(), 32 * n, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g1_mul_generator, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->s1, d_s.p, d_o.p, (int)n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out48, d_o, 48 * n, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(out48, d_o.p, 48 * n, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     return KZG_OK;
 } catch (const std::bad_alloc&) {
@@ -341,17 +333,17 @@ extern "C" KzgRet kzg_pairing_check(bool* ok, const uint8_t a[48], const uint8_t
     KzgRet rc = ws_reserve(s, 2, 1, STAGE_NONE);
     if (rc != KZG_OK) return rc;
     Workspace& w = s->ws;
-    HIPCHK(hipMemcpyAsync(w.d_bytes, a, 48, hipMemcpyHostToDevice, s->s1));
-    HIPCHK(hipMemcpyAsync(w.d_bytes + 48, b, 48, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g1_decode, dim3(1), dim3(64), 0, s->s1, w.d_bytes, w.d_bytes, 2, w.d_points, w.d_pflag, 2, 0);
-    hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points, w.d_pflag, w.d_slp_in);
+    HIPCHK(hipMemcpyAsync(w.d_bytes.p, a, 48, hipMemcpyHostToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_bytes.p + 48, b, 48, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g1_decode, dim3(1), dim3(64), 0, s->s1, w.d_bytes.p, w.d_bytes.p, 2, w.d_points.p, w.d_pflag.p, 2, 0);
+    hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points.p, w.d_pflag.p, w.d_slp_in.p);
     HIPCHK(hipGetLastError());
-    uint32_t* h = reinterpret_cast<uint32_t*>(w.h_buf);
-    HIPCHK(hipMemcpyAsync(h, w.d_pflag, 8, hipMemcpyDeviceToHost, s->s1));
+    uint32_t* h = reinterpret_cast<uint32_t*>(w.h_buf.p);
+    HIPCHK(hipMemcpyAsync(h, w.d_pflag.p, 8, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
-    if ((rc = run_verify(s, w.d_slp_in, w.d_slp_out, 1, s->s1)) != KZG_OK) return rc;
+    if ((rc = run_verify(s, w.d_slp_in.p, w.d_slp_out.p, 1, s->s1)) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[4], s->s1));
-    HIPCHK(hipMemcpyAsync(h + 2, w.d_slp_out, sizeof(Fp) * 6, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(h + 2, w.d_slp_out.p, sizeof(Fp) * 6, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     elapsed(&s->timings[3], s->ev[3], s->ev[4]);
     if (h[0] == G1_INVALID || h[1] == G1_INVALID) return fail(KZG_BADARGS, "invalid G1 point");
@@ -378,13 +370,15 @@ extern "C" KzgRet kzg_pairings_verify(bool* ok, const uint8_t a1[48], const uint
     KzgRet rc = ws_reserve(s, 2, 1, STAGE_NONE);
     if (rc != KZG_OK) return rc;
     Workspace& w = s->ws;
-    const size_t n_lines = (size_t)2 * s->prep.p.n_out;
-    DevTmp t_g2b, t_q, t_flag, t_lines, t_lines29;
-    HIPCHK(hipMalloc(&t_g2b.p, 192));
-    HIPCHK(hipMalloc(&t_q.p, sizeof(Fp) * 8));
-    HIPCHK(hipMalloc(&t_flag.p, 8));
-    HIPCHK(hipMalloc(&t_lines.p, sizeof(Fp) * n_lines));
-    HIPCHK(hipMalloc(&t_lines29.p, (size_t)64 * n_lines));
+    const size_t n_lines = (size_t)2 * s->t->prep.p.n_out;
+    DevBuf<uint8_t> t_g2b;
+    DevBuf<Fp> t_q, t_lines;
+    DevBuf<uint32_t> t_flag, t_lines29;
+    HIPCHK(t_g2b.alloc(192));
+    HIPCHK(t_q.alloc(8));
+    HIPCHK(t_flag.alloc(2));
+    HIPCHK(t_lines.alloc(n_lines));
+    HIPCHK(t_lines29.alloc(16 * n_lines));
     auto g2_is_identity_encoding = [](const uint8_t* b) {
         if (b[0] != 0xC0) return false;
         for (int i = 1; i < 96; i++)
@@ -392,39 +386,39 @@ extern "C" KzgRet kzg_pairings_verify(bool* ok, const uint8_t a1[48], const uint
         return true;
     };
     const bool inf[2] = {g2_is_identity_encoding(a2), g2_is_identity_encoding(b2)};
-    uint8_t* h = w.h_buf;  // pinned: [a1 | b1 | a2 | b2] in, then flags and the program's output
+    uint8_t* h = w.h_buf.p;  // pinned: [a1 | b1 | a2 | b2] in, then flags and the program's output
     memcpy(h, a1, 48);
     memcpy(h + 48, b1, 48);
     memcpy(h + 96, a2, 96);
     memcpy(h + 192, b2, 96);
-    HIPCHK(hipMemcpyAsync(w.d_bytes, h, 96, hipMemcpyHostToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_bytes.p, h, 96, hipMemcpyHostToDevice, s->s1));
     HIPCHK(hipMemcpyAsync(t_g2b.p, h + 96, 192, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g1_decode, dim3(1), dim3(64), 0, s->s1, w.d_bytes, w.d_bytes, 2, w.d_points, w.d_pflag, 2, 0);
-    hipLaunchKernelGGL(k_g2_decompress_n, dim3(2), dim3(64), 0, s->s1, t_g2b.as<uint8_t>(), t_q.as<Fp>(), t_flag.as<uint32_t>());
+    hipLaunchKernelGGL(k_g1_decode, dim3(1), dim3(64), 0, s->s1, w.d_bytes.p, w.d_bytes.p, 2, w.d_points.p, w.d_pflag.p, 2, 0);
+    hipLaunchKernelGGL(k_g2_decompress_n, dim3(2), dim3(64), 0, s->s1, t_g2b.p, t_q.p, t_flag.p);
     HIPCHK(hipGetLastError());
     uint32_t* hf = reinterpret_cast<uint32_t*>(h + 320);  // [g1 flags 2 | g2 flags 2 | out 72]
-    HIPCHK(hipMemcpyAsync(hf, w.d_pflag, 8, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(hf, w.d_pflag.p, 8, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipMemcpyAsync(hf + 2, t_flag.p, 8, hipMemcpyDeviceToHost, s->s1));
     static const uint32_t one_flag = G1_INFINITY;
     for (int k = 0; k < 2; k++)
         if (inf[k]) {  // e(P, O) = 1: the pair leaves the product
-            hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, t_q.as<Fp>() + 4 * k);
-            HIPCHK(hipMemcpyAsync(w.d_pflag + k, &one_flag, 4, hipMemcpyHostToDevice, s->s1));
+            hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, t_q.p + 4 * k);
+            HIPCHK(hipMemcpyAsync(w.d_pflag.p + k, &one_flag, 4, hipMemcpyHostToDevice, s->s1));
         }
-    hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points, w.d_pflag, w.d_slp_in);
+    hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points.p, w.d_pflag.p, w.d_slp_in.p);
     HIPCHK(hipGetLastError());
-    if ((rc = run_program(s->prep, t_q.as<Fp>(), nullptr, t_lines.as<Fp>(), 2, s->s1)) != KZG_OK) return rc;
+    if ((rc = run_program(s->t->prep, t_q.p, nullptr, t_lines.p, 2, s->s1)) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
     if (pairing_latency_form(1)) {
-        hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s->s1, t_lines.as<Fp>(), t_lines29.as<uint32_t>(), (int)n_lines);
+        hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s->s1, t_lines.p, t_lines29.p, (int)n_lines);
         HIPCHK(hipGetLastError());
-        rc = run_program2(s->verify2, w.d_slp_in, t_lines29.as<uint32_t>(), w.d_slp_out, 1, s->s1);
+        rc = run_program2(s->t->verify2, w.d_slp_in.p, t_lines29.p, w.d_slp_out.p, 1, s->s1);
     } else {
-        rc = run_program(s->verify, w.d_slp_in, t_lines.as<Fp>(), w.d_slp_out, 1, s->s1);
+        rc = run_program(s->t->verify, w.d_slp_in.p, t_lines.p, w.d_slp_out.p, 1, s->s1);
     }
     if (rc != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[4], s->s1));
-    HIPCHK(hipMemcpyAsync(hf + 4, w.d_slp_out, sizeof(Fp) * 6, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(hf + 4, w.d_slp_out.p, sizeof(Fp) * 6, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     elapsed(&s->timings[3], s->ev[3], s->ev[4]);
     if (hf[0] == G1_INVALID || hf[1] == G1_INVALID) return fail(KZG_BADARGS, "invalid G1 point");
@@ -441,7 +435,7 @@ extern "C" KzgRet kzg_settings_root_of_unity(const KzgSettings* s, size_t i, uin
     HIPCHK(hipSetDevice(s->device));
     // the table holds w*R mod r; strip the Montgomery factor with one host-side REDC (test/diagnostic path only)
     Fr m;
-    HIPCHK(hipMemcpy(&m, s->d_M + i, sizeof(Fr), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&m, s->t->d_M.p + i, sizeof(Fr), hipMemcpyDeviceToHost));
     // host Montgomery reduction of one element: t = m * R^-1 mod r with 64-bit arithmetic
     const uint32_t* MOD = consts::FR_MOD;
     uint32_t t[9] = {0};
@@ -472,42 +466,39 @@ extern "C" KzgRet kzg_settings_tau_g2(const KzgSettings* s, uint8_t out[96]) {
     if (!s || !out) return fail(KZG_BADARGS, "null argument");
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
-    DevTmp t;
-    HIPCHK(hipMalloc(&t.p, 96));
-    uint8_t* d = t.as<uint8_t>();
-    hipLaunchKernelGGL(k_g2_compress, dim3(1), dim3(64), 0, s->s1, s->d_tau4, d);
+    DevBuf<uint8_t> d;
+    HIPCHK(d.alloc(96));
+    hipLaunchKernelGGL(k_g2_compress, dim3(1), dim3(64), 0, s->s1, s->t->d_tau4.p, d.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d, 96, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(out, d.p, 96, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     return KZG_OK;
 }
 
 extern "C" KzgRet kzg_settings_g1_point(const KzgSettings* s, size_t i, uint8_t out[48]) {
     if (!s || !out || i >= FE_PER_BLOB) return fail(KZG_BADARGS, "bad argument");
-    if (!s->d_g1) return fail(KZG_BADARGS, "these settings were not loaded from a trusted-setup file");
+    if (!s->t->d_g1.p) return fail(KZG_BADARGS, "these settings were not loaded from a trusted-setup file");
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
-    DevTmp t;
-    HIPCHK(hipMalloc(&t.p, 48));
-    uint8_t* d = t.as<uint8_t>();
-    hipLaunchKernelGGL(k_aff_compress, dim3(1), dim3(64), 0, s->s1, s->d_g1 + i, s->d_g1_flag + i, d, 1);
+    DevBuf<uint8_t> d;
+    HIPCHK(d.alloc(48));
+    hipLaunchKernelGGL(k_aff_compress, dim3(1), dim3(64), 0, s->s1, s->t->d_g1.p + i, s->t->d_g1_flag.p + i, d.p, 1);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d, 48, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(out, d.p, 48, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     return KZG_OK;
 }
 
 extern "C" KzgRet kzg_settings_g2_point(const KzgSettings* s, size_t i, uint8_t out[96]) {
     if (!s || !out) return fail(KZG_BADARGS, "bad argument");
-    if (!s->d_g2 || i >= s->n_g2) return fail(KZG_BADARGS, "no such G2 point in these settings");
+    if (!s->t->d_g2.p || i >= s->n_g2) return fail(KZG_BADARGS, "no such G2 point in these settings");
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
-    DevTmp t;
-    HIPCHK(hipMalloc(&t.p, 96));
-    uint8_t* d = t.as<uint8_t>();
-    hipLaunchKernelGGL(k_g2_compress, dim3(1), dim3(64), 0, s->s1, s->d_g2 + 4 * i, d);
+    DevBuf<uint8_t> d;
+    HIPCHK(d.alloc(96));
+    hipLaunchKernelGGL(k_g2_compress, dim3(1), dim3(64), 0, s->s1, s->t->d_g2.p + 4 * i, d.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d, 96, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(out, d.p, 96, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     return KZG_OK;
 }
@@ -518,6 +509,6 @@ extern "C" KzgRet kzg_pairing_check(bool* ok, const uint8_t a[48], const uint8_t
 // Lagrange-form file the crate ships.
 extern "C" KzgRet kzg_settings_is_monomial_form(bool* ok, const KzgSettings* s) {
     if (!s || !ok) return fail(KZG_BADARGS, "null argument");
-    if (!s->d_g1) return fail(KZG_BADARGS, "these settings were not loaded from a trusted-setup file");
+    if (!s->t->d_g1.p) return fail(KZG_BADARGS, "these settings were not loaded from a trusted-setup file");
     return kzg_pairing_check(ok, s->g1_first[0], s->g1_first[1], s);  // e(g1[0], [tau]G2) == e(g1[1], G2)
 }

@@ -152,8 +152,8 @@ extern "C" KzgRet kzg_debug_lane_records(uint8_t* out, size_t lane, size_t first
     std::lock_guard<std::mutex> lk(s->mu);
     if (lane > s->lanes.size()) return fail(KZG_BADARGS, "no such lane");
     const KzgSettings* l = lane_of(s, lane);
-    if (!l->ws.h_buf || first + count > l->ws.cap_n) return fail(KZG_BADARGS, "records out of range");
-    memcpy(out, l->ws.h_buf + 160 * first, 160 * count);
+    if (!l->ws.h_buf.p || first + count > l->ws.cap_n) return fail(KZG_BADARGS, "records out of range");
+    memcpy(out, l->ws.h_buf.p + 160 * first, 160 * count);
     return KZG_OK;
 }
 

@@ -6,39 +6,34 @@
 // Lagrange points, PROVER_CHUNK blobs per launch of the MSM kernels.
 constexpr size_t PROVER_CHUNK = 64;
 struct ProverBufs {
-    uint8_t *d_blobs = nullptr, *d_out = nullptr, *d_cm = nullptr;
-    Fr *d_sc = nullptr, *d_z = nullptr, *d_y = nullptr;
-    uint32_t *d_tp = nullptr, *d_ts = nullptr, *d_sorted = nullptr, *d_status = nullptr, *d_cflag = nullptr;
-    G1Jac *d_win = nullptr, *d_res = nullptr;
-    G1Aff* d_cpts = nullptr;
-    G1Jac29Mem* d_cmult = nullptr;  // the commitments' multiples, a by-product of their eight-lane decode (never read)
-    ~ProverBufs() {
-        void* ptrs[] = {d_blobs, d_out, d_cm, d_sc, d_z, d_y, d_tp, d_ts, d_sorted, d_status, d_cflag, d_win, d_res, d_cpts, d_cmult};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-    }
+    DevBuf<uint8_t> d_blobs, d_out, d_cm;
+    DevBuf<Fr> d_sc, d_z, d_y;
+    DevBuf<uint32_t> d_tp, d_ts, d_sorted, d_status, d_cflag;
+    DevBuf<G1Jac> d_win, d_res;
+    DevBuf<G1Aff> d_cpts;
+    DevBuf<G1Jac29Mem> d_cmult;  // the commitments' multiples, a by-product of their eight-lane decode (never read)
     KzgRet alloc() {
         const size_t NT = (size_t)FE_PER_BLOB, CH = PROVER_CHUNK;
-        HIPCHK(hipMalloc(&d_blobs, (size_t)BLOB_BYTES * CH));
-        HIPCHK(hipMalloc(&d_sc, sizeof(Fr) * NT * CH));
-        HIPCHK(hipMalloc(&d_tp, 4 * NT * CH));
-        HIPCHK(hipMalloc(&d_ts, 4 * NT * CH));
-        HIPCHK(hipMalloc(&d_sorted, 4 * NT * CH * MSM_WINDOWS));
-        HIPCHK(hipMalloc(&d_status, 4 * CH));
-        HIPCHK(hipMalloc(&d_win, sizeof(G1Jac) * MSM_WINDOWS * CH));
-        HIPCHK(hipMalloc(&d_res, sizeof(G1Jac) * CH));
-        HIPCHK(hipMalloc(&d_out, 48 * CH));
-        HIPCHK(hipMalloc(&d_z, sizeof(Fr) * CH));
-        HIPCHK(hipMalloc(&d_y, sizeof(Fr) * CH));
-        HIPCHK(hipMalloc(&d_cm, 48 * CH));
-        HIPCHK(hipMalloc(&d_cflag, 4 * CH));
-        HIPCHK(hipMalloc(&d_cpts, sizeof(G1Aff) * CH));
-        HIPCHK(hipMalloc(&d_cmult, sizeof(G1Jac29Mem) * MSM_CHUNKS_LATENCY * CH));
+        HIPCHK(d_blobs.alloc((size_t)BLOB_BYTES * CH));
+        HIPCHK(d_sc.alloc(NT * CH));
+        HIPCHK(d_tp.alloc(NT * CH));
+        HIPCHK(d_ts.alloc(NT * CH));
+        HIPCHK(d_sorted.alloc(NT * CH * MSM_WINDOWS));
+        HIPCHK(d_status.alloc(CH));
+        HIPCHK(d_win.alloc(MSM_WINDOWS * CH));
+        HIPCHK(d_res.alloc(CH));
+        HIPCHK(d_out.alloc(48 * CH));
+        HIPCHK(d_z.alloc(CH));
+        HIPCHK(d_y.alloc(CH));
+        HIPCHK(d_cm.alloc(48 * CH));
+        HIPCHK(d_cflag.alloc(CH));
+        HIPCHK(d_cpts.alloc(CH));
+        HIPCHK(d_cmult.alloc(MSM_CHUNKS_LATENCY * CH));
         return KZG_OK;
     }
 };
 static KzgRet prover_ready(const KzgSettings* s) {
-    if (!s->d_g1_mult) return fail(KZG_BADARGS, "these settings were not loaded from a trusted-setup file");
+    if (!s->t->d_g1_mult.p) return fail(KZG_BADARGS, "these settings were not loaded from a trusted-setup file");
     if (!s->g1_in_subgroup) return fail(KZG_BAD_SETUP, "a G1 setup point is outside the r-torsion subgroup");
     return KZG_OK;
 }
@@ -70,44 +65,37 @@ static KzgRet setup_msm(const KzgSettings* s, ProverBufs& b, size_t m) {
     // the window kernels below need ~1.6 ms for one blob and pay off from a handful of blobs per launch on).  The row sums stay on the
     // main stream here: the proof path's second stream is busy with the commitments' decode.
     static const size_t fb_max_blobs = (size_t)std::max(0L, std::min(8L, opt_int("prover_fixed_base_max_blobs", 2)));
-    if (m <= fb_max_blobs && msm_affine_enabled() && s->d_g1_mult_aff && (size_t)s->n_g1 == NT && NT * 2 * FBM_WINDOWS <= 131072) {
+    if (m <= fb_max_blobs && msm_affine_enabled() && s->t->d_g1_mult_aff.p && (size_t)s->n_g1 == NT && NT * 2 * FBM_WINDOWS <= 131072) {
         KzgRet rc = fb_rows_ready(s);
         if (rc != KZG_OK) return rc;
         const int L = FBM_SLICE_ENTRIES;
         const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * NT, L);
         Workspace& w = s->ws;
-        const size_t save_bytes = (size_t)Z * 256 * MSM_SAVE2_WORDS * 4;
-        if (save_bytes > w.cap_msm_save) {
-            if (w.d_msm_save) (void)hipFree(w.d_msm_save);
-            w.d_msm_save = nullptr;
-            w.cap_msm_save = 0;
-            HIPCHK(hipMalloc(&w.d_msm_save, save_bytes));
-            w.cap_msm_save = save_bytes;
-        }
+        if ((rc = msm_save_grow(s, (size_t)Z * 256 * MSM_SAVE2_WORDS * 4)) != KZG_OK) return rc;
         int gp = 0;
         (void)msm_large_tail_groups(Z, std::max(11, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
         uint8_t* tmp = nullptr;
         if ((rc = g1msm_scratch(s, fb_tail_bytes(gp), &tmp)) != KZG_OK) return rc;
         for (size_t k = 0; k < m; k++)
-            HIPCHK(fb_msm_launch(b.d_sc + k * NT, s->d_g1_flag, (int)NT, s->n_g1, s->d_g1_fb_rows, s->d_fb_plan, b.d_sorted, w.d_msm_save, tmp, b.d_res + k, L, 11, nullptr, s->s1));
-        hipLaunchKernelGGL(k_jac_compress_n, dim3(1), dim3(64), 0, s->s1, b.d_res, b.d_out, (int)m);
+            HIPCHK(fb_msm_launch(b.d_sc.p + k * NT, s->t->d_g1_flag.p, (int)NT, s->n_g1, s->t->d_g1_fb_rows.p, s->t->d_fb_plan.p, b.d_sorted.p, w.d_msm_save.p, tmp, b.d_res.p + k, L, 11, nullptr, s->s1));
+        hipLaunchKernelGGL(k_jac_compress_n, dim3(1), dim3(64), 0, s->s1, b.d_res.p, b.d_out.p, (int)m);
         HIPCHK(hipGetLastError());
         return KZG_OK;
     }
-    hipLaunchKernelGGL(k_commit_terms, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s->s1, b.d_tp, b.d_ts, total);
-    hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s->s1, b.d_sc, total);
+    hipLaunchKernelGGL(k_commit_terms, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s->s1, b.d_tp.p, b.d_ts.p, total);
+    hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s->s1, b.d_sc.p, total);
     // the setup's AFFINE table rows when the handle has them (mixed additions: 8M + 3S instead of 12M + 4S per bucket entry), and the
     // (window, chunk group) workgroups sized so that their sorted lists stay in LDS: one chunk (4 096 entries) per workgroup for a few
     // blobs, two (8 192) from 16 blobs on - rounds 2-5 ran Jacobian rows with four chunks per workgroup and the list in global memory
-    const bool aff = msm_affine_enabled() && s->d_g1_mult_aff != nullptr;
+    const bool aff = msm_affine_enabled() && s->t->d_g1_mult_aff.p != nullptr;
     MsmDesc d{};
-    d.mult = aff ? (void*)s->d_g1_mult_aff : s->d_g1_mult;
-    d.pflag = s->d_g1_flag;
-    d.scalars = b.d_sc;
-    d.term_point = b.d_tp;
-    d.term_scalar = b.d_ts;
-    d.sorted = b.d_sorted;
-    d.window_sums = b.d_win;
+    d.mult = aff ? (void*)s->t->d_g1_mult_aff.p : s->t->d_g1_mult.p;
+    d.pflag = s->t->d_g1_flag.p;
+    d.scalars = b.d_sc.p;
+    d.term_point = b.d_tp.p;
+    d.term_scalar = b.d_ts.p;
+    d.sorted = b.d_sorted.p;
+    d.window_sums = b.d_win.p;
     d.nterms[0] = d.nterms[1] = (int)NT;
     d.max_terms = (int)NT;
     d.stride = (int)NT;
@@ -117,10 +105,10 @@ static KzgRet setup_msm(const KzgSettings* s, ProverBufs& b, size_t m) {
     const unsigned slots = MSM_CHUNKS / d.chunks_per_block;
     KzgRet rc_save = msm_save_reserve(s, 8, slots, (unsigned)m);
     if (rc_save != KZG_OK) return rc_save;
-    if (aff) msm_window_launch<Curve29Aff, true>(d, 8, slots, (unsigned)m, s->ws.d_msm_save, s->ws.cap_msm_save, s->s1);
-    else msm_window_launch<Curve29, false>(d, 8, slots, (unsigned)m, s->ws.d_msm_save, s->ws.cap_msm_save, s->s1);
-    hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)m), dim3(64), 0, s->s1, b.d_win, b.d_res, (int)slots, 8);
-    hipLaunchKernelGGL(k_jac_compress_n, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, b.d_res, b.d_out, (int)m);
+    if (aff) msm_window_launch<Curve29Aff, true>(d, 8, slots, (unsigned)m, s->ws.d_msm_save.p, msm_save_bytes(s->ws), s->s1);
+    else msm_window_launch<Curve29, false>(d, 8, slots, (unsigned)m, s->ws.d_msm_save.p, msm_save_bytes(s->ws), s->s1);
+    hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)m), dim3(64), 0, s->s1, b.d_win.p, b.d_res.p, (int)slots, 8);
+    hipLaunchKernelGGL(k_jac_compress_n, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, b.d_res.p, b.d_out.p, (int)m);
     HIPCHK(hipGetLastError());
     return KZG_OK;
 }
@@ -139,13 +127,13 @@ extern "C" KzgRet kzg_blob_to_kzg_commitment(uint8_t* out48, const uint8_t* blob
     for (size_t lo = 0; lo < n; lo += PROVER_CHUNK) {
         const size_t m = std::min(PROVER_CHUNK, n - lo);
         const int total = (int)(m * FE_PER_BLOB);
-        HIPCHK(hipMemcpyAsync(b.d_blobs, blobs + (size_t)BLOB_BYTES * lo, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, s->s1));
-        HIPCHK(hipMemsetAsync(b.d_status, 0, 4 * m, s->s1));
-        hipLaunchKernelGGL(k_blob_scalars, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s->s1, b.d_blobs, b.d_sc, b.d_status, total);
+        HIPCHK(hipMemcpyAsync(b.d_blobs.p, blobs + (size_t)BLOB_BYTES * lo, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemsetAsync(b.d_status.p, 0, 4 * m, s->s1));
+        hipLaunchKernelGGL(k_blob_scalars, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s->s1, b.d_blobs.p, b.d_sc.p, b.d_status.p, total);
         if ((rc = setup_msm(s, b, m)) != KZG_OK) return rc;
         std::vector<uint32_t> st(m);
-        HIPCHK(hipMemcpyAsync(out48 + 48 * lo, b.d_out, 48 * m, hipMemcpyDeviceToHost, s->s1));
-        HIPCHK(hipMemcpyAsync(st.data(), b.d_status, 4 * m, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(out48 + 48 * lo, b.d_out.p, 48 * m, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(st.data(), b.d_status.p, 4 * m, hipMemcpyDeviceToHost, s->s1));
         HIPCHK(hipStreamSynchronize(s->s1));
         for (size_t i = 0; i < m; i++)
             if (st[i]) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");  // (sic) Blob::as_polynomial, src/dtypes.rs:48-57
@@ -181,14 +169,14 @@ static KzgRet compute_proofs(uint8_t* proofs48, uint8_t* ys32, const uint8_t* bl
     const size_t host_hash_max = std::min<size_t>(PROVER_CHUNK, host_challenge_max_blobs());
     for (size_t lo = 0; lo < n; lo += PROVER_CHUNK) {
         const size_t m = std::min(PROVER_CHUNK, n - lo);
-        HIPCHK(hipMemcpyAsync(b.d_blobs, blobs + (size_t)BLOB_BYTES * lo, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, s->s1));
-        HIPCHK(hipMemsetAsync(b.d_status, 0, 4 * m, s->s1));
+        HIPCHK(hipMemcpyAsync(b.d_blobs.p, blobs + (size_t)BLOB_BYTES * lo, (size_t)BLOB_BYTES * m, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemsetAsync(b.d_status.p, 0, 4 * m, s->s1));
         if (zs) {
             for (size_t i = 0; i < m; i++) reverse32(le.data() + 32 * i, zs + 32 * (lo + i));
-            HIPCHK(hipMemcpyAsync(b.d_z, le.data(), 32 * m, hipMemcpyHostToDevice, s->s1));
+            HIPCHK(hipMemcpyAsync(b.d_z.p, le.data(), 32 * m, hipMemcpyHostToDevice, s->s1));
             HIPCHK(hipStreamSynchronize(s->s1));  // `le` is reused by the next chunk
         } else {
-            HIPCHK(hipMemcpyAsync(b.d_cm, commitments + 48 * lo, 48 * m, hipMemcpyHostToDevice, s->s1));
+            HIPCHK(hipMemcpyAsync(b.d_cm.p, commitments + 48 * lo, 48 * m, hipMemcpyHostToDevice, s->s1));
             hipStream_t dec = s->s1;
             if (side) {  // decode + subgroup test of the commitments (2.5 ms on one lane each): only their verdict is needed
                 HIPCHK(hipEventRecord(s->ev[5], s->s1));
@@ -201,29 +189,29 @@ static KzgRet compute_proofs(uint8_t* proofs48, uint8_t* ys32, const uint8_t* bl
             static const bool dec_quads = ab_flag("decode_quads", true);
             const unsigned qblocks = (unsigned)((m + DECQ_POINTS_PER_BLOCK - 1) / DECQ_POINTS_PER_BLOCK);
             if (dec_quads && (int)qblocks <= s->n_cus && DYN_LDS(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, DECQ_LDS_BYTES) == hipSuccess)
-                hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, dim3(qblocks), dim3(64), DECQ_LDS_BYTES, dec, (const uint8_t*)b.d_cm, (const uint8_t*)b.d_cm, (int)m,
-                                   b.d_cpts, b.d_cflag, b.d_cmult, (int)m, (int)PROVER_CHUNK);
+                hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, dim3(qblocks), dim3(64), DECQ_LDS_BYTES, dec, (const uint8_t*)b.d_cm.p, (const uint8_t*)b.d_cm.p, (int)m,
+                                   b.d_cpts.p, b.d_cflag.p, b.d_cmult.p, (int)m, (int)PROVER_CHUNK);
             else
-                hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, dec, b.d_cm, b.d_cm, (int)m, b.d_cpts, b.d_cflag, (int)m, 1);
+                hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, dec, b.d_cm.p, b.d_cm.p, (int)m, b.d_cpts.p, b.d_cflag.p, (int)m, 1);
             if (m <= host_hash_max) {
                 const size_t threads = (size_t)std::max(1L, std::min(16L, opt_int("host_threads", 16)));
                 host_blob_challenges(le.data(), blobs + (size_t)BLOB_BYTES * lo, commitments + 48 * lo, m, threads);
-                HIPCHK(hipMemcpyAsync(b.d_z, le.data(), 32 * m, hipMemcpyHostToDevice, s->s1));
+                HIPCHK(hipMemcpyAsync(b.d_z.p, le.data(), 32 * m, hipMemcpyHostToDevice, s->s1));
                 HIPCHK(hipStreamSynchronize(s->s1));  // `le` is reused by the next chunk
-            } else if ((rc = launch_challenge(s, b.d_blobs, b.d_cm, b.d_z, m)) != KZG_OK) {
+            } else if ((rc = launch_challenge(s, b.d_blobs.p, b.d_cm.p, b.d_z.p, m)) != KZG_OK) {
                 return rc;
             }
         }
-        if ((rc = launch_evaluate(s, b.d_blobs, b.d_z, b.d_y, b.d_status, m, /*alone=*/true)) != KZG_OK) return rc;
-        hipLaunchKernelGGL(k_blob_quotient, dim3((unsigned)m), dim3(64), 0, s->s1, b.d_blobs, b.d_z, b.d_y, s->d_M, b.d_sc, b.d_status);
+        if ((rc = launch_evaluate(s, b.d_blobs.p, b.d_z.p, b.d_y.p, b.d_status.p, m, /*alone=*/true)) != KZG_OK) return rc;
+        hipLaunchKernelGGL(k_blob_quotient, dim3((unsigned)m), dim3(64), 0, s->s1, b.d_blobs.p, b.d_z.p, b.d_y.p, s->t->d_M.p, b.d_sc.p, b.d_status.p);
         HIPCHK(hipGetLastError());
         if ((rc = setup_msm(s, b, m)) != KZG_OK) return rc;
         std::vector<uint32_t> st(m), cf(m, 0);
         std::vector<uint8_t> yl(32 * m);
-        HIPCHK(hipMemcpyAsync(proofs48 + 48 * lo, b.d_out, 48 * m, hipMemcpyDeviceToHost, s->s1));
-        HIPCHK(hipMemcpyAsync(st.data(), b.d_status, 4 * m, hipMemcpyDeviceToHost, s->s1));
-        HIPCHK(hipMemcpyAsync(yl.data(), b.d_y, 32 * m, hipMemcpyDeviceToHost, s->s1));
-        if (!zs) HIPCHK(hipMemcpyAsync(cf.data(), b.d_cflag, 4 * m, hipMemcpyDeviceToHost, side ? side : s->s1));
+        HIPCHK(hipMemcpyAsync(proofs48 + 48 * lo, b.d_out.p, 48 * m, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(st.data(), b.d_status.p, 4 * m, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(yl.data(), b.d_y.p, 32 * m, hipMemcpyDeviceToHost, s->s1));
+        if (!zs) HIPCHK(hipMemcpyAsync(cf.data(), b.d_cflag.p, 4 * m, hipMemcpyDeviceToHost, side ? side : s->s1));
         HIPCHK(hipStreamSynchronize(s->s1));
         if (!zs && side) HIPCHK(hipStreamSynchronize(side));
         for (size_t i = 0; i < m; i++) {
@@ -259,24 +247,22 @@ extern "C" KzgRet kzg_compute_blob_kzg_proof(uint8_t* proofs48, const uint8_t* b
 // option g1_msm_setup_form = window | fixed forces one (tests, A/B).  timings: [2] the MSM, [6] = 0 (no decode, no tables).
 constexpr size_t FBM_MIN_TERMS = 1;
 static KzgRet fb_rows_ready(const KzgSettings* s) {
-    if (s->d_g1_fb_rows) return KZG_OK;
+    if (s->t->d_g1_fb_rows.p) return KZG_OK;
     const int N = s->n_g1;
-    DevTmp t_jac;
-    G1Aff29Mem* rows = nullptr;
-    HIPCHK(hipMalloc(&t_jac.p, sizeof(G1Jac29Mem) * (size_t)(2 * FBM_WINDOWS - 1) * N));
-    HIPCHK(hipMalloc(&rows, sizeof(G1Aff29Mem) * (size_t)2 * FBM_WINDOWS * N));
-    DevTmp own;
-    own.p = rows;  // (released on an error path)
-    if (!s->d_fb_plan) HIPCHK(hipMalloc(&s->d_fb_plan, 4 * FBM_PLAN_WORDS));
-    HIPCHK(hipMemcpyAsync(rows, s->d_g1_mult_aff, sizeof(G1Aff29Mem) * (size_t)N, hipMemcpyDeviceToDevice, s->s1));  // row 0 = P_j
-    hipLaunchKernelGGL(k_fb_build_rows, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s->s1, (const G1Aff29Mem*)s->d_g1_mult_aff, (const uint32_t*)s->d_g1_flag,
-                       t_jac.as<G1Jac29Mem>(), N);
+    DevBuf<G1Jac29Mem> t_jac;
+    DevBuf<G1Aff29Mem> t_rows;  // (released on an error path)
+    HIPCHK(t_jac.alloc((size_t)(2 * FBM_WINDOWS - 1) * N));
+    HIPCHK(t_rows.alloc((size_t)2 * FBM_WINDOWS * N));
+    G1Aff29Mem* const rows = t_rows.p;
+    HIPCHK(s->t->d_fb_plan.grow(FBM_PLAN_WORDS));
+    HIPCHK(hipMemcpyAsync(rows, s->t->d_g1_mult_aff.p, sizeof(G1Aff29Mem) * (size_t)N, hipMemcpyDeviceToDevice, s->s1));  // row 0 = P_j
+    hipLaunchKernelGGL(k_fb_build_rows, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s->s1, (const G1Aff29Mem*)s->t->d_g1_mult_aff.p, (const uint32_t*)s->t->d_g1_flag.p,
+                       t_jac.p, N);
     const int m = (2 * FBM_WINDOWS - 1) * N;
-    hipLaunchKernelGGL(k_jac29_to_aff29, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.as<G1Jac29Mem>(), rows + N, m);
+    hipLaunchKernelGGL(k_jac29_to_aff29, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.p, rows + N, m);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->s1));
-    own.p = nullptr;
-    s->d_g1_fb_rows = rows;
+    s->t->d_g1_fb_rows = std::move(t_rows);
     return KZG_OK;
 }
 extern "C" KzgRet kzg_g1_msm_setup(uint8_t out[48], const uint8_t* scalars, size_t n, const KzgSettings* s) try {
@@ -290,7 +276,7 @@ extern "C" KzgRet kzg_g1_msm_setup(uint8_t out[48], const uint8_t* scalars, size
     if ((rc = ws_reserve(s, (n + 1) / 2 + 1, 1, STAGE_NONE)) != KZG_OK) return rc;
     Workspace& w = s->ws;
     StreamDrain drain{s->s1};
-    const bool aff = msm_affine_enabled() && s->d_g1_mult_aff;
+    const bool aff = msm_affine_enabled() && s->t->d_g1_mult_aff.p;
     static const int forced = opt_is("g1_msm_setup_form", "window") ? 1 : opt_is("g1_msm_setup_form", "fixed") ? 2 : 0;
     static const int L = (int)std::max(1024L, std::min((long)FBM_SLICE_ENTRIES, ab_int("g1_msm_fb_slice", (long)FBM_SLICE_ENTRIES)));
     const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * n, L);
@@ -299,29 +285,23 @@ extern "C" KzgRet kzg_g1_msm_setup(uint8_t out[48], const uint8_t* scalars, size
     if (n && (rc = g1_msm_scalars_in(s, scalars, n, 0)) != KZG_OK) return rc;
     s->timings[6] = 0.0f;
     if (!fixed) {
-        const G1MsmTables tb{aff ? (const void*)s->d_g1_mult_aff : (const void*)s->d_g1_mult, s->d_g1_flag, s->n_g1, aff, true};
+        const G1MsmTables tb{aff ? (const void*)s->t->d_g1_mult_aff.p : (const void*)s->t->d_g1_mult.p, s->t->d_g1_flag.p, s->n_g1, aff, true};
         return g1_msm_core(s, n, tb, out);
     }
     if ((rc = fb_rows_ready(s)) != KZG_OK) return rc;
-    if (save_bytes > w.cap_msm_save) {  // (grow-only, like msm_save_reserve; this form's layers are 48 KB each)
-        if (w.d_msm_save) (void)hipFree(w.d_msm_save);
-        w.d_msm_save = nullptr;
-        w.cap_msm_save = 0;
-        HIPCHK(hipMalloc(&w.d_msm_save, save_bytes));
-        w.cap_msm_save = save_bytes;
-    }
+    if ((rc = msm_save_grow(s, save_bytes)) != KZG_OK) return rc;  // (this form's layers are 48 KB each)
     static const int fold_per_opt = (int)std::max(2L, std::min(64L, ab_int("g1_msm_fold_per", 11)));
     int gp = 0;
     (void)msm_large_tail_groups(Z, std::max(fold_per_opt, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
     uint8_t* tmp = nullptr;
     if ((rc = g1msm_scratch(s, fb_tail_bytes(gp), &tmp)) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[2], s->s1));
-    HIPCHK(fb_msm_launch(w.d_scalars, s->d_g1_flag, (int)n, s->n_g1, s->d_g1_fb_rows, s->d_fb_plan, w.d_sorted, w.d_msm_save, tmp, w.d_ab, L, fold_per_opt,
-                         w.d_ktime ? w.d_ktime + 8 : nullptr, s->s1, s->s2, s->ev[7], s->ev[8]));
+    HIPCHK(fb_msm_launch(w.d_scalars.p, s->t->d_g1_flag.p, (int)n, s->n_g1, s->t->d_g1_fb_rows.p, s->t->d_fb_plan.p, w.d_sorted.p, w.d_msm_save.p, tmp, w.d_ab.p, L, fold_per_opt,
+                         w.d_ktime.p ? w.d_ktime.p + 8 : nullptr, s->s1, s->s2, s->ev[7], s->ev[8]));
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
-    hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, w.d_ab, w.d_bytes, 1);
+    hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, w.d_ab.p, w.d_bytes.p, 1);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, w.d_bytes, 48, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(out, w.d_bytes.p, 48, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     elapsed(&s->timings[2], s->ev[2], s->ev[3]);
     return KZG_OK;

@@ -8,12 +8,12 @@
 // ---------------------------------------------------------------- settings
 struct DevProgram {
     SlpProgram p{};
-    void* blob = nullptr;  // device copy of the whole program
+    DevBuf<uint8_t> blob;  // device copy of the whole program
 };
 
 struct DevProgram2 {  // a latency program (slp2.hpp)
     Slp2Program p{};
-    void* blob = nullptr;
+    DevBuf<uint8_t> blob;
 };
 
 constexpr size_t MAX_WORLD = 64;
@@ -22,72 +22,81 @@ constexpr size_t MAX_BATCHES_PER_LAUNCH = 16384;
 constexpr unsigned MSM_MAX_SLICES = 32;
 constexpr size_t SLICED_MAX_BLOBS = 16384;  // host batches up to this size arrive in slices across the blobs (the range of the two-lane challenge form, which runs in segments)
 constexpr size_t LATENCY_MAX_BLOBS = 4096;  // launches up to this size: CU-split stream pair + the latency MSM layout
-struct Workspace {
+// The buffers that ws_reserve rebuilds as a whole when cap_n or cap_b grows, and the state of the launch group in flight on them
+struct GroupBufs {
     size_t cap_n = 0;       // batch capacity
     size_t cap_b = 0;       // batches-per-group capacity
     size_t pending_n = 0, pending_b = 0, finish_b = 0;  // group currently in flight on this handle
     int chunks = MSM_CHUNKS;                              // MSM layout of the group in flight (msm.hpp)
     size_t off_r = 0, off_part = 0, off_out = 0, off_parts = 0;  // pinned-buffer layout
-    size_t cap_stage = 0, cap_stage_cp = 0;   // staged host-input capacity: blobs | (commitment, proof) pairs
-    Fr *d_z = nullptr, *d_y = nullptr, *d_scalars = nullptr, *d_partial = nullptr, *d_r = nullptr;
-    uint32_t *d_status = nullptr, *d_pflag = nullptr, *d_term_point = nullptr, *d_term_scalar = nullptr, *d_sorted = nullptr;
-    G1Aff* d_points = nullptr;
-    G1Jac *d_window = nullptr, *d_window_sl = nullptr, *d_ab = nullptr, *d_parts = nullptr;
-    G1Jac* d_send = nullptr;  // a shard's contribution to the RCCL all-gather of partial sums: up to MAX_WORLD pieces x (A, B) (capi_multi.hpp)
-    uint32_t* d_msm_save = nullptr;  // the window kernel's bucket sums between its row and column trees (msm.hpp MsmDesc::save)
-    size_t cap_msm_save = 0;         // bytes
-    void* d_mult = nullptr;  // MSM tables: G1Jac29Mem / G1Aff29Mem entries (msm_affine_enabled())
+    DevBuf<Fr> d_z, d_y, d_scalars, d_partial, d_r;
+    DevBuf<uint32_t> d_status, d_pflag, d_term_point, d_term_scalar, d_sorted;
+    DevBuf<G1Aff> d_points;
+    DevBuf<G1Jac> d_window, d_window_sl, d_ab, d_parts;
+    DevBuf<G1Jac> d_send;  // a shard's contribution to the RCCL all-gather of partial sums: up to MAX_WORLD pieces x (A, B) (capi_multi.hpp)
+    DevBuf<uint8_t> d_mult;  // MSM tables: G1Jac29Mem / G1Aff29Mem entries (msm_affine_enabled())
     // in-kernel stamps of the last launch group (field.hpp kstamp_in / kstamp_out): 16 words - [0, 4) the throughput-form
     // challenge kernel (its interval and its clock, fr_kernels.hpp), [4, 6) k_blob_evaluate, [6, 8) the decode pass, [8, 10) the
     // MSM window kernel
-    unsigned long long* d_ktime = nullptr;
+    DevBuf<unsigned long long> d_ktime;
     bool ktime_valid = false;   // [0, 4) were written (the challenge took its throughput form)
     bool kstamps_valid = false; // [4, 10) belong to the group in flight
-    G1Jac29Mem* d_jtmp = nullptr;  // 2^64 P of every decoded point on its way to the affine table (k_mult_to_affine29)
-    bool mult_affine = false;      // format of d_mult as the last decode left it
-    Fp *d_slp_in = nullptr, *d_slp_out = nullptr;
-    uint8_t* d_g1msm = nullptr;  // kzg_g1_msm / kzg_g1_msm_setup: window sums, fold trees, the large-sum tail (grow-only; a per-call hipFree stalls every lane of the device)
-    size_t cap_g1msm = 0;
-    uint8_t *d_stage_blobs = nullptr, *d_stage_cp = nullptr, *d_bytes = nullptr, *d_records = nullptr;
-    uint32_t* d_sha_mid = nullptr;  // SHA-256 midstates between the segments of a sliced challenge chain, 32 B per blob
+    DevBuf<G1Jac29Mem> d_jtmp;  // 2^64 P of every decoded point on its way to the affine table (k_mult_to_affine29)
+    bool mult_affine = false;   // format of d_mult as the last decode left it
+    DevBuf<Fp> d_slp_in, d_slp_out;
+    DevBuf<uint8_t> d_bytes, d_records;
+    DevBuf<uint32_t> d_sha_mid;  // SHA-256 midstates between the segments of a sliced challenge chain, 32 B per blob
+    PinnedBuf<uint8_t> h_buf;    // pinned host mirrors
+    // Two scratch areas that grow on demand (msm_save_grow, g1msm_scratch) and are RELEASED with the group: up to 512 MiB of save
+    // area does not stay allocated while a larger set is made; the next MSM allocates its area again
+    DevBuf<uint32_t> d_msm_save;  // the window kernel's bucket sums between its row and column trees (msm.hpp MsmDesc::save)
+    DevBuf<uint8_t> d_g1msm;  // kzg_g1_msm / kzg_g1_msm_setup: window sums, fold trees, the large-sum tail (a per-call hipFree stalls every lane of the device)
+    void reset() { *this = GroupBufs(); }  // everything above released, capacities and state back to their defaults
+};
+// ... and the grow-only staging buffers with lifetimes of their own, which ws_reserve never touches
+struct Workspace : GroupBufs {
+    DevBuf<uint8_t> d_stage_blobs, d_stage_cp;  // staged host input: blobs | (commitment, proof) pairs
     // host-fed stream of batches (kzg_verify_blob_kzg_proof_batches): two staging sets, each [blobs | commitments | proofs]
     // of one chunk, filled on the copy stream while the other one is verified
-    uint8_t* d_hstage[2] = {nullptr, nullptr};
-    size_t cap_hstage = 0;  // blobs per staging set
-    // pinned host mirrors
-    uint8_t* h_buf = nullptr;
-    size_t h_cap = 0;
+    DevBuf<uint8_t> d_hstage[2];
 };
 
 #include "small_queue.hpp"
 
-struct KzgSettings {
-    int device = 0;
-    Fr *d_M = nullptr, *d_DM = nullptr;            // roots of unity, 8x32 Montgomery (R, R^2 scalings)
-    Fr29Mem *d_M29 = nullptr, *d_DM29 = nullptr;   // the same in radix 2^29 (fr29.hpp)
-    uint4 *d_eval_a = nullptr, *d_eval_b = nullptr;  // ... in the order k_blob_evaluate reads them (k_eval_tables)
-    uint32_t* d_eval_c = nullptr;
-    Fp* d_tau4 = nullptr;   // [tau]G2 affine (x.c0 x.c1 y.c0 y.c1), Montgomery
-    Fp* d_prep = nullptr;   // prepared lines: [tau]G2 then generator (2 * 408 Fp)
-    void* d_gen_mult = nullptr;   // the generator's MSM tables (G1Jac29Mem): [0, 4) the default layout, [4, 36) the latency layout (msm.hpp)
-    G1Aff29Mem* d_gen_mult_aff = nullptr;  // [0, 4) as affine entries
+// What is immutable once a handle is constructed: tables, prepared lines, uploaded programs.  The handle made by settings_build
+// owns one; its lanes (settings_lane) read it through KzgSettings::t.
+struct SettingsTables {
+    DevBuf<Fr> d_M, d_DM;            // roots of unity, 8x32 Montgomery (R, R^2 scalings)
+    DevBuf<Fr29Mem> d_M29, d_DM29;   // the same in radix 2^29 (fr29.hpp)
+    DevBuf<uint4> d_eval_a, d_eval_b;  // ... in the order k_blob_evaluate reads them (k_eval_tables)
+    DevBuf<uint32_t> d_eval_c;
+    DevBuf<Fp> d_tau4;   // [tau]G2 affine (x.c0 x.c1 y.c0 y.c1), Montgomery
+    DevBuf<Fp> d_prep;   // prepared lines: [tau]G2 then generator (2 * 408 Fp)
+    DevBuf<G1Jac29Mem> d_gen_mult;      // the generator's MSM tables: [0, 4) the default layout, [4, 36) the latency layout (msm.hpp)
+    DevBuf<G1Aff29Mem> d_gen_mult_aff;  // [0, 4) as affine entries
     // full trusted setup (kzg_settings_load_trusted_setup only; not needed by verification):
-    G1Aff* d_g1 = nullptr;            // g1_points, bit-reversal permuted (build.rs:79,89-105), 4096 entries
-    uint32_t* d_g1_flag = nullptr;    // 0 finite / 1 identity (unchecked decode, build.rs:68)
-    void* d_g1_mult = nullptr;        // their MSM multiples (msm.hpp), valid iff g1_in_subgroup
-    G1Aff29Mem* d_g1_mult_aff = nullptr;  // the same as AFFINE rows (the throughput layout of the verification path's MSM): kzg_g1_msm_setup's 8-bit form
-    int n_g1 = 0;                     // number of G1 Lagrange points (4096)
-    mutable G1Aff29Mem* d_g1_fb_rows = nullptr;  // fixed-base rows 2^(16 v) P_j (msm_fixed.hpp), made by the first large kzg_g1_msm_setup call
-    mutable uint32_t* d_fb_plan = nullptr;       // ... and that form's device-side plan words
-    bool g1_in_subgroup = false;      // every G1 point lies in the r-torsion (what the GLV multiples need)
-    Fp* d_g2 = nullptr;               // g2_points (monomial), n_g2 x 4 Fp
-    size_t n_g2 = 0;
-    uint8_t g1_first[2][48] = {};     // g1_points[0], [1] of the FILE order, for the monomial-form check (build.rs:107-129)
+    DevBuf<G1Aff> d_g1;            // g1_points, bit-reversal permuted (build.rs:79,89-105), 4096 entries
+    DevBuf<uint32_t> d_g1_flag;    // 0 finite / 1 identity (unchecked decode, build.rs:68)
+    DevBuf<G1Jac29Mem> d_g1_mult;  // their MSM multiples (msm.hpp), valid iff g1_in_subgroup
+    DevBuf<G1Aff29Mem> d_g1_mult_aff;  // the same as AFFINE rows (the throughput layout of the verification path's MSM): kzg_g1_msm_setup's 8-bit form
+    mutable DevBuf<G1Aff29Mem> d_g1_fb_rows;  // fixed-base rows 2^(16 v) P_j (msm_fixed.hpp), made by the first large kzg_g1_msm_setup call
+    mutable DevBuf<uint32_t> d_fb_plan;       // ... and that form's device-side plan words
+    DevBuf<Fp> d_g2;               // g2_points (monomial), n_g2 x 4 Fp
     DevProgram prep, verify;
     DevProgram2 verify2;            // VERIFY scheduled for one check at a time (kzg_rs_amd/slp/schedule2.py)
     DevProgram2 scalars, verify3;   // the one-proof path (proof_kernels.hpp): [y]G, the lines of [tau]G2 - [z]G2 | the pairing behind them
-    Fp* d_fixed_base = nullptr;     // fixed-base tables of the two generators (tools/gen_fixed_base.py), 3.4 MB
-    uint32_t* d_prep29 = nullptr;   // d_prep in the latency program's format (radix 2^29, 16 words per element)
+    DevBuf<Fp> d_fixed_base;        // fixed-base tables of the two generators (tools/gen_fixed_base.py), 3.4 MB
+    DevBuf<uint32_t> d_prep29;      // d_prep in the latency program's format (radix 2^29, 16 words per element)
+};
+
+struct KzgSettings {
+    int device = 0;
+    SettingsTables own;               // empty on a lane
+    const SettingsTables* t = &own;   // a lane: its parent's - but not the full-setup members (d_g1*, d_fb_plan, d_g2): a lane's n_g1 / n_g2 stay 0
+    int n_g1 = 0;                     // number of G1 Lagrange points (4096)
+    bool g1_in_subgroup = false;      // every G1 point lies in the r-torsion (what the GLV multiples need)
+    size_t n_g2 = 0;
+    uint8_t g1_first[2][48] = {};     // g1_points[0], [1] of the FILE order, for the monomial-form check (build.rs:107-129)
     // s1 / s2: the two streams the current launch uses (challenge chain | point decode).  They point at the plain pair,
     // or - for a small launch (a single batch) - at a pair confined to disjoint halves of the CUs: the 16 two-wave
     // workgroups of the challenge chain and the 32 decode waves otherwise land on the same first CUs of every XCD and,
@@ -101,16 +110,15 @@ struct KzgSettings {
     hipEvent_t ev[12] = {};
     mutable hipStream_t s_copy = nullptr;  // host -> device staging copies of the host-fed stream (made on first use)
     mutable hipStream_t s_aux = nullptr;   // the one-proof path's third stream: the subgroup test beside the pairing (made on first use)
-    mutable Fp* d_proof = nullptr;         // ... and its device buffers: SCALARS' inputs | VERIFY3's inputs (made on first use)
-    mutable Fp *d_proofs = nullptr, *d_proofs_out = nullptr;  // the same for MANY independent proofs (kzg_verify_kzg_proofs): [cap] records each
-    mutable uint8_t* h_proofs = nullptr;   // ... and their pinned mirror
+    mutable DevBuf<Fp> d_proof;            // ... and its device buffers: SCALARS' inputs | VERIFY3's inputs (made on first use)
+    mutable DevBuf<Fp> d_proofs, d_proofs_out;  // the same for MANY independent proofs (kzg_verify_kzg_proofs): [cap_proofs] records each
+    mutable PinnedBuf<uint8_t> h_proofs;   // ... and their pinned mirror
     mutable size_t cap_proofs = 0;
     mutable hipEvent_t ev_copy[2] = {nullptr, nullptr};
     mutable hipEvent_t ev_slice[17] = {};  // a host Vec<Blob> arriving in slices: [0] commitments + proofs landed, [1 + j] slice j landed
     mutable std::mutex mu;
     mutable Workspace ws;
-    mutable uint32_t* d_eval_scratch = nullptr;  // between the three evaluation kernels (launch_evaluate)
-    mutable size_t eval_scratch_cap = 0;
+    mutable DevBuf<uint32_t> d_eval_scratch;  // between the three evaluation kernels (launch_evaluate)
     mutable float timings[8] = {};
     mutable double tsum[8] = {};   // the same, summed over every group finished on this handle since the last reset
     mutable uint64_t tcount = 0;
@@ -130,7 +138,6 @@ struct KzgSettings {
     struct MultiState* multi = nullptr;
     // further private handles on THIS device (capi_pipeline.hpp): one per launch group kept in flight beyond the first
     mutable std::vector<KzgSettings*> lanes;
-    bool borrowed = false;          // a lane: the tables and programs above belong to the handle it was made from (settings_lane)
     uint8_t tau_g2_bytes[96] = {};  // g2_points[1] as given
     mutable float multi_ms[8] = {};  // host wall-clock stages of the last sharded call (kzg_multi_last_timings)
     mutable uint8_t multi_last_r[32] = {};  // the batch challenge of the last sharded call, little-endian (test hook kzg_debug_multi_last_r)
@@ -148,11 +155,11 @@ static KzgRet upload_program(DevProgram& dp, const unsigned char* begin, const u
     size_t len = (size_t)(end - begin);
     const uint32_t* w = reinterpret_cast<const uint32_t*>(begin);
     if (len < 64 || w[0] != SLP_MAGIC) return fail(KZG_ERROR, "embedded SLP program is corrupt");
-    HIPCHK(hipMalloc(&dp.blob, len));
-    HIPCHK(hipMemcpy(dp.blob, begin, len, hipMemcpyHostToDevice));
+    HIPCHK(dp.blob.alloc(len));
+    HIPCHK(hipMemcpy(dp.blob.p, begin, len, hipMemcpyHostToDevice));
     SlpProgram& p = dp.p;
     p.lanes = w[1]; p.n_slots = w[2]; p.n_steps = w[3]; p.n_const = w[4]; p.n_in = w[5]; p.n_set = w[6]; p.n_out = w[7];
-    const uint32_t* d = reinterpret_cast<const uint32_t*>(dp.blob);
+    const uint32_t* d = reinterpret_cast<const uint32_t*>(dp.blob.p);
     size_t off = 16;
     p.consts = reinterpret_cast<const Fp*>(d + off);
     off += (size_t)12 * p.n_const;
@@ -169,12 +176,12 @@ static KzgRet upload_program2(DevProgram2& dp, const unsigned char* begin, const
     size_t len = (size_t)(end - begin);
     const uint32_t* w = reinterpret_cast<const uint32_t*>(begin);
     if (len < 64 || w[0] != SLP2_MAGIC) return fail(KZG_ERROR, "embedded latency program is corrupt");
-    HIPCHK(hipMalloc(&dp.blob, len));
-    HIPCHK(hipMemcpy(dp.blob, begin, len, hipMemcpyHostToDevice));
+    HIPCHK(dp.blob.alloc(len));
+    HIPCHK(hipMemcpy(dp.blob.p, begin, len, hipMemcpyHostToDevice));
     Slp2Program& p = dp.p;
     p.lanes = w[1]; p.n_slots = w[2]; p.n_steps = w[3]; p.n_const = w[4]; p.n_in = w[5]; p.n_set = w[6]; p.n_out = w[7]; p.n_load_steps = w[8]; p.out_values = w[9];
     if (p.n_load_steps >= p.n_steps) return fail(KZG_ERROR, "embedded latency program has no compute steps");
-    const uint32_t* d = reinterpret_cast<const uint32_t*>(dp.blob);
+    const uint32_t* d = reinterpret_cast<const uint32_t*>(dp.blob.p);
     size_t off = 16;
     p.consts = d + off;
     off += (size_t)16 * p.n_const;
@@ -226,8 +233,8 @@ static KzgRet run_program(const DevProgram& dp, const Fp* d_in, const Fp* d_set,
 
 // the pairing check of `instances` (A, B) pairs against the handle's prepared lines, in the form that suits the launch size
 static KzgRet run_verify(const KzgSettings* s, const Fp* d_in, Fp* d_out, int instances, hipStream_t st) {
-    if (pairing_latency_form((size_t)instances)) return run_program2(s->verify2, d_in, s->d_prep29, d_out, instances, st);
-    return run_program(s->verify, d_in, s->d_prep, d_out, instances, st);
+    if (pairing_latency_form((size_t)instances)) return run_program2(s->t->verify2, d_in, s->t->d_prep29.p, d_out, instances, st);
+    return run_program(s->t->verify, d_in, s->t->d_prep.p, d_out, instances, st);
 }
 
 static KzgRet settings_build(KzgSettings* s, const uint8_t tau_g2[96]);
@@ -290,13 +297,7 @@ static KzgRet settings_streams(KzgSettings* s, bool single_stream, int priority 
 // caller has set the parent's device.  Freed with the parent (kzg_settings_free), never handed out.
 static KzgRet settings_lane(KzgSettings** out, const KzgSettings* parent, int priority = 0) {
     KzgSettings* l = new KzgSettings();
-    l->borrowed = true;
-    l->d_M = parent->d_M; l->d_DM = parent->d_DM; l->d_M29 = parent->d_M29; l->d_DM29 = parent->d_DM29;
-    l->d_eval_a = parent->d_eval_a; l->d_eval_b = parent->d_eval_b; l->d_eval_c = parent->d_eval_c;
-    l->d_tau4 = parent->d_tau4; l->d_prep = parent->d_prep; l->d_prep29 = parent->d_prep29;
-    l->d_gen_mult = parent->d_gen_mult; l->d_gen_mult_aff = parent->d_gen_mult_aff;
-    l->prep = parent->prep; l->verify = parent->verify; l->verify2 = parent->verify2;
-    l->scalars = parent->scalars; l->verify3 = parent->verify3; l->d_fixed_base = parent->d_fixed_base;
+    l->t = parent->t;
     memcpy(l->tau_g2_bytes, parent->tau_g2_bytes, 96);
     KzgRet rc = settings_streams(l, /*single_stream=*/!parent->s_plain[1], priority);
     if (rc != KZG_OK) {
@@ -312,117 +313,118 @@ static KzgRet settings_build(KzgSettings* s, const uint8_t tau_g2[96]) {
     memcpy(s->tau_g2_bytes, tau_g2, 96);
     KzgRet rc_streams = settings_streams(s, opt_flag("single_stream", false));
     if (rc_streams != KZG_OK) return rc_streams;
-    HIPCHK(hipMalloc(&s->d_M, sizeof(Fr) * FE_PER_BLOB));
-    HIPCHK(hipMalloc(&s->d_DM, sizeof(Fr) * FE_PER_BLOB));
-    HIPCHK(hipMalloc(&s->d_M29, sizeof(Fr29Mem) * FE_PER_BLOB));
-    HIPCHK(hipMalloc(&s->d_DM29, sizeof(Fr29Mem) * FE_PER_BLOB));
-    hipLaunchKernelGGL(k_roots_tables, dim3(FE_PER_BLOB / 64), dim3(64), 0, s->s1, s->d_M, s->d_DM);
-    hipLaunchKernelGGL(k_roots_tables29, dim3(FE_PER_BLOB / 64), dim3(64), 0, s->s1, s->d_M, s->d_M29, s->d_DM29);
-    HIPCHK(hipMalloc(&s->d_eval_a, sizeof(uint4) * EVAL_SLOTS * 64));
-    HIPCHK(hipMalloc(&s->d_eval_b, sizeof(uint4) * EVAL_SLOTS * 64));
-    HIPCHK(hipMalloc(&s->d_eval_c, 4 * EVAL_SLOTS * 64));
-    hipLaunchKernelGGL(k_eval_tables, dim3(EVAL_SLOTS), dim3(64), 0, s->s1, s->d_M29, s->d_DM29, s->d_eval_a, s->d_eval_b, s->d_eval_c);
+    SettingsTables& t = s->own;
+    HIPCHK(t.d_M.alloc(FE_PER_BLOB));
+    HIPCHK(t.d_DM.alloc(FE_PER_BLOB));
+    HIPCHK(t.d_M29.alloc(FE_PER_BLOB));
+    HIPCHK(t.d_DM29.alloc(FE_PER_BLOB));
+    hipLaunchKernelGGL(k_roots_tables, dim3(FE_PER_BLOB / 64), dim3(64), 0, s->s1, t.d_M.p, t.d_DM.p);
+    hipLaunchKernelGGL(k_roots_tables29, dim3(FE_PER_BLOB / 64), dim3(64), 0, s->s1, t.d_M.p, t.d_M29.p, t.d_DM29.p);
+    HIPCHK(t.d_eval_a.alloc(EVAL_SLOTS * 64));
+    HIPCHK(t.d_eval_b.alloc(EVAL_SLOTS * 64));
+    HIPCHK(t.d_eval_c.alloc(EVAL_SLOTS * 64));
+    hipLaunchKernelGGL(k_eval_tables, dim3(EVAL_SLOTS), dim3(64), 0, s->s1, t.d_M29.p, t.d_DM29.p, t.d_eval_a.p, t.d_eval_b.p, t.d_eval_c.p);
     HIPCHK(hipGetLastError());
     KzgRet rc;
-    if ((rc = upload_program(s->prep, kzg_slp_prep_begin, kzg_slp_prep_end)) != KZG_OK) return rc;
-    if ((rc = upload_program(s->verify, kzg_slp_verify_begin, kzg_slp_verify_end)) != KZG_OK) return rc;
-    if ((rc = upload_program2(s->verify2, kzg_slp_verify2_begin, kzg_slp_verify2_end)) != KZG_OK) return rc;
-    if ((rc = upload_program2(s->scalars, kzg_slp_scalars_begin, kzg_slp_scalars_end)) != KZG_OK) return rc;
-    if ((rc = upload_program2(s->verify3, kzg_slp_verify3_begin, kzg_slp_verify3_end)) != KZG_OK) return rc;
+    if ((rc = upload_program(t.prep, kzg_slp_prep_begin, kzg_slp_prep_end)) != KZG_OK) return rc;
+    if ((rc = upload_program(t.verify, kzg_slp_verify_begin, kzg_slp_verify_end)) != KZG_OK) return rc;
+    if ((rc = upload_program2(t.verify2, kzg_slp_verify2_begin, kzg_slp_verify2_end)) != KZG_OK) return rc;
+    if ((rc = upload_program2(t.scalars, kzg_slp_scalars_begin, kzg_slp_scalars_end)) != KZG_OK) return rc;
+    if ((rc = upload_program2(t.verify3, kzg_slp_verify3_begin, kzg_slp_verify3_end)) != KZG_OK) return rc;
     if ((size_t)(kzg_fixed_base_end - kzg_fixed_base_begin) != FB_TABLE_BYTES) return fail(KZG_ERROR, "embedded fixed-base table has the wrong size");
-    HIPCHK(hipMalloc(&s->d_fixed_base, FB_TABLE_BYTES));
-    HIPCHK(hipMemcpy(s->d_fixed_base, kzg_fixed_base_begin, FB_TABLE_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(t.d_fixed_base.alloc(FB_TABLE_BYTES / sizeof(Fp)));
+    HIPCHK(hipMemcpy(t.d_fixed_base.p, kzg_fixed_base_begin, FB_TABLE_BYTES, hipMemcpyHostToDevice));
     // decompress [tau]G2 on the device, then prepare the lines of [tau]G2 and of the generator
-    DevTmp t_bytes, t_flag, t_q;  // released on every path out of this function
-    HIPCHK(hipMalloc(&t_bytes.p, 96));
-    HIPCHK(hipMalloc(&t_flag.p, 4));
-    HIPCHK(hipMalloc(&t_q.p, sizeof(Fp) * 8));  // 2 instances x 4 Fp
-    uint8_t* d_bytes = t_bytes.as<uint8_t>();
-    uint32_t* d_flag = t_flag.as<uint32_t>();
-    Fp* d_q = t_q.as<Fp>();
-    HIPCHK(hipMalloc(&s->d_tau4, sizeof(Fp) * 4));
-    HIPCHK(hipMalloc(&s->d_prep, sizeof(Fp) * 2 * s->prep.p.n_out));
-    HIPCHK(hipMemcpyAsync(d_bytes, tau_g2, 96, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g2_decompress, dim3(1), dim3(64), 0, s->s1, d_bytes, d_q, d_flag);
-    hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, d_q + 4);
+    DevBuf<uint8_t> d_bytes;  // released on every path out of this function
+    DevBuf<uint32_t> d_flag;
+    DevBuf<Fp> d_q;  // 2 instances x 4 Fp
+    HIPCHK(d_bytes.alloc(96));
+    HIPCHK(d_flag.alloc(1));
+    HIPCHK(d_q.alloc(8));
+    HIPCHK(t.d_tau4.alloc(4));
+    HIPCHK(t.d_prep.alloc(2 * t.prep.p.n_out));
+    HIPCHK(hipMemcpyAsync(d_bytes.p, tau_g2, 96, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g2_decompress, dim3(1), dim3(64), 0, s->s1, d_bytes.p, d_q.p, d_flag.p);
+    hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, d_q.p + 4);
     HIPCHK(hipGetLastError());
     uint32_t flag = 0;
-    HIPCHK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s->s1));
-    HIPCHK(hipMemcpyAsync(s->d_tau4, d_q, sizeof(Fp) * 4, hipMemcpyDeviceToDevice, s->s1));
-    if ((rc = run_program(s->prep, d_q, nullptr, s->d_prep, 2, s->s1)) != KZG_OK) return rc;
+    HIPCHK(hipMemcpyAsync(&flag, d_flag.p, 4, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(t.d_tau4.p, d_q.p, sizeof(Fp) * 4, hipMemcpyDeviceToDevice, s->s1));
+    if ((rc = run_program(t.prep, d_q.p, nullptr, t.d_prep.p, 2, s->s1)) != KZG_OK) return rc;
     {  // the same lines for the latency program
-        const int np = (int)(2 * s->prep.p.n_out);
-        HIPCHK(hipMalloc(&s->d_prep29, (size_t)64 * np));
-        hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, s->s1, s->d_prep, s->d_prep29, np);
+        const int np = (int)(2 * t.prep.p.n_out);
+        HIPCHK(t.d_prep29.alloc((size_t)16 * np));
+        hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, s->s1, t.d_prep.p, t.d_prep29.p, np);
         HIPCHK(hipGetLastError());
     }
     {  // multiples of the generator (msm.hpp): the same for every batch
-        DevTmp t_g, t_gf, t_gm;
-        HIPCHK(hipMalloc(&t_g.p, sizeof(G1Aff)));
-        HIPCHK(hipMalloc(&t_gf.p, 4));
         constexpr int NG = MSM_CHUNKS + MSM_CHUNKS_LATENCY;
-        HIPCHK(hipMalloc(&t_gm.p, sizeof(G1Jac) * NG));
-        G1Aff* d_g = t_g.as<G1Aff>();
-        uint32_t* d_gf = t_gf.as<uint32_t>();
-        G1Jac* d_gm = t_gm.as<G1Jac>();
-        hipLaunchKernelGGL(k_set_generator, dim3(1), dim3(64), 0, s->s1, d_g, d_gf, 0);
-        hipLaunchKernelGGL(k_g1_multiples, dim3(1), dim3(64), 0, s->s1, d_g, d_gf, d_gm, 1, 1, MSM_CHUNKS);
-        hipLaunchKernelGGL(k_g1_multiples, dim3(1), dim3(64), 0, s->s1, d_g, d_gf, d_gm + MSM_CHUNKS, 1, 1, MSM_CHUNKS_LATENCY);
-        HIPCHK(hipMalloc(&s->d_gen_mult, sizeof(G1Jac29Mem) * NG));
-        hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(64), 0, s->s1, d_gm, (G1Jac29Mem*)s->d_gen_mult, NG);
-        HIPCHK(hipMalloc(&s->d_gen_mult_aff, sizeof(G1Aff29Mem) * MSM_CHUNKS));
-        hipLaunchKernelGGL(k_jac29_to_aff29, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)s->d_gen_mult, s->d_gen_mult_aff, MSM_CHUNKS);
+        DevBuf<G1Aff> d_g;
+        DevBuf<uint32_t> d_gf;
+        DevBuf<G1Jac> d_gm;
+        HIPCHK(d_g.alloc(1));
+        HIPCHK(d_gf.alloc(1));
+        HIPCHK(d_gm.alloc(NG));
+        hipLaunchKernelGGL(k_set_generator, dim3(1), dim3(64), 0, s->s1, d_g.p, d_gf.p, 0);
+        hipLaunchKernelGGL(k_g1_multiples, dim3(1), dim3(64), 0, s->s1, d_g.p, d_gf.p, d_gm.p, 1, 1, MSM_CHUNKS);
+        hipLaunchKernelGGL(k_g1_multiples, dim3(1), dim3(64), 0, s->s1, d_g.p, d_gf.p, d_gm.p + MSM_CHUNKS, 1, 1, MSM_CHUNKS_LATENCY);
+        HIPCHK(t.d_gen_mult.alloc(NG));
+        hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(64), 0, s->s1, d_gm.p, t.d_gen_mult.p, NG);
+        HIPCHK(t.d_gen_mult_aff.alloc(MSM_CHUNKS));
+        hipLaunchKernelGGL(k_jac29_to_aff29, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)t.d_gen_mult.p, t.d_gen_mult_aff.p, MSM_CHUNKS);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s->s1));  // before the temporaries of this scope are released
     }
     HIPCHK(hipStreamSynchronize(s->s1));
     if (flag != G1_OK) return fail(KZG_BAD_SETUP, "g2_points[1] is not a valid (finite) compressed G2 point");
-    if (s->verify.p.n_set != 2 * s->prep.p.n_out || s->verify.p.n_in != 6 || s->prep.p.n_in != 4 || s->verify2.p.n_set != s->verify.p.n_set ||
-        s->verify2.p.n_in != 6 || s->verify2.p.n_out != s->verify.p.n_out)
+    if (t.verify.p.n_set != 2 * t.prep.p.n_out || t.verify.p.n_in != 6 || t.prep.p.n_in != 4 || t.verify2.p.n_set != t.verify.p.n_set ||
+        t.verify2.p.n_in != 6 || t.verify2.p.n_out != t.verify.p.n_out)
         return fail(KZG_ERROR, "embedded SLP programs do not fit together");
-    if (s->scalars.p.n_in != (uint32_t)SCALARS_INPUTS || s->scalars.p.n_set != 0 || !s->scalars.p.out_values || s->scalars.p.n_out + 6 != (uint32_t)VERIFY3_INPUTS ||
-        s->verify3.p.n_in != (uint32_t)VERIFY3_INPUTS || s->verify3.p.n_set != s->verify.p.n_set || s->verify3.p.n_out != (uint32_t)VERIFY3_OUTPUTS || s->verify3.p.out_values)
+    if (t.scalars.p.n_in != (uint32_t)SCALARS_INPUTS || t.scalars.p.n_set != 0 || !t.scalars.p.out_values || t.scalars.p.n_out + 6 != (uint32_t)VERIFY3_INPUTS ||
+        t.verify3.p.n_in != (uint32_t)VERIFY3_INPUTS || t.verify3.p.n_set != t.verify.p.n_set || t.verify3.p.n_out != (uint32_t)VERIFY3_OUTPUTS || t.verify3.p.out_values)
         return fail(KZG_ERROR, "embedded one-proof programs do not fit together");
     return KZG_OK;
 }
 
 // Device half of kzg_settings_load_trusted_setup: the G1 Lagrange points - unchecked decode (build.rs:66-70) for the table, and
 // the decode + subgroup test + multiples pass of the MSM (msm.hpp) so that commitments can be computed against them - and
-// all G2 monomial points (build.rs:72-75; verification itself reads only [1]).  Temporaries live in DevTmp, so every
+// all G2 monomial points (build.rs:72-75; verification itself reads only [1]).  Temporaries are DevBuf locals, so every
 // return path releases them; the caller releases the handle on failure.
 static KzgRet settings_load_points(KzgSettings* s, const std::vector<uint8_t>& g1b, const std::vector<uint8_t>& g2b, int N, size_t n2) {
-    DevTmp t_bytes, t_flag2, t_gflag, t_tmp;
-    HIPCHK(hipMalloc(&t_bytes.p, std::max(g1b.size(), g2b.size())));
-    HIPCHK(hipMalloc(&t_flag2.p, 4 * (size_t)N));
-    HIPCHK(hipMalloc(&t_tmp.p, sizeof(G1Aff) * (size_t)N));
-    uint8_t* d_bytes = t_bytes.as<uint8_t>();
-    uint32_t* d_flag2 = t_flag2.as<uint32_t>();
-    G1Aff* d_tmp = t_tmp.as<G1Aff>();
-    HIPCHK(hipMalloc(&s->d_g1, sizeof(G1Aff) * (size_t)N));
-    HIPCHK(hipMalloc(&s->d_g1_flag, 4 * (size_t)N));
-    HIPCHK(hipMalloc(&s->d_g1_mult, MULT_ENTRY_BYTES * MSM_CHUNKS * (size_t)N));
-    HIPCHK(hipMemcpyAsync(d_bytes, g1b.data(), g1b.size(), hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s->s1, d_bytes, d_bytes, N, s->d_g1, s->d_g1_flag, N, 0);
-    hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((N + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, d_bytes, d_bytes, N, d_tmp,
-                       d_flag2, s->d_g1_mult, (G1Jac29Mem*)nullptr, N, N);
+    SettingsTables& t = s->own;
+    DevBuf<uint8_t> d_bytes;
+    DevBuf<uint32_t> d_flag2, d_gflag;
+    DevBuf<G1Aff> d_tmp;
+    HIPCHK(d_bytes.alloc(std::max(g1b.size(), g2b.size())));
+    HIPCHK(d_flag2.alloc((size_t)N));
+    HIPCHK(d_tmp.alloc((size_t)N));
+    HIPCHK(t.d_g1.alloc((size_t)N));
+    HIPCHK(t.d_g1_flag.alloc((size_t)N));
+    static_assert(MULT_ENTRY_BYTES == sizeof(G1Jac29Mem), "d_g1_mult holds entries of the larger form");
+    HIPCHK(t.d_g1_mult.alloc(MSM_CHUNKS * (size_t)N));
+    HIPCHK(hipMemcpyAsync(d_bytes.p, g1b.data(), g1b.size(), hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s->s1, d_bytes.p, d_bytes.p, N, t.d_g1.p, t.d_g1_flag.p, N, 0);
+    hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((N + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, d_bytes.p, d_bytes.p, N, d_tmp.p,
+                       d_flag2.p, (void*)t.d_g1_mult.p, (G1Jac29Mem*)nullptr, N, N);
     HIPCHK(hipGetLastError());
     s->n_g1 = N;
-    DevTmp t_jtmp, t_aff_pts;
+    DevBuf<G1Jac29Mem> d_jtmp;
+    DevBuf<G1Aff> d_aff_pts;
     if (msm_affine_enabled()) {
         // the same points as affine table rows (P, 2^64 P, -phi(P), -phi(2^64 P)): sums over the setup's own points
         // (kzg_g1_msm_setup) then run on the verification path's mixed-addition window kernel without a per-call decode
-        HIPCHK(hipMalloc(&s->d_g1_mult_aff, sizeof(G1Aff29Mem) * MSM_CHUNKS * (size_t)N));
-        HIPCHK(hipMalloc(&t_jtmp.p, sizeof(G1Jac29Mem) * (size_t)N));
-        HIPCHK(hipMalloc(&t_aff_pts.p, sizeof(G1Aff) * (size_t)N));
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3((unsigned)((N + 255) / 256)), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, d_bytes,
-                           d_bytes, N, t_aff_pts.as<G1Aff>(), d_flag2, (void*)s->d_g1_mult_aff, t_jtmp.as<G1Jac29Mem>(), N, N);
+        HIPCHK(t.d_g1_mult_aff.alloc(MSM_CHUNKS * (size_t)N));
+        HIPCHK(d_jtmp.alloc((size_t)N));
+        HIPCHK(d_aff_pts.alloc((size_t)N));
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3((unsigned)((N + 255) / 256)), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, d_bytes.p,
+                           d_bytes.p, N, d_aff_pts.p, d_flag2.p, (void*)t.d_g1_mult_aff.p, d_jtmp.p, N, N);
         const unsigned conv_blocks = (unsigned)((N + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
-        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, t_jtmp.as<G1Jac29Mem>(), d_flag2, s->d_g1_mult_aff, N, N);
+        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, d_jtmp.p, d_flag2.p, t.d_g1_mult_aff.p, N, N);
         HIPCHK(hipGetLastError());
     }
     std::vector<uint32_t> f1((size_t)N), f2((size_t)N);
-    HIPCHK(hipMemcpyAsync(f1.data(), s->d_g1_flag, 4 * (size_t)N, hipMemcpyDeviceToHost, s->s1));
-    HIPCHK(hipMemcpyAsync(f2.data(), d_flag2, 4 * (size_t)N, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(f1.data(), t.d_g1_flag.p, 4 * (size_t)N, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(f2.data(), d_flag2.p, 4 * (size_t)N, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     s->g1_in_subgroup = true;
     for (int i = 0; i < N; i++) {
@@ -430,14 +432,13 @@ static KzgRet settings_load_points(KzgSettings* s, const std::vector<uint8_t>& g
         if (f2[i] == G1_INVALID) s->g1_in_subgroup = false;
     }
     s->n_g2 = n2;
-    HIPCHK(hipMalloc(&s->d_g2, sizeof(Fp) * 4 * n2));
-    HIPCHK(hipMalloc(&t_gflag.p, 4 * n2));
-    uint32_t* d_gflag = t_gflag.as<uint32_t>();
-    HIPCHK(hipMemcpyAsync(d_bytes, g2b.data(), g2b.size(), hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_g2_decompress_n, dim3((unsigned)n2), dim3(64), 0, s->s1, d_bytes, s->d_g2, d_gflag);
+    HIPCHK(t.d_g2.alloc(4 * n2));
+    HIPCHK(d_gflag.alloc(n2));
+    HIPCHK(hipMemcpyAsync(d_bytes.p, g2b.data(), g2b.size(), hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_g2_decompress_n, dim3((unsigned)n2), dim3(64), 0, s->s1, d_bytes.p, t.d_g2.p, d_gflag.p);
     HIPCHK(hipGetLastError());
     std::vector<uint32_t> fg(n2);
-    HIPCHK(hipMemcpyAsync(fg.data(), d_gflag, 4 * n2, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(fg.data(), d_gflag.p, 4 * n2, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipStreamSynchronize(s->s1));
     for (size_t i = 0; i < n2; i++)
         if (fg[i] == G1_INVALID) return fail(KZG_BAD_SETUP, "load_trusted_setup Invalid g2 bytes");
@@ -563,16 +564,6 @@ extern "C" KzgRet kzg_settings_from_tau_g2_devices(KzgSettings** out, const uint
     return rc != KZG_OK ? rc : constructed(settings_on_devices(out, tau_g2, devs), out);
 }
 
-static void ws_free(Workspace& w) {
-    void* ptrs[] = {w.d_z, w.d_y, w.d_scalars, w.d_partial, w.d_r, w.d_status, w.d_pflag, w.d_term_point, w.d_term_scalar,
-                    w.d_sorted, w.d_points, w.d_window, w.d_window_sl, w.d_ab, w.d_send, w.d_mult, w.d_jtmp, w.d_ktime, w.d_parts, w.d_slp_in, w.d_slp_out, w.d_stage_blobs, w.d_stage_cp, w.d_bytes,
-                    w.d_records, w.d_hstage[0], w.d_hstage[1], w.d_msm_save, w.d_sha_mid, w.d_g1msm};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (w.h_buf) (void)hipHostFree(w.h_buf);
-    w = Workspace();
-}
-
 static void prover_release(const KzgSettings* s);  // (capi_prover.hpp)
 static void cells_release(const KzgSettings* s);   // (capi_cells.hpp)
 static void cell_prover_release(const KzgSettings* s);  // (capi_cell_prover.hpp)
@@ -585,20 +576,16 @@ extern "C" void kzg_settings_free(KzgSettings* s) {
     for (KzgSettings* l : s->lanes) kzg_settings_free(l);
     s->lanes.clear();
     (void)hipSetDevice(s->device);
-    ws_free(s->ws);
-    if (s->d_eval_scratch) (void)hipFree(s->d_eval_scratch);
-    if (s->d_proof) (void)hipFree(s->d_proof);
-    if (s->d_proofs) (void)hipFree(s->d_proofs);
-    if (s->d_proofs_out) (void)hipFree(s->d_proofs_out);
-    if (s->h_proofs) (void)hipHostFree(s->h_proofs);
+    s->ws = Workspace();
+    s->d_eval_scratch.release();
+    s->d_proof.release();
+    s->d_proofs.release();
+    s->d_proofs_out.release();
+    s->h_proofs.release();
     prover_release(s);
     cells_release(s);
     cell_prover_release(s);
-    if (!s->borrowed) {  // (a lane reads its parent's tables)
-        void* ptrs[] = {s->d_g1, s->d_g1_flag, s->d_g1_mult, s->d_g1_mult_aff, s->d_g1_fb_rows, s->d_fb_plan, s->d_g2, s->d_M, s->d_DM, s->d_M29, s->d_DM29, s->d_eval_a, s->d_eval_b, s->d_eval_c, s->d_tau4, s->d_prep, s->d_gen_mult, s->d_gen_mult_aff, s->prep.blob, s->verify.blob, s->verify2.blob, s->d_prep29, s->scalars.blob, s->verify3.blob, s->d_fixed_base};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-    }
+    s->own = SettingsTables();  // (a lane's is empty: it reads its parent's, which is freed after its lanes)
     for (auto& e : s->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : s->ev_copy)

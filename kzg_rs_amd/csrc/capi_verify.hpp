@@ -6,17 +6,12 @@
 // stamp: the kernel records its own execution interval in the workspace's stamp words (phase 1 has zeroed them)
 static KzgRet launch_evaluate(const KzgSettings* s, const void* d_blobs, const Fr* d_z, Fr* d_y, uint32_t* d_status, size_t T, bool alone = false,
                               bool stamp = false) {
-    unsigned long long* const kt = stamp && s->ws.d_ktime ? s->ws.d_ktime + 4 : nullptr;
-    if (T > s->eval_scratch_cap) {  // 576 bytes per blob between the three kernels (fr_kernels.hpp); callers hold the handle's lock
-        if (s->d_eval_scratch) HIPCHK(hipFree(s->d_eval_scratch));  // waits for the kernels that may still read it
-        s->d_eval_scratch = nullptr;
-        s->eval_scratch_cap = 0;
-        const size_t cap = T < 1024 ? 1024 : T;
-        HIPCHK(hipMalloc(&s->d_eval_scratch, 4 * (size_t)EVAL_SCRATCH_WORDS * cap));
-        s->eval_scratch_cap = cap;
-    }
+    unsigned long long* const kt = stamp && s->ws.d_ktime.p ? s->ws.d_ktime.p + 4 : nullptr;
+    // 576 bytes per blob between the three kernels (fr_kernels.hpp), 1 024 blobs at least; callers hold the handle's lock
+    // (growing waits for the kernels that may still read the old one)
+    HIPCHK(s->d_eval_scratch.grow((size_t)EVAL_SCRATCH_WORDS * std::max<size_t>(T, 1024)));
     const unsigned per_lane = (unsigned)((T + 63) / 64);
-    hipLaunchKernelGGL(k_eval_powers, dim3(per_lane), dim3(64), 0, s->s1, d_z, s->d_eval_scratch, (int)T);
+    hipLaunchKernelGGL(k_eval_powers, dim3(per_lane), dim3(64), 0, s->s1, d_z, s->d_eval_scratch.p, (int)T);
     // A launch that leaves CUs free asks for enough (unused) dynamic LDS that no CU takes a second workgroup: the dispatcher
     // otherwise pairs workgroups on half the CUs, two wavefronts per SIMD, and the single batch waits twice as long.
     const unsigned eval_blocks = (unsigned)((T + EVAL_BLOBS_PER_BLOCK - 1) / EVAL_BLOBS_PER_BLOCK);
@@ -35,8 +30,8 @@ static KzgRet launch_evaluate(const KzgSettings* s, const void* d_blobs, const F
         spread_lds = 0;
     }
     hipLaunchKernelGGL(k_blob_evaluate_t<true>, dim3(eval_blocks), dim3(64 * EVAL_BLOBS_PER_BLOCK), spread_lds, s->s1,
-                       (const uint8_t*)d_blobs, EvalTables{s->d_eval_a, s->d_eval_b, s->d_eval_c}, s->d_eval_scratch, d_status, (int)T, kt);
-    hipLaunchKernelGGL(k_eval_finish, dim3(per_lane), dim3(64), 0, s->s1, s->d_eval_scratch, d_y, (int)T);
+                       (const uint8_t*)d_blobs, EvalTables{s->t->d_eval_a.p, s->t->d_eval_b.p, s->t->d_eval_c.p}, s->d_eval_scratch.p, d_status, (int)T, kt);
+    hipLaunchKernelGGL(k_eval_finish, dim3(per_lane), dim3(64), 0, s->s1, s->d_eval_scratch.p, d_y, (int)T);
     return KZG_OK;
 }
 
@@ -55,7 +50,7 @@ static KzgRet launch_challenge(const KzgSettings* s, const void* d_blobs, const 
     const int form = forced ? forced : T <= 16384 ? 3 : T <= 49152 ? 2 : 1;
     s->ws.ktime_valid = false;
     if (form == 1) {
-        unsigned long long* kt = s->ws.d_ktime;  // null for callers that never reserved the workspace
+        unsigned long long* kt = s->ws.d_ktime.p;  // null for callers that never reserved the workspace
         if (kt) {
             HIPCHK(hipMemsetAsync(kt, 0, 32, st));
             s->ws.ktime_valid = true;
@@ -78,73 +73,47 @@ enum { STAGE_NONE = 0, STAGE_BLOBS = 1, STAGE_CP = 2 };
 static KzgRet ws_reserve(const KzgSettings* s, size_t T, size_t B, int stage) {
     Workspace& w = s->ws;
     if (T > w.cap_n || B > w.cap_b) {
-        size_t keep_stage = w.cap_stage, keep_cp = w.cap_stage_cp, keep_h = w.cap_hstage;
-        uint8_t *sb = w.d_stage_blobs, *sc = w.d_stage_cp, *h0 = w.d_hstage[0], *h1 = w.d_hstage[1];
-        w.d_stage_blobs = nullptr;
-        w.d_stage_cp = nullptr;
-        w.d_hstage[0] = w.d_hstage[1] = nullptr;
         size_t capT = T > w.cap_n ? T : w.cap_n, capB = B > w.cap_b ? B : w.cap_b;
-        ws_free(w);
-        w.d_stage_blobs = sb;
-        w.d_stage_cp = sc;
-        w.cap_stage = keep_stage;
-        w.cap_stage_cp = keep_cp;
-        w.d_hstage[0] = h0;
-        w.d_hstage[1] = h1;
-        w.cap_hstage = keep_h;
+        w.reset();  // (GroupBufs: everything released before the first allocation, which bounds the peak)
         if (capT < 16) capT = 16;
         const size_t np = 2 * capT + 1;            // points: C's, pi's, generator
         const size_t nsc = 2 * capT + capB;        // scalars: (2n+1) per batch
         const size_t nterm = 4 * capT + 2 * capB;  // term table rows: [2B][2n+1]
-        HIPCHK(hipMalloc(&w.d_z, sizeof(Fr) * capT));
-        HIPCHK(hipMalloc(&w.d_y, sizeof(Fr) * capT));
-        HIPCHK(hipMalloc(&w.d_scalars, sizeof(Fr) * nsc));
-        HIPCHK(hipMalloc(&w.d_partial, sizeof(Fr) * ((capT + 255) / 256 + capB)));
-        HIPCHK(hipMalloc(&w.d_r, sizeof(Fr) * capB));
-        HIPCHK(hipMalloc(&w.d_status, 4 * capT));
-        HIPCHK(hipMalloc(&w.d_pflag, 4 * np));
-        HIPCHK(hipMalloc(&w.d_term_point, 4 * nterm));
-        HIPCHK(hipMalloc(&w.d_term_scalar, 4 * nterm));
-        HIPCHK(hipMalloc(&w.d_sorted, 4 * MSM_WINDOWS * nterm));
-        HIPCHK(hipMalloc(&w.d_points, sizeof(G1Aff) * np));
-        HIPCHK(hipMalloc(&w.d_window, sizeof(G1Jac) * 2 * MSM_WINDOWS * capB));
-        HIPCHK(hipMalloc(&w.d_window_sl, sizeof(G1Jac) * 2 * MSM_WINDOWS * MSM_MAX_SLICES * 4));  // sliced launches have <= 4 batches
-        HIPCHK(hipMalloc(&w.d_mult, MULT_ENTRY_BYTES * std::max((size_t)MSM_CHUNKS * np, (size_t)MSM_CHUNKS_LATENCY * std::min(np, (size_t)(2 * LATENCY_MAX_BLOBS + 1)))));
-        HIPCHK(hipMalloc(&w.d_ab, sizeof(G1Jac) * 2 * capB));
-        HIPCHK(hipMalloc(&w.d_ktime, 128));
-        if (msm_affine_enabled()) HIPCHK(hipMalloc(&w.d_jtmp, sizeof(G1Jac29Mem) * np));
-        HIPCHK(hipMalloc(&w.d_parts, sizeof(G1Jac) * 2 * capB * MAX_WORLD));
-        HIPCHK(hipMalloc(&w.d_send, sizeof(G1Jac) * 2 * MAX_WORLD));
-        HIPCHK(hipMalloc(&w.d_slp_in, sizeof(Fp) * 6 * capB));
-        HIPCHK(hipMalloc(&w.d_slp_out, sizeof(Fp) * 6 * capB));
-        HIPCHK(hipMalloc(&w.d_bytes, 96 * np));
-        HIPCHK(hipMalloc(&w.d_records, 160 * capT));
-        HIPCHK(hipMalloc(&w.d_sha_mid, 32 * std::min(capT, (size_t)SLICED_MAX_BLOBS)));
+        HIPCHK(w.d_z.alloc(capT));
+        HIPCHK(w.d_y.alloc(capT));
+        HIPCHK(w.d_scalars.alloc(nsc));
+        HIPCHK(w.d_partial.alloc((capT + 255) / 256 + capB));
+        HIPCHK(w.d_r.alloc(capB));
+        HIPCHK(w.d_status.alloc(capT));
+        HIPCHK(w.d_pflag.alloc(np));
+        HIPCHK(w.d_term_point.alloc(nterm));
+        HIPCHK(w.d_term_scalar.alloc(nterm));
+        HIPCHK(w.d_sorted.alloc(MSM_WINDOWS * nterm));
+        HIPCHK(w.d_points.alloc(np));
+        HIPCHK(w.d_window.alloc(2 * MSM_WINDOWS * capB));
+        HIPCHK(w.d_window_sl.alloc(2 * MSM_WINDOWS * MSM_MAX_SLICES * 4));  // sliced launches have <= 4 batches
+        HIPCHK(w.d_mult.alloc(MULT_ENTRY_BYTES * std::max((size_t)MSM_CHUNKS * np, (size_t)MSM_CHUNKS_LATENCY * std::min(np, (size_t)(2 * LATENCY_MAX_BLOBS + 1)))));
+        HIPCHK(w.d_ab.alloc(2 * capB));
+        HIPCHK(w.d_ktime.alloc(16));
+        if (msm_affine_enabled()) HIPCHK(w.d_jtmp.alloc(np));
+        HIPCHK(w.d_parts.alloc(2 * capB * MAX_WORLD));
+        HIPCHK(w.d_send.alloc(2 * MAX_WORLD));
+        HIPCHK(w.d_slp_in.alloc(6 * capB));
+        HIPCHK(w.d_slp_out.alloc(6 * capB));
+        HIPCHK(w.d_bytes.alloc(96 * np));
+        HIPCHK(w.d_records.alloc(160 * capT));
+        HIPCHK(w.d_sha_mid.alloc(8 * std::min(capT, (size_t)SLICED_MAX_BLOBS)));
         w.off_r = 256 * capT + 4096;                 // pinned layout: [per-blob area | r | own partials | out | gathered partials]
         w.off_part = w.off_r + 32 * capB;
         w.off_out = w.off_part + 288 * capB;
         w.off_parts = w.off_out + 288 * capB;
-        w.h_cap = w.off_parts + 288 * capB * MAX_WORLD;
-        HIPCHK(hipHostMalloc(&w.h_buf, w.h_cap));
+        HIPCHK(w.h_buf.alloc(w.off_parts + 288 * capB * MAX_WORLD));
         w.cap_n = capT;
         w.cap_b = capB;
     }
-    if (stage != STAGE_NONE && T > w.cap_stage_cp) {  // 96 bytes per tuple: what the proof-tuple entry points stage
-        if (w.d_stage_cp) (void)hipFree(w.d_stage_cp);
-        w.d_stage_cp = nullptr;
-        w.cap_stage_cp = 0;
-        size_t cap = T < 4 ? 4 : T;
-        HIPCHK(hipMalloc(&w.d_stage_cp, 96 * cap));
-        w.cap_stage_cp = cap;
-    }
-    if (stage == STAGE_BLOBS && T > w.cap_stage) {  // 128 KiB per blob: only the host-blob entry points pay for it
-        if (w.d_stage_blobs) (void)hipFree(w.d_stage_blobs);
-        w.d_stage_blobs = nullptr;
-        w.cap_stage = 0;
-        size_t cap = T < 4 ? 4 : T;
-        HIPCHK(hipMalloc(&w.d_stage_blobs, (size_t)BLOB_BYTES * cap));
-        w.cap_stage = cap;
-    }
+    const size_t n_stage = std::max<size_t>(T, 4);
+    if (stage != STAGE_NONE) HIPCHK(w.d_stage_cp.grow(96 * n_stage));  // 96 bytes per tuple: what the proof-tuple entry points stage
+    if (stage == STAGE_BLOBS) HIPCHK(w.d_stage_blobs.grow((size_t)BLOB_BYTES * n_stage));  // 128 KiB per blob: only the host-blob entry points pay for it
     return KZG_OK;
 }
 
@@ -159,20 +128,16 @@ static int msm_chunks_per_block(size_t B) {
     return B >= 32 ? 4 : B >= 16 ? 2 : 1;
 }
 
-// The window kernel's save area (msm.hpp MsmDesc::save): grow-only, one z-layer at least, 512 MiB at most - a larger grid
-// is launched in z-pieces by msm_window_launch.
-static KzgRet msm_save_reserve(const KzgSettings* s, unsigned gx, unsigned gy, unsigned gz) {
-    Workspace& w = s->ws;
-    const size_t layer = msm_save_layer_bytes(gx, gy, MSM_SAVE2_WORDS);  // (the larger of the forms' point sizes)
-    const size_t want = std::max(layer, std::min(layer * gz, (size_t)512 << 20));
-    if (want > w.cap_msm_save) {
-        if (w.d_msm_save) (void)hipFree(w.d_msm_save);
-        w.d_msm_save = nullptr;
-        w.cap_msm_save = 0;
-        HIPCHK(hipMalloc(&w.d_msm_save, want));
-        w.cap_msm_save = want;
-    }
+// The window kernel's save area (msm.hpp MsmDesc::save), grow-only between two growths of the workspace
+static KzgRet msm_save_grow(const KzgSettings* s, size_t bytes) {
+    HIPCHK(s->ws.d_msm_save.grow((bytes + 3) / 4));
     return KZG_OK;
+}
+static size_t msm_save_bytes(const Workspace& w) { return w.d_msm_save.cap * 4; }
+// ... for a window grid: one z-layer at least, 512 MiB at most - a larger grid is launched in z-pieces by msm_window_launch.
+static KzgRet msm_save_reserve(const KzgSettings* s, unsigned gx, unsigned gy, unsigned gz) {
+    const size_t layer = msm_save_layer_bytes(gx, gy, MSM_SAVE2_WORDS);  // (the larger of the forms' point sizes)
+    return msm_save_grow(s, std::max(layer, std::min(layer * gz, (size_t)512 << 20)));
 }
 
 // ---------------------------------------------------------------- the tail: MSM + pairing
@@ -181,21 +146,21 @@ static KzgRet msm_save_reserve(const KzgSettings* s, unsigned gx, unsigned gy, u
 static KzgRet run_msm(const KzgSettings* s, size_t n, size_t B) {
     Workspace& w = s->ws;
     const int T = (int)(n * B), mt = (int)(2 * n + 1);
-    hipLaunchKernelGGL(k_batch_terms, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s->s1, w.d_term_point,
-                       w.d_term_scalar, (int)n, T, mt);
+    hipLaunchKernelGGL(k_batch_terms, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s->s1, w.d_term_point.p,
+                       w.d_term_scalar.p, (int)n, T, mt);
     MsmDesc d{};
-    d.mult = w.d_mult;
-    d.pflag = w.d_pflag;
-    d.scalars = w.d_scalars;
-    d.term_point = w.d_term_point;
-    d.term_scalar = w.d_term_scalar;
-    d.sorted = w.d_sorted;
-    d.window_sums = w.d_window;
+    d.mult = w.d_mult.p;
+    d.pflag = w.d_pflag.p;
+    d.scalars = w.d_scalars.p;
+    d.term_point = w.d_term_point.p;
+    d.term_scalar = w.d_term_scalar.p;
+    d.sorted = w.d_sorted.p;
+    d.window_sums = w.d_window.p;
     d.nterms[0] = (int)n;
     d.nterms[1] = (int)(2 * n + 1);
     d.max_terms = mt;
     d.stride = 2 * T + 1;
-    d.ktime = w.kstamps_valid ? w.d_ktime + 8 : nullptr;
+    d.ktime = w.kstamps_valid ? w.d_ktime.p + 8 : nullptr;
     d.chunks = w.chunks;
     d.chunks_per_block = w.chunks == MSM_CHUNKS ? msm_chunks_per_block(B) : 1;
     // option msm_xcd=0: A/B measurement of the XCD placement (msm.hpp MSM_FLAG_XCD; profiles/r3_ab_msm.txt: +2 % throughput)
@@ -220,41 +185,41 @@ static KzgRet run_msm(const KzgSettings* s, size_t n, size_t B) {
     while (S < MSM_MAX_SLICES && slice_terms(S) > lds_cap && n / (2 * S) >= 1024 && 2 * S * B <= 128) S *= 2;  // (d_window_sl holds S B <= 128 slice sets)
     const bool lds_sort = slice_terms(S) + 1 <= lds_cap;  // (+1: slice boundaries round either way)
     d.slices = (int)S;
-    d.window_sums = S > 1 ? w.d_window_sl : w.d_window;
+    d.window_sums = S > 1 ? w.d_window_sl.p : w.d_window.p;
     HIPCHK(hipEventRecord(s->ev[2], s->s1));
     const int nsc = (int)(B * (2 * n + 1));
-    hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((nsc + 255) / 256)), dim3(256), 0, s->s1, w.d_scalars, nsc);
+    hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((nsc + 255) / 256)), dim3(256), 0, s->s1, w.d_scalars.p, nsc);
     const unsigned gz = (unsigned)(2 * B * S);
     KzgRet rc_save = msm_save_reserve(s, W, slots, gz);
     if (rc_save != KZG_OK) return rc_save;
     if (w.mult_affine) {
-        if (lds_sort) msm_window_launch<Curve29Aff, true>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-        else msm_window_launch<Curve29Aff, false>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
+        if (lds_sort) msm_window_launch<Curve29Aff, true>(d, W, slots, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1);
+        else msm_window_launch<Curve29Aff, false>(d, W, slots, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1);
     } else {
         // the latency layout's few workgroups run their reduction trees with four lanes per addition (option msm_tree_quads=0: A/B)
         static const bool tree_quads = ab_flag("msm_tree_quads", true);
         if (tree_quads && d.chunks != MSM_CHUNKS && B <= 4) {
-            if (lds_sort) msm_window_launch<Curve29Quads, true>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-            else msm_window_launch<Curve29Quads, false>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-        } else if (lds_sort) msm_window_launch<Curve29, true>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
-        else msm_window_launch<Curve29, false>(d, W, slots, gz, w.d_msm_save, w.cap_msm_save, s->s1);
+            if (lds_sort) msm_window_launch<Curve29Quads, true>(d, W, slots, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1);
+            else msm_window_launch<Curve29Quads, false>(d, W, slots, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1);
+        } else if (lds_sort) msm_window_launch<Curve29, true>(d, W, slots, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1);
+        else msm_window_launch<Curve29, false>(d, W, slots, gz, w.d_msm_save.p, msm_save_bytes(w), s->s1);
     }
     // the latency layout (one window per chunk) of a few batches: every output is the plain sum of its slots x slices window
     // sums - one workgroup per output, four lanes per addition (option msm_sum_quads=0: the fold + combine kernels, A/B)
     static const bool sum_quads = ab_flag("msm_sum_quads", true);
     if (sum_quads && W == 1 && slots * S >= 2 && slots * S <= (unsigned)SUMQ_MAX_POINTS && 2 * B < 64) {
         HIPCHK(DYN_LDS(k_msm_sum_quads, SUMQ_LDS_BYTES));
-        hipLaunchKernelGGL(k_msm_sum_quads, dim3((unsigned)(2 * B)), dim3(256), SUMQ_LDS_BYTES, s->s1, d.window_sums, w.d_ab, (int)(slots * S));
+        hipLaunchKernelGGL(k_msm_sum_quads, dim3((unsigned)(2 * B)), dim3(256), SUMQ_LDS_BYTES, s->s1, d.window_sums, w.d_ab.p, (int)(slots * S));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(s->ev[3], s->s1));
         return KZG_OK;
     }
     if (S > 1)
-        hipLaunchKernelGGL(k_msm_fold_slices, dim3((unsigned)(2 * B * slots * W)), dim3(64), 0, s->s1, w.d_window_sl, w.d_window, (int)S, (int)W);
+        hipLaunchKernelGGL(k_msm_fold_slices, dim3((unsigned)(2 * B * slots * W)), dim3(64), 0, s->s1, w.d_window_sl.p, w.d_window.p, (int)S, (int)W);
     if (2 * B >= 64)  // enough outputs to fill wavefronts with one lane each
-        hipLaunchKernelGGL(k_msm_combine_lanes, dim3((unsigned)((2 * B + 63) / 64)), dim3(64), 0, s->s1, w.d_window, w.d_ab, (int)slots, (int)W, (int)(2 * B));
+        hipLaunchKernelGGL(k_msm_combine_lanes, dim3((unsigned)((2 * B + 63) / 64)), dim3(64), 0, s->s1, w.d_window.p, w.d_ab.p, (int)slots, (int)W, (int)(2 * B));
     else
-        hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)(2 * B)), dim3(64), 0, s->s1, w.d_window, w.d_ab, (int)slots, (int)W);
+        hipLaunchKernelGGL(k_msm_combine, dim3((unsigned)(2 * B)), dim3(64), 0, s->s1, w.d_window.p, w.d_ab.p, (int)slots, (int)W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
     return KZG_OK;
@@ -274,20 +239,20 @@ static KzgRet launch_decode(const KzgSettings* s, const void* d_commitments, con
     w.mult_affine = msm_affine_enabled() && w.chunks == MSM_CHUNKS;
     if (w.mult_affine) {
         // affine tables: rows 0 and 2 straight from the decode pass, rows 1 and 3 from 2^64 P through one inversion per 16 points
-        G1Aff29Mem* mult = (G1Aff29Mem*)w.d_mult;
+        G1Aff29Mem* mult = (G1Aff29Mem*)w.d_mult.p;
         // 256-thread workgroups: their four waves are dealt one to each SIMD of a CU (single-wave workgroups are placed unevenly)
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3((unsigned)((2 * T + 255) / 256)), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points, w.d_pflag, w.d_mult, w.d_jtmp, n2, np,
-                           w.kstamps_valid ? w.d_ktime + 6 : nullptr);
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3((unsigned)((2 * T + 255) / 256)), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, n2, np,
+                           w.kstamps_valid ? w.d_ktime.p + 6 : nullptr);
         const unsigned conv_blocks = (unsigned)((n2 + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
-        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s2, w.d_jtmp, w.d_pflag, mult, n2, np);
+        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s2, w.d_jtmp.p, w.d_pflag.p, mult, n2, np);
         HIPCHK(hipEventRecord(s->ev[10], s->s2));
-        hipLaunchKernelGGL(k_set_generator_multiples<G1Aff29Mem>, dim3(1), dim3(64), 0, s->s2, w.d_points, w.d_pflag, mult,
-                           (const G1Aff29Mem*)s->d_gen_mult_aff, n2, np, w.chunks);
+        hipLaunchKernelGGL(k_set_generator_multiples<G1Aff29Mem>, dim3(1), dim3(64), 0, s->s2, w.d_points.p, w.d_pflag.p, mult,
+                           (const G1Aff29Mem*)s->t->d_gen_mult_aff.p, n2, np, w.chunks);
     } else {
-        G1Jac29Mem* mult = (G1Jac29Mem*)w.d_mult;
+        G1Jac29Mem* mult = (G1Jac29Mem*)w.d_mult.p;
         // (the generator's rows first: behind the decode kernel they would sit on the critical path of a proof-tuple call)
-        hipLaunchKernelGGL(k_set_generator_multiples<G1Jac29Mem>, dim3(1), dim3(64), 0, s->s2, w.d_points, w.d_pflag, mult,
-                           (const G1Jac29Mem*)s->d_gen_mult + gen_off, n2, np, w.chunks);
+        hipLaunchKernelGGL(k_set_generator_multiples<G1Jac29Mem>, dim3(1), dim3(64), 0, s->s2, w.d_points.p, w.d_pflag.p, mult,
+                           (const G1Jac29Mem*)s->t->d_gen_mult.p + gen_off, n2, np, w.chunks);
         // the latency layouts: eight lanes per point, one wavefront of 8 points per CU (option decode_quads=0: one lane, A/B)
         static const bool dec_quads = ab_flag("decode_quads", true);
         // (while every workgroup can have a CU to itself, and not beside the challenge chain: there the decode hides behind the
@@ -295,11 +260,11 @@ static KzgRet launch_decode(const KzgSettings* s, const void* d_commitments, con
         if (dec_quads && w.chunks != MSM_CHUNKS && !behind_sha && (2 * T + DECQ_POINTS_PER_BLOCK - 1) / DECQ_POINTS_PER_BLOCK <= (size_t)s->n_cus) {
             blocks = (unsigned)((2 * T + DECQ_POINTS_PER_BLOCK - 1) / DECQ_POINTS_PER_BLOCK);
             HIPCHK(DYN_LDS(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, DECQ_LDS_BYTES));
-            hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, dim3(blocks), dim3(64), DECQ_LDS_BYTES, s->s2, c, p, (int)T, w.d_points, w.d_pflag, mult, n2, np);
+            hipLaunchKernelGGL(k_g1_decode_multiples29_quads<MSM_CHUNKS_LATENCY>, dim3(blocks), dim3(64), DECQ_LDS_BYTES, s->s2, c, p, (int)T, w.d_points.p, w.d_pflag.p, mult, n2, np);
         } else if (w.chunks == MSM_CHUNKS_LATENCY)
-            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS_LATENCY, false>), dim3(blocks), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, n2, np);
+            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS_LATENCY, false>), dim3(blocks), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points.p, w.d_pflag.p, w.d_mult.p, (G1Jac29Mem*)nullptr, n2, np);
         else
-            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3(blocks), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points, w.d_pflag, w.d_mult, (G1Jac29Mem*)nullptr, n2, np);
+            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3(blocks), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s2, c, p, (int)T, w.d_points.p, w.d_pflag.p, w.d_mult.p, (G1Jac29Mem*)nullptr, n2, np);
         HIPCHK(hipEventRecord(s->ev[10], s->s2));
     }
     HIPCHK(hipGetLastError());
@@ -410,7 +375,7 @@ static KzgRet sliced_segments(const KzgSettings* s, const HostBatch& host, void*
         HIPCHK(hipEventRecord(s->ev_slice[1 + j], s->s_copy));
         HIPCHK(hipStreamWaitEvent(st, s->ev_slice[1 + j], 0));
         hipLaunchKernelGGL(k_blob_challenge_split2_t<true>, dim3((unsigned)((T + 63) / 64)), dim3(192), 0, st, (const uint8_t*)d_blobs,
-                           (const uint8_t*)d_commitments, d_z, (int)T, (int)(1024 / S * j), (int)(1024 / S * (j + 1)), s->ws.d_sha_mid);
+                           (const uint8_t*)d_commitments, d_z, (int)T, (int)(1024 / S * j), (int)(1024 / S * (j + 1)), s->ws.d_sha_mid.p);
     }
     HIPCHK(hipGetLastError());
     return KZG_OK;
@@ -425,8 +390,8 @@ static KzgRet phase1_launch_locked(const void* d_blobs, const void* d_commitment
     KzgRet rc;
     select_streams(s, T);
     const unsigned S = host && !host->z_le ? host_slices(T) : 1;
-    w.kstamps_valid = w.d_ktime != nullptr;
-    if (w.kstamps_valid) HIPCHK(hipMemsetAsync(w.d_ktime, 0, 128, s->s1));  // (before ev[0]: every stream of the launch is ordered behind it)
+    w.kstamps_valid = w.d_ktime.p != nullptr;
+    if (w.kstamps_valid) HIPCHK(hipMemsetAsync(w.d_ktime.p, 0, 128, s->s1));  // (before ev[0]: every stream of the launch is ordered behind it)
     HIPCHK(hipEventRecord(s->ev[0], s->s1));
     if (host && S == 1) {  // one copy of everything, on the stream the kernels follow on
         HIPCHK(hipMemcpyAsync(const_cast<void*>(d_commitments), host->commitments, 48 * T, hipMemcpyHostToDevice, s->s1));
@@ -444,7 +409,7 @@ static KzgRet phase1_launch_locked(const void* d_blobs, const void* d_commitment
     // (with the challenges from the host there is no SHA-256 chain to hide behind: the eight-lane decode, as for proof tuples)
     if ((rc = launch_decode(s, d_commitments, d_proofs, T, /*behind_sha=*/!(host && host->z_le))) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[6], s->s2));
-    HIPCHK(hipMemsetAsync(w.d_status, 0, 4 * T, s->s1));
+    HIPCHK(hipMemsetAsync(w.d_status.p, 0, 4 * T, s->s1));
     if (s->s_sha != s->s1) {
         HIPCHK(hipEventRecord(s->ev[11], s->s1));
         HIPCHK(hipStreamWaitEvent(s->s_sha, s->ev[11], 0));
@@ -452,39 +417,39 @@ static KzgRet phase1_launch_locked(const void* d_blobs, const void* d_commitment
     if (host && host->z_le) {  // the host hashes the blobs: z crosses as 32 bytes per blob (pinned mirror, bytes [192 T, 224 T))
         w.ktime_valid = false;
         if (host->z_job) hostpool::finish(*host->z_job);
-        memcpy(w.h_buf + 192 * T, host->z_le, 32 * T);
-        HIPCHK(hipMemcpyAsync(w.d_z, w.h_buf + 192 * T, 32 * T, hipMemcpyHostToDevice, s->s_sha));
+        memcpy(w.h_buf.p + 192 * T, host->z_le, 32 * T);
+        HIPCHK(hipMemcpyAsync(w.d_z.p, w.h_buf.p + 192 * T, 32 * T, hipMemcpyHostToDevice, s->s_sha));
     } else if (host && S > 1) {
-        if ((rc = sliced_segments(s, *host, const_cast<void*>(d_blobs), d_commitments, w.d_z, T, S, s->s_sha)) != KZG_OK) return rc;
-    } else if ((rc = launch_challenge(s, d_blobs, d_commitments, w.d_z, T, s->s_sha)) != KZG_OK) return rc;
+        if ((rc = sliced_segments(s, *host, const_cast<void*>(d_blobs), d_commitments, w.d_z.p, T, S, s->s_sha)) != KZG_OK) return rc;
+    } else if ((rc = launch_challenge(s, d_blobs, d_commitments, w.d_z.p, T, s->s_sha)) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[7], s->s_sha));
     if (s->s_sha != s->s1) {  // both joins in one place: each wait on another stream's event is a ~13 us bubble, even when it has long fired
         HIPCHK(hipStreamWaitEvent(s->s1, s->ev[7], 0));
         HIPCHK(hipStreamWaitEvent(s->s1, s->ev[6], 0));
     }
-    if ((rc = launch_evaluate(s, d_blobs, w.d_z, w.d_y, w.d_status, T, false, w.kstamps_valid)) != KZG_OK) return rc;
+    if ((rc = launch_evaluate(s, d_blobs, w.d_z.p, w.d_y.p, w.d_status.p, T, false, w.kstamps_valid)) != KZG_OK) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[8], s->s1));
     if (s->s_sha == s->s1) HIPCHK(hipStreamWaitEvent(s->s1, s->ev[6], 0));
     HIPCHK(hipEventRecord(s->ev[1], s->s1));
     // the transcript records, packed on the device; pinned host mirror: [records 160 T | status 4 T | point flags 8 T]
-    uint8_t* h = w.h_buf;
+    uint8_t* h = w.h_buf.p;
     if (T <= LATENCY_MAX_BLOBS) {  // the kernel writes the mirror itself: every dispatch of a single batch's chain is ~10 us of latency
         hipLaunchKernelGGL(k_pack_records_mirror, dim3((unsigned)((43 * T + 255) / 256)), dim3(256), 0, s->s1, (const uint32_t*)d_commitments,
-                           (const uint32_t*)d_proofs, (const uint32_t*)w.d_z, (const uint32_t*)w.d_y, (uint32_t*)w.d_records, (uint32_t*)h,
-                           (const uint32_t*)w.d_status, (const uint32_t*)w.d_pflag, (int)T);
+                           (const uint32_t*)d_proofs, (const uint32_t*)w.d_z.p, (const uint32_t*)w.d_y.p, (uint32_t*)w.d_records.p, (uint32_t*)h,
+                           (const uint32_t*)w.d_status.p, (const uint32_t*)w.d_pflag.p, (int)T);
         HIPCHK(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_pack_records, dim3((unsigned)((40 * T + 255) / 256)), dim3(256), 0, s->s1, (const uint32_t*)d_commitments,
-                           (const uint32_t*)d_proofs, (const uint32_t*)w.d_z, (const uint32_t*)w.d_y, (uint32_t*)w.d_records, (int)T);
+                           (const uint32_t*)d_proofs, (const uint32_t*)w.d_z.p, (const uint32_t*)w.d_y.p, (uint32_t*)w.d_records.p, (int)T);
         HIPCHK(hipGetLastError());
         uint32_t* h_status = reinterpret_cast<uint32_t*>(h + 160 * T);
         uint32_t* h_pflag = h_status + T;
-        HIPCHK(hipMemcpyAsync(h, w.d_records, 160 * T, hipMemcpyDeviceToHost, s->s1));
-        HIPCHK(hipMemcpyAsync(h_status, w.d_status, 4 * T, hipMemcpyDeviceToHost, s->s1));
-        HIPCHK(hipMemcpyAsync(h_pflag, w.d_pflag, 8 * T, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(h, w.d_records.p, 160 * T, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(h_status, w.d_status.p, 4 * T, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(h_pflag, w.d_pflag.p, 8 * T, hipMemcpyDeviceToHost, s->s1));
     }
-    if (w.ktime_valid || w.kstamps_valid) HIPCHK(hipMemcpyAsync(h + 176 * T, w.d_ktime, 64, hipMemcpyDeviceToHost, s->s1));  // challenge | evaluate | decode
+    if (w.ktime_valid || w.kstamps_valid) HIPCHK(hipMemcpyAsync(h + 176 * T, w.d_ktime.p, 64, hipMemcpyDeviceToHost, s->s1));  // challenge | evaluate | decode
     w.pending_n = n;
     w.pending_b = B;
     return KZG_OK;
@@ -501,7 +466,7 @@ static KzgRet phase1_wait_locked(uint8_t* records_out, uint8_t* bad_out, const K
     elapsed(&s->timings[4], s->ev[7], s->ev[8]);
     elapsed(&s->timings[5], s->ev[0], s->ev[7]);
     if (w.ktime_valid) {  // the throughput-form kernel stamps its own execution interval (100 MHz ticks): no queueing time in it
-        const unsigned long long* kt = reinterpret_cast<const unsigned long long*>(w.h_buf + 176 * T);
+        const unsigned long long* kt = reinterpret_cast<const unsigned long long*>(w.h_buf.p + 176 * T);
         if (kt[0] && kt[1] && kt[1] > ~kt[0]) s->timings[5] = (float)((double)(kt[1] - ~kt[0]) * 1e-5);
         s->clk_sum[0] += (double)kt[2];  // shader cycles and 100 MHz reference ticks of the kernel's waves (kzg_debug_shader_clock)
         s->clk_sum[1] += (double)kt[3];
@@ -509,13 +474,13 @@ static KzgRet phase1_wait_locked(uint8_t* records_out, uint8_t* bad_out, const K
     elapsed(&s->timings[6], s->ev[5], s->ev[10]);
     elapsed(&s->timings[7], s->ev[10], s->ev[6]);
     {  // the kernels' own intervals (100 MHz ticks): challenge (its throughput form only) | evaluate | decode + multiples
-        const unsigned long long* kt = reinterpret_cast<const unsigned long long*>(w.h_buf + 176 * T);
+        const unsigned long long* kt = reinterpret_cast<const unsigned long long*>(w.h_buf.p + 176 * T);
         auto ms_of = [&](int k) { return kt[k] && kt[k + 1] && kt[k + 1] > ~kt[k] ? (float)((double)(kt[k + 1] - ~kt[k]) * 1e-5) : 0.f; };
         s->kstamp_ms[0] = w.ktime_valid ? ms_of(0) : 0.f;
         s->kstamp_ms[1] = w.kstamps_valid ? ms_of(4) : 0.f;
         s->kstamp_ms[2] = w.kstamps_valid ? ms_of(6) : 0.f;
     }
-    uint8_t* h = w.h_buf;
+    uint8_t* h = w.h_buf.p;
     uint32_t* h_status = reinterpret_cast<uint32_t*>(h + 160 * T);
     uint32_t* h_pflag = h_status + T;
     // error order of the reference: commitments (:503), proofs (:508), then blobs (:263); all map to BadArgs
@@ -543,29 +508,29 @@ static KzgRet phase2_launch_locked(const uint8_t* all_records, size_t n_total, s
     const size_t n = w.pending_n, B = w.pending_b;
     if (!all_records && !r_le) {
         if (n_total != n || offset != 0) return fail(KZG_BADARGS, "local phase 2 needs n_total == n_local");
-        all_records = w.h_buf;
+        all_records = w.h_buf.p;
         world = 0;
     }
     if (world && n_total != world * n) return fail(KZG_BADARGS, "gathered phase 2 needs equal shards");
     if (n_total == 1) {
         // verify_blob_kzg_proof path (:482-489): r^0 = 1, no batch challenge
-        hipLaunchKernelGGL(k_single_scalars, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_z, w.d_y, w.d_scalars);
+        hipLaunchKernelGGL(k_single_scalars, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_z.p, w.d_y.p, w.d_scalars.p);
     } else {
-        uint8_t* h_r = w.h_buf + w.off_r;  // pinned staging for the async H2D copy
+        uint8_t* h_r = w.h_buf.p + w.off_r;  // pinned staging for the async H2D copy
         if (r_le) memcpy(h_r, r_le, 32 * B);
         else if (!host_batch_challenges(h_r, all_records, B, n, n_total, world)) return fail(KZG_MALLOC, "batch transcript buffer");
-        const Fr* d_r = w.d_r;
+        const Fr* d_r = w.d_r.p;
         if (n * B <= LATENCY_MAX_BLOBS) d_r = reinterpret_cast<const Fr*>(h_r);  // a small launch reads r where the host wrote it (pinned memory)
-        else HIPCHK(hipMemcpyAsync(w.d_r, h_r, 32 * B, hipMemcpyHostToDevice, s->s1));
+        else HIPCHK(hipMemcpyAsync(w.d_r.p, h_r, 32 * B, hipMemcpyHostToDevice, s->s1));
         unsigned blocks = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(k_batch_scalars, dim3(blocks, (unsigned)B), dim3(256), 0, s->s1, d_r, w.d_z, w.d_y, w.d_scalars,
-                           w.d_partial, (int)n, (unsigned long long)offset);
-        hipLaunchKernelGGL(k_finish_g, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_partial, (int)blocks, w.d_scalars, (int)n);
+        hipLaunchKernelGGL(k_batch_scalars, dim3(blocks, (unsigned)B), dim3(256), 0, s->s1, d_r, w.d_z.p, w.d_y.p, w.d_scalars.p,
+                           w.d_partial.p, (int)n, (unsigned long long)offset);
+        hipLaunchKernelGGL(k_finish_g, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_partial.p, (int)blocks, w.d_scalars.p, (int)n);
     }
     HIPCHK(hipGetLastError());
     KzgRet rc = run_msm(s, n, B);
     if (rc != KZG_OK) return rc;
-    if (want_partials) HIPCHK(hipMemcpyAsync(w.h_buf + w.off_part, w.d_ab, 288 * B, hipMemcpyDeviceToHost, s->s1));  // (the local callers go straight on to the pairing)
+    if (want_partials) HIPCHK(hipMemcpyAsync(w.h_buf.p + w.off_part, w.d_ab.p, 288 * B, hipMemcpyDeviceToHost, s->s1));  // (the local callers go straight on to the pairing)
     return KZG_OK;
 }
 
@@ -573,7 +538,7 @@ static KzgRet phase2_wait_locked(uint8_t* partial_out /* B x 288 */, const KzgSe
     Workspace& w = s->ws;
     HIPCHK(hipStreamSynchronize(s->s1));
     elapsed(&s->timings[2], s->ev[2], s->ev[3]);
-    if (partial_out) memcpy(partial_out, w.h_buf + w.off_part, 288 * w.pending_b);
+    if (partial_out) memcpy(partial_out, w.h_buf.p + w.off_part, 288 * w.pending_b);
     return KZG_OK;
 }
 
@@ -585,21 +550,21 @@ static KzgRet finish_launch_locked(const uint8_t* partials, size_t world, size_t
     if (partials || parts_on_device) {
         if (world > MAX_WORLD) return fail(KZG_BADARGS, "world size above 64");
         if (!parts_on_device) {
-            memcpy(w.h_buf + w.off_parts, partials, 288 * world * B);
-            HIPCHK(hipMemcpyAsync(w.d_parts, w.h_buf + w.off_parts, 288 * world * B, hipMemcpyHostToDevice, s->s1));
+            memcpy(w.h_buf.p + w.off_parts, partials, 288 * world * B);
+            HIPCHK(hipMemcpyAsync(w.d_parts.p, w.h_buf.p + w.off_parts, 288 * world * B, hipMemcpyHostToDevice, s->s1));
         }
-        hipLaunchKernelGGL(k_fold_partials, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_parts, (int)world, (int)B, w.d_ab);
+        hipLaunchKernelGGL(k_fold_partials, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_parts.p, (int)world, (int)B, w.d_ab.p);
     }
-    hipLaunchKernelGGL(k_jac_to_slp, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_ab, w.d_slp_in);
+    hipLaunchKernelGGL(k_jac_to_slp, dim3((unsigned)B), dim3(64), 0, s->s1, w.d_ab.p, w.d_slp_in.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[4], s->s1));
     // (a handful of instances write their 288 bytes straight into the pinned mirror: one dispatch less at the end of the chain)
     const bool direct = B <= LATENCY_PAIRING_MAX;
-    KzgRet rc = run_verify(s, w.d_slp_in, direct ? reinterpret_cast<Fp*>(w.h_buf + w.off_out) : w.d_slp_out, (int)B, s->s1);
+    KzgRet rc = run_verify(s, w.d_slp_in.p, direct ? reinterpret_cast<Fp*>(w.h_buf.p + w.off_out) : w.d_slp_out.p, (int)B, s->s1);
     if (rc != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[9], s->s1));
-    if (!direct) HIPCHK(hipMemcpyAsync(w.h_buf + w.off_out, w.d_slp_out, sizeof(Fp) * 6 * B, hipMemcpyDeviceToHost, s->s1));
-    if (w.kstamps_valid && w.pending_n) HIPCHK(hipMemcpyAsync(w.h_buf + 176 * w.pending_n * w.pending_b + 64, w.d_ktime + 8, 16, hipMemcpyDeviceToHost, s->s1));  // the MSM window kernel's interval
+    if (!direct) HIPCHK(hipMemcpyAsync(w.h_buf.p + w.off_out, w.d_slp_out.p, sizeof(Fp) * 6 * B, hipMemcpyDeviceToHost, s->s1));
+    if (w.kstamps_valid && w.pending_n) HIPCHK(hipMemcpyAsync(w.h_buf.p + 176 * w.pending_n * w.pending_b + 64, w.d_ktime.p + 8, 16, hipMemcpyDeviceToHost, s->s1));  // the MSM window kernel's interval
     w.finish_b = B;
     return KZG_OK;
 }
@@ -607,7 +572,7 @@ static KzgRet finish_launch_locked(const uint8_t* partials, size_t world, size_t
 static KzgRet finish_wait_locked(bool* ok /* B */, const KzgSettings* s) {
     Workspace& w = s->ws;
     HIPCHK(hipStreamSynchronize(s->s1));
-    const uint32_t* h = reinterpret_cast<const uint32_t*>(w.h_buf + w.off_out);
+    const uint32_t* h = reinterpret_cast<const uint32_t*>(w.h_buf.p + w.off_out);
     for (size_t b = 0; b < w.finish_b; b++) {
         uint32_t any = 0;
         for (int i = 0; i < 72; i++) any |= h[72 * b + i];
@@ -619,7 +584,7 @@ static KzgRet finish_wait_locked(bool* ok /* B */, const KzgSettings* s) {
     for (int i = 0; i < 8; i++) s->tsum[i] += s->timings[i];
     s->tcount++;
     if (w.kstamps_valid && w.pending_n) {
-        const unsigned long long* kt = reinterpret_cast<const unsigned long long*>(w.h_buf + 176 * w.pending_n * w.pending_b + 64);
+        const unsigned long long* kt = reinterpret_cast<const unsigned long long*>(w.h_buf.p + 176 * w.pending_n * w.pending_b + 64);
         s->kstamp_ms[3] = kt[0] && kt[1] && kt[1] > ~kt[0] ? (float)((double)(kt[1] - ~kt[0]) * 1e-5) : 0.f;
         for (int i = 0; i < 4; i++) s->kstamp_sum[i] += s->kstamp_ms[i];
         s->kstamp_count++;
@@ -690,7 +655,7 @@ extern "C" KzgRet kzg_batch_challenges(uint8_t* r_le_out, const uint8_t* records
 }
 extern "C" KzgRet kzg_shard_records_device(void* d_records_out, const KzgSettings* s) {
     KZG_ENTER(s && d_records_out && s->ws.pending_n);
-    HIPCHK(hipMemcpyAsync(d_records_out, s->ws.d_records, 160 * s->ws.pending_n * s->ws.pending_b, hipMemcpyDeviceToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(d_records_out, s->ws.d_records.p, 160 * s->ws.pending_n * s->ws.pending_b, hipMemcpyDeviceToDevice, s->s1));
     return KZG_OK;
 }
 extern "C" KzgRet kzg_shard_phase2_wait(uint8_t* partial_out, const KzgSettings* s) {
@@ -856,7 +821,7 @@ extern "C" KzgRet kzg_verify_blob_kzg_proof_batch(bool* ok, const uint8_t* blobs
         hostpool::post(z_job, (size_t)std::max(1L, std::min(16L, opt_int("host_threads", 16))));
         host.z_job = z_job.get();
     }
-    rc = batch_device_locked(ok, w.d_stage_blobs, w.d_stage_cp, w.d_stage_cp + 48 * n, n, s, &host);
+    rc = batch_device_locked(ok, w.d_stage_blobs.p, w.d_stage_cp.p, w.d_stage_cp.p + 48 * n, n, s, &host);
     if (z_job) hostpool::finish(*z_job);  // (an error path may not have come by: no worker may still read the caller's memory)
     if (rc != KZG_OK && s->s_copy) {  // nothing may still read the caller's memory when the error goes back
         const std::string msg = g_err;
@@ -906,27 +871,21 @@ static KzgRet host_stream_locked(bool* ok_out, uint8_t* err_out, const uint8_t* 
     KzgRet rc = ws_reserve(s, G * n, G, STAGE_NONE);
     if (rc != KZG_OK) return rc;
     const size_t set_blobs = G * n, set_bytes = set_blobs * ((size_t)BLOB_BYTES + 96);
-    if (set_blobs > w.cap_hstage) {
-        for (auto& p : w.d_hstage) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-        w.cap_hstage = 0;
-        HIPCHK(hipMalloc(&w.d_hstage[0], set_bytes));
-        HIPCHK(hipMalloc(&w.d_hstage[1], set_bytes));
-        w.cap_hstage = set_blobs;
+    if (set_bytes > w.d_hstage[1].cap) {  // (the set allocated last: both are there when it is)
+        for (auto& b : w.d_hstage) b.release();
+        for (auto& b : w.d_hstage) HIPCHK(b.alloc(set_bytes));
     }
     if (!s->s_copy) {
         HIPCHK(hipStreamCreateWithFlags(&s->s_copy, hipStreamNonBlocking));
         for (auto& e : s->ev_copy) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    const size_t cap_set = w.cap_hstage;  // the layout of a staging set follows its capacity
+    const size_t cap_set = w.d_hstage[1].cap / ((size_t)BLOB_BYTES + 96);  // blobs per set: the layout of a staging set follows its capacity
     const size_t n_chunks = (n_batches + G - 1) / G;
     auto batches_of = [&](size_t c) { return std::min(G, n_batches - c * G); };
     // staging set layout: [blobs of the chunk | commitments | proofs]; `part` 0 / 1 = first / second half of the blobs
     // (the 96 bytes per blob of commitments and proofs travel with the first half)
     auto copy_part = [&](size_t c, int part) -> KzgRet {
-        uint8_t* dst = w.d_hstage[c & 1];
+        uint8_t* dst = w.d_hstage[c & 1].p;
         const size_t nb = batches_of(c) * n, first = c * G * n;
         const size_t half = (nb / 2) * (size_t)BLOB_BYTES, total = nb * (size_t)BLOB_BYTES;
         if (part == 0) {
@@ -954,7 +913,7 @@ static KzgRet host_stream_locked(bool* ok_out, uint8_t* err_out, const uint8_t* 
     if ((rc = copy_part(0, 0)) != KZG_OK || (rc = copy_part(0, 1)) != KZG_OK) return drained(rc);
     for (size_t c = 0; c < n_chunks; c++) {
         const size_t B = batches_of(c);
-        uint8_t* st = w.d_hstage[c & 1];
+        uint8_t* st = w.d_hstage[c & 1].p;
         select_streams(s, B * n);
         if (hipStreamWaitEvent(s->s1, s->ev_copy[c & 1], 0) != hipSuccess) return drained(fail(KZG_ERROR, "HIP: hipStreamWaitEvent"));  // this chunk has landed
         if ((rc = phase1_launch_locked(st, st + cap_set * (size_t)BLOB_BYTES, st + cap_set * ((size_t)BLOB_BYTES + 48), n, B, s)) != KZG_OK) return drained(rc);
@@ -980,13 +939,8 @@ static KzgRet host_stream_locked(bool* ok_out, uint8_t* err_out, const uint8_t* 
         const long v = opt_int("hstage_keep_mib", 4608);
         return (size_t)(v < 0 ? 0 : v) << 20;
     }();
-    if (w.cap_hstage * ((size_t)BLOB_BYTES + 96) > keep_bytes) {
-        for (auto& p : w.d_hstage) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-        w.cap_hstage = 0;
-    }
+    if (w.d_hstage[1].cap > keep_bytes)
+        for (auto& b : w.d_hstage) b.release();
     return KZG_OK;
 }
 
@@ -1008,7 +962,7 @@ extern "C" KzgRet kzg_verify_kzg_proof_batch(bool* ok, const uint8_t* commitment
 struct ProofStreams {
     hipStream_t sa, sb, sc;
 };
-// the buffers and streams of the one-proof path, made on first use; the pinned mirror (w.h_buf) holds
+// the buffers and streams of the one-proof path, made on first use; the pinned mirror (w.h_buf.p) holds
 //   [0, 64) z | y little-endian (verify_kzg_proof)   [64, 160) C | pi   [160, 168) status of the decompression
 //   [176, 184) status of the full decode   [1024, 1408) VERIFY3's eight outputs
 static KzgRet proof_reserve(ProofStreams& ps, const KzgSettings* s) {
@@ -1021,7 +975,7 @@ static KzgRet proof_reserve(ProofStreams& ps, const KzgSettings* s) {
     // batches/s at T = 8 and 414 at T = 16 (10 and 39 ms per call); without it 1 270 and 1 310 - 1 920 and 2 270 with 16 queues.
     select_streams(s, (size_t)-1);
     s->ws.kstamps_valid = false;  // (no launch group on this handle: the decode pass of these paths does not stamp)
-    if (!s->d_proof) HIPCHK(hipMalloc(&s->d_proof, sizeof(Fp) * (SCALARS_INPUTS + VERIFY3_INPUTS)));
+    HIPCHK(s->d_proof.grow(SCALARS_INPUTS + VERIFY3_INPUTS));
     const bool one_stream = !s->s_plain[1];  // option single_stream: everything in sequence (profiling)
     // A lane of the small-call queue runs chain C (the subgroup test) BEHIND chain B on B's stream: the square roots end at
     // ~0.65 ms and the test at ~1.5 ms, still before A's pairing (~1.7 ms), and a lane then holds two streams instead of three -
@@ -1040,13 +994,13 @@ static KzgRet proof_reserve(ProofStreams& ps, const KzgSettings* s) {
 // B and C: the two square roots -> VERIFY3's point inputs (event ev[6]); the full decode for the subgroup verdict
 static KzgRet proof_points_launch(const ProofStreams& ps, const uint8_t* commitment, const uint8_t* proof, const KzgSettings* s) {
     Workspace& w = s->ws;
-    uint8_t* const h = w.h_buf;
+    uint8_t* const h = w.h_buf.p;
     memcpy(h + 64, commitment, 48);
     memcpy(h + 112, proof, 48);
     uint32_t* const h_pre = reinterpret_cast<uint32_t*>(h + 160);
     uint32_t* const h_full = reinterpret_cast<uint32_t*>(h + 176);
     h_pre[0] = h_pre[1] = h_full[0] = h_full[1] = G1_INVALID;
-    Fp* const d_v3in = s->d_proof + SCALARS_INPUTS;
+    Fp* const d_v3in = s->d_proof.p + SCALARS_INPUTS;
     hipLaunchKernelGGL(k_proof_decompress, dim3(1), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), ps.sb, h + 64, h + 112, 1, d_v3in, h_pre);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[6], ps.sb));
@@ -1058,23 +1012,23 @@ static KzgRet proof_points_launch(const ProofStreams& ps, const uint8_t* commitm
     s->s2 = ps.sc;
     KzgRet rc = launch_decode(s, h + 64, h + 112, 1, /*behind_sha=*/false);
     if (rc != KZG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(h_full, w.d_pflag, 8, hipMemcpyDeviceToHost, ps.sc));
+    HIPCHK(hipMemcpyAsync(h_full, w.d_pflag.p, 8, hipMemcpyDeviceToHost, ps.sc));
     return KZG_OK;
 }
 // A: the scalars' chain from z and y (8 little-endian limbs each; pinned host or device memory; ordered behind what stream
 // sa already holds), then the pairing once the points are there; waits, and reads the verdicts
 static KzgRet proof_tail_locked(bool* ok, bool* general, const ProofStreams& ps, const uint32_t* z, const uint32_t* y, const KzgSettings* s) {
     Workspace& w = s->ws;
-    uint8_t* const h = w.h_buf;
-    Fp* const d_scal_in = s->d_proof;
-    Fp* const d_v3in = s->d_proof + SCALARS_INPUTS;
+    uint8_t* const h = w.h_buf.p;
+    Fp* const d_scal_in = s->d_proof.p;
+    Fp* const d_v3in = s->d_proof.p + SCALARS_INPUTS;
     Fp* const h_out = reinterpret_cast<Fp*>(h + 1024);
-    hipLaunchKernelGGL(k_proof_select, dim3(1), dim3(128), 0, ps.sa, z, y, 0u, s->d_fixed_base, s->d_tau4, d_scal_in);
-    KzgRet rc = run_program2(s->scalars, d_scal_in, nullptr, d_v3in + 6, 1, ps.sa);
+    hipLaunchKernelGGL(k_proof_select, dim3(1), dim3(128), 0, ps.sa, z, y, 0u, s->t->d_fixed_base.p, s->t->d_tau4.p, d_scal_in);
+    KzgRet rc = run_program2(s->t->scalars, d_scal_in, nullptr, d_v3in + 6, 1, ps.sa);
     if (rc != KZG_OK) return rc;
     if (ps.sb != ps.sa) HIPCHK(hipStreamWaitEvent(ps.sa, s->ev[6], 0));
     HIPCHK(hipEventRecord(s->ev[4], ps.sa));
-    if ((rc = run_program2(s->verify3, d_v3in, s->d_prep29, h_out, 1, ps.sa)) != KZG_OK) return rc;  // the eight outputs go straight into the mirror
+    if ((rc = run_program2(s->t->verify3, d_v3in, s->t->d_prep29.p, h_out, 1, ps.sa)) != KZG_OK) return rc;  // the eight outputs go straight into the mirror
     HIPCHK(hipEventRecord(s->ev[9], ps.sa));
     HIPCHK(hipStreamSynchronize(ps.sa));
     if (ps.sc != ps.sa) HIPCHK(hipStreamSynchronize(ps.sc));
@@ -1111,7 +1065,7 @@ static KzgRet proof_single_locked(bool* ok, bool* general, const uint8_t* commit
     ProofStreams ps{};
     KzgRet rc = proof_reserve(ps, s);
     if (rc != KZG_OK) return rc;
-    uint8_t* const h = s->ws.h_buf;
+    uint8_t* const h = s->ws.h_buf.p;
     reverse32(h, z_be);
     reverse32(h + 32, y_be);
     HIPCHK(hipEventRecord(s->ev[0], ps.sa));
@@ -1129,19 +1083,19 @@ static KzgRet blob_single_locked(bool* ok, bool* general, const uint8_t* blob, c
     KzgRet rc = proof_reserve(ps, s);
     if (rc != KZG_OK) return rc;
     Workspace& w = s->ws;
-    uint8_t* const h = w.h_buf;
+    uint8_t* const h = w.h_buf.p;
     HIPCHK(hipEventRecord(s->ev[0], ps.sa));
     if ((rc = proof_points_launch(ps, commitment, proof, s)) != KZG_OK) return rc;
-    HIPCHK(hipMemsetAsync(w.d_status, 0, 4, ps.sa));
-    HIPCHK(hipMemcpyAsync(w.d_stage_blobs, blob, BLOB_BYTES, hipMemcpyHostToDevice, ps.sa));  // (pageable: the call returns when the bytes have left)
+    HIPCHK(hipMemsetAsync(w.d_status.p, 0, 4, ps.sa));
+    HIPCHK(hipMemcpyAsync(w.d_stage_blobs.p, blob, BLOB_BYTES, hipMemcpyHostToDevice, ps.sa));  // (pageable: the call returns when the bytes have left)
     if (job) {  // (a caller that queued behind other calls hashed its blob while it waited: capi_coalesce.hpp)
         hostpool::finish(*job);
         memcpy(h + 192, job->z_le, 32);
     } else host_blob_challenge(h + 192, blob, commitment);
-    HIPCHK(hipMemcpyAsync(w.d_z, h + 192, 32, hipMemcpyHostToDevice, ps.sa));
-    if ((rc = launch_evaluate(s, w.d_stage_blobs, w.d_z, w.d_y, w.d_status, 1)) != KZG_OK) return rc;  // (on s->s1 = sa)
-    HIPCHK(hipMemcpyAsync(h + 224, w.d_status, 4, hipMemcpyDeviceToHost, ps.sa));
-    rc = proof_tail_locked(ok, general, ps, reinterpret_cast<const uint32_t*>(w.d_z), reinterpret_cast<const uint32_t*>(w.d_y), s);
+    HIPCHK(hipMemcpyAsync(w.d_z.p, h + 192, 32, hipMemcpyHostToDevice, ps.sa));
+    if ((rc = launch_evaluate(s, w.d_stage_blobs.p, w.d_z.p, w.d_y.p, w.d_status.p, 1)) != KZG_OK) return rc;  // (on s->s1 = sa)
+    HIPCHK(hipMemcpyAsync(h + 224, w.d_status.p, 4, hipMemcpyDeviceToHost, ps.sa));
+    rc = proof_tail_locked(ok, general, ps, reinterpret_cast<const uint32_t*>(w.d_z.p), reinterpret_cast<const uint32_t*>(w.d_y.p), s);
     // A runtime failure inside the tail is reported as what it is: the mirrors below are only meaningful once the streams were
     // synchronised (before that they hold the G1_INVALID they were initialised with, or are still being written), and an
     // infrastructure failure must never look like the reference's Err(BadArgs) for an invalid input.
@@ -1173,20 +1127,18 @@ static KzgRet proofs_reserve(ProofStreams& ps, ProofsLaunch& pl, size_t m, int s
     KzgRet rc = proof_reserve(ps, s);
     if (rc != KZG_OK) return rc;
     if (m > s->cap_proofs) {
-        if (s->d_proofs) (void)hipFree(s->d_proofs);
-        if (s->d_proofs_out) (void)hipFree(s->d_proofs_out);
-        if (s->h_proofs) (void)hipHostFree(s->h_proofs);
-        s->d_proofs = s->d_proofs_out = nullptr;
-        s->h_proofs = nullptr;
         s->cap_proofs = 0;
+        s->d_proofs.release();  // (all three before the first allocation)
+        s->d_proofs_out.release();
+        s->h_proofs.release();
         const size_t cap = std::max<size_t>(m, 64);
-        HIPCHK(hipMalloc(&s->d_proofs, sizeof(Fp) * (SCALARS_INPUTS + VERIFY3_INPUTS) * cap));
-        HIPCHK(hipMalloc(&s->d_proofs_out, sizeof(Fp) * VERIFY3_OUTPUTS * cap));
-        HIPCHK(hipHostMalloc(&s->h_proofs, PROOFS_MIRROR_BYTES * cap));
+        HIPCHK(s->d_proofs.alloc((SCALARS_INPUTS + VERIFY3_INPUTS) * cap));
+        HIPCHK(s->d_proofs_out.alloc(VERIFY3_OUTPUTS * cap));
+        HIPCHK(s->h_proofs.alloc(PROOFS_MIRROR_BYTES * cap));
         s->cap_proofs = cap;
     }
     if ((rc = ws_reserve(s, m, 1, stage)) != KZG_OK) return rc;
-    uint8_t* const h = s->h_proofs;
+    uint8_t* const h = s->h_proofs.p;
     pl.m = m;
     pl.h_zy = reinterpret_cast<uint32_t*>(h);
     pl.h_c = h + 64 * m;
@@ -1194,8 +1146,8 @@ static KzgRet proofs_reserve(ProofStreams& ps, ProofsLaunch& pl, size_t m, int s
     pl.h_pre = reinterpret_cast<uint32_t*>(pl.h_p + 48 * m);
     pl.h_full = pl.h_pre + 2 * m;
     pl.h_out = reinterpret_cast<Fp*>(pl.h_full + 2 * m);
-    pl.d_scal_in = s->d_proofs;
-    pl.d_v3in = s->d_proofs + (size_t)SCALARS_INPUTS * m;
+    pl.d_scal_in = s->d_proofs.p;
+    pl.d_v3in = s->d_proofs.p + (size_t)SCALARS_INPUTS * m;
     return KZG_OK;
 }
 // streams B and C for m proofs: the square roots (two lanes per proof) -> VERIFY3's point inputs (event ev[6]); the full
@@ -1219,20 +1171,20 @@ static KzgRet proofs_points_launch(const ProofStreams& ps, const ProofsLaunch& p
     s->s2 = ps.sc;
     const KzgRet rc = launch_decode(s, pl.h_c, pl.h_p, m, /*behind_sha=*/false);
     if (rc != KZG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(pl.h_full, s->ws.d_pflag, 8 * m, hipMemcpyDeviceToHost, ps.sc));
+    HIPCHK(hipMemcpyAsync(pl.h_full, s->ws.d_pflag.p, 8 * m, hipMemcpyDeviceToHost, ps.sc));
     return KZG_OK;
 }
 // stream A for m proofs: z and y (8 little-endian limbs each, stride_words apart; pinned host or device memory; behind what
 // stream sa already holds) -> select -> SCALARS -> (points there) -> VERIFY3 -> the mirror; waits for A and C
 static KzgRet proofs_tail_locked(const ProofStreams& ps, const ProofsLaunch& pl, const uint32_t* z, const uint32_t* y, uint32_t stride_words, const KzgSettings* s) {
     const size_t m = pl.m;
-    hipLaunchKernelGGL(k_proof_select, dim3((unsigned)m), dim3(128), 0, ps.sa, z, y, stride_words, s->d_fixed_base, s->d_tau4, pl.d_scal_in);
-    KzgRet rc = run_program2(s->scalars, pl.d_scal_in, nullptr, pl.d_v3in + 6, (int)m, ps.sa, 0, VERIFY3_INPUTS);
+    hipLaunchKernelGGL(k_proof_select, dim3((unsigned)m), dim3(128), 0, ps.sa, z, y, stride_words, s->t->d_fixed_base.p, s->t->d_tau4.p, pl.d_scal_in);
+    KzgRet rc = run_program2(s->t->scalars, pl.d_scal_in, nullptr, pl.d_v3in + 6, (int)m, ps.sa, 0, VERIFY3_INPUTS);
     if (rc != KZG_OK) return rc;
     if (ps.sb != ps.sa) HIPCHK(hipStreamWaitEvent(ps.sa, s->ev[6], 0));
     HIPCHK(hipEventRecord(s->ev[4], ps.sa));
-    if ((rc = run_program2(s->verify3, pl.d_v3in, s->d_prep29, s->d_proofs_out, (int)m, ps.sa)) != KZG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(pl.h_out, s->d_proofs_out, sizeof(Fp) * VERIFY3_OUTPUTS * m, hipMemcpyDeviceToHost, ps.sa));
+    if ((rc = run_program2(s->t->verify3, pl.d_v3in, s->t->d_prep29.p, s->d_proofs_out.p, (int)m, ps.sa)) != KZG_OK) return rc;
+    HIPCHK(hipMemcpyAsync(pl.h_out, s->d_proofs_out.p, sizeof(Fp) * VERIFY3_OUTPUTS * m, hipMemcpyDeviceToHost, ps.sa));
     HIPCHK(hipEventRecord(s->ev[9], ps.sa));
     HIPCHK(hipStreamSynchronize(ps.sa));
     if (ps.sc != ps.sa) HIPCHK(hipStreamSynchronize(ps.sc));
@@ -1328,10 +1280,10 @@ static KzgRet blobs_parts_locked(BlobsPart* parts, size_t n_parts, size_t m, con
     }
     HIPCHK(hipEventRecord(s->ev[0], ps.sa));
     if ((rc = proofs_points_launch(ps, pl, nullptr, nullptr, s)) != KZG_OK) return rc;
-    HIPCHK(hipMemsetAsync(w.d_status, 0, 4 * m, ps.sa));
+    HIPCHK(hipMemsetAsync(w.d_status.p, 0, 4 * m, ps.sa));
     off = 0;
     for (size_t k = 0; k < n_parts; k++) {  // (pageable: each call returns when its bytes have left)
-        HIPCHK(hipMemcpyAsync(w.d_stage_blobs + off * (size_t)BLOB_BYTES, parts[k].blobs, parts[k].n * (size_t)BLOB_BYTES, hipMemcpyHostToDevice, ps.sa));
+        HIPCHK(hipMemcpyAsync(w.d_stage_blobs.p + off * (size_t)BLOB_BYTES, parts[k].blobs, parts[k].n * (size_t)BLOB_BYTES, hipMemcpyHostToDevice, ps.sa));
         off += parts[k].n;
     }
     off = 0;
@@ -1342,10 +1294,10 @@ static KzgRet blobs_parts_locked(BlobsPart* parts, size_t n_parts, size_t m, con
         } else hostpool::finish(*own[k]);
         off += parts[k].n;
     }
-    HIPCHK(hipMemcpyAsync(w.d_z, h_z, 32 * m, hipMemcpyHostToDevice, ps.sa));
-    if ((rc = launch_evaluate(s, w.d_stage_blobs, w.d_z, w.d_y, w.d_status, m)) != KZG_OK) return rc;  // (on s->s1 = sa)
-    HIPCHK(hipMemcpyAsync(h_status, w.d_status, 4 * m, hipMemcpyDeviceToHost, ps.sa));
-    if ((rc = proofs_tail_locked(ps, pl, reinterpret_cast<const uint32_t*>(w.d_z), reinterpret_cast<const uint32_t*>(w.d_y), 8u, s)) != KZG_OK) return rc;
+    HIPCHK(hipMemcpyAsync(w.d_z.p, h_z, 32 * m, hipMemcpyHostToDevice, ps.sa));
+    if ((rc = launch_evaluate(s, w.d_stage_blobs.p, w.d_z.p, w.d_y.p, w.d_status.p, m)) != KZG_OK) return rc;  // (on s->s1 = sa)
+    HIPCHK(hipMemcpyAsync(h_status, w.d_status.p, 4 * m, hipMemcpyDeviceToHost, ps.sa));
+    if ((rc = proofs_tail_locked(ps, pl, reinterpret_cast<const uint32_t*>(w.d_z.p), reinterpret_cast<const uint32_t*>(w.d_y.p), 8u, s)) != KZG_OK) return rc;
     off = 0;
     for (size_t k = 0; k < n_parts; k++) {
         BlobsPart& pt = parts[k];
@@ -1517,12 +1469,12 @@ extern "C" KzgRet kzg_verify_kzg_proof_batch(bool* ok, const uint8_t* commitment
         reverse32(o + 48, zs + 32 * i);
         reverse32(o + 80, ys + 32 * i);
         memcpy(o + 112, proofs + 48 * i, 48);
-        memcpy(w.h_buf + 32 * i, o + 48, 32);
-        memcpy(w.h_buf + 32 * n + 32 * i, o + 80, 32);
+        memcpy(w.h_buf.p + 32 * i, o + 48, 32);
+        memcpy(w.h_buf.p + 32 * n + 32 * i, o + 80, 32);
     }
-    HIPCHK(hipMemcpyAsync(w.d_z, w.h_buf, 32 * n, hipMemcpyHostToDevice, s->s1));
-    HIPCHK(hipMemcpyAsync(w.d_y, w.h_buf + 32 * n, 32 * n, hipMemcpyHostToDevice, s->s1));
-    uint32_t* h_pflag = reinterpret_cast<uint32_t*>(w.h_buf + 64 * n);
+    HIPCHK(hipMemcpyAsync(w.d_z.p, w.h_buf.p, 32 * n, hipMemcpyHostToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_y.p, w.h_buf.p + 32 * n, 32 * n, hipMemcpyHostToDevice, s->s1));
+    uint32_t* h_pflag = reinterpret_cast<uint32_t*>(w.h_buf.p + 64 * n);
     // A small call keeps the host out of the chain: the decode kernel reads the points where they lie (a pinned copy - the
     // caller's memory is pageable), the MSM waits for it through an event, and the point flags are looked at after the
     // pairing (flagged points have identity table rows: the work on them is wasted, not wrong).
@@ -1533,18 +1485,18 @@ extern "C" KzgRet kzg_verify_kzg_proof_batch(bool* ok, const uint8_t* commitment
         ~RestoreS2() { s->s2 = keep; }
     } restore_s2{s, s->s2};
     if (chained) {
-        uint8_t* h_cp = w.h_buf + 72 * n;
+        uint8_t* h_cp = w.h_buf.p + 72 * n;
         memcpy(h_cp, commitments, 48 * n);
         memcpy(h_cp + 48 * n, proofs, 48 * n);
         s->s2 = s->s1;  // nothing runs beside the decode here: one stream, no event between the kernels (select_streams resets the pair)
         if ((rc = launch_decode(s, h_cp, h_cp + 48 * n, n, /*behind_sha=*/false)) != KZG_OK) return rc;
-        HIPCHK(hipMemcpyAsync(h_pflag, w.d_pflag, 8 * n, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipMemcpyAsync(h_pflag, w.d_pflag.p, 8 * n, hipMemcpyDeviceToHost, s->s1));
     } else {
-        HIPCHK(hipMemcpyAsync(w.d_stage_cp, commitments, 48 * n, hipMemcpyHostToDevice, s->s1));
-        HIPCHK(hipMemcpyAsync(w.d_stage_cp + 48 * n, proofs, 48 * n, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemcpyAsync(w.d_stage_cp.p, commitments, 48 * n, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemcpyAsync(w.d_stage_cp.p + 48 * n, proofs, 48 * n, hipMemcpyHostToDevice, s->s1));
         HIPCHK(hipStreamSynchronize(s->s1));
-        if ((rc = launch_decode(s, w.d_stage_cp, w.d_stage_cp + 48 * n, n, /*behind_sha=*/false)) != KZG_OK) return rc;
-        HIPCHK(hipMemcpyAsync(h_pflag, w.d_pflag, 8 * n, hipMemcpyDeviceToHost, s->s2));
+        if ((rc = launch_decode(s, w.d_stage_cp.p, w.d_stage_cp.p + 48 * n, n, /*behind_sha=*/false)) != KZG_OK) return rc;
+        HIPCHK(hipMemcpyAsync(h_pflag, w.d_pflag.p, 8 * n, hipMemcpyDeviceToHost, s->s2));
         HIPCHK(hipStreamSynchronize(s->s2));
         for (size_t i = 0; i < 2 * n; i++)
             if (h_pflag[i] == G1_INVALID) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");

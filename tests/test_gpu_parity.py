@@ -1138,7 +1138,8 @@ def test_host_slices_forced_in_child_process(slices):
 
 def test_handles_release_device_memory_and_oom_is_malloc():
     """(a) 50 settings handles created, used (so that each grows its workspace) and freed: the device's free memory returns
-    to where it was (no leak in the handle, its streams, tables or workspace).  (b) a request the device cannot hold is
+    to where it was (no leak in the handle, its streams, tables or workspace); the same for handles over the full setup that
+    used the prover side, the cell verifier and the cell prover.  (b) a request the device cannot hold is
     KZG_MALLOC - c-kzg-4844's C_KZG_MALLOC, not a generic error - and the handle keeps working afterwards."""
     import ctypes as C
     import torch
@@ -1188,7 +1189,31 @@ def test_handles_release_device_memory_and_oom_is_malloc():
     torch.cuda.synchronize()
     free_b, _ = torch.cuda.mem_get_info()
     assert free_a - free_b < (8 << 20), "prover buffers not returned: %d bytes" % (free_a - free_b)
-    free1 = free_b
+    # ... and that ran the cell paths: the cell verifier's state, the cell prover's state with its 48 MB FK20 table
+    cell_blob = tup[0]
+    h = KzgSettings.load_trusted_setup_file()
+    cells, cell_proofs = api.compute_cells_and_kzg_proofs([cell_blob], h)
+    h.close()
+    cell_args = ([Bytes48(tup[1])] * 128, list(range(128)), cells[0], [Bytes48(p) for p in cell_proofs[0]])
+
+    def cell_cycle(k, proofs):
+        for _ in range(k):
+            h = KzgSettings.load_trusted_setup_file()
+            assert KzgProof.verify_cell_kzg_proof_batch(*cell_args, h) is True
+            assert [c.data for c in api.compute_cells([cell_blob], h)[0]] == [c.data for c in cells[0]]
+            if proofs:  # (derives the FK20 table: ~1.2 s per handle)
+                assert api.compute_cells_and_kzg_proofs([cell_blob], h)[1] == cell_proofs
+            h.close()
+
+    cell_cycle(2, True)
+    torch.cuda.synchronize()
+    free_c, _ = torch.cuda.mem_get_info()
+    cell_cycle(4, True)
+    cell_cycle(20, False)  # the call buffers of the two cheap paths alone are ~0.6 MB per handle: enough handles for the bound to see them
+    torch.cuda.synchronize()
+    free_d, _ = torch.cuda.mem_get_info()
+    assert free_c - free_d < (8 << 20), "cell buffers not returned: %d bytes" % (free_c - free_d)
+    free1 = free_d
     # (b) a launch group of 2^36 blobs: the very first workspace array (2 TiB) cannot be allocated - nothing is launched
     HipBackend(st0)  # declares the argtypes
     rc = api.lib().kzg_shard_phase1_launch(d_b.data_ptr(), d_c.data_ptr(), d_p.data_ptr(), 1 << 36, 1, st0._h)
