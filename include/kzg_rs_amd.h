@@ -306,6 +306,23 @@ KzgRet kzg_compute_cells(uint8_t *cells_out, const uint8_t *blobs, size_t n, con
 /* the same cells (cells_out may be NULL) and the n * 128 proofs */
 KzgRet kzg_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint8_t *blobs, size_t n,
                                         const KzgSettings *s);
+/* EIP-7594 cell recovery (not in the reference: c-kzg-4844's recover_cells_and_kzg_proofs).  n blobs, each given by num_cells of its
+ * 128 cells (64 <= num_cells <= 128): the indices of blob b are cell_indices[b * num_cells + k], strictly ascending within a blob
+ * (every blob has its own list), its cells are at cells + (b * num_cells + k) * 2048; host pointers.  cells_out, proofs_out: as in
+ * kzg_compute_cells_and_kzg_proofs, ALL 128 cells (the given ones come out byte for byte as they went in) and all 128 proofs of
+ * every blob; either may be NULL, not both, and without proofs_out neither the FK20 table nor the proof chain is touched.  The
+ * erasure decoding is not the spec's 8 192-point form: the vanishing polynomial of the missing cells is a polynomial in X^64, so a
+ * blob splits into 64 independent 128-point problems; the proofs are the cell prover's FK20 chain on the recovered
+ * coefficients.  KZG_BADARGS (no output is promised; the handle stays usable) for num_cells outside 64..128, an index >= 128, indices
+ * that are not strictly ascending, a field element >= r, settings without G1 points, and cells that are not the evaluations of one
+ * polynomial of degree < 4096 (an exact test, which 64 cells always pass); KZG_BAD_SETUP for an off-subgroup set-up point; n == 0 is
+ * KZG_OK.  The index lists are checked on the host before anything is copied.  The handle's lock is taken; a multi-device handle
+ * runs the call on its first device; blobs are processed 64 per launch.  Measured from 64 cells (DESIGN.md 4b,
+ * profiles/cell_recover_probe.json): 6.5 ms for one blob, 9.9 ms for six, 62.5 ms for 64 with proofs - 0.3 ms more than
+ * kzg_compute_cells_and_kzg_proofs on the same blobs - and 0.5 / 0.6 / 1.1 ms with proofs_out == NULL.  Bad input is rejected
+ * before the proof chain is started.  The buffers (another ~85 MB for 64 blobs) stay on the handle. */
+KzgRet kzg_recover_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint64_t *cell_indices,
+                                        const uint8_t *cells, size_t num_cells, size_t n, const KzgSettings *s);
 
 /* EIP-7594 cell proofs (not in the reference: c-kzg-4844's verify_cell_kzg_proof_batch, the consensus spec's
  * verify_cell_kzg_proof_batch_impl).  Cell k of the batch is (commitment k, cell index k, 64 big-endian field elements - the

@@ -127,6 +127,7 @@ def lib():
         L.kzg_verify_cell_kzg_proof_batch.argtypes = [bp, u8, C.POINTER(C.c_uint64), u8, u8, sz, vp]
         L.kzg_compute_cells.argtypes = [u8, u8, sz, vp]
         L.kzg_compute_cells_and_kzg_proofs.argtypes = [u8, u8, u8, sz, vp]
+        L.kzg_recover_cells_and_kzg_proofs.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, sz, sz, vp]
         L.kzg_cell_batch_challenge.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz]
         L.kzg_settings_g1_monomial_point.argtypes = [vp, sz, u8]
         L.kzg_verify_kzg_proof.argtypes = [bp, u8, u8, u8, u8, vp]
@@ -718,6 +719,36 @@ def compute_cells_and_kzg_proofs(blobs, kzg_settings):
     out = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * max(n, 1))
     pr = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(n, 1))
     _chk(lib().kzg_compute_cells_and_kzg_proofs(out, pr, b"".join(data), n, kzg_settings._h))
+    raw = pr.raw
+    proofs = [[raw[48 * (CELLS_PER_EXT_BLOB * b + c): 48 * (CELLS_PER_EXT_BLOB * b + c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
+              for b in range(n)]
+    return _cells_of(out, n), proofs
+
+
+def recover_cells_and_kzg_proofs(cell_indices, cells, kzg_settings):
+    """c-kzg-4844's recover_cells_and_kzg_proofs (EIP-7594) for a list of blobs: cell_indices[b] = the strictly ascending indices
+    of the cells of blob b that are known (64 to 128 of them, the same number for every blob of a call), cells[b] = those cells
+    (Cell or bytes).  -> (cells, proofs) as compute_cells_and_kzg_proofs returns them: all 128 of each, per blob.  Lists of
+    unequal length, blobs with differing cell counts and a cell of the wrong size raise InvalidBytesLength before any device call;
+    everything else that is wrong with the input (include/kzg_rs_amd.h) raises BadArgs."""
+    if len(cell_indices) != len(cells):
+        raise InvalidBytesLength("cell_indices and cells differ in length: %d and %d blobs" % (len(cell_indices), len(cells)))
+    n = len(cells)
+    data = [[c.data if isinstance(c, Cell) else bytes(c) for c in per] for per in cells]
+    per = len(data[0]) if n else 0
+    for idx, cs in zip(cell_indices, data):
+        if len(idx) != len(cs) or len(cs) != per:
+            raise InvalidBytesLength("every blob needs as many cell indices as cells, and the same number as the other blobs")
+        for c in cs:
+            if len(c) != BYTES_PER_CELL:
+                raise InvalidBytesLength("Invalid cell length: %d bytes, expected %d" % (len(c), BYTES_PER_CELL))
+    flat = [int(c) for idx in cell_indices for c in idx]
+    if any(not 0 <= c < 1 << 64 for c in flat):
+        raise KzgError("BadArgs", "cell index out of range")
+    out = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * max(n, 1))
+    pr = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(n, 1))
+    idx = (C.c_uint64 * max(len(flat), 1))(*flat)
+    _chk(lib().kzg_recover_cells_and_kzg_proofs(out, pr, idx, b"".join(c for cs in data for c in cs), per, n, kzg_settings._h))
     raw = pr.raw
     proofs = [[raw[48 * (CELLS_PER_EXT_BLOB * b + c): 48 * (CELLS_PER_EXT_BLOB * b + c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
               for b in range(n)]

@@ -1,0 +1,120 @@
+// capi_cell_recover.hpp - EIP-7594 cell recovery (c-kzg-4844 recover_cells_and_kzg_proofs; not in the reference): the entry point.
+// Part of the single translation unit kzg_capi.hip; not a stand-alone header.  Device side: recover_kernels.hpp; the algorithm (64
+// independent 128-point problems instead of the spec's 8 192-point one): recover_ntt.hpp.
+//
+// Data flow of one call, PROVER_CHUNK blobs per launch of every kernel (the blob is a grid dimension):
+//   host     the index lists are checked (range, strictly ascending) before anything is copied; per blob the map cell -> slot
+//   copy     the given cells, the index lists and the maps to the device
+//   recover  k_recover_cell_idft, k_recover_vanishing -> k_recover_poly: the blob's coefficients in the cell prover's d_coef
+//   cells    k_recover_cells: all 128 cells (the given ones come out as they went in)
+//   verdict  the status words are read BEFORE the proof chain is queued: bad input is rejected after the small kernels alone
+//   proofs   the cell prover's chain, unchanged, on d_coef: k_fk20_tvec_dft -> ... -> k_fk20_compress
+// The coefficients and the proof chain's buffers are the cell prover's (CellProverState::reserve); what only recovery needs lives
+// in CellRecoverState beside it.  A call without proofs_out touches neither the FK20 table nor the chain.
+
+struct CellRecoverState {
+    size_t cap = 0;  // blobs
+    DevBuf<uint8_t> d_cells, d_cidx, d_slot, d_out;
+    DevBuf<Fr29> d_u, d_zev, d_invz, d_ev;
+    KzgRet reserve(size_t m) {
+        if (m <= cap) return KZG_OK;
+        cap = 0;
+        HIPCHK(d_cells.alloc((size_t)RECOVER_N * CELL_FE * 32 * m));
+        HIPCHK(d_cidx.alloc((size_t)RECOVER_N * m));
+        HIPCHK(d_slot.alloc((size_t)RECOVER_N * m));
+        HIPCHK(d_out.alloc((size_t)RECOVER_N * CELL_FE * 32 * m));
+        HIPCHK(d_u.alloc((size_t)RECOVER_N * CELL_FE * m));
+        HIPCHK(d_zev.alloc((size_t)RECOVER_N * m));
+        HIPCHK(d_invz.alloc((size_t)RECOVER_N * m));
+        HIPCHK(d_ev.alloc((size_t)RECOVER_N * CELL_FE * m));
+        cap = m;
+        return KZG_OK;
+    }
+};
+static void cell_recover_release(const KzgSettings* s) {
+    delete s->cell_recover;
+    s->cell_recover = nullptr;
+}
+
+static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, size_t per, size_t n,
+                               const KzgSettings* s) {
+    KzgRet rc = prover_ready(s);
+    if (rc != KZG_OK) return rc;
+    if (per < (size_t)RECOVER_N / 2 || per > (size_t)RECOVER_N) return fail(KZG_BADARGS, "between 64 and 128 cells per blob are needed");
+    std::vector<uint8_t> cidx(n * per), slot(n * RECOVER_N, RECOVER_MISSING);
+    for (size_t b = 0; b < n; b++)
+        for (size_t k = 0; k < per; k++) {
+            const uint64_t c = cell_indices[b * per + k];
+            if (c >= (uint64_t)RECOVER_N) return fail(KZG_BADARGS, "cell index out of range");
+            if (k && c <= cell_indices[b * per + k - 1]) return fail(KZG_BADARGS, "a blob's cell indices are not strictly ascending");
+            cidx[b * per + k] = (uint8_t)c;
+            slot[b * RECOVER_N + c] = (uint8_t)k;
+        }
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
+    const size_t cap = std::min(n, PROVER_CHUNK);
+    CellProverState* cp = nullptr;
+    if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cp->reserve(cap, proofs_out != nullptr)) != KZG_OK) return rc;
+    if (proofs_out && (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
+    if (!s->cell_recover) s->cell_recover = new CellRecoverState();
+    if ((rc = s->cell_recover->reserve(cap)) != KZG_OK) return rc;
+    CellProverState& c = *cp;
+    CellRecoverState& r = *s->cell_recover;
+    const Fr29Mem* W = c.d_W.p;
+    std::vector<uint32_t> st(PROVER_CHUNK);
+    StreamDrain drain{s->s1};  // (declared after the host buffers the copies read and write)
+    auto verdict = [&st](size_t m) {  // after the stream has delivered the chunk's status words
+        for (size_t b = 0; b < m; b++) {
+            if (st[b] & RECOVER_BAD_ELEMENT) return fail(KZG_BADARGS, "a cell holds a field element >= r");
+            if (st[b] & RECOVER_INCONSISTENT) return fail(KZG_BADARGS, "a blob's cells are not the evaluations of one polynomial of degree < 4096");
+        }
+        return KZG_OK;
+    };
+    constexpr size_t CELL_BYTES = (size_t)CELL_FE * 32, CELLS_BYTES = CELL_BYTES * RECOVER_N, PROOFS_BYTES = (size_t)48 * FK20_K2;
+    for (size_t lo = 0; lo < n; lo += PROVER_CHUNK) {
+        const size_t m = std::min(PROVER_CHUNK, n - lo);
+        const unsigned mb = (unsigned)m;
+        HIPCHK(hipMemcpyAsync(r.d_cells.p, cells + CELL_BYTES * per * lo, CELL_BYTES * per * m, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemcpyAsync(r.d_cidx.p, cidx.data() + per * lo, per * m, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemcpyAsync(r.d_slot.p, slot.data() + (size_t)RECOVER_N * lo, (size_t)RECOVER_N * m, hipMemcpyHostToDevice, s->s1));
+        HIPCHK(hipMemsetAsync(c.d_status.p, 0, 4 * m, s->s1));
+        hipLaunchKernelGGL(k_recover_cell_idft, dim3((unsigned)per, mb), dim3(64), 0, s->s1, (const uint8_t*)r.d_cells.p, (const uint8_t*)r.d_cidx.p, (int)per, W,
+                           r.d_u.p, c.d_status.p);
+        hipLaunchKernelGGL(k_recover_vanishing, dim3(mb), dim3(RECOVER_N), 0, s->s1, (const uint8_t*)r.d_slot.p, W, r.d_zev.p, r.d_invz.p);
+        hipLaunchKernelGGL(k_recover_poly, dim3(CELL_FE, mb), dim3(64), 0, s->s1, (const Fr29*)r.d_u.p, (const uint8_t*)r.d_slot.p, (int)per, (const Fr29*)r.d_zev.p,
+                           (const Fr29*)r.d_invz.p, W, c.d_coef.p, r.d_ev.p, c.d_status.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(st.data(), c.d_status.p, 4 * m, hipMemcpyDeviceToHost, s->s1));
+        if (cells_out) {
+            hipLaunchKernelGGL(k_recover_cells, dim3(RECOVER_N, mb), dim3(64), 0, s->s1, (const Fr29*)r.d_ev.p, W, r.d_out.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(cells_out + CELLS_BYTES * lo, r.d_out.p, CELLS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
+        }
+        if (proofs_out) {
+            // the verdict on the input first: a rejected blob (the adversarial case) must not cost the proof chain's 60 ms
+            HIPCHK(hipStreamSynchronize(s->s1));
+            if ((rc = verdict(m)) != KZG_OK) return rc;
+            hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, mb), dim3(64), 0, s->s1, (const Fr*)c.d_coef.p, W, c.d_sc.p);
+            hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X.p, (const Fr*)c.d_sc.p, c.d_H.p);
+            hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)(m * FK20_K2));
+            hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_circ.p, c.d_P.p);
+            hipLaunchKernelGGL(k_fk20_compress, dim3(mb), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(proofs_out + PROOFS_BYTES * lo, c.d_out.p, PROOFS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
+        }
+        HIPCHK(hipStreamSynchronize(s->s1));
+        if (!proofs_out && (rc = verdict(m)) != KZG_OK) return rc;
+    }
+    return KZG_OK;
+}
+
+extern "C" KzgRet kzg_recover_cells_and_kzg_proofs(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, size_t num_cells,
+                                                   size_t n, const KzgSettings* s) try {
+    if (!s) return fail(KZG_BADARGS, "null argument");
+    if (n == 0) return KZG_OK;
+    if ((!cells_out && !proofs_out) || !cell_indices || !cells) return fail(KZG_BADARGS, "null argument");
+    return cell_recover_run(cells_out, proofs_out, cell_indices, cells, num_cells, n, s);
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");
+}

@@ -125,6 +125,7 @@ struct KzgSettings {
     mutable struct ProverBufs* prover = nullptr;  // the prover-side entry points' buffers, made by the first of those calls (capi_prover.hpp)
     mutable struct CellState* cells = nullptr;    // the cell-proof entry points' tables and buffers, made by the first of those calls (capi_cells.hpp)
     mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
+    mutable struct CellRecoverState* cell_recover = nullptr;  // cell recovery's own buffers, made by its first call (capi_cell_recover.hpp)
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the
     // last launch group, and summed over the groups finished since the last reset (kzg_kernel_stamp_totals)
@@ -567,6 +568,7 @@ extern "C" KzgRet kzg_settings_from_tau_g2_devices(KzgSettings** out, const uint
 static void prover_release(const KzgSettings* s);  // (capi_prover.hpp)
 static void cells_release(const KzgSettings* s);   // (capi_cells.hpp)
 static void cell_prover_release(const KzgSettings* s);  // (capi_cell_prover.hpp)
+static void cell_recover_release(const KzgSettings* s);  // (capi_cell_recover.hpp)
 extern "C" void kzg_settings_free(KzgSettings* s) {
     if (!s) return;
     int prev = -1;
@@ -585,6 +587,7 @@ extern "C" void kzg_settings_free(KzgSettings* s) {
     prover_release(s);
     cells_release(s);
     cell_prover_release(s);
+    cell_recover_release(s);
     s->own = SettingsTables();  // (a lane's is empty: it reads its parent's, which is freed after its lanes)
     for (auto& e : s->ev)
         if (e) (void)hipEventDestroy(e);

@@ -178,4 +178,30 @@ impl KzgProof {
         let proofs: Result<Vec<Bytes48>, KzgError> = proofs.chunks_exact(48).map(Bytes48::from_slice).collect();
         Ok((cells?, proofs?))
     }
+
+    /// c-kzg-4844's `recover_cells_and_kzg_proofs` for one blob: all 128 cells and proofs from at least 64 of its cells, the
+    /// indices strictly ascending (include/kzg_rs_amd.h).  Slices of unequal length are `InvalidBytesLength`; fewer than 64 or
+    /// more than 128 cells, an index >= 128, a non-canonical field element and cells that lie on no polynomial of degree < 4096
+    /// are `BadArgs`.
+    pub fn recover_cells_and_kzg_proofs(cell_indices: &[u64], cells: &[Cell], kzg_settings: &KzgSettings) -> Result<(Vec<Cell>, Vec<Bytes48>), KzgError> {
+        if cell_indices.len() != cells.len() {
+            return Err(KzgError::InvalidBytesLength("cell indices and cells differ in length".to_string()));
+        }
+        let mut out: Vec<u8> = alloc::vec![0u8; 128 * crate::dtypes::BYTES_PER_CELL];
+        let mut proofs: Vec<u8> = alloc::vec![0u8; 128 * 48];
+        ffi::check(unsafe {
+            ffi::kzg_recover_cells_and_kzg_proofs(
+                out.as_mut_ptr(),
+                proofs.as_mut_ptr(),
+                cell_indices.as_ptr(),
+                cells.as_ptr().cast::<u8>(),
+                cells.len(),
+                1,
+                kzg_settings.raw(),
+            )
+        })?;
+        let out: Result<Vec<Cell>, KzgError> = out.chunks_exact(crate::dtypes::BYTES_PER_CELL).map(Cell::from_slice).collect();
+        let proofs: Result<Vec<Bytes48>, KzgError> = proofs.chunks_exact(48).map(Bytes48::from_slice).collect();
+        Ok((out?, proofs?))
+    }
 }
