@@ -75,6 +75,31 @@ def test_library_challenge_dedup_order():
     assert int.from_bytes(r2, "big") == M.challenge([b, a, b, a], [1, 2, 3, 4], cells, proofs)
 
 
+def test_cell_size_table_sits_on_the_msm_seams():
+    """The batches of tests/test_gpu_cells_sizes.py against g1_msm_core's shape formula (cell_prover_util.msm_shape, its constants
+    read from csrc/capi_pieces.hpp): every row has the n and N = n + m + 64 it states, and both sums fall in the class it
+    claims - one slice, sliced with fold trees, sliced with the large tail."""
+    import cell_prover_util as U
+    slice_terms, tail_layers = U.g1_msm_constants()
+    assert (slice_terms, tail_layers) == (3072, 16)
+    assert U.msm_shape(2 * slice_terms) == (1, 2, False) and U.msm_shape(2 * slice_terms + 1) == (4, 8, False)
+    assert U.msm_shape(8 * slice_terms) == (4, 8, False) and U.msm_shape(8 * slice_terms + 1) == (8, 16, True)
+    assert U.msm_shape(24704, 256, tail_layers) == (52, 104, True)   # the A/B children's g1_msm_slice_terms=256
+    seen = set()
+    for name, make, n, N, ll, rl in U.CELL_SIZES:
+        ids = make()
+        m = len(set((ids >> 7).tolist()))
+        assert len(ids) == n and n + m + 64 == N, name
+        assert 0 <= ids.min() and ids.max() < 128 * U.CELL_SIZE_BLOBS, name
+        assert (U.msm_class(n), U.msm_class(N)) == (ll, rl), name
+        seen.add((ll, rl))
+    # both sides of every seam, and the window where the two sums of one call differ in shape
+    assert seen == {("one", "one"), ("one", "sliced"), ("sliced", "sliced"), ("sliced", "tail"), ("tail", "tail")}
+    by_name = {row[0]: row for row in U.CELL_SIZES}
+    assert (by_name["48x128"][2] + 1) // 2 == slice_terms == (by_name["48x128+1"][2] + 1) // 2 - 1   # LL: the last unsliced size, the first sliced
+    assert U.msm_shape(by_name["192x128"][2])[1] == 8 and U.msm_shape(by_name["192x128"][3])[1] == tail_layers
+
+
 def test_cell_argument_lengths():
     from kzg_rs_amd import api
     with pytest.raises(api.KzgError) as e:
