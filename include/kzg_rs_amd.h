@@ -299,9 +299,12 @@ KzgRet kzg_compute_blob_kzg_proof(uint8_t *proofs_out, const uint8_t *blobs, con
  * as one circulant product (128 sums of 65 terms).  Blobs are processed 64 per launch.  The identity proof is 0xC0 00 .. 00.
  * KZG_BADARGS for a field element >= r (no output is promised) or settings without G1 points, KZG_BAD_SETUP for an off-subgroup
  * set-up point; n == 0 is KZG_OK.  No G2 point is read.  The handle's lock is taken; a multi-device handle runs the call on its
- * first device.  The FIRST proof call on a handle derives the FK20 table: 8 192 points x 32 rows = 48 MB kept on the handle, built
- * by 128 launches of the 64-blob commitment path: that call takes 1.24 s - MORE THAN A SECOND - against 6.2 ms for one blob, 9.7 ms
- * for six and 62 ms for 64 afterwards; kzg_compute_cells alone needs a 384 KB twiddle table only (0.24 ms a blob).  The call buffers (up to ~100 MB for 64 blobs with proofs) stay on the handle. */
+ * first device.  The first proof call on a handle derives the FK20 table, unless kzg_settings_precompute did so before: 8 192 points
+ * x 32 rows = 48 MB kept on the handle, made by group DFTs over G1 (csrc/g1_ntt.hpp): one 4 096-point transform of the Lagrange
+ * points gives the monomial points (12 stages of 2 048 butterflies), 64 transforms of 128 of those the table (7 stages of 4 096
+ * butterflies).  That call takes a time not yet measured on an MI355X (KZG_OPTIONS fk20_table=msm, the earlier derivation by 8 192 MSMs: 1.24 s when it was the only form) against 6.2 ms
+ * for one blob afterwards, 9.7 ms for six and 62 ms for 64 (profiles/fk20_setup_probe.json); kzg_compute_cells alone
+ * needs a 384 KB twiddle table only (0.24 ms a blob).  The call buffers (up to ~100 MB for 64 blobs with proofs) stay on the handle. */
 KzgRet kzg_compute_cells(uint8_t *cells_out, const uint8_t *blobs, size_t n, const KzgSettings *s);
 /* the same cells (cells_out may be NULL) and the n * 128 proofs */
 KzgRet kzg_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint8_t *blobs, size_t n,
@@ -351,6 +354,21 @@ KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t *commitments, c
 /* [tau^i]G1, i < 64, compressed: derived from the handle's Lagrange points by the first cell call or the first call of this
  * accessor.  KZG_BADARGS for i >= 64 and for the settings the cell verifier refuses. */
 KzgRet kzg_settings_g1_monomial_point(const KzgSettings *s, size_t i, uint8_t out[48]);
+/* ALL monomial points: out48[48 k] = [tau^(first + k)]G1 compressed, k < count, first + count <= 4096.  They are ONE forward
+ * 4 096-point group DFT of the handle's Lagrange points ([tau^i]G1 = sum_j w_j^i L_j; kzg_g1_ntt's kernels, 12 stages), made by
+ * the first call of this accessor or with the FK20 table and then kept on the handle (768 KB of device memory and 192 KB of host
+ * memory, released with the cell prover's state): not yet measured for the first call.  KZG_BADARGS for settings without G1 points or a
+ * range out of bounds, KZG_BAD_SETUP for an off-subgroup set-up point; no G2 point is read.  kzg_settings_g1_monomial_point above
+ * (i < 64, the cell verifier's own derivation) is unchanged. */
+KzgRet kzg_settings_g1_monomial_points(const KzgSettings *s, size_t first, size_t count, uint8_t *out48);
+/* Builds now what the first call of a family would build, so that this first call runs at its warm time.  `what` is a sum of
+ * KZG_PRECOMPUTE_CELL_VERIFY (the 64 monomial points and the lines of g2_points[64] of kzg_verify_cell_kzg_proof_batch) and
+ * KZG_PRECOMPUTE_CELL_PROOFS (the twiddles, the circulant and the FK20 table of kzg_compute_cells_and_kzg_proofs and
+ * kzg_recover_cells_and_kzg_proofs).  Idempotent; what == 0 is KZG_OK; unknown bits are KZG_BADARGS; settings the family refuses
+ * are refused here with the family's error. */
+#define KZG_PRECOMPUTE_CELL_VERIFY 1u
+#define KZG_PRECOMPUTE_CELL_PROOFS 2u
+KzgRet kzg_settings_precompute(const KzgSettings *s, uint32_t what);
 
 /* ---- pieces of the path, exposed for parity tests and the per-kernel benchmarks ---- */
 /* compute_challenge (src/kzg_proof.rs:46-72) for n blobs: z_out = n * 32 bytes, big-endian canonical.
@@ -389,6 +407,14 @@ KzgRet kzg_g1_msm(uint8_t out[48], const uint8_t *points48, const uint8_t *scala
  * (random, or hash-derived as in the verifier): a million EQUAL scalars put every entry of a window into one bucket, which one
  * lane then adds one after the other - the sum is still exact, the call takes on the order of a second. */
 KzgRet kzg_g1_msm_setup(uint8_t out[48], const uint8_t *scalars, size_t n, const KzgSettings *s);
+/* The group DFT over G1 (c-kzg-4844's g1_fft / g1_ifft): out[i] = sum_t w_n^(i t) points[t], n a power of two <= 4096, w_n the
+ * n-th root of unity of kzg_settings_root_of_unity's table, natural order on both sides; inverse != 0: w_n^-1 and the factor
+ * 1 / n.  points48 / out48: n * 48 bytes compressed, host pointers; the points are decoded and subgroup-tested as in kzg_g1_msm
+ * (an invalid point is KZG_BADARGS; the identity is allowed and comes out as 0xC0 00 .. 00).  n not a power of two or n > 4096 is
+ * KZG_BADARGS, n == 0 is KZG_OK.  Radix 2, one kernel launch per stage, one lane per butterfly, every butterfly a full-width
+ * scalar multiplication (csrc/g1_ntt.hpp): not yet measured at n = 128, not yet measured at n = 4096.  No setup point is read: any handle
+ * serves.  The handle's lock is taken. */
+KzgRet kzg_g1_ntt(uint8_t *out48, const uint8_t *points48, size_t n, int inverse, const KzgSettings *s);
 /* out48[i] = compress(scalars[i] * G1::generator()); scalars n * 32 bytes big-endian (reduced mod r).
  * Prover-side helper used to build synthetic (commitment, proof) pairs under a
  * known-tau test setup (the `G1Affine::generator() * scalar` of src/kzg_proof.rs:388,423). */

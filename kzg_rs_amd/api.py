@@ -31,6 +31,8 @@ BYTES_PER_BLOB = 131072
 FIELD_ELEMENTS_PER_CELL = 64
 BYTES_PER_CELL = 2048
 CELLS_PER_EXT_BLOB = 128
+PRECOMPUTE_CELL_VERIFY = 1  # KzgSettings.precompute / kzg_settings_precompute
+PRECOMPUTE_CELL_PROOFS = 2
 BYTES_PER_COMMITMENT = 48
 BYTES_PER_PROOF = 48
 
@@ -130,6 +132,10 @@ def lib():
         L.kzg_recover_cells_and_kzg_proofs.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, sz, sz, vp]
         L.kzg_cell_batch_challenge.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz]
         L.kzg_settings_g1_monomial_point.argtypes = [vp, sz, u8]
+        L.kzg_settings_g1_monomial_points.argtypes = [vp, sz, sz, u8]
+        L.kzg_settings_precompute.argtypes = [vp, C.c_uint32]
+        L.kzg_g1_ntt.argtypes = [u8, u8, sz, C.c_int, vp]
+        L.kzg_debug_fk20_table_point.argtypes = [vp, sz, sz, sz, u8]
         L.kzg_verify_kzg_proof.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_verify_kzg_proof_batch.argtypes = [bp, u8, u8, u8, u8, sz, vp]
         L.kzg_verify_kzg_proofs.argtypes = [bp, u8, u8, u8, u8, u8, sz, vp]
@@ -332,6 +338,20 @@ class KzgSettings:
         out = C.create_string_buffer(48)
         _chk(lib().kzg_settings_g1_monomial_point(self._h, i, out))
         return out.raw
+
+    def g1_monomial_points(self, first=0, count=4096):
+        """[tau^i]G1 for first <= i < first + count <= 4096, a list of 48-byte compressed points: one 4 096-point group DFT of the
+        Lagrange points on first use, then kept on the handle (kzg_settings_g1_monomial_points)."""
+        if not (0 <= first < 1 << 64 and 0 <= count < 1 << 64):
+            raise BadArgs("monomial point range out of bounds")
+        out = C.create_string_buffer(48 * max(min(count, 4096), 1))  # (a larger count is refused before anything is written)
+        _chk(lib().kzg_settings_g1_monomial_points(self._h, first, count, out))
+        return [out.raw[48 * i: 48 * i + 48] for i in range(count)]
+
+    def precompute(self, cell_verify=False, cell_proofs=False):
+        """Build now what the first cell verification (cell_verify) or the first cell proof call (cell_proofs: the FK20 table)
+        on this handle would build (kzg_settings_precompute)."""
+        _chk(lib().kzg_settings_precompute(self._h, (PRECOMPUTE_CELL_VERIFY if cell_verify else 0) | (PRECOMPUTE_CELL_PROOFS if cell_proofs else 0)))
 
     def g2_point(self, i):
         out = C.create_string_buffer(96)
@@ -633,6 +653,15 @@ def g1_msm(points, scalars, kzg_settings):
     out = C.create_string_buffer(48)
     _chk(lib().kzg_g1_msm(out, b"".join(points), b"".join(scalars), n, kzg_settings._h))
     return out.raw
+
+
+def g1_ntt(points, kzg_settings, inverse=False):
+    """The group DFT over G1 (c-kzg-4844's g1_fft / g1_ifft; kzg_g1_ntt): out[i] = sum_t w_n^(i t) points[t] for a list of n
+    48-byte compressed points, n a power of two <= 4096, natural order on both sides; inverse: w_n^-1 and the factor 1 / n."""
+    n = len(points)
+    out = C.create_string_buffer(48 * max(n, 1))
+    _chk(lib().kzg_g1_ntt(out, b"".join(points), n, 1 if inverse else 0, kzg_settings._h))
+    return [out.raw[48 * i: 48 * i + 48] for i in range(n)]
 
 
 def g1_msm_setup(scalars, kzg_settings):

@@ -8,9 +8,13 @@
 //            cells 64..127
 //   proofs   k_fk20_tvec_dft -> k_fk20_msm<Fixed> over the handle's FK20 table -> k_fk20_rows -> k_fk20_msm<Variable> ->
 //            k_fk20_compress
-// The FK20 table (8 192 points x 32 rows of 192 bytes = 48 MB on the handle) is made by the first proof call: 128 launches of the
-// prover's 64-blob commitment path over the Lagrange points, one per column k (see kzg_rs_amd.h for the measured time).  A call
-// that wants cells alone makes only the twiddle table (8 192 x 48 bytes).  Neither call reads a G2 point.
+// The FK20 table (8 192 points x 32 rows of 192 bytes = 48 MB on the handle) is made by the first proof call, or ahead of it by
+// kzg_settings_precompute, with group DFTs over G1 (g1_ntt.hpp): the 4 096 monomial points [tau^i]G1 are ONE forward transform of
+// the Lagrange points (12 stages of 2 048 butterflies), the table's 8 192 points 64 forward transforms of 128 monomial points
+// each, run as one batch (7 stages of 4 096 butterflies); see kzg_rs_amd.h for the measured time.  KZG_OPTIONS fk20_table=msm
+// keeps the earlier derivation - 128 launches of the prover's 64-blob commitment path over the Lagrange points, one per column
+// k - as the differential check of the transform.  A call that wants cells alone makes only the twiddle table (8 192 x 48
+// bytes).  Neither call reads a G2 point.
 
 struct CellProverCallBufs {  // what CellProverState::reserve rebuilds as a whole
     size_t cap = 0;                // blobs the call buffers hold
@@ -26,6 +30,8 @@ struct CellProverState : CellProverCallBufs {
     DevBuf<Fr29Mem> d_W;        // the same as twiddle entries of cell_ntt.hpp
     DevBuf<G1Jac29Mem> d_X;     // FK20 table: rows 2^(8c) X[i][k] at ((k * 64 + i) * 32 + c); empty until a proof call
     DevBuf<Fr> d_circ;          // the circulant's 65 scalars
+    DevBuf<G1Jac29Mem> d_mono;  // [tau^i]G1, i < 4096 (768 KB); empty until cell_prover_monomial
+    std::vector<uint8_t> mono48;  // ... compressed (192 KB of host memory)
     KzgRet reserve(size_t m, bool proofs) {
         if (m <= cap && (cap_proofs || !proofs)) return KZG_OK;
         const size_t c = std::max(m, cap);
@@ -67,28 +73,87 @@ static KzgRet cell_prover_state(const KzgSettings* s, CellProverState** out) {
     *out = s->cell_prover;
     return KZG_OK;
 }
-// the FK20 table, column by column: X[.][k] = the commitments of the 64 "blobs" of k_fk20_setup_scalars
-static KzgRet cell_prover_tables(const KzgSettings* s, CellProverState& c) {
-    if (c.d_X.p) return KZG_OK;
+// The stages of `batch` transforms of n points (g1_ntt.hpp) on the main stream: element e of vector v at d_v[v * vs + e * es], input
+// in bit-reversed order, output in natural order.  d_T: the w8192 power table.  Nothing is waited for.
+static KzgRet g1_ntt_stages(const KzgSettings* s, const Fr* d_T, G1Jac29Mem* d_v, int n, int batch, bool inverse, int es, int vs) {
+    if (n < 2) return KZG_OK;
+    HIPCHK(DYN_LDS(k_g1_ntt_stage<true>, G1NTT_LDS));
+    const int total = batch * (n / 2);
+    const dim3 grid((unsigned)((total + G1NTT_THREADS - 1) / G1NTT_THREADS));
+    hipLaunchKernelGGL(k_g1_ntt_stage<false>, grid, dim3(G1NTT_THREADS), 0, s->s1, d_v, d_T, n, 1, (int)inverse, es, vs, total);
+    for (int half = 2; half < n; half <<= 1)
+        hipLaunchKernelGGL(k_g1_ntt_stage<true>, grid, dim3(G1NTT_THREADS), G1NTT_LDS, s->s1, d_v, d_T, n, half, (int)inverse, es, vs, total);
+    HIPCHK(hipGetLastError());
+    return KZG_OK;
+}
+// [tau^i]G1 = sum_j w_j^i g1_points[j] for all i < 4096: one forward transform of the Lagrange points, whose order on the handle
+// (bit-reversed) is the transform's input order.  The caller holds the handle's lock and has checked prover_ready.
+static KzgRet cell_prover_monomial(const KzgSettings* s, CellProverState& c) {
+    if (c.d_mono.p) return KZG_OK;
+    if (s->n_g1 != FE_PER_BLOB) return fail(KZG_BADARGS, "the monomial points need 4096 G1 setup points");
+    DevBuf<G1Jac29Mem> t_mono;
+    DevBuf<uint8_t> t_out;
+    std::vector<uint8_t> h((size_t)48 * FE_PER_BLOB);
+    StreamDrain drain{s->s1};
+    HIPCHK(t_mono.alloc(FE_PER_BLOB));
+    HIPCHK(t_out.alloc((size_t)48 * FE_PER_BLOB));
+    hipLaunchKernelGGL(k_g1_ntt_load, dim3(FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const G1Aff*)s->t->d_g1.p, (const uint32_t*)s->t->d_g1_flag.p, t_mono.p, FE_PER_BLOB, 0);
+    KzgRet rc = g1_ntt_stages(s, c.d_T.p, t_mono.p, FE_PER_BLOB, 1, false, 1, FE_PER_BLOB);
+    if (rc != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_fk20_compress, dim3(FE_PER_BLOB / FK20_K2), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)t_mono.p, t_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h.data(), t_out.p, h.size(), hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipStreamSynchronize(s->s1));
+    c.d_mono = std::move(t_mono);
+    c.mono48 = std::move(h);
+    return KZG_OK;
+}
+// the FK20 table, column by column: X[.][k] = the commitments of the 64 "blobs" of k_fk20_setup_scalars (KZG_OPTIONS fk20_table=msm)
+static KzgRet cell_prover_tables_msm(const KzgSettings* s, CellProverState& c, G1Jac29Mem* t_X) {
     ProverBufs* bp = nullptr;
     KzgRet rc = prover_bufs(s, &bp);
     if (rc != KZG_OK) return rc;
-    StreamDrain drain{s->s1};
-    DevBuf<G1Jac29Mem> t_jac, t_X;
+    DevBuf<G1Jac29Mem> t_jac;
     HIPCHK(t_jac.alloc(CELL_FE));
-    HIPCHK(t_X.alloc((size_t)CELL_FE * FK20_K2 * FK20_ROWS));
-    HIPCHK(c.d_circ.grow(FK20_CIRC_TERMS));
-    hipLaunchKernelGGL(k_fk20_circulant, dim3(1), dim3(128), 0, s->s1, (const Fr*)c.d_T.p, c.d_circ.p);
     for (int k = 0; k < FK20_K2; k++) {
         hipLaunchKernelGGL(k_fk20_setup_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->t->d_M.p, (const Fr*)c.d_T.p, k, bp->d_sc.p);
         HIPCHK(hipGetLastError());
         if ((rc = setup_msm(s, *bp, CELL_FE)) != KZG_OK) return rc;
         hipLaunchKernelGGL(k_jac_to_jac29, dim3(1), dim3(CELL_FE), 0, s->s1, (const G1Jac*)bp->d_res.p, t_jac.p, CELL_FE);
-        hipLaunchKernelGGL(k_fk20_rows, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.p,
-                           t_X.p + (size_t)k * CELL_FE * FK20_ROWS, CELL_FE);
+        hipLaunchKernelGGL(k_fk20_rows, dim3(1), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.p, t_X + (size_t)k * CELL_FE * FK20_ROWS, CELL_FE);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipStreamSynchronize(s->s1));
+    HIPCHK(hipStreamSynchronize(s->s1));  // (t_jac is released on return)
+    return KZG_OK;
+}
+// The FK20 table by transform: X[i][.] is the forward 128-point transform of v_i = ([tau^(4031-i-64j)]G1 for j < 63, then 65
+// identities).  The 64 vectors are one interleaved batch, so that X[i][k] comes out at k * 64 + i, where k_fk20_rows reads it.
+static KzgRet cell_prover_tables_ntt(const KzgSettings* s, CellProverState& c, G1Jac29Mem* t_X) {
+    KzgRet rc = cell_prover_monomial(s, c);
+    if (rc != KZG_OK) return rc;
+    DevBuf<G1Jac29Mem> t_v;
+    HIPCHK(t_v.alloc((size_t)CELL_FE * FK20_K2));
+    hipLaunchKernelGGL(k_fk20_gather, dim3(CELL_FE * FK20_K2 / 256), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_mono.p, t_v.p);
+    if ((rc = g1_ntt_stages(s, c.d_T.p, t_v.p, FK20_K2, CELL_FE, false, CELL_FE, 1)) != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_fk20_rows, dim3(CELL_FE * FK20_K2 / 64), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_v.p, t_X, CELL_FE * FK20_K2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s->s1));  // (t_v is released on return)
+    return KZG_OK;
+}
+// KZG_OPTIONS fk20_table=ntt (default) | msm, read when a handle's table is built
+static KzgRet cell_prover_tables(const KzgSettings* s, CellProverState& c) {
+    if (c.d_X.p) return KZG_OK;
+    const char* form = opt_str("fk20_table");
+    const bool msm = form && strcmp(form, "msm") == 0;
+    if (form && !msm && strcmp(form, "ntt") != 0) return fail(KZG_BADARGS, "KZG_OPTIONS fk20_table: expected ntt or msm");
+    StreamDrain drain{s->s1};
+    DevBuf<G1Jac29Mem> t_X;
+    HIPCHK(t_X.alloc((size_t)CELL_FE * FK20_K2 * FK20_ROWS));
+    HIPCHK(c.d_circ.grow(FK20_CIRC_TERMS));
+    hipLaunchKernelGGL(k_fk20_circulant, dim3(1), dim3(128), 0, s->s1, (const Fr*)c.d_T.p, c.d_circ.p);
+    HIPCHK(hipGetLastError());
+    const KzgRet rc = msm ? cell_prover_tables_msm(s, c, t_X.p) : cell_prover_tables_ntt(s, c, t_X.p);
+    if (rc != KZG_OK) return rc;
     c.d_X = std::move(t_X);
     return KZG_OK;
 }

@@ -78,6 +78,30 @@ extern "C" KzgRet kzg_debug_msm_sum_quads(uint8_t out[144], const uint8_t* point
     return KZG_OK;
 }
 
+// test hook (tests/test_gpu_g1_ntt.py): row c of the FK20 table's point X[i][k] = 2^(8c) sum_(j<63) w128^(jk) [tau^(4031-i-64j)]G1,
+// compressed; builds the table if it is absent
+extern "C" KzgRet kzg_debug_fk20_table_point(const KzgSettings* s, size_t i, size_t k, size_t c, uint8_t out[48]) {
+    if (!s || !out || i >= (size_t)CELL_FE || k >= (size_t)FK20_K2 || c >= (size_t)FK20_ROWS) return fail(KZG_BADARGS, "bad argument");
+    KzgRet rc = prover_ready(s);
+    if (rc != KZG_OK) return rc;
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);
+    CellProverState* cp = nullptr;
+    if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
+    DevBuf<G1Jac29Mem> t_in;  // k_fk20_compress takes a whole group of 128 points: the one asked for, then identities (Z = 0)
+    DevBuf<uint8_t> t_out;
+    HIPCHK(t_in.alloc(FK20_K2));
+    HIPCHK(t_out.alloc(48 * FK20_K2));
+    HIPCHK(hipMemsetAsync(t_in.p, 0, sizeof(G1Jac29Mem) * FK20_K2, s->s1));
+    HIPCHK(hipMemcpyAsync(t_in.p, cp->d_X.p + ((k * CELL_FE + i) * FK20_ROWS + c), sizeof(G1Jac29Mem), hipMemcpyDeviceToDevice, s->s1));
+    hipLaunchKernelGGL(k_fk20_compress, dim3(1), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)t_in.p, t_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, t_out.p, 48, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipStreamSynchronize(s->s1));
+    return KZG_OK;
+}
+
 // diagnostic: placement and duration of the first wavefront of the last latency-layout decode kernel (g_decode_dbg)
 extern "C" KzgRet kzg_debug_decode_placement(unsigned long long out[4], const KzgSettings* s) {
     if (!s || !out) return fail(KZG_BADARGS, "null argument");

@@ -28,6 +28,7 @@
 #include "proof_kernels.hpp"
 #include "cell_kernels.hpp"
 #include "fk20_kernels.hpp"
+#include "g1_ntt.hpp"
 #include "recover_kernels.hpp"
 
 using namespace kzg;
@@ -68,4 +69,5 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_cells.hpp"
 #include "capi_cell_prover.hpp"
 #include "capi_cell_recover.hpp"
+#include "capi_g1_ntt.hpp"
 #include "capi_debug.hpp"
