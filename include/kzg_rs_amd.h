@@ -351,6 +351,34 @@ KzgRet kzg_verify_cell_kzg_proof_batch(bool *ok, const uint8_t *commitments, con
  * hashed as given (nothing is validated). */
 KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t *commitments, const uint64_t *cell_indices,
                                 const uint8_t *cells, const uint8_t *proofs, size_t n);
+/* MANY independent cell-proof batches in one call, a verdict each (a PeerDAS node's column sidecars of one slot: each needs its
+ * own verdict, and one merged batch would give one).  Batch b is entries [off_b, off_b + batch_sizes[b]) of the four host arrays,
+ * off_b the prefix sum of batch_sizes; the arrays have the layout of kzg_verify_cell_kzg_proof_batch.  For every b, ok_out[b] and
+ * err_out[b] are exactly what kzg_verify_cell_kzg_proof_batch returns on that slice alone: the distinct commitments are listed per
+ * batch (nothing is shared across batches), r_b is that slice's challenge (kzg_cell_batch_challenges), an empty batch is true.
+ * err_out[b] (optional) = 1 and ok_out[b] = false where the single call would return KZG_BADARGS - a cell index >= 128, a field
+ * element >= r, a commitment or proof that is not a G1 point - and the other batches keep their own verdicts; without err_out any
+ * such batch fails the whole call with KZG_BADARGS.  Errors of the call, KZG_BADARGS: null pointers, settings the cell verifier
+ * refuses, more than 2^20 cells in total, more than KZG_CELL_GROUP_MAX_BATCHES batches; KZG_BAD_SETUP for an off-subgroup monomial
+ * point.  n_batches == 0 is KZG_OK.  After any error the handle stays usable.
+ * The batches of up to KZG_CELL_GROUP_MAX_CELLS cells (T; one blob's 128 cells and any column of up to 256 blobs are below it) run
+ * as ONE group of launches with the batch dimension inside the kernels: one decode of all points and cells, the transcript hashes
+ * on host threads (KZG_OPTIONS host_threads) meanwhile, one segmented launch each for the powers of r_b, the column sums and the
+ * term tables, one window-kernel launch over 2 n_batches sums (a longer list than 2 T + 64 terms does not fit the kernel's LDS
+ * list) and one pairing program with an instance per batch.  Batches above T run through kzg_verify_cell_kzg_proof_batch one after
+ * another inside the call; the contract is the same on both sides of T.  The handle's lock is taken; a multi-device handle runs
+ * the call on its first device.  kzg_last_timings afterwards holds the single call's slots, [1] being the wall clock of the
+ * parallel hashing.  Two runs of a group give the same bytes: every device sum has a fixed order.  Measured (DESIGN.md 4b,
+ * profiles/cell_group_probe.json): not yet measured on an MI355X. */
+#define KZG_CELL_GROUP_MAX_CELLS 256
+#define KZG_CELL_GROUP_MAX_BATCHES 4096
+KzgRet kzg_verify_cell_kzg_proof_batches(bool *ok_out, uint8_t *err_out, const uint8_t *commitments,
+                                         const uint64_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
+                                         const size_t *batch_sizes, size_t n_batches, const KzgSettings *s);
+/* The challenges r_b of the above alone: r_out = n_batches x 32 big-endian bytes, r_b = kzg_cell_batch_challenge on slice b.  Pure
+ * host code - no handle, no device; nothing is validated; the batches are spread over host threads (KZG_OPTIONS host_threads). */
+KzgRet kzg_cell_batch_challenges(uint8_t *r_out, const uint8_t *commitments, const uint64_t *cell_indices,
+                                 const uint8_t *cells, const uint8_t *proofs, const size_t *batch_sizes, size_t n_batches);
 /* [tau^i]G1, i < 64, compressed: derived from the handle's Lagrange points by the first cell call or the first call of this
  * accessor.  KZG_BADARGS for i >= 64 and for the settings the cell verifier refuses. */
 KzgRet kzg_settings_g1_monomial_point(const KzgSettings *s, size_t i, uint8_t out[48]);

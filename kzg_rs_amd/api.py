@@ -131,6 +131,8 @@ def lib():
         L.kzg_compute_cells_and_kzg_proofs.argtypes = [u8, u8, u8, sz, vp]
         L.kzg_recover_cells_and_kzg_proofs.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, sz, sz, vp]
         L.kzg_cell_batch_challenge.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz]
+        L.kzg_verify_cell_kzg_proof_batches.argtypes = [bp, u8, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(C.c_size_t), sz, vp]
+        L.kzg_cell_batch_challenges.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(C.c_size_t), sz]
         L.kzg_settings_g1_monomial_point.argtypes = [vp, sz, u8]
         L.kzg_settings_g1_monomial_points.argtypes = [vp, sz, sz, u8]
         L.kzg_settings_precompute.argtypes = [vp, C.c_uint32]
@@ -484,6 +486,19 @@ class KzgProof:
         return bool(ok.value)
 
     @staticmethod
+    def verify_cell_kzg_proof_batches(batches, kzg_settings, return_errors=False):
+        """Many independent verify_cell_kzg_proof_batch checks through one call (kzg_verify_cell_kzg_proof_batches): `batches` is a
+        list of (commitments, cell_indices, cells, proofs) tuples, each validated like the single call's arguments before any
+        device call (InvalidBytesLength).  -> a list of bool, one verdict per batch; a batch the single call would refuse raises
+        BadArgs - or, with return_errors=True, is reported as "BadArgs" in its place while the others keep their verdicts."""
+        cm, idx, ce, pr, sizes = _cell_group_args(batches)
+        B = len(batches)
+        ok = (C.c_bool * max(B, 1))()
+        err = (C.c_uint8 * max(B, 1))()
+        _chk(lib().kzg_verify_cell_kzg_proof_batches(ok, C.cast(err, C.c_char_p) if return_errors else None, cm, idx, ce, pr, sizes, B, kzg_settings._h))
+        return ["BadArgs" if return_errors and err[b] else bool(ok[b]) for b in range(B)]
+
+    @staticmethod
     def verify_blob_kzg_proof_batch_device(d_blobs, d_commitments, d_proofs, n, kzg_settings):
         """Device-resident form: arguments are device pointers (ints), e.g. torch tensor .data_ptr()."""
         ok = C.c_bool(False)
@@ -513,6 +528,22 @@ def cell_batch_challenge(commitments, cell_indices, cells, proofs):
     out = C.create_string_buffer(32)
     _chk(lib().kzg_cell_batch_challenge(out, *_cell_args(commitments, cell_indices, cells, proofs)))
     return out.raw
+
+
+def _cell_group_args(batches):
+    parts = [_cell_args(*b) for b in batches]
+    sizes = (C.c_size_t * max(len(parts), 1))(*[p[4] for p in parts])
+    total = sum(p[4] for p in parts)
+    idx = (C.c_uint64 * max(total, 1))(*[int(c) for b in batches for c in b[1]])
+    return b"".join(p[0] for p in parts), idx, b"".join(p[2] for p in parts), b"".join(p[3] for p in parts), sizes
+
+
+def cell_batch_challenges(batches):
+    """The challenges r_b of verify_cell_kzg_proof_batches (host code, no device): a list of 32 big-endian bytes per batch."""
+    cm, idx, ce, pr, sizes = _cell_group_args(batches)
+    out = C.create_string_buffer(32 * max(len(batches), 1))
+    _chk(lib().kzg_cell_batch_challenges(out, cm, idx, ce, pr, sizes, len(batches)))
+    return [out.raw[32 * b: 32 * b + 32] for b in range(len(batches))]
 
 
 def verify_kzg_proofs(commitments, zs, ys, proofs, kzg_settings):

@@ -1,0 +1,366 @@
+// capi_cell_groups.hpp - kzg_verify_cell_kzg_proof_batches: MANY independent cell-proof batches in one call, a verdict each (a
+// PeerDAS node's column sidecars of one slot).  Part of the single translation unit kzg_capi.hip; not a stand-alone header.
+// Host plan: cell_group_plan.hpp; device side: cell_group_kernels.hpp.
+//
+// Batch b is the check of capi_cells.hpp on its own slice, with its own transcript, r_b, pair of sums (LL_b, RL_b) and pairing
+// instance; the verdict and the error flag are the single call's on that slice.  What changes is the shape of the launches - the
+// batch dimension inside the kernels is what fills the machine (capi_verify.hpp's launch groups):
+//   host    per-batch dedup and counting sorts (cell_group_plan), the batches of up to T = CELL_GROUP_MAX_CELLS cells numbered as
+//           slots of the group; larger ones go through kzg_verify_cell_kzg_proof_batch one after another, before the group
+//   host    the slots' transcript hashes, independent chains, spread over host threads (option host_threads) WHILE
+//   device  ONE decode of [all proofs | every slot's distinct commitments | [tau^i]G1 once | the identity] and ONE of all cells;
+//           the flags are folded to a status per slot on the host and a bad slot is masked out of the term tables
+//   device  r_b^k, commitment weights, a wavefront per (slot, touched column), a wavefront per slot for the cross-column sum
+//   device  ONE window-kernel launch over 2 G outputs: term tables [2 G][longest list], padded with terms on the identity
+//   device  the VERIFY program with G instances against the handle's cached lines of (g2_points[64], G2)
+// Every sum has the order the plan lays out and nothing is accumulated with atomics: a group gives the same bytes on every run.
+
+// ---------------------------------------------------------------- host: the challenges of a group
+static size_t cell_group_threshold() {  // option cell_group_max_cells (A/B build): a smaller T, to reach both sides of it with few cells
+    static const size_t t = (size_t)std::max(1L, std::min((long)CELL_GROUP_MAX_CELLS, ab_int("cell_group_max_cells", (long)CELL_GROUP_MAX_CELLS)));
+    return t;
+}
+// r_be + 32 j = the single call's r of batch which[j] (every batch when which == nullptr), hashed by whoever calls work(): the
+// batches are claimed from a counter, so the poster and any number of helper threads share them
+struct CellGroupHash {
+    uint8_t* r_be = nullptr;
+    const uint8_t *commitments = nullptr, *cells = nullptr, *proofs = nullptr;
+    const uint64_t* cell_indices = nullptr;
+    const size_t* off = nullptr;       // prefix sums of the batch sizes
+    const uint32_t* which = nullptr;
+    size_t count = 0;
+    std::atomic<size_t> next{0};
+    std::atomic<bool> failed{false};
+    std::mutex mu;
+    std::chrono::steady_clock::time_point t0{}, t1{};
+    bool started = false;
+    std::vector<std::thread> helpers;
+    void work() {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!started) t0 = std::chrono::steady_clock::now(), started = true;
+        }
+        try {
+            std::vector<uint32_t> ci, uniq;
+            for (;;) {
+                const size_t j = next.fetch_add(1, std::memory_order_relaxed);
+                if (j >= count) break;
+                const size_t b = which ? which[j] : j, e = off[b], n = off[b + 1] - e;
+                cell_dedup(commitments + 48 * e, n, ci, uniq);
+                cell_challenge(r_be + 32 * j, commitments + 48 * e, ci, uniq, cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, n);
+            }
+        } catch (const std::bad_alloc&) {
+            failed = true;
+        }
+        const auto now = std::chrono::steady_clock::now();
+        std::lock_guard<std::mutex> lk(mu);
+        if (now > t1) t1 = now;
+    }
+    // up to host_threads - 1 helpers, one per 128 KB of transcript at most (a thread costs more than a short chain)
+    void start() {
+        size_t bytes = 0;
+        for (size_t j = 0; j < count; j++) {
+            const size_t b = which ? which[j] : j;
+            bytes += (off[b + 1] - off[b]) * (CELL_BYTES + 112);
+        }
+        const long opt = KZG_HOST_THREADS_OPTION;
+        const size_t nthr = std::min(std::min((size_t)(opt < 1 ? 1 : opt > 64 ? 64 : opt), count), bytes / (128 * 1024) + 1);
+        try {
+            for (size_t k = 1; k < nthr; k++) helpers.emplace_back([this] { work(); });
+        } catch (const std::system_error&) {  // (no thread to be had: the caller hashes what is left)
+        }
+    }
+    void finish() {  // the caller takes its share, then waits for the helpers
+        work();
+        for (auto& t : helpers)
+            if (t.joinable()) t.join();
+        helpers.clear();
+    }
+    double ms() const { return started ? std::chrono::duration<double, std::milli>(t1 - t0).count() : 0.0; }
+    ~CellGroupHash() {
+        next = count;  // (an error path: nothing more is claimed; the helpers read the caller's arrays until they are joined)
+        for (auto& t : helpers)
+            if (t.joinable()) t.join();
+    }
+};
+static bool cell_group_sizes(size_t* total, const size_t* batch_sizes, size_t n_batches) {
+    size_t t = 0;
+    for (size_t b = 0; b < n_batches; b++) {
+        if (batch_sizes[b] > CELL_MAX_CELLS || (t += batch_sizes[b]) > CELL_MAX_CELLS) return false;
+    }
+    *total = t;
+    return true;
+}
+extern "C" KzgRet kzg_cell_batch_challenges(uint8_t* r_out, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                                            const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches) try {
+    if (n_batches == 0) return KZG_OK;
+    if (!r_out || !batch_sizes) return fail(KZG_BADARGS, "null argument");
+    std::vector<size_t> off(n_batches + 1, 0);
+    for (size_t b = 0; b < n_batches; b++) off[b + 1] = off[b] + batch_sizes[b];
+    if (off[n_batches] && (!commitments || !cell_indices || !cells || !proofs)) return fail(KZG_BADARGS, "null argument");
+    CellGroupHash h;
+    h.r_be = r_out, h.commitments = commitments, h.cell_indices = cell_indices, h.cells = cells, h.proofs = proofs, h.off = off.data(), h.count = n_batches;
+    h.start();
+    h.finish();
+    if (h.failed) return fail(KZG_MALLOC, "host buffers of the call");
+    return KZG_OK;
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");
+}
+
+// ---------------------------------------------------------------- the group's buffers: grow-only, on the handle's cell state
+struct CellGroupBufs {
+    DevBuf<uint8_t> d_cells, d_bytes, d_mult;
+    DevBuf<Fr> d_vals, d_rM, d_sc, d_coef, d_r;
+    DevBuf<uint32_t> d_bad, d_idx, d_live, d_pflag, d_term_point, d_term_scalar;
+    DevBuf<G1Aff> d_points;
+    DevBuf<G1Jac29Mem> d_jtmp;
+    DevBuf<G1Jac> d_window, d_ab;
+    DevBuf<Fp> d_slp_in, d_slp_out;
+    PinnedBuf<uint8_t> h_buf;
+    KzgRet reserve(const CellGroupPlan& P, size_t NP, size_t terms, size_t h_bytes, bool aff) {
+        const size_t nG = P.nG, G = P.G;
+        HIPCHK(d_cells.grow(CELL_BYTES * nG));
+        HIPCHK(d_vals.grow(CELL_FE * nG));
+        HIPCHK(d_bad.grow(nG));
+        HIPCHK(d_rM.grow(nG));
+        HIPCHK(d_sc.grow(cell_group_scalars(P.nG, P.mtot, P.G)));
+        HIPCHK(d_coef.grow((size_t)CELL_FE * P.Utot));
+        HIPCHK(d_r.grow(G));
+        HIPCHK(d_live.grow(G));
+        HIPCHK(d_idx.grow(P.idx.size()));
+        HIPCHK(d_bytes.grow(48 * NP + 16));
+        HIPCHK(d_points.grow(NP));
+        HIPCHK(d_pflag.grow(NP));
+        HIPCHK(d_mult.grow(MULT_ENTRY_BYTES * MSM_CHUNKS * NP));
+        if (aff) HIPCHK(d_jtmp.grow(NP));
+        HIPCHK(d_term_point.grow(terms));
+        HIPCHK(d_term_scalar.grow(terms));
+        HIPCHK(d_window.grow(2 * MSM_WINDOWS * G));
+        HIPCHK(d_ab.grow(2 * G));
+        HIPCHK(d_slp_in.grow(6 * G));
+        HIPCHK(d_slp_out.grow(6 * G));
+        HIPCHK(h_buf.grow(h_bytes));
+        return KZG_OK;
+    }
+};
+CellState::~CellState() { delete group; }
+
+// ---------------------------------------------------------------- the entry point
+extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, const uint64_t* cell_indices,
+                                                    const uint8_t* cells, const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches,
+                                                    const KzgSettings* s) try {
+    if (!s || (n_batches && (!ok_out || !batch_sizes))) return fail(KZG_BADARGS, "null argument");
+    KzgRet rc = cells_ready(s);
+    if (rc != KZG_OK) return rc;
+    if (n_batches > CELL_GROUP_MAX_BATCHES) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batches: more than 4096 batches");
+    size_t total = 0;
+    if (!cell_group_sizes(&total, batch_sizes, n_batches)) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batches: more than 2^20 cells");
+    if (total && (!commitments || !cell_indices || !cells || !proofs)) return fail(KZG_BADARGS, "null argument");
+    if (n_batches == 0) return KZG_OK;
+    const auto t_call = std::chrono::steady_clock::now();
+    CellGroupPlan P;
+    cell_group_plan(P, commitments, cell_indices, batch_sizes, n_batches, cell_group_threshold());
+    for (size_t b = 0; b < n_batches; b++)
+        if (P.kind[b] == CELL_GROUP_BAD_INDEX && !err_out) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
+    for (size_t b = 0; b < n_batches; b++) {
+        ok_out[b] = P.kind[b] != CELL_GROUP_BAD_INDEX;  // (an empty batch is true; the others get their verdict below)
+        if (err_out) err_out[b] = P.kind[b] == CELL_GROUP_BAD_INDEX ? 1 : 0;
+    }
+    // the slots' hashes start now and run beside everything up to the first wait on the device
+    std::vector<uint8_t> r_be(32 * (size_t)P.G);
+    CellGroupHash hash;  // (declared after what its helper threads read and write: joined first)
+    hash.r_be = r_be.data(), hash.commitments = commitments, hash.cell_indices = cell_indices, hash.cells = cells, hash.proofs = proofs,
+    hash.off = P.off.data(), hash.which = P.slot_batch.data(), hash.count = P.G;
+    if (P.G) hash.start();
+    // batches above T: the single call, one after another (it takes the handle's lock itself); its stage times are added below
+    float t_large[8] = {};
+    for (size_t b = 0; b < n_batches; b++) {
+        if (P.kind[b] != CELL_GROUP_LARGE) continue;
+        const size_t e = P.off[b];
+        bool okb = false;
+        rc = kzg_verify_cell_kzg_proof_batch(&okb, commitments + 48 * e, cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, batch_sizes[b], s);
+        if (rc == KZG_BADARGS && err_out) {
+            err_out[b] = 1;
+            okb = false;
+        } else if (rc != KZG_OK) {
+            return rc;
+        }
+        ok_out[b] = okb;
+        for (int i = 1; i < 8; i++) t_large[i] += s->timings[i];
+    }
+    auto finish_timings = [&](double hash_ms, float msm, float pairing, float between, float decode) {
+        s->timings[0] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        s->timings[1] = (float)hash_ms + t_large[1];
+        s->timings[2] = msm + t_large[2];
+        s->timings[3] = pairing + t_large[3];
+        s->timings[4] = between + t_large[4];
+        s->timings[6] = decode + t_large[6];
+        s->timings[5] = s->timings[7] = 0.0f;
+    };
+    if (P.G == 0) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        finish_timings(0.0, 0.f, 0.f, 0.f, 0.f);
+        return KZG_OK;
+    }
+
+    const uint32_t G = P.G, nG = P.nG, mtot = P.mtot, NP = cell_group_points(nG, mtot), nsc = cell_group_scalars(nG, mtot, G);
+    const uint32_t max_terms = P.max_rl;
+    const size_t terms = (size_t)2 * G * max_terms;
+    const bool aff = msm_affine_enabled();
+    // pinned: [point bytes | point flags | cell flags | r | live | the pairing program's outputs]
+    auto up = [](size_t x) { return (x + 63) & ~(size_t)63; };
+    const size_t h_pflag = up(48 * (size_t)NP), h_bad = h_pflag + up(4 * (size_t)NP), h_r = h_bad + up(4 * (size_t)nG), h_live = h_r + up(32 * (size_t)G),
+                 h_out = h_live + up(4 * (size_t)G), h_bytes = h_out + sizeof(Fp) * 6 * G;
+
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
+    CellState* cs = nullptr;
+    if ((rc = cells_state(s, &cs)) != KZG_OK) return rc;
+    if (!cs->group) cs->group = new CellGroupBufs();
+    CellGroupBufs& g = *cs->group;
+    if ((rc = g.reserve(P, NP, terms, h_bytes, aff)) != KZG_OK) return rc;
+    StreamDrain drain{s->s1};
+    hipStream_t st = s->s1;
+
+    // 1. decode: the points with their subgroup test and table rows, the cells with their canonical check - none of it needs r
+    uint8_t* const hp = g.h_buf.p;
+    for (uint32_t sl = 0; sl < G; sl++) {
+        const size_t e = P.off[P.slot_batch[sl]], n = batch_sizes[P.slot_batch[sl]];
+        memcpy(hp + 48 * (size_t)P.idx[P.o_cstart + sl], proofs + 48 * e, 48 * n);
+    }
+    for (uint32_t i = 0; i < mtot; i++) memcpy(hp + 48 * ((size_t)nG + i), commitments + 48 * (size_t)P.uniq_entry[i], 48);
+    memcpy(hp + 48 * ((size_t)nG + mtot), cs->mono, sizeof cs->mono);
+    uint8_t* const skip = hp + 48 * (size_t)cell_group_skip_point(nG, mtot);
+    memset(skip, 0, 48);
+    skip[0] = 0xc0;  // the identity, compressed
+    HIPCHK(hipEventRecord(s->ev[5], st));
+    HIPCHK(hipMemcpyAsync(g.d_bytes.p, hp, 48 * (size_t)NP, hipMemcpyHostToDevice, st));
+    if (aff) {
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3((NP + 255) / 256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), st,
+                           g.d_bytes.p, g.d_bytes.p, (int)NP, g.d_points.p, g.d_pflag.p, g.d_mult.p, g.d_jtmp.p, (int)NP, (int)NP);
+        const unsigned conv_blocks = (NP + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH);
+        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, st, g.d_jtmp.p, g.d_pflag.p, (G1Aff29Mem*)g.d_mult.p, (int)NP, (int)NP);
+    } else {
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((NP + 63) / 64), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), st,
+                           g.d_bytes.p, g.d_bytes.p, (int)NP, g.d_points.p, g.d_pflag.p, g.d_mult.p, (G1Jac29Mem*)nullptr, (int)NP, (int)NP);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(g.d_idx.p, P.idx.data(), 4 * P.idx.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(g.d_bad.p, 0, 4 * (size_t)nG, st));
+    for (uint32_t sl = 0; sl < G;) {  // the cells of consecutive slots that are consecutive batches cross in one copy
+        uint32_t to = sl + 1;
+        while (to < G && P.slot_batch[to] == P.slot_batch[to - 1] + 1) to++;
+        const size_t e = P.off[P.slot_batch[sl]], c0 = P.idx[P.o_cstart + sl], c1 = P.idx[P.o_cstart + to];
+        HIPCHK(hipMemcpyAsync(g.d_cells.p + CELL_BYTES * c0, cells + CELL_BYTES * e, CELL_BYTES * (c1 - c0), hipMemcpyHostToDevice, st));
+        sl = to;
+    }
+    hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * (size_t)nG + 255) / 256)), dim3(256), 0, st, (const uint8_t*)g.d_cells.p, g.d_vals.p, g.d_bad.p,
+                       (int)(CELL_FE * nG));
+    HIPCHK(hipGetLastError());
+    uint32_t* const f_point = reinterpret_cast<uint32_t*>(hp + h_pflag);
+    uint32_t* const f_cell = reinterpret_cast<uint32_t*>(hp + h_bad);
+    HIPCHK(hipMemcpyAsync(f_cell, g.d_bad.p, 4 * (size_t)nG, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(f_point, g.d_pflag.p, 4 * (size_t)NP, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(s->ev[6], st));
+    hash.finish();
+    if (hash.failed) return fail(KZG_MALLOC, "host buffers of the call");
+    HIPCHK(hipStreamSynchronize(st));
+    // the flags folded to a status per slot; a bad slot leaves the group here (its term tables point at the identity)
+    for (uint32_t i = nG + mtot; i < nG + mtot + CELL_FE; i++)
+        if (f_point[i] == G1_INVALID) return fail(KZG_BAD_SETUP, "a monomial setup point is outside G1");
+    uint32_t* const live = reinterpret_cast<uint32_t*>(hp + h_live);
+    uint8_t* const r_le = hp + h_r;
+    for (uint32_t sl = 0; sl < G; sl++) {
+        const uint32_t c0 = P.idx[P.o_cstart + sl], c1 = P.idx[P.o_cstart + sl + 1], u0 = P.idx[P.o_ustart + sl], u1 = P.idx[P.o_ustart + sl + 1];
+        const char* why = nullptr;
+        for (uint32_t q = c0; q < c1 && !why; q++)
+            if (f_cell[q]) why = "a cell holds a field element >= r";
+        for (uint32_t q = c0; q < c1 && !why; q++)
+            if (f_point[q] == G1_INVALID) why = "invalid proof (not a G1 point)";
+        for (uint32_t i = u0; i < u1 && !why; i++)
+            if (f_point[nG + i] == G1_INVALID) why = "invalid commitment (not a G1 point)";
+        live[sl] = why ? 0u : 1u;
+        if (why) {
+            if (!err_out) return fail(KZG_BADARGS, why);
+            err_out[P.slot_batch[sl]] = 1;
+            memset(r_le + 32 * (size_t)sl, 0, 32);
+        } else {
+            reverse32(r_le + 32 * (size_t)sl, r_be.data() + 32 * (size_t)sl);
+        }
+    }
+
+    // 2.-4. r_b -> the scalars and the term tables
+    const uint32_t* const ix = g.d_idx.p;
+    HIPCHK(hipEventRecord(s->ev[7], st));
+    HIPCHK(hipMemcpyAsync(g.d_r.p, r_le, 32 * (size_t)G, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(g.d_live.p, live, 4 * (size_t)G, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_cellg_powers, dim3((nG + 255) / 256), dim3(256), 0, st, (const Fr*)g.d_r.p, ix + P.o_cell_slot, ix + P.o_cstart, ix + P.o_cidx,
+                       (const Fr*)cs->d_T.p, g.d_rM.p, g.d_sc.p, (int)nG);
+    hipLaunchKernelGGL(k_cellg_commitment_weights, dim3((mtot + 63) / 64), dim3(64), 0, st, (const Fr*)g.d_rM.p, ix + P.o_wlist, ix + P.o_wstart,
+                       g.d_sc.p + 2 * (size_t)nG, (int)mtot);
+    hipLaunchKernelGGL(k_cellg_column_ifft, dim3(P.Utot), dim3(64), 0, st, (const Fr*)g.d_vals.p, (const Fr*)g.d_rM.p, ix + P.o_order, ix + P.o_col_start,
+                       ix + P.o_col_id, (const Fr*)cs->d_T.p, g.d_coef.p);
+    hipLaunchKernelGGL(k_cellg_interp_sum, dim3(G), dim3(64), 0, st, (const Fr*)g.d_coef.p, ix + P.o_colstart, g.d_sc.p + 2 * (size_t)nG + mtot);
+    hipLaunchKernelGGL(k_cellg_terms, dim3((unsigned)((terms + 255) / 256)), dim3(256), 0, st, g.d_term_point.p, g.d_term_scalar.p, ix + P.o_cstart,
+                       ix + P.o_ustart, (const uint32_t*)g.d_live.p, (int)G, (int)nG, (int)mtot, (int)max_terms);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[8], st));
+
+    // 4. the 2 G sums in one window-kernel launch: the layout of the verification path's MSM (run_msm), each list sorted in LDS
+    MsmDesc d{};
+    d.mult = g.d_mult.p;
+    d.pflag = g.d_pflag.p;
+    d.scalars = g.d_sc.p;
+    d.term_point = g.d_term_point.p;
+    d.term_scalar = g.d_term_scalar.p;
+    d.sorted = nullptr;  // (LDSSORT: no global list)
+    d.window_sums = g.d_window.p;
+    d.nterms[0] = (int)P.max_ll;
+    d.nterms[1] = (int)P.max_rl;
+    d.max_terms = (int)max_terms;
+    d.stride = (int)NP;
+    d.slices = 1;
+    d.chunks = MSM_CHUNKS;
+    d.chunks_per_block = msm_chunks_per_block(G);
+    d.flags = MSM_FLAG_XCD;
+    const unsigned slots = MSM_CHUNKS / d.chunks_per_block, W = MSM_WINDOWS / MSM_CHUNKS, gz = 2 * G;
+    if ((size_t)d.chunks_per_block * (max_terms + 1) + 4 > (size_t)msm_lds_sort_capacity<Curve29>())
+        return fail(KZG_ERROR, "cell group: a term list longer than the window kernel's LDS list");
+    if ((rc = msm_save_reserve(s, W, slots, gz)) != KZG_OK) return rc;
+    HIPCHK(hipEventRecord(s->ev[2], st));
+    hipLaunchKernelGGL(k_glv_split, dim3((nsc + 255) / 256), dim3(256), 0, st, g.d_sc.p, (int)nsc);
+    if (aff) msm_window_launch<Curve29Aff, true>(d, W, slots, gz, s->ws.d_msm_save.p, msm_save_bytes(s->ws), st);
+    else msm_window_launch<Curve29, true>(d, W, slots, gz, s->ws.d_msm_save.p, msm_save_bytes(s->ws), st);
+    if (gz >= 64) hipLaunchKernelGGL(k_msm_combine_lanes, dim3((gz + 63) / 64), dim3(64), 0, st, (const G1Jac*)g.d_window.p, g.d_ab.p, (int)slots, (int)W, (int)gz);
+    else hipLaunchKernelGGL(k_msm_combine, dim3(gz), dim3(64), 0, st, (const G1Jac*)g.d_window.p, g.d_ab.p, (int)slots, (int)W);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[3], st));
+
+    // 5. e(LL_b, g2_points[64]) == e(RL_b, G2) for every slot, on the cached lines
+    hipLaunchKernelGGL(k_jac_to_slp, dim3(G), dim3(64), 0, st, (const G1Jac*)g.d_ab.p, g.d_slp_in.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[4], st));
+    rc = pairing_latency_form(G) ? run_program2(s->t->verify2, g.d_slp_in.p, cs->d_lines29.p, g.d_slp_out.p, (int)G, st)
+                                 : run_program(s->t->verify, g.d_slp_in.p, cs->d_lines.p, g.d_slp_out.p, (int)G, st);
+    if (rc != KZG_OK) return rc;
+    HIPCHK(hipEventRecord(s->ev[9], st));
+    const uint32_t* const out = reinterpret_cast<const uint32_t*>(hp + h_out);
+    HIPCHK(hipMemcpyAsync(hp + h_out, g.d_slp_out.p, sizeof(Fp) * 6 * G, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t sl = 0; sl < G; sl++) {
+        uint32_t any = 0;
+        for (int i = 0; i < 72; i++) any |= out[72 * (size_t)sl + i];
+        ok_out[P.slot_batch[sl]] = live[sl] && any == 0;
+    }
+    float t_msm = 0.f, t_pair = 0.f, t_between = 0.f, t_decode = 0.f;
+    elapsed(&t_msm, s->ev[2], s->ev[3]);
+    elapsed(&t_pair, s->ev[4], s->ev[9]);
+    elapsed(&t_between, s->ev[7], s->ev[8]);
+    elapsed(&t_decode, s->ev[5], s->ev[6]);
+    finish_timings(hash.ms(), t_msm, t_pair, t_between, t_decode);
+    return KZG_OK;
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
+}

@@ -81,7 +81,10 @@ struct CellCallBufs {  // what CellState::reserve rebuilds as a whole
     DevBuf<uint32_t> d_bad, d_idx;
     void reset() { *this = CellCallBufs(); }
 };
+struct CellGroupBufs;  // kzg_verify_cell_kzg_proof_batches' own grow-only buffers (capi_cell_groups.hpp), made by its first call
 struct CellState : CellCallBufs {
+    CellGroupBufs* group = nullptr;
+    ~CellState();
     DevBuf<Fr> d_T;                             // w8192^e, e < 8192, Montgomery
     uint8_t mono[CELL_FE * 48] = {};            // [tau^i]G1, compressed
     DevBuf<Fp> d_lines;                         // prepared lines of g2_points[64] then G2, 8x32 Montgomery (VERIFY)

@@ -27,6 +27,7 @@
 #include "slp2.hpp"
 #include "proof_kernels.hpp"
 #include "cell_kernels.hpp"
+#include "cell_group_kernels.hpp"
 #include "fk20_kernels.hpp"
 #include "g1_ntt.hpp"
 #include "recover_kernels.hpp"
@@ -67,6 +68,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_pieces.hpp"
 #include "capi_prover.hpp"
 #include "capi_cells.hpp"
+#include "capi_cell_groups.hpp"
 #include "capi_cell_prover.hpp"
 #include "capi_cell_recover.hpp"
 #include "capi_g1_ntt.hpp"
