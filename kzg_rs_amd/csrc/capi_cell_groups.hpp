@@ -1,10 +1,13 @@
 // capi_cell_groups.hpp - kzg_verify_cell_kzg_proof_batches: MANY independent cell-proof batches in one call, a verdict each (a
 // PeerDAS node's column sidecars of one slot).  Part of the single translation unit kzg_capi.hip; not a stand-alone header.
-// Host plan: cell_group_plan.hpp; device side: cell_group_kernels.hpp.
+// Host plan: cell_group_plan.hpp; device side: cell_kernels.hpp.
 //
 // Batch b is the check of capi_cells.hpp on its own slice, with its own transcript, r_b, pair of sums (LL_b, RL_b) and pairing
-// instance; the verdict and the error flag are the single call's on that slice.  What changes is the shape of the launches - the
-// batch dimension inside the kernels is what fills the machine (capi_verify.hpp's launch groups):
+// instance; the verdict and the error flag are the single call's on that slice.  The plan, the cell decode and the r -> scalars
+// stage ARE the single call's (cells_decode, cells_scalars over the handle's one set of stage buffers: that call is G = 1); what
+// differs is the form of the sums - one window-kernel launch over term tables instead of g1_msm_core twice - and the pairing's
+// input, which stays on the device.  The batch dimension inside the kernels is what fills the machine (capi_verify.hpp's launch
+// groups):
 //   host    per-batch dedup and counting sorts (cell_group_plan), the batches of up to T = CELL_GROUP_MAX_CELLS cells numbered as
 //           slots of the group; larger ones go through kzg_verify_cell_kzg_proof_batch one after another, before the group
 //   host    the slots' transcript hashes, independent chains, spread over host threads (option host_threads) WHILE
@@ -20,14 +23,15 @@ static size_t cell_group_threshold() {  // option cell_group_max_cells (A/B buil
     static const size_t t = (size_t)std::max(1L, std::min((long)CELL_GROUP_MAX_CELLS, ab_int("cell_group_max_cells", (long)CELL_GROUP_MAX_CELLS)));
     return t;
 }
-// r_be + 32 j = the single call's r of batch which[j] (every batch when which == nullptr), hashed by whoever calls work(): the
-// batches are claimed from a counter, so the poster and any number of helper threads share them
+// r_be + 32 j = the single call's r of slot j of `plan` - its dedup is the plan's - or, without a plan, of batch j, deduplicated
+// here; hashed by whoever calls work(): the batches are claimed from a counter, so the poster and any number of helper threads
+// share them
 struct CellGroupHash {
     uint8_t* r_be = nullptr;
     const uint8_t *commitments = nullptr, *cells = nullptr, *proofs = nullptr;
     const uint64_t* cell_indices = nullptr;
     const size_t* off = nullptr;       // prefix sums of the batch sizes
-    const uint32_t* which = nullptr;
+    const CellGroupPlan* plan = nullptr;
     size_t count = 0;
     std::atomic<size_t> next{0};
     std::atomic<bool> failed{false};
@@ -45,9 +49,18 @@ struct CellGroupHash {
             for (;;) {
                 const size_t j = next.fetch_add(1, std::memory_order_relaxed);
                 if (j >= count) break;
-                const size_t b = which ? which[j] : j, e = off[b], n = off[b + 1] - e;
-                cell_dedup(commitments + 48 * e, n, ci, uniq);
-                cell_challenge(r_be + 32 * j, commitments + 48 * e, ci, uniq, cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, n);
+                const size_t b = plan ? plan->slot_batch[j] : j, e = off[b], n = off[b + 1] - e;
+                if (plan) {
+                    const uint32_t *cstart = plan->idx.data() + plan->o_cstart, *ustart = plan->idx.data() + plan->o_ustart;
+                    cell_challenge(r_be + 32 * j, commitments, plan->ci.data() + cstart[j], plan->uniq_entry.data() + ustart[j], ustart[j + 1] - ustart[j],
+                                   cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, n);
+                } else {
+                    ci.resize(n);
+                    uniq.clear();
+                    cell_dedup(commitments + 48 * e, n, ci.data(), uniq);
+                    cell_challenge(r_be + 32 * j, commitments + 48 * e, ci.data(), uniq.data(), uniq.size(), cell_indices + e, cells + CELL_BYTES * e,
+                                   proofs + 48 * e, n);
+                }
             }
         } catch (const std::bad_alloc&) {
             failed = true;
@@ -60,7 +73,7 @@ struct CellGroupHash {
     void start() {
         size_t bytes = 0;
         for (size_t j = 0; j < count; j++) {
-            const size_t b = which ? which[j] : j;
+            const size_t b = plan ? plan->slot_batch[j] : j;
             bytes += (off[b + 1] - off[b]) * (CELL_BYTES + 112);
         }
         const long opt = KZG_HOST_THREADS_OPTION;
@@ -108,27 +121,18 @@ extern "C" KzgRet kzg_cell_batch_challenges(uint8_t* r_out, const uint8_t* commi
     return fail(KZG_MALLOC, "host buffers of the call");
 }
 
-// ---------------------------------------------------------------- the group's buffers: grow-only, on the handle's cell state
+// ---------------------------------------------------------------- the group's own buffers: grow-only, on the handle's cell state
+// (cells, index words, r and scalars are the stage buffers both entry points share: CellStageBufs, capi_cells.hpp)
 struct CellGroupBufs {
-    DevBuf<uint8_t> d_cells, d_bytes, d_mult;
-    DevBuf<Fr> d_vals, d_rM, d_sc, d_coef, d_r;
-    DevBuf<uint32_t> d_bad, d_idx, d_live, d_pflag, d_term_point, d_term_scalar;
+    DevBuf<uint8_t> d_bytes, d_mult;
+    DevBuf<uint32_t> d_live, d_pflag, d_term_point, d_term_scalar;
     DevBuf<G1Aff> d_points;
     DevBuf<G1Jac29Mem> d_jtmp;
     DevBuf<G1Jac> d_window, d_ab;
     DevBuf<Fp> d_slp_in, d_slp_out;
     PinnedBuf<uint8_t> h_buf;
-    KzgRet reserve(const CellGroupPlan& P, size_t NP, size_t terms, size_t h_bytes, bool aff) {
-        const size_t nG = P.nG, G = P.G;
-        HIPCHK(d_cells.grow(CELL_BYTES * nG));
-        HIPCHK(d_vals.grow(CELL_FE * nG));
-        HIPCHK(d_bad.grow(nG));
-        HIPCHK(d_rM.grow(nG));
-        HIPCHK(d_sc.grow(cell_group_scalars(P.nG, P.mtot, P.G)));
-        HIPCHK(d_coef.grow((size_t)CELL_FE * P.Utot));
-        HIPCHK(d_r.grow(G));
+    KzgRet reserve(size_t G, size_t NP, size_t terms, size_t h_bytes, bool aff) {
         HIPCHK(d_live.grow(G));
-        HIPCHK(d_idx.grow(P.idx.size()));
         HIPCHK(d_bytes.grow(48 * NP + 16));
         HIPCHK(d_points.grow(NP));
         HIPCHK(d_pflag.grow(NP));
@@ -171,9 +175,11 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     std::vector<uint8_t> r_be(32 * (size_t)P.G);
     CellGroupHash hash;  // (declared after what its helper threads read and write: joined first)
     hash.r_be = r_be.data(), hash.commitments = commitments, hash.cell_indices = cell_indices, hash.cells = cells, hash.proofs = proofs,
-    hash.off = P.off.data(), hash.which = P.slot_batch.data(), hash.count = P.G;
+    hash.off = P.off.data(), hash.plan = &P, hash.count = P.G;
     if (P.G) hash.start();
-    // batches above T: the single call, one after another (it takes the handle's lock itself); its stage times are added below
+    // batches above T: the single call, one after another (it takes the handle's lock itself); its stage times are added below.
+    // It uses - and may regrow - the stage buffers the group is about to use: each of these calls has drained its stream before
+    // it returns, and the group sizes the buffers for itself only afterwards, under the lock
     float t_large[8] = {};
     for (size_t b = 0; b < n_batches; b++) {
         if (P.kind[b] != CELL_GROUP_LARGE) continue;
@@ -220,7 +226,8 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     if ((rc = cells_state(s, &cs)) != KZG_OK) return rc;
     if (!cs->group) cs->group = new CellGroupBufs();
     CellGroupBufs& g = *cs->group;
-    if ((rc = g.reserve(P, NP, terms, h_bytes, aff)) != KZG_OK) return rc;
+    if ((rc = cs->stage.reserve(P)) != KZG_OK || (rc = g.reserve(G, NP, terms, h_bytes, aff)) != KZG_OK) return rc;
+    CellStageBufs& sb = cs->stage;
     StreamDrain drain{s->s1};
     hipStream_t st = s->s1;
 
@@ -237,31 +244,11 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     skip[0] = 0xc0;  // the identity, compressed
     HIPCHK(hipEventRecord(s->ev[5], st));
     HIPCHK(hipMemcpyAsync(g.d_bytes.p, hp, 48 * (size_t)NP, hipMemcpyHostToDevice, st));
-    if (aff) {
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3((NP + 255) / 256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), st,
-                           g.d_bytes.p, g.d_bytes.p, (int)NP, g.d_points.p, g.d_pflag.p, g.d_mult.p, g.d_jtmp.p, (int)NP, (int)NP);
-        const unsigned conv_blocks = (NP + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH);
-        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, st, g.d_jtmp.p, g.d_pflag.p, (G1Aff29Mem*)g.d_mult.p, (int)NP, (int)NP);
-    } else {
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((NP + 63) / 64), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), st,
-                           g.d_bytes.p, g.d_bytes.p, (int)NP, g.d_points.p, g.d_pflag.p, g.d_mult.p, (G1Jac29Mem*)nullptr, (int)NP, (int)NP);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(g.d_idx.p, P.idx.data(), 4 * P.idx.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(g.d_bad.p, 0, 4 * (size_t)nG, st));
-    for (uint32_t sl = 0; sl < G;) {  // the cells of consecutive slots that are consecutive batches cross in one copy
-        uint32_t to = sl + 1;
-        while (to < G && P.slot_batch[to] == P.slot_batch[to - 1] + 1) to++;
-        const size_t e = P.off[P.slot_batch[sl]], c0 = P.idx[P.o_cstart + sl], c1 = P.idx[P.o_cstart + to];
-        HIPCHK(hipMemcpyAsync(g.d_cells.p + CELL_BYTES * c0, cells + CELL_BYTES * e, CELL_BYTES * (c1 - c0), hipMemcpyHostToDevice, st));
-        sl = to;
-    }
-    hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * (size_t)nG + 255) / 256)), dim3(256), 0, st, (const uint8_t*)g.d_cells.p, g.d_vals.p, g.d_bad.p,
-                       (int)(CELL_FE * nG));
+    g1_decode_tables(g.d_bytes.p, NP, g.d_points.p, g.d_pflag.p, g.d_mult.p, g.d_jtmp.p, (int)NP, aff, st);
     HIPCHK(hipGetLastError());
     uint32_t* const f_point = reinterpret_cast<uint32_t*>(hp + h_pflag);
     uint32_t* const f_cell = reinterpret_cast<uint32_t*>(hp + h_bad);
-    HIPCHK(hipMemcpyAsync(f_cell, g.d_bad.p, 4 * (size_t)nG, hipMemcpyDeviceToHost, st));
+    if ((rc = cells_decode(s, *cs, P, cells, f_cell)) != KZG_OK) return rc;
     HIPCHK(hipMemcpyAsync(f_point, g.d_pflag.p, 4 * (size_t)NP, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(s->ev[6], st));
     hash.finish();
@@ -292,18 +279,11 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     }
 
     // 2.-4. r_b -> the scalars and the term tables
-    const uint32_t* const ix = g.d_idx.p;
+    const uint32_t* const ix = sb.d_idx.p;
     HIPCHK(hipEventRecord(s->ev[7], st));
-    HIPCHK(hipMemcpyAsync(g.d_r.p, r_le, 32 * (size_t)G, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(g.d_live.p, live, 4 * (size_t)G, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_cellg_powers, dim3((nG + 255) / 256), dim3(256), 0, st, (const Fr*)g.d_r.p, ix + P.o_cell_slot, ix + P.o_cstart, ix + P.o_cidx,
-                       (const Fr*)cs->d_T.p, g.d_rM.p, g.d_sc.p, (int)nG);
-    hipLaunchKernelGGL(k_cellg_commitment_weights, dim3((mtot + 63) / 64), dim3(64), 0, st, (const Fr*)g.d_rM.p, ix + P.o_wlist, ix + P.o_wstart,
-                       g.d_sc.p + 2 * (size_t)nG, (int)mtot);
-    hipLaunchKernelGGL(k_cellg_column_ifft, dim3(P.Utot), dim3(64), 0, st, (const Fr*)g.d_vals.p, (const Fr*)g.d_rM.p, ix + P.o_order, ix + P.o_col_start,
-                       ix + P.o_col_id, (const Fr*)cs->d_T.p, g.d_coef.p);
-    hipLaunchKernelGGL(k_cellg_interp_sum, dim3(G), dim3(64), 0, st, (const Fr*)g.d_coef.p, ix + P.o_colstart, g.d_sc.p + 2 * (size_t)nG + mtot);
-    hipLaunchKernelGGL(k_cellg_terms, dim3((unsigned)((terms + 255) / 256)), dim3(256), 0, st, g.d_term_point.p, g.d_term_scalar.p, ix + P.o_cstart,
+    if ((rc = cells_scalars(s, *cs, P, r_le)) != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_cell_terms, dim3((unsigned)((terms + 255) / 256)), dim3(256), 0, st, g.d_term_point.p, g.d_term_scalar.p, ix + P.o_cstart,
                        ix + P.o_ustart, (const uint32_t*)g.d_live.p, (int)G, (int)nG, (int)mtot, (int)max_terms);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[8], st));
@@ -312,7 +292,7 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     MsmDesc d{};
     d.mult = g.d_mult.p;
     d.pflag = g.d_pflag.p;
-    d.scalars = g.d_sc.p;
+    d.scalars = sb.d_sc.p;
     d.term_point = g.d_term_point.p;
     d.term_scalar = g.d_term_scalar.p;
     d.sorted = nullptr;  // (LDSSORT: no global list)
@@ -330,7 +310,7 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
         return fail(KZG_ERROR, "cell group: a term list longer than the window kernel's LDS list");
     if ((rc = msm_save_reserve(s, W, slots, gz)) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[2], st));
-    hipLaunchKernelGGL(k_glv_split, dim3((nsc + 255) / 256), dim3(256), 0, st, g.d_sc.p, (int)nsc);
+    hipLaunchKernelGGL(k_glv_split, dim3((nsc + 255) / 256), dim3(256), 0, st, sb.d_sc.p, (int)nsc);
     if (aff) msm_window_launch<Curve29Aff, true>(d, W, slots, gz, s->ws.d_msm_save.p, msm_save_bytes(s->ws), st);
     else msm_window_launch<Curve29, true>(d, W, slots, gz, s->ws.d_msm_save.p, msm_save_bytes(s->ws), st);
     if (gz >= 64) hipLaunchKernelGGL(k_msm_combine_lanes, dim3((gz + 63) / 64), dim3(64), 0, st, (const G1Jac*)g.d_window.p, g.d_ab.p, (int)slots, (int)W, (int)gz);

@@ -6,11 +6,13 @@
 //     e(sum_k r^k pi_k, [tau^64]G2) == e(sum_i w_i U_i - [I(tau)]G1 + sum_k r^k h_(c_k)^64 pi_k, G2)
 // with U_i the distinct commitments, w_i the sum of r^k over the cells of U_i and I the sum over the columns of the
 // interpolants of the r-weighted column sums.  Data flow of one call:
-//   host    argument and cell-index checks, dedup of the commitments, counting sorts by column and by commitment
+//   host    argument checks, then the plan of one batch (cell_group_plan.hpp: cell-index check, dedup of the commitments, stable
+//           counting sorts by column and by commitment) - the G = 1 case of kzg_verify_cell_kzg_proof_batches' plan
 //   host    the transcript hash (one serial SHA-256 chain of ~2.1 KB per cell) on a thread of its own, WHILE
 //   device  the points [proofs | unique commitments | [tau^i]G1] are decoded with their subgroup test and table rows, and the
 //           cells are decoded with their canonical check - none of that needs r
-//   device  r^k, the column sums, the 64-point inverse DFTs, the MSM scalars (cell_kernels.hpp)
+//   device  r^k, the column sums, the 64-point inverse DFTs, the MSM scalars (cell_kernels.hpp) - the same stage, over the same
+//           buffers, as the group call's (cells_decode and cells_scalars below)
 //   device  two sums over the one set of decoded tables (g1_msm_core): LL over the proofs, RL over all N = n + m + 64 points
 //   device  one pairing against the prepared lines of (g2_points[64], G2), made with the monomial table and kept on the handle
 // The hash stays on the host: a GPU lane runs SHA-256 at ~1.4 us per 64-byte block, a SHA-NI core at ~1.5 GB/s, and the chain
@@ -19,36 +21,24 @@
 constexpr size_t CELL_BYTES = (size_t)CELL_FE * 32;   // BYTES_PER_CELL
 constexpr size_t CELL_MAX_CELLS = (size_t)1 << 20;    // 8 192 blobs x 128 cells per call
 
-// ---------------------------------------------------------------- host: dedup and the batch challenge
+// ---------------------------------------------------------------- host: the batch challenge
 static void cell_u64be(uint8_t o[8], uint64_t v) {
     for (int i = 0; i < 8; i++) o[i] = (uint8_t)(v >> (56 - 8 * i));
 }
-// ci[k] = index of commitment k among the distinct commitments (compared as bytes), numbered in first-seen order; uniq[i] = the
-// first k that holds distinct commitment i
-static void cell_dedup(const uint8_t* commitments, size_t n, std::vector<uint32_t>& ci, std::vector<uint32_t>& uniq) {
-    std::unordered_map<std::string, uint32_t> seen;
-    seen.reserve(n);
-    ci.resize(n);
-    uniq.clear();
-    for (size_t k = 0; k < n; k++) {
-        auto it = seen.emplace(std::string(reinterpret_cast<const char*>(commitments + 48 * k), 48), (uint32_t)uniq.size());
-        if (it.second) uniq.push_back((uint32_t)k);
-        ci[k] = it.first->second;
-    }
-}
 // compute_verify_cell_kzg_proof_batch_challenge: SHA-256("RCKZGCBATCH__V1_" || u64be(4096) || u64be(64) || u64be(m) || u64be(n) ||
-// unique commitments || per cell: u64be(commitment index) || u64be(cell index) || cell || proof), read big-endian, mod r
-static void cell_challenge(uint8_t r_be[32], const uint8_t* commitments, const std::vector<uint32_t>& ci, const std::vector<uint32_t>& uniq,
+// unique commitments || per cell: u64be(commitment index) || u64be(cell index) || cell || proof), read big-endian, mod r.  ci and uniq:
+// cell_dedup's (cell_group_plan.hpp); uniq[i] indexes `commitments`, which need not start where the batch does
+static void cell_challenge(uint8_t r_be[32], const uint8_t* commitments, const uint32_t* ci, const uint32_t* uniq, size_t m,
                            const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n) {
     hostsha::Stream h;
     uint8_t hdr[48];
     memcpy(hdr, "RCKZGCBATCH__V1_", 16);
     cell_u64be(hdr + 16, (uint64_t)FE_PER_BLOB);
     cell_u64be(hdr + 24, (uint64_t)CELL_FE);
-    cell_u64be(hdr + 32, (uint64_t)uniq.size());
+    cell_u64be(hdr + 32, (uint64_t)m);
     cell_u64be(hdr + 40, (uint64_t)n);
     h.update(hdr, 48);
-    for (uint32_t k : uniq) h.update(commitments + 48 * (size_t)k, 48);
+    for (size_t i = 0; i < m; i++) h.update(commitments + 48 * (size_t)uniq[i], 48);
     for (size_t k = 0; k < n; k++) {
         uint8_t ix[16];
         cell_u64be(ix, ci[k]);
@@ -63,9 +53,9 @@ static void cell_challenge(uint8_t r_be[32], const uint8_t* commitments, const s
 extern "C" KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
                                            const uint8_t* proofs, size_t n) try {
     if (!r_out || (n && (!commitments || !cell_indices || !cells || !proofs))) return fail(KZG_BADARGS, "null argument");
-    std::vector<uint32_t> ci, uniq;
-    cell_dedup(commitments, n, ci, uniq);
-    cell_challenge(r_out, commitments, ci, uniq, cell_indices, cells, proofs, n);
+    std::vector<uint32_t> ci(n), uniq;
+    cell_dedup(commitments, n, ci.data(), uniq);
+    cell_challenge(r_out, commitments, ci.data(), uniq.data(), uniq.size(), cell_indices, cells, proofs, n);
     return KZG_OK;
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");
@@ -74,37 +64,39 @@ extern "C" KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t* com
 // ---------------------------------------------------------------- the handle's cell state
 // Made by the first cell call (or monomial-point accessor) under the handle's lock, like the prover's buffers, and released with
 // the handle: the w8192 power table, [tau^i]G1 for i < 64, the prepared lines of (g2_points[64], G2), and grow-only call buffers.
-struct CellCallBufs {  // what CellState::reserve rebuilds as a whole
-    size_t cap = 0;                             // cells the call buffers hold
-    DevBuf<uint8_t> d_cells;                    // [cap] x 2048 bytes as given
-    DevBuf<Fr> d_vals, d_rM, d_sc_ll, d_sc_rl;
-    DevBuf<uint32_t> d_bad, d_idx;
-    void reset() { *this = CellCallBufs(); }
+//
+// The stage buffers serve BOTH entry points (one batch is a group of one slot), sized by the plan of the call: nG dense cells,
+// mtot dense commitments, Utot dense columns, G slots.  A call holds the handle's lock from its reserve() to the drain of its
+// stream, so the next call - of either kind - finds them idle, with contents it overwrites before it reads.
+struct CellStageBufs {
+    DevBuf<uint8_t> d_cells;   // [nG] x 2048 bytes as given
+    DevBuf<Fr> d_vals;         // [64 nG] the cells' elements, plain
+    DevBuf<uint32_t> d_bad;    // [nG] a cell holds an element >= r
+    DevBuf<uint32_t> d_idx;    // the plan's index words
+    DevBuf<Fr> d_r, d_rM;      // [G] the challenges, plain; [nG] r^k, Montgomery
+    DevBuf<Fr> d_sc;           // [r^k nG | r^k h^64 nG | commitment weights mtot | -I_i 64 per slot] (cell_group_scalars), plain
+    DevBuf<Fr> d_coef;         // [64 Utot] the columns' interpolants
+    KzgRet reserve(const CellGroupPlan& P) {
+        HIPCHK(d_cells.grow(CELL_BYTES * P.nG));
+        HIPCHK(d_vals.grow((size_t)CELL_FE * P.nG));
+        HIPCHK(d_bad.grow(P.nG));
+        HIPCHK(d_idx.grow(P.idx.size()));
+        HIPCHK(d_r.grow(P.G));
+        HIPCHK(d_rM.grow(P.nG));
+        HIPCHK(d_sc.grow(cell_group_scalars(P.nG, P.mtot, P.G)));
+        HIPCHK(d_coef.grow((size_t)CELL_FE * P.Utot));
+        return KZG_OK;
+    }
 };
-struct CellGroupBufs;  // kzg_verify_cell_kzg_proof_batches' own grow-only buffers (capi_cell_groups.hpp), made by its first call
-struct CellState : CellCallBufs {
+struct CellGroupBufs;  // what is kzg_verify_cell_kzg_proof_batches' own (capi_cell_groups.hpp), made by its first call
+struct CellState {
+    CellStageBufs stage;
     CellGroupBufs* group = nullptr;
     ~CellState();
     DevBuf<Fr> d_T;                             // w8192^e, e < 8192, Montgomery
     uint8_t mono[CELL_FE * 48] = {};            // [tau^i]G1, compressed
     DevBuf<Fp> d_lines;                         // prepared lines of g2_points[64] then G2, 8x32 Montgomery (VERIFY)
     DevBuf<uint32_t> d_lines29;                 // the same in the latency program's format (VERIFY2)
-    DevBuf<Fr> d_coef, d_r;
-    static size_t idx_words(size_t n) { return 4 * n + 2 * CELLS_PER_EXT_BLOB + 4; }  // see kzg_verify_cell_kzg_proof_batch
-    KzgRet reserve(size_t n) {
-        if (n <= cap) return KZG_OK;
-        CellCallBufs::reset();
-        const size_t c = std::max<size_t>(n, 64);
-        HIPCHK(d_cells.alloc(CELL_BYTES * c));
-        HIPCHK(d_vals.alloc(CELL_FE * c));
-        HIPCHK(d_rM.alloc(c));
-        HIPCHK(d_sc_ll.alloc(c));
-        HIPCHK(d_sc_rl.alloc(2 * c + CELL_FE));
-        HIPCHK(d_bad.alloc(c));
-        HIPCHK(d_idx.alloc(idx_words(c)));
-        cap = c;
-        return KZG_OK;
-    }
 };
 static void cells_release(const KzgSettings* s) {
     delete s->cells;
@@ -124,8 +116,6 @@ static KzgRet cells_state(const KzgSettings* s, CellState** out) {
     std::unique_ptr<CellState> c(new CellState());
     StreamDrain drain{s->s1};
     HIPCHK(c->d_T.alloc(EXT_FE));
-    HIPCHK(c->d_coef.alloc(CELL_FE * CELLS_PER_EXT_BLOB));
-    HIPCHK(c->d_r.alloc(1));
     hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T.p);
     // [tau^i]G1 = sum_j w_j^i g1_points[j]: the commitments of 64 "blobs" over the Lagrange points, on the prover's MSM path
     ProverBufs* bp = nullptr;
@@ -180,6 +170,47 @@ static KzgRet cells_pairing(const KzgSettings* s, const CellState& c, const uint
     return KZG_OK;
 }
 
+// ---------------------------------------------------------------- the stage both entry points share
+// Before r: the plan's index words and the cells of its slots cross to the device, the cells are decoded with their canonical check
+// and the flags start back to h_bad [nG] (read them after the stream has drained).  `cells`: the caller's array, batch after batch.
+static KzgRet cells_decode(const KzgSettings* s, CellState& cs, const CellGroupPlan& P, const uint8_t* cells, uint32_t* h_bad) {
+    CellStageBufs& b = cs.stage;
+    hipStream_t st = s->s1;
+    const uint32_t* const cstart = P.idx.data() + P.o_cstart;
+    HIPCHK(hipMemcpyAsync(b.d_idx.p, P.idx.data(), 4 * P.idx.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(b.d_bad.p, 0, 4 * (size_t)P.nG, st));
+    for (uint32_t sl = 0; sl < P.G;) {  // the cells of consecutive slots that are consecutive batches cross in one copy
+        uint32_t to = sl + 1;
+        while (to < P.G && P.slot_batch[to] == P.slot_batch[to - 1] + 1) to++;
+        const size_t e = P.off[P.slot_batch[sl]], c0 = cstart[sl], c1 = cstart[to];
+        HIPCHK(hipMemcpyAsync(b.d_cells.p + CELL_BYTES * c0, cells + CELL_BYTES * e, CELL_BYTES * (c1 - c0), hipMemcpyHostToDevice, st));
+        sl = to;
+    }
+    hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * (size_t)P.nG + 255) / 256)), dim3(256), 0, st, (const uint8_t*)b.d_cells.p, b.d_vals.p, b.d_bad.p,
+                       (int)(CELL_FE * P.nG));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_bad, b.d_bad.p, 4 * (size_t)P.nG, hipMemcpyDeviceToHost, st));
+    return KZG_OK;
+}
+// After r: r_le [G] x 32 bytes (little-endian; zeroes for a slot that is not live) -> every scalar of stage.d_sc.  Every sum runs
+// in the plan's order.
+static KzgRet cells_scalars(const KzgSettings* s, CellState& cs, const CellGroupPlan& P, const uint8_t* r_le) {
+    CellStageBufs& b = cs.stage;
+    hipStream_t st = s->s1;
+    const uint32_t* const ix = b.d_idx.p;
+    const Fr *T = cs.d_T.p, *rM = b.d_rM.p;
+    HIPCHK(hipMemcpyAsync(b.d_r.p, r_le, 32 * (size_t)P.G, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_cell_powers, dim3((P.nG + 255) / 256), dim3(256), 0, st, (const Fr*)b.d_r.p, ix + P.o_cell_slot, ix + P.o_cstart, ix + P.o_cidx, T,
+                       b.d_rM.p, b.d_sc.p, (int)P.nG);
+    hipLaunchKernelGGL(k_cell_commitment_weights, dim3((P.mtot + 63) / 64), dim3(64), 0, st, rM, ix + P.o_wlist, ix + P.o_wstart, b.d_sc.p + 2 * (size_t)P.nG,
+                       (int)P.mtot);
+    hipLaunchKernelGGL(k_cell_column_ifft, dim3(P.Utot), dim3(64), 0, st, (const Fr*)b.d_vals.p, rM, ix + P.o_order, ix + P.o_col_start, ix + P.o_col_id, T,
+                       b.d_coef.p);
+    hipLaunchKernelGGL(k_cell_interp_sum, dim3(P.G), dim3(64), 0, st, (const Fr*)b.d_coef.p, ix + P.o_colstart, b.d_sc.p + 2 * (size_t)P.nG + P.mtot);
+    HIPCHK(hipGetLastError());
+    return KZG_OK;
+}
+
 // ---------------------------------------------------------------- entry points
 extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
                                                   const uint8_t* proofs, size_t n, const KzgSettings* s) try {
@@ -187,45 +218,22 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     KzgRet rc = cells_ready(s);
     if (rc != KZG_OK) return rc;
     if (n > CELL_MAX_CELLS) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batch: more than 2^20 cells");
-    for (size_t k = 0; k < n; k++)
-        if (cell_indices[k] >= (uint64_t)CELLS_PER_EXT_BLOB) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
     if (n == 0) {
         *ok = true;
         return KZG_OK;
     }
     const auto t_call = std::chrono::steady_clock::now();
-    // r-independent host work: the distinct commitments, the cells by column and by commitment (stable counting sorts: every
-    // device sum runs in ascending k).  idx: [cell index n | order by column n | column starts U + 1 | columns U | order by
-    // commitment n | commitment starts m + 1] at the fixed offsets below
-    std::vector<uint32_t> ci, uniq;
-    cell_dedup(commitments, n, ci, uniq);
-    const size_t m = uniq.size(), N = n + m + CELL_FE;
-    std::vector<uint32_t> idx(CellState::idx_words(n), 0u);
-    uint32_t *h_cidx = idx.data(), *h_order = h_cidx + n, *h_start = h_order + n, *h_cols = h_start + CELLS_PER_EXT_BLOB + 1,
-             *h_wlist = h_cols + CELLS_PER_EXT_BLOB, *h_wstart = h_wlist + n;
-    uint32_t cnt[CELLS_PER_EXT_BLOB + 1] = {};
-    for (size_t k = 0; k < n; k++) cnt[(h_cidx[k] = (uint32_t)cell_indices[k]) + 1]++;
-    for (int c = 0; c < CELLS_PER_EXT_BLOB; c++) cnt[c + 1] += cnt[c];
-    int U = 0;
-    for (int c = 0; c < CELLS_PER_EXT_BLOB; c++)
-        if (cnt[c + 1] > cnt[c]) {
-            h_start[U] = cnt[c];
-            h_cols[U++] = (uint32_t)c;
-        }
-    h_start[U] = (uint32_t)n;
-    for (size_t k = 0; k < n; k++) h_order[cnt[h_cidx[k]]++] = (uint32_t)k;
-    for (size_t k = 0; k < n; k++) h_wstart[ci[k] + 1]++;
-    for (size_t i = 0; i < m; i++) h_wstart[i + 1] += h_wstart[i];
-    {
-        std::vector<uint32_t> pos(h_wstart, h_wstart + m);
-        for (size_t k = 0; k < n; k++) h_wlist[pos[ci[k]]++] = (uint32_t)k;
-    }
+    // r-independent host work: the plan of a group of this one batch.  No batch is above the threshold, so it is slot 0 of G = 1
+    CellGroupPlan P;
+    cell_group_plan(P, commitments, cell_indices, &n, 1, CELL_MAX_CELLS);
+    if (P.kind[0] == CELL_GROUP_BAD_INDEX) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
+    const size_t m = P.mtot, N = n + m + CELL_FE;
 
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     CellState* cs = nullptr;
-    if ((rc = cells_state(s, &cs)) != KZG_OK || (rc = cs->reserve(n)) != KZG_OK || (rc = ws_reserve(s, (N + 1) / 2 + 1, 1, STAGE_NONE)) != KZG_OK)
+    if ((rc = cells_state(s, &cs)) != KZG_OK || (rc = cs->stage.reserve(P)) != KZG_OK || (rc = ws_reserve(s, (N + 1) / 2 + 1, 1, STAGE_NONE)) != KZG_OK)
         return rc;
     Workspace& w = s->ws;
     std::vector<uint32_t> h_bad(n), h_pflag(N);
@@ -236,7 +244,7 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     double hash_ms = 0.0;
     auto hash = [&] {
         const auto t0 = std::chrono::steady_clock::now();
-        cell_challenge(r_be, commitments, ci, uniq, cell_indices, cells, proofs, n);
+        cell_challenge(r_be, commitments, P.ci.data(), P.uniq_entry.data(), m, cell_indices, cells, proofs, n);
         hash_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     };
     std::thread hasher;
@@ -254,32 +262,15 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     // points [proofs | distinct commitments | [tau^i]G1] -> decoded, subgroup-tested, table rows (kzg_g1_msm's decode)
     uint8_t* hp = w.h_buf.p;  // pinned, at least 128 N bytes (ws_reserve)
     memcpy(hp, proofs, 48 * n);
-    for (size_t i = 0; i < m; i++) memcpy(hp + 48 * (n + i), commitments + 48 * (size_t)uniq[i], 48);
+    for (size_t i = 0; i < m; i++) memcpy(hp + 48 * (n + i), commitments + 48 * (size_t)P.uniq_entry[i], 48);
     memcpy(hp + 48 * (n + m), cs->mono, sizeof cs->mono);
     HIPCHK(hipEventRecord(s->ev[5], s->s1));
     HIPCHK(hipMemcpyAsync(w.d_bytes.p, hp, 48 * N, hipMemcpyHostToDevice, s->s1));
     const bool aff = msm_affine_enabled();
-    const unsigned blocks256 = (unsigned)((N + 255) / 256);
-    if (aff) {
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3(blocks256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, w.d_bytes.p,
-                           w.d_bytes.p, (int)N, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, (int)N, (int)N);
-        const unsigned conv_blocks = (unsigned)((N + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
-        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp.p, w.d_pflag.p, (G1Aff29Mem*)w.d_mult.p, (int)N, (int)N);
-    } else {
-        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((N + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1,
-                           w.d_bytes.p, w.d_bytes.p, (int)N, w.d_points.p, w.d_pflag.p, w.d_mult.p, (G1Jac29Mem*)nullptr, (int)N, (int)N);
-    }
+    g1_decode_tables(w.d_bytes.p, N, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, (int)N, aff, s->s1);
     HIPCHK(hipGetLastError());
-    // the cells -> plain limbs with their canonical flags, and the index arrays
-    uint32_t* const d_cidx = cs->d_idx.p;
-    const size_t o_order = n, o_start = 2 * n, o_cols = o_start + CELLS_PER_EXT_BLOB + 1, o_wlist = o_cols + CELLS_PER_EXT_BLOB, o_wstart = o_wlist + n;
-    HIPCHK(hipMemcpyAsync(cs->d_idx.p, idx.data(), 4 * (o_wstart + m + 1), hipMemcpyHostToDevice, s->s1));
-    HIPCHK(hipMemsetAsync(cs->d_bad.p, 0, 4 * n, s->s1));
-    HIPCHK(hipMemcpyAsync(cs->d_cells.p, cells, CELL_BYTES * n, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * n + 255) / 256)), dim3(256), 0, s->s1, (const uint8_t*)cs->d_cells.p, cs->d_vals.p, cs->d_bad.p,
-                       (int)(CELL_FE * n));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_bad.data(), cs->d_bad.p, 4 * n, hipMemcpyDeviceToHost, s->s1));
+    // the cells -> plain limbs with their canonical flags, and the index words
+    if ((rc = cells_decode(s, *cs, P, cells, h_bad.data())) != KZG_OK) return rc;
     HIPCHK(hipMemcpyAsync(h_pflag.data(), w.d_pflag.p, 4 * N, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipEventRecord(s->ev[6], s->s1));
     if (hasher.joinable()) hasher.join();
@@ -291,29 +282,21 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     for (size_t i = n + m; i < N; i++)
         if (h_pflag[i] == G1_INVALID) return fail(KZG_BAD_SETUP, "a monomial setup point is outside G1");
 
-    // r -> the scalars: [r^k | -] for LL, [r^k h^64 | w_i | -I_i] for RL
+    // r -> the scalars [r^k n | r^k h^64 n | w_i m | -I_i 64]: LL's are the first n, RL's the N from offset n on
     uint8_t r_le[32];
     reverse32(r_le, r_be);
     HIPCHK(hipEventRecord(s->ev[7], s->s1));
-    HIPCHK(hipMemcpyAsync(cs->d_r.p, r_le, 32, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_cell_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, (const Fr*)cs->d_r.p, (const uint32_t*)d_cidx, (const Fr*)cs->d_T.p, cs->d_rM.p,
-                       cs->d_sc_ll.p, cs->d_sc_rl.p, (int)n);
-    hipLaunchKernelGGL(k_cell_commitment_weights, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const Fr*)cs->d_rM.p, (const uint32_t*)(d_cidx + o_wlist),
-                       (const uint32_t*)(d_cidx + o_wstart), cs->d_sc_rl.p + n, (int)m);
-    hipLaunchKernelGGL(k_cell_column_ifft, dim3((unsigned)U), dim3(64), 0, s->s1, (const Fr*)cs->d_vals.p, (const Fr*)cs->d_rM.p, (const uint32_t*)(d_cidx + o_order),
-                       (const uint32_t*)(d_cidx + o_start), (const uint32_t*)(d_cidx + o_cols), (const Fr*)cs->d_T.p, cs->d_coef.p);
-    hipLaunchKernelGGL(k_cell_interp_sum, dim3(1), dim3(64), 0, s->s1, (const Fr*)cs->d_coef.p, U, cs->d_sc_rl.p + n + m);
-    HIPCHK(hipGetLastError());
+    if ((rc = cells_scalars(s, *cs, P, r_le)) != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[8], s->s1));
     // the two sums over the one set of tables (each decoded proof serves both); g1_msm_core splits its scalars in place
     const G1MsmTables tb{w.d_mult.p, w.d_pflag.p, (int)N, aff, false};
     uint8_t ll[48], rl[48];
-    HIPCHK(hipMemcpyAsync(w.d_scalars.p, cs->d_sc_ll.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_scalars.p, cs->stage.d_sc.p, sizeof(Fr) * n, hipMemcpyDeviceToDevice, s->s1));
     if ((rc = g1_msm_core(s, n, tb, ll)) != KZG_OK) return rc;
     const float msm_ll = s->timings[2];
     elapsed(&s->timings[6], s->ev[5], s->ev[6]);
     elapsed(&s->timings[4], s->ev[7], s->ev[8]);
-    HIPCHK(hipMemcpyAsync(w.d_scalars.p, cs->d_sc_rl.p, sizeof(Fr) * N, hipMemcpyDeviceToDevice, s->s1));
+    HIPCHK(hipMemcpyAsync(w.d_scalars.p, cs->stage.d_sc.p + n, sizeof(Fr) * N, hipMemcpyDeviceToDevice, s->s1));
     if ((rc = g1_msm_core(s, N, tb, rl)) != KZG_OK) return rc;
     s->timings[2] += msm_ll;
     if ((rc = cells_pairing(s, *cs, ll, rl, ok)) != KZG_OK) return rc;

@@ -101,7 +101,7 @@ extern "C" KzgRet kzg_settings_precompute(const KzgSettings* s, unsigned what) t
     select_streams(s, (size_t)-1);
     if (what & KZG_PRECOMPUTE_CELL_VERIFY) {
         CellState* cs = nullptr;
-        if ((rc = cells_state(s, &cs)) != KZG_OK || (rc = cs->reserve(1)) != KZG_OK) return rc;
+        if ((rc = cells_state(s, &cs)) != KZG_OK) return rc;  // (the call buffers are sized by the first call's plan)
     }
     if (what & KZG_PRECOMPUTE_CELL_PROOFS) {
         CellProverState* cp = nullptr;

@@ -244,6 +244,20 @@ static KzgRet g1_msm_core(const KzgSettings* s, size_t n, const G1MsmTables& tb,
     elapsed(&s->timings[2], s->ev[2], s->ev[3]);
     return KZG_OK;
 }
+// n compressed points at `bytes` (device) -> decoded and subgroup-tested: the affine points, their flags and the MSM table rows of
+// g1_msm_core at `stride` points per row (aff: the affine rows, 2^64 P by way of jtmp; else Jacobian rows and jtmp is not touched)
+static void g1_decode_tables(const uint8_t* bytes, size_t n, G1Aff* points, uint32_t* pflag, void* mult, G1Jac29Mem* jtmp, int stride, bool aff,
+                             hipStream_t stream) {
+    if (aff) {
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), stream,
+                           bytes, bytes, (int)n, points, pflag, mult, jtmp, (int)n, stride);
+        const unsigned conv_blocks = (unsigned)((n + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
+        hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, stream, (const G1Jac29Mem*)jtmp, (const uint32_t*)pflag, (G1Aff29Mem*)mult, (int)n, stride);
+    } else {
+        hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), stream,
+                           bytes, bytes, (int)n, points, pflag, mult, (G1Jac29Mem*)nullptr, (int)n, stride);
+    }
+}
 // scalars: big-endian, any value below 2^256 -> canonical limbs at ws.d_scalars, reduced on the device (round 5 reduced and
 // reversed them on the host: 10 ms of a 2^20-term call); staged behind `skip` bytes of ws.d_bytes
 static KzgRet g1_msm_scalars_in(const KzgSettings* s, const uint8_t* scalars, size_t n, size_t skip) {
@@ -272,16 +286,7 @@ extern "C" KzgRet kzg_g1_msm(uint8_t out[48], const uint8_t* points48, const uin
         HIPCHK(hipMemcpyAsync(w.d_bytes.p, points48, 48 * n, hipMemcpyHostToDevice, s->s1));
         if ((rc = g1_msm_scalars_in(s, scalars, n, 48 * n)) != KZG_OK) return rc;
         HIPCHK(hipEventRecord(s->ev[5], s->s1));
-        const unsigned blocks256 = (unsigned)((n + 255) / 256);
-        if (aff) {
-            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, true>), dim3(blocks256), dim3(256), 256 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1, w.d_bytes.p,
-                               w.d_bytes.p, (int)n, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, (int)n, np);
-            const unsigned conv_blocks = (unsigned)((n + 64 * AFFINE_BATCH - 1) / (64 * AFFINE_BATCH));
-            hipLaunchKernelGGL(k_mult_to_affine29, dim3(conv_blocks), dim3(64), 0, s->s1, w.d_jtmp.p, w.d_pflag.p, (G1Aff29Mem*)w.d_mult.p, (int)n, np);
-        } else {
-            hipLaunchKernelGGL((k_g1_decode_multiples29<MSM_CHUNKS, false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), s->s1,
-                               w.d_bytes.p, w.d_bytes.p, (int)n, w.d_points.p, w.d_pflag.p, w.d_mult.p, (G1Jac29Mem*)nullptr, (int)n, np);
-        }
+        g1_decode_tables(w.d_bytes.p, n, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, np, aff, s->s1);
         HIPCHK(hipGetLastError());
         // (a point outside G1 has the digit 0 in every window - the kernel reads its flag - so the verdict on the inputs is
         // looked at after the sum: one wait at the end)

@@ -1,6 +1,8 @@
-// cell_group_plan.hpp - host planning of kzg_verify_cell_kzg_proof_batches (capi_cell_groups.hpp): which batches ride in the group
-// launch, and the index words its kernels (cell_group_kernels.hpp) read.  Plain C++ without HIP calls, so that
-// tests/host/cell_group_plan_host.cpp builds it with g++; cell_group_term below is also what the term-table kernel runs.
+// cell_group_plan.hpp - host planning of the cell verifiers: which batches of kzg_verify_cell_kzg_proof_batches
+// (capi_cell_groups.hpp) ride in the group launch, and the index words the r -> scalars kernels (cell_kernels.hpp) read.
+// kzg_verify_cell_kzg_proof_batch (capi_cells.hpp) plans its one batch here too, with a threshold no batch exceeds: G = 1.
+// Plain C++ without HIP calls, so that tests/host/cell_group_plan_host.cpp builds it with g++; cell_group_term below is also what
+// the term-table kernel runs.
 //
 // A call brings n_batches independent batches; batch b is entries [off[b], off[b + 1]) of the caller's arrays.  A batch is
 //   EMPTY      no cells: true, nothing to launch
@@ -10,7 +12,7 @@
 // The cells of the GROUP batches are numbered densely, slot after slot ("dense cell" q); the distinct commitments of a slot - compared
 // as bytes, first-seen order, nothing shared between slots - likewise ("dense commitment" i), and its touched columns in ascending
 // cell index ("dense column" u).  Every list below is a STABLE counting sort, so every device sum runs in ascending k within its
-// batch: exactly the order of the single call's kernels.
+// batch, whichever entry point the batch came through.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -66,11 +68,24 @@ KZG_CG_HD inline CellGroupTerm cell_group_term(uint32_t o, uint32_t t, uint32_t 
     return r;
 }
 
+// ci[k] = index of commitment k among the distinct ones of the n given (compared as bytes), numbered in first-seen order;
+// uniq gains base + the first k that holds distinct commitment i, for every i
+inline void cell_dedup(const uint8_t* commitments, size_t n, uint32_t* ci, std::vector<uint32_t>& uniq, size_t base = 0) {
+    std::unordered_map<std::string, uint32_t> seen;
+    seen.reserve(n);
+    for (size_t k = 0; k < n; k++) {
+        auto it = seen.emplace(std::string(reinterpret_cast<const char*>(commitments + 48 * k), 48), (uint32_t)seen.size());
+        if (it.second) uniq.push_back((uint32_t)(base + k));
+        ci[k] = it.first->second;
+    }
+}
+
 struct CellGroupPlan {
     std::vector<uint8_t> kind;     // [n_batches]
     std::vector<size_t> off;       // [n_batches + 1] prefix sums of batch_sizes
     std::vector<uint32_t> slot_batch;  // [G] batch of slot g
     std::vector<uint32_t> uniq_entry;  // [mtot] entry of the caller's arrays that holds dense commitment i (its first cell)
+    std::vector<uint32_t> ci;          // [nG] commitment of dense cell q among its slot's distinct ones (the transcript's index)
     uint32_t G = 0, nG = 0, mtot = 0, Utot = 0;
     uint32_t max_ll = 0, max_rl = 0;   // the longest output 0 / output 1 list: max n, max (n + m + 64)
     // the device words, one upload: every array at its offset
@@ -103,18 +118,14 @@ inline void cell_group_plan(CellGroupPlan& P, const uint8_t* commitments, const 
     P.G = (uint32_t)P.slot_batch.size();
     const uint32_t G = P.G, nG = P.nG;
     // first pass: the distinct commitments and the touched columns of every slot
-    std::vector<uint32_t> ci(nG), cstart(G + 1, 0), ustart(G + 1, 0), colstart(G + 1, 0), col_id;
-    std::unordered_map<std::string, uint32_t> seen;
+    std::vector<uint32_t> cstart(G + 1, 0), ustart(G + 1, 0), colstart(G + 1, 0), col_id;
+    P.ci.resize(nG);
+    const std::vector<uint32_t>& ci = P.ci;
     for (uint32_t g = 0; g < G; g++) {
         const size_t e0 = P.off[P.slot_batch[g]], n = batch_sizes[P.slot_batch[g]];
-        seen.clear();
+        cell_dedup(commitments + 48 * e0, n, P.ci.data() + cstart[g], P.uniq_entry, e0);
         bool touched[CELL_GROUP_COLUMNS] = {};
-        for (size_t k = 0; k < n; k++) {
-            auto it = seen.emplace(std::string(reinterpret_cast<const char*>(commitments + 48 * (e0 + k)), 48), (uint32_t)seen.size());
-            if (it.second) P.uniq_entry.push_back((uint32_t)(e0 + k));
-            ci[cstart[g] + k] = it.first->second;
-            touched[cell_indices[e0 + k]] = true;
-        }
+        for (size_t k = 0; k < n; k++) touched[cell_indices[e0 + k]] = true;
         for (uint32_t c = 0; c < CELL_GROUP_COLUMNS; c++)
             if (touched[c]) col_id.push_back(c);
         cstart[g + 1] = cstart[g] + (uint32_t)n;

@@ -1,15 +1,17 @@
-// cell_kernels.hpp - device side of EIP-7594 cell-proof batch verification (kzg_verify_cell_kzg_proof_batch, capi_cells.hpp).
+// cell_kernels.hpp - device side of EIP-7594 cell-proof batch verification: kzg_verify_cell_kzg_proof_batch (capi_cells.hpp) and
+// kzg_verify_cell_kzg_proof_batches (capi_cell_groups.hpp) run the same kernels over the index words of cell_group_plan.hpp.
 //
 // A cell is 64 field elements of the 8 192-point extended blob; entry j of cell c is the evaluation at h_c * w64^brp6(j) with
 // h_c = w8192^brp7(c).  The verifier needs, after the host has hashed the batch transcript into r:
 //   r^k per cell, the cells summed column by column with those weights, each column's 64-point inverse DFT over its coset, the
 //   coefficients summed over the columns, and the MSM scalars built from all of it.
-// Every sum here runs in a FIXED order the host lays out (counting sort by column / by commitment): the verdict does not depend
+// Every sum here runs in a FIXED order the host lays out (stable counting sorts by column / by commitment): the verdict does not depend
 // on the order, but a run-to-run identical reduction is what makes a wrong answer reproducible.  Field values are the 8x32-limb
 // Fr of field.hpp; "plain" = canonical integer limbs, "Montgomery" = times R (FrF::mul(Montgomery a, plain b) = a * b, plain).
 // Sizes are small (at most 128 columns, 64 coefficients), so no kernel here is on a hot path: one lane per element, one
 // wavefront per column.
 #pragma once
+#include "cell_group_plan.hpp"
 #include "fr_kernels.hpp"
 
 namespace kzg {
@@ -72,50 +74,57 @@ __global__ void k_cell_decode(const uint8_t* __restrict__ cells, Fr* __restrict_
     vals[t] = v;
 }
 
-// Per cell k (cell index cidx[k] < 128): rM[k] = r^k (Montgomery), sc_ll[k] = r^k and sc_rl[k] = r^k * h_c^64 (plain): the
-// scalars of proof k in the left and right MSMs.  r: one plain element.
-__global__ void k_cell_powers(const Fr* __restrict__ r, const uint32_t* __restrict__ cidx, const Fr* __restrict__ T, Fr* __restrict__ rM,
-                              Fr* __restrict__ sc_ll, Fr* __restrict__ sc_rl, int n) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const Fr rk = fr_pow_small(FrF::to_mont(r[0]), (uint32_t)k);
-    rM[k] = rk;
-    sc_ll[k] = FrF::from_mont(rk);
-    const uint32_t c = cidx[k] & (CELLS_PER_EXT_BLOB - 1);  // (validated on the host)
-    sc_rl[k] = FrF::mul(rk, FrF::from_mont(T[CELL_FE * bitrev7(c)]));  // h_c^64 = w8192^(64 brp7(c))
+// The r -> scalars kernels carry the batch dimension inside: G independent batches ("slots") lie behind one another in every array -
+// dense cells, dense commitments, dense columns, numbered by the host plan (cell_group_plan.hpp) - and each kernel is ONE launch
+// over all of them: a lane per dense cell or commitment, a wavefront per dense column or per slot.  Each slot has its own challenge
+// r[g], and every sum runs in the order of the plan's stable sorts - ascending k within the batch - with no atomics, so a call gives
+// the same bytes on every run.  kzg_verify_cell_kzg_proof_batch is the case G = 1 (cstart[0] = 0, cell_slot[q] = 0).
+
+// Per dense cell q of slot g = cell_slot[q] (cell index cidx[q] < 128), k = q - cstart[g]: rM[q] = r_g^k (Montgomery), sc[q] = r_g^k
+// and sc[nG + q] = r_g^k h_c^64 (plain): the scalars of proof k in the left and right MSMs.  r: G plain elements.
+__global__ void k_cell_powers(const Fr* __restrict__ r, const uint32_t* __restrict__ cell_slot, const uint32_t* __restrict__ cstart,
+                              const uint32_t* __restrict__ cidx, const Fr* __restrict__ T, Fr* __restrict__ rM, Fr* __restrict__ sc, int nG) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nG) return;
+    const uint32_t g = cell_slot[q];
+    const Fr rk = fr_pow_small(FrF::to_mont(r[g]), (uint32_t)q - cstart[g]);
+    rM[q] = rk;
+    sc[q] = FrF::from_mont(rk);
+    const uint32_t c = cidx[q] & (CELLS_PER_EXT_BLOB - 1);  // (validated on the host)
+    sc[(size_t)nG + q] = FrF::mul(rk, FrF::from_mont(T[CELL_FE * bitrev7(c)]));  // h_c^64 = w8192^(64 brp7(c))
 }
 
-// w_i = sum of r^k over the cells of unique commitment i, in ascending k (wlist[wstart[i] .. wstart[i + 1])): the scalar of
+// w_i = sum of r^k over the cells of dense commitment i, in ascending k (wlist[wstart[i] .. wstart[i + 1])): the scalar of
 // commitment i in the right MSM, plain.
 __global__ void k_cell_commitment_weights(const Fr* __restrict__ rM, const uint32_t* __restrict__ wlist, const uint32_t* __restrict__ wstart,
-                                          Fr* __restrict__ out, int m) {
+                                          Fr* __restrict__ out, int mtot) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
+    if (i >= mtot) return;
     Fr acc = FrF::zero();
     for (uint32_t q = wstart[i]; q < wstart[i + 1]; q++) acc = FrF::add(acc, rM[wlist[q]]);
     out[i] = FrF::from_mont(acc);
 }
 
-// One wavefront per touched column u (cell index cols[u]):
-//   agg[j] = sum of r^k * cell_k[j] over the cells of that column in ascending k (order[start[u] .. start[u + 1]))
+// One wavefront per dense column u (cell index col_id[u] of its slot):
+//   agg[j] = sum of r^k * cell_k[j] over the cells of that column in ascending k (order[col_start[u] .. col_start[u + 1]))
 //   then I_c, the polynomial of degree < 64 through (h_c w64^brp6(j), agg[j]): entry j sits at the bit-reversed position of
 //   the coset's natural order, which is the input order of a decimation-in-time FFT, so the six radix-2 stages run in LDS on
 //   agg as it is and leave A[i] = sum_t v_t w64^(-i t) = 64 h_c^i I_i in natural order; coef[u][i] = A[i] h_c^(-i) / 64 (plain).
 __global__ __launch_bounds__(64) void k_cell_column_ifft(const Fr* __restrict__ vals, const Fr* __restrict__ rM, const uint32_t* __restrict__ order,
-                                                         const uint32_t* __restrict__ start, const uint32_t* __restrict__ cols,
+                                                         const uint32_t* __restrict__ col_start, const uint32_t* __restrict__ col_id,
                                                          const Fr* __restrict__ T, Fr* __restrict__ coef) {
     __shared__ Fr a[CELL_FE];
     const int u = blockIdx.x, j = threadIdx.x;
     Fr acc = FrF::zero();
-    for (uint32_t q = start[u]; q < start[u + 1]; q++) {
-        const uint32_t k = order[q];
-        acc = FrF::add(acc, FrF::mul(rM[k], vals[(size_t)k * CELL_FE + j]));
+    for (uint32_t p = col_start[u]; p < col_start[u + 1]; p++) {
+        const uint32_t q = order[p];
+        acc = FrF::add(acc, FrF::mul(rM[q], vals[(size_t)q * CELL_FE + j]));
     }
     a[j] = acc;
     __syncthreads();
     for (int half = 1; half < CELL_FE; half <<= 1) {
         if (j < CELL_FE / 2) {
-            const int g = j / half, kk = j % half, i0 = 2 * half * g + kk, i1 = i0 + half;
+            const int gr = j / half, kk = j % half, i0 = 2 * half * gr + kk, i1 = i0 + half;
             const Fr tw = T[(EXT_FE - kk * (EXT_FE / (2 * half))) & (EXT_FE - 1)];  // w_(2 half)^(-kk) = w8192^(-kk 8192 / (2 half))
             const Fr x = a[i0], y = FrF::mul(tw, a[i1]);
             a[i0] = FrF::add(x, y);
@@ -123,17 +132,31 @@ __global__ __launch_bounds__(64) void k_cell_column_ifft(const Fr* __restrict__ 
         }
         __syncthreads();
     }
-    const uint32_t e = (bitrev7(cols[u] & (CELLS_PER_EXT_BLOB - 1)) * (uint32_t)j) & (EXT_FE - 1);  // h_c^i = w8192^(brp7(c) i)
-    const Fr s = FrF::mul(FrF::to_mont(cell_inv64()), T[(EXT_FE - e) & (EXT_FE - 1)]);    // h_c^(-i) / 64, Montgomery
+    const uint32_t e = (bitrev7(col_id[u] & (CELLS_PER_EXT_BLOB - 1)) * (uint32_t)j) & (EXT_FE - 1);  // h_c^i = w8192^(brp7(c) i)
+    const Fr s = FrF::mul(FrF::to_mont(cell_inv64()), T[(EXT_FE - e) & (EXT_FE - 1)]);      // h_c^(-i) / 64, Montgomery
     coef[(size_t)u * CELL_FE + j] = FrF::mul(s, a[j]);
 }
 
-// out[i] = -(sum over the U touched columns, in column order, of coef[u][i]): the scalar of [tau^i]G1 in the right MSM, plain.
-__global__ __launch_bounds__(64) void k_cell_interp_sum(const Fr* __restrict__ coef, int U, Fr* __restrict__ out) {
-    const int i = threadIdx.x;
+// One wavefront per slot g: out[64 g + i] = -(the sum over its dense columns, in column order, of coef[u][i]): the scalar of
+// [tau^i]G1 in the right MSM, plain.
+__global__ __launch_bounds__(64) void k_cell_interp_sum(const Fr* __restrict__ coef, const uint32_t* __restrict__ colstart, Fr* __restrict__ out) {
+    const int g = blockIdx.x, i = threadIdx.x;
     Fr acc = FrF::zero();
-    for (int u = 0; u < U; u++) acc = FrF::add(acc, coef[(size_t)u * CELL_FE + i]);
-    out[i] = FrF::neg(acc);
+    for (uint32_t u = colstart[g]; u < colstart[g + 1]; u++) acc = FrF::add(acc, coef[(size_t)u * CELL_FE + i]);
+    out[(size_t)g * CELL_FE + i] = FrF::neg(acc);
+}
+
+// The group call's term tables [2 G][max_terms] for the window kernel (cell_group_term); live[g] == 0 masks slot g out: all its
+// terms on SKIP
+__global__ void k_cell_terms(uint32_t* __restrict__ term_point, uint32_t* __restrict__ term_scalar, const uint32_t* __restrict__ cstart,
+                             const uint32_t* __restrict__ ustart, const uint32_t* __restrict__ live, int G, int nG, int mtot, int max_terms) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)2 * G * max_terms) return;
+    const uint32_t bo = (uint32_t)(e / max_terms), t = (uint32_t)(e % max_terms), g = bo >> 1;
+    const CellGroupTerm tm = cell_group_term(bo & 1, t, g, cstart[g], cstart[g + 1] - cstart[g], ustart[g], ustart[g + 1] - ustart[g], (uint32_t)nG,
+                                             (uint32_t)mtot, live[g] != 0);
+    term_point[e] = tm.point;
+    term_scalar[e] = tm.scalar;
 }
 
 }  // namespace kzg

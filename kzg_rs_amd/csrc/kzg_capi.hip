@@ -27,7 +27,6 @@
 #include "slp2.hpp"
 #include "proof_kernels.hpp"
 #include "cell_kernels.hpp"
-#include "cell_group_kernels.hpp"
 #include "fk20_kernels.hpp"
 #include "g1_ntt.hpp"
 #include "recover_kernels.hpp"

@@ -1,5 +1,5 @@
-// Host build of kzg_rs_amd/csrc/cell_group_plan.hpp for tests/test_cell_groups_cpu.py: the plan of
-// kzg_verify_cell_kzg_proof_batches as the library makes it, and the term tables as its kernel fills them (cell_group_term).
+// Host build of kzg_rs_amd/csrc/cell_group_plan.hpp for tests/test_cell_groups_cpu.py: the plan of both cell verifiers as the
+// library makes it, and the term tables as the group call's kernel fills them (cell_group_term).
 #include "cell_group_plan.hpp"
 using namespace kzg;
 extern "C" {
@@ -17,16 +17,16 @@ size_t h_cg_number(const void* p_, int which) {
                         p.o_order, p.o_col_start, p.o_col_id, p.o_wlist, p.o_wstart, CELL_GROUP_MAX_CELLS, CELL_GROUP_MAX_BATCHES};
     return v[which];
 }
-// 0 kind [n_batches], 1 slot_batch [G], 2 uniq_entry [mtot], 3 idx
+// 0 kind [n_batches], 1 slot_batch [G], 2 uniq_entry [mtot], 3 idx, 4 ci [nG]
 void h_cg_array(const void* p_, int which, uint32_t* out) {
     const CellGroupPlan& p = *static_cast<const CellGroupPlan*>(p_);
     if (which == 0)
         for (size_t i = 0; i < p.kind.size(); i++) out[i] = p.kind[i];
-    const std::vector<uint32_t>* v = which == 1 ? &p.slot_batch : which == 2 ? &p.uniq_entry : which == 3 ? &p.idx : nullptr;
+    const std::vector<uint32_t>* v = which == 1 ? &p.slot_batch : which == 2 ? &p.uniq_entry : which == 3 ? &p.idx : which == 4 ? &p.ci : nullptr;
     if (v)
         for (size_t i = 0; i < v->size(); i++) out[i] = (*v)[i];
 }
-// the term tables [2 G][max_rl] as k_cellg_terms writes them
+// the term tables [2 G][max_rl] as k_cell_terms writes them
 void h_cg_terms(const void* p_, const uint32_t* live, uint32_t* term_point, uint32_t* term_scalar) {
     const CellGroupPlan& p = *static_cast<const CellGroupPlan*>(p_);
     const uint32_t* cstart = p.idx.data() + p.o_cstart;

@@ -1,7 +1,7 @@
 """kzg_verify_cell_kzg_proof_batches without a GPU: the interface is there, the group's challenges (kzg_cell_batch_challenges,
 host code) are the single call's on every slice and the model's, and the host plan of the group launch - built for the host from
-kzg_rs_amd/csrc/cell_group_plan.hpp, the code the library runs - gives every batch the lists the single call's planning gives its
-slice, with every pad term on the skipped point."""
+kzg_rs_amd/csrc/cell_group_plan.hpp, the code the library runs for both cell verifiers - gives every batch the lists of the Python
+model of one batch's planning (_single_plan) on its slice, with every pad term on the skipped point."""
 import ctypes as C
 import os
 import random
@@ -123,7 +123,7 @@ def _plan(lib, batches, threshold, live=None):
             lib.h_cg_array(p, which, buf)
             return list(buf[:count])
 
-        out = dict(n, kind=arr(0, len(sizes)), slot_batch=arr(1, n["G"]), uniq_entry=arr(2, n["mtot"]), idx=arr(3, n["words"]))
+        out = dict(n, kind=arr(0, len(sizes)), slot_batch=arr(1, n["G"]), uniq_entry=arr(2, n["mtot"]), idx=arr(3, n["words"]), ci=arr(4, n["nG"]))
         lv = (C.c_uint32 * max(n["G"], 1))(*(live if live is not None else [1] * n["G"]))
         tp, ts = ((C.c_uint32 * max(2 * n["G"] * n["max_rl"], 1))() for _ in range(2))
         lib.h_cg_terms(p, lv, tp, ts)
@@ -134,8 +134,9 @@ def _plan(lib, batches, threshold, live=None):
 
 
 def _single_plan(commitments, idx):
-    """What kzg_verify_cell_kzg_proof_batch's planning gives for one batch (csrc/capi_cells.hpp): the distinct commitments in
-    first-seen order, the cells by column and by commitment (stable), and its two term lists over the points
+    """The model of one batch's planning, stated independently of csrc/cell_group_plan.hpp (which kzg_verify_cell_kzg_proof_batch
+    runs on its one batch and kzg_verify_cell_kzg_proof_batches on every slot): the distinct commitments in first-seen order, every
+    cell's commitment index among them, the cells by column and by commitment (stable), and the two term lists over the points
     [proofs | distinct commitments | monomial points] and the scalars laid out alike (k_plain_terms: term t = point t, scalar t)."""
     n = len(idx)
     first = {}
@@ -151,7 +152,7 @@ def _single_plan(commitments, idx):
     m = len(uniq)
     ll = [("proof", t, "r^k", t) for t in range(n)]
     rl = [("proof", t, "r^k h^64", t) for t in range(n)] + [("commitment", i, "weight", i) for i in range(m)] + [("monomial", i, "-I", i) for i in range(64)]
-    return dict(uniq=uniq, cols=cols, order=order, start=start, wlist=wlist, wstart=wstart, ll=ll, rl=rl)
+    return dict(uniq=uniq, ci=ci, cols=cols, order=order, start=start, wlist=wlist, wstart=wstart, ll=ll, rl=rl)
 
 
 def _check_group(lib, batches, threshold, live=None):
@@ -224,6 +225,31 @@ def test_plan_gives_every_batch_the_single_calls_lists(host):
     P = _check_group(host, _mixed_group(), 256)
     assert P["G"] == 5 and P["kind"][1] == EMPTY and P["kind"][5] == BAD_INDEX
     assert P["mtot"] == 2 + 2 + 3 + 1 + 3 and P["max_ll"] == 12 and P["max_rl"] == 12 + 1 + 64
+
+
+def test_one_batch_is_a_group_of_one_slot(host):
+    """the shape kzg_verify_cell_kzg_proof_batch relies on: its batch planned alone, under a threshold no batch exceeds"""
+    rnd = random.Random(300)
+    cms = [rnd.randbytes(48) for _ in range(5)]
+    cm = [cms[rnd.randrange(5)] for _ in range(300)]
+    idx = [rnd.randrange(128) for _ in range(300)]
+    cm[299], idx[299] = cm[17], idx[17]                                   # a repeated (commitment, cell)
+    assert len(set(cm)) == 5 and len(set(idx)) < 300 and len(set(zip(cm, idx))) < 300
+    P = _check_group(host, [(cm, idx)], 1 << 20)
+    assert P["kind"] == [GROUP] and P["G"] == 1 and P["nG"] == 300 and P["mtot"] == 5 and P["slot_batch"] == [0]
+    assert P["ci"] == _single_plan(cm, idx)["ci"]
+    w = P["idx"]
+    assert w[P["cstart"]: P["cstart"] + 2] == [0, 300] and w[P["cell_slot"]: P["cell_slot"] + 300] == [0] * 300
+    assert _plan(host, [(cm, idx)], 256)["kind"] == [LARGE]
+
+
+def test_plan_keeps_every_cells_commitment_index(host):
+    batches = _mixed_group()
+    P = _plan(host, batches, 256)
+    cstart = P["idx"][P["cstart"]: P["cstart"] + P["G"] + 1]
+    assert P["G"] == 5 and len(P["ci"]) == P["nG"]
+    for g, b in enumerate(P["slot_batch"]):
+        assert P["ci"][cstart[g]: cstart[g + 1]] == _single_plan(*batches[b])["ci"], (g, b)
 
 
 def test_plan_thresholds_and_pad_terms_on_both_sides(host):

@@ -256,3 +256,41 @@ def test_same_bytes_on_every_run_and_over_stale_buffers(fx):
     tm = (C.c_float * 8)()
     fx["api"].lib().kzg_last_timings(fx["st"]._h, tm)
     assert tm[0] > 0 and tm[2] > 0 and tm[3] > 0 and tm[6] > 0 and tm[0] >= tm[2]
+
+
+def _model(args):
+    cm, idx, ce, pr = args
+    return M.verify([x.tobytes() for x in cm], [int(i) for i in idx], [x.tobytes() for x in ce], [x.tobytes() for x in pr])
+
+
+def test_alternating_entry_points_share_their_buffers(fx):
+    """The single call and the group call run the same plan and r -> scalars stage over ONE set of grow-only buffers on the handle:
+    alternated with growing and shrinking sizes, every verdict is the model's, and a step repeated after a different one gives
+    the same answer (nothing stale is read)."""
+    s3 = _batch(fx, [_id(1, 3), _id(2, 3), _id(3, 9)])
+    g25 = [_batch(fx, _column_ids(2, 20)), _batch(fx, [_id(4, c) for c in range(5)])]
+    s70 = _batch(fx, _column_ids(70, 41))
+    lone = _batch(fx, [_id(5, 64)])
+    wrong = lone[3].copy()
+    wrong[0] = fx["proofs"][_id(5, 65)]  # a point of G1, the proof of another cell
+    assert (wrong[0] != lone[3][0]).any()
+    g619 = [_batch(fx, _column_ids(6, 77)), [lone[0], lone[1], lone[2], wrong], _batch(fx, [_id(6, c) for c in range(100, 109)])]
+    bad3 = _tamper(fx, s3, "element 63 + 1", 1)
+    steps = [(s3, True), (g25, [True, True]), (s70, True), (g619, [True, False, True]), (bad3, False)]
+    assert [len(b[1]) if isinstance(want, bool) else [len(x[1]) for x in b] for b, want in steps] == [3, [2, 5], 70, [6, 1, 9], 3]
+    # the CPU half: the model gives exactly these verdicts on the fixture
+    model = [_model(b) if isinstance(want, bool) else [_model(x) for x in b] for b, want in steps]
+    assert model == [want for _, want in steps]
+
+    def run(b, want):
+        if isinstance(want, bool):
+            rc, ok = _single(fx, b)
+            return rc, ok
+        rc, ok, err = _group(fx, b)
+        assert err == [0] * len(b)
+        return rc, ok
+
+    got = [run(b, want) for b, want in steps]
+    assert got == [(0, v) for v in model]
+    again = [run(b, want) for b, want in steps[3:]]
+    assert again == got[3:]
