@@ -342,9 +342,19 @@ KzgRet kzg_recover_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out,
  * and the lines of g2_points[64]; a few ms) and keeps them with ~5 KB per cell of grow-only buffers.  Cost of a call: the
  * transcript hash runs on a host thread (SHA-NI: ~1 ms per 1 000 cells) while the points and cells are copied,
  * decoded and checked on the device; then column sums and 64-point inverse DFTs, two MSMs (n terms; n + m + 64 terms) and one
- * pairing.  Multi-device handles run it on their first device.  kzg_last_timings afterwards: [0] the call (host wall clock),
- * [1] the transcript hash (host), [2] the two MSMs, [3] the pairing, [4] the kernels between r and the MSMs, [6] the copies and
- * decode of the points and cells. */
+ * pairing.  kzg_last_timings afterwards: [0] the call (host wall clock), [1] the transcript hash (host), [2] the two MSMs, [3] the
+ * pairing, [4] the kernels between r and the MSMs, [6] the copies and decode of the points and cells.
+ * Threads: call it from as many threads as you like on ONE shared handle.  A call of 1 .. KZG_CELL_GROUP_MAX_CELLS (T) cells does
+ * not take the handle's lock: it becomes a request of the handle's small-call queue (as kzg_verify_kzg_proof and small blob
+ * batches do), and the calls that wait while a launch is in flight leave TOGETHER - up to 128 calls and 128 T cells - as the slots
+ * of one kzg_verify_cell_kzg_proof_batches group on a private lane of the handle, each with its own challenge, sums and pairing
+ * instance.  Verdict and error are exactly the lone call's: a wrong proof or a KZG_BADARGS in one caller's input never changes
+ * another caller's answer.  A caller that waits hashes its own transcript meanwhile.  A call that finds the handle idle runs at
+ * once and alone, on the path described above (no added wait); after it kzg_last_timings reports what it always did, after a
+ * shared launch the group call's slots for that launch.  Calls above T, and every call on a handle made under KZG_OPTIONS
+ * cell_coalesce=0 (or coalesce=0), run one at a time under the handle's lock as before.  A multi-device handle deals the lanes
+ * of its queue to its devices in turn, but the cell set-up (the 64 monomial points, the lines of g2_points[64]) exists on its
+ * first device only: cell launches keep to the first device's lanes, and calls above T run there too. */
 KzgRet kzg_verify_cell_kzg_proof_batch(bool *ok, const uint8_t *commitments, const uint64_t *cell_indices,
                                        const uint8_t *cells, const uint8_t *proofs, size_t n, const KzgSettings *s);
 /* The batch challenge r of the above alone, as 32 big-endian bytes: host code, no device and no settings needed; inputs are
@@ -471,6 +481,17 @@ KzgRet kzg_timing_totals(const KzgSettings *s, double out_sum_ms[8], uint64_t *c
  * pipeline lanes; MHz = 100 * out[0] / out[1] (0 / 0 when that kernel has not run).  bench.py prices cycles per instruction
  * with it instead of the nominal 2.4 GHz. */
 KzgRet kzg_debug_shader_clock(const KzgSettings *s, double out[2], int reset);
+/* Diagnostic: the coalescing of concurrent kzg_verify_cell_kzg_proof_batch calls on this handle since the last reset:
+ * out = { launches, calls carried (requests), cells, the largest launch in calls }.  launches == requests: every call ran alone.
+ * All zero on a handle made with KZG_OPTIONS cell_coalesce=0, and for calls above KZG_CELL_GROUP_MAX_CELLS cells. */
+KzgRet kzg_debug_cell_queue_stats(const KzgSettings *s, uint64_t out[4], int reset);
+/* Measurement hook: `threads` host threads inside the library call kzg_verify_cell_kzg_proof_batch on this one handle for
+ * `seconds`; the calls are the n_calls batches of the four arrays (layout of kzg_verify_cell_kzg_proof_batches), expect[i] =
+ * 0 false | 1 true | 2 KZG_BADARGS.  out = { calls completed, elapsed seconds, answers that differ from expect, mean latency ms,
+ * longest latency ms }. */
+KzgRet kzg_debug_concurrent_cell_callers(double out[5], size_t threads, double seconds, const uint8_t *commitments,
+                                         const uint64_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
+                                         const size_t *batch_sizes, const uint8_t *expect, size_t n_calls, const KzgSettings *s);
 
 const char *kzg_last_error(void);
 

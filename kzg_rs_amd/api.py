@@ -165,6 +165,8 @@ def lib():
         L.kzg_settings_note.restype = C.c_char_p
         L.kzg_debug_small_queue_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.kzg_debug_concurrent_callers.argtypes = [C.POINTER(C.c_double), C.c_int, sz, C.c_double, u8, u8, u8, u8, u8, u8, sz, sz, vp]
+        L.kzg_debug_cell_queue_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.kzg_debug_concurrent_cell_callers.argtypes = [C.POINTER(C.c_double), sz, C.c_double, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(sz), u8, sz, vp]
         _lib = L
     return _lib
 
@@ -302,6 +304,14 @@ class KzgSettings:
         o = (C.c_uint64 * 5)()
         _chk(lib().kzg_debug_small_queue_stats(self._h, o, int(reset)))
         return dict(zip(("launches", "requests", "items", "max_items", "lanes"), (int(x) for x in o)))
+
+    def cell_queue_stats(self, reset=False):
+        """Concurrent verify_cell_kzg_proof_batch calls on this handle since the last reset (csrc/capi_cell_groups.hpp
+        small_run_cells): {launches, requests (calls carried), cells, max_requests (the largest launch, in calls)}.  All zero
+        with KZG_OPTIONS cell_coalesce=0."""
+        o = (C.c_uint64 * 4)()
+        _chk(lib().kzg_debug_cell_queue_stats(self._h, o, int(reset)))
+        return dict(zip(("launches", "requests", "cells", "max_requests"), (int(x) for x in o)))
 
     def concurrent_callers(self, kind, threads, seconds, c, p, expect, z=None, y=None, blobs=None, per_call=1):
         """T host threads INSIDE the library (no interpreter lock) calling the public small entry points on this one handle for

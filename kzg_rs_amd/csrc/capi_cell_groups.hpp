@@ -23,14 +23,46 @@ static size_t cell_group_threshold() {  // option cell_group_max_cells (A/B buil
     static const size_t t = (size_t)std::max(1L, std::min((long)CELL_GROUP_MAX_CELLS, ab_int("cell_group_max_cells", (long)CELL_GROUP_MAX_CELLS)));
     return t;
 }
+// The batches of one group, each where its caller keeps it: batch b = batch_sizes[b] commitments, cell indices, cells and proofs
+// behind the b-th pointers (kzg_verify_cell_kzg_proof_batches: into its four arrays; the requests of concurrent callers,
+// small_run_cells below: into theirs - nothing is stitched together on the host).
+struct CellGroupIn {
+    const uint8_t* const* commitments = nullptr;
+    const uint64_t* const* cell_indices = nullptr;
+    const uint8_t* const* cells = nullptr;
+    const uint8_t* const* proofs = nullptr;
+    const size_t* batch_sizes = nullptr;
+    size_t n_batches = 0;
+};
+// the same for arrays that hold batch after batch
+struct CellGroupInArrays {
+    std::vector<const uint8_t*> c, ce, p;
+    std::vector<const uint64_t*> ix;
+    CellGroupIn in;
+    CellGroupInArrays(const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, const size_t* batch_sizes,
+                      size_t n_batches)
+        : c(n_batches), ce(n_batches), p(n_batches), ix(n_batches) {
+        size_t e = 0;
+        for (size_t b = 0; b < n_batches; b++) {
+            c[b] = commitments + 48 * e, ix[b] = cell_indices + e, ce[b] = cells + CELL_BYTES * e, p[b] = proofs + 48 * e;
+            e += batch_sizes[b];
+        }
+        in = CellGroupIn{c.data(), ix.data(), ce.data(), p.data(), batch_sizes, n_batches};
+    }
+};
+// A challenge that may exist already: the owner of a queued request computes its own while it waits (small_cell_wait_work).
+// state 0: nobody has started - whoever moves it to 1 computes r_be and then stores 2.
+struct CellKnownR {
+    std::atomic<int>* state = nullptr;
+    uint8_t* r_be = nullptr;
+};
 // r_be + 32 j = the single call's r of slot j of `plan` - its dedup is the plan's - or, without a plan, of batch j, deduplicated
 // here; hashed by whoever calls work(): the batches are claimed from a counter, so the poster and any number of helper threads
-// share them
+// share them.  known (optional, per batch): challenges computed beforehand, or being computed - those are collected, not hashed again.
 struct CellGroupHash {
     uint8_t* r_be = nullptr;
-    const uint8_t *commitments = nullptr, *cells = nullptr, *proofs = nullptr;
-    const uint64_t* cell_indices = nullptr;
-    const size_t* off = nullptr;       // prefix sums of the batch sizes
+    CellGroupIn in;
+    const CellKnownR* known = nullptr;
     const CellGroupPlan* plan = nullptr;
     size_t count = 0;
     std::atomic<size_t> next{0};
@@ -49,20 +81,31 @@ struct CellGroupHash {
             for (;;) {
                 const size_t j = next.fetch_add(1, std::memory_order_relaxed);
                 if (j >= count) break;
-                const size_t b = plan ? plan->slot_batch[j] : j, e = off[b], n = off[b + 1] - e;
+                const size_t b = plan ? plan->slot_batch[j] : j, n = in.batch_sizes[b];
+                uint8_t* const out = r_be + 32 * j;
+                int idle = 0;
+                if (known && known[b].state && !known[b].state->compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) {
+                    // its owner has it, or is at it (one chain of at most T cells: well under a millisecond)
+                    while (known[b].state->load(std::memory_order_acquire) != 2) std::this_thread::yield();
+                    memcpy(out, known[b].r_be, 32);
+                    continue;
+                }
                 if (plan) {
                     const uint32_t *cstart = plan->idx.data() + plan->o_cstart, *ustart = plan->idx.data() + plan->o_ustart;
-                    cell_challenge(r_be + 32 * j, commitments, plan->ci.data() + cstart[j], plan->uniq_entry.data() + ustart[j], ustart[j + 1] - ustart[j],
-                                   cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, n);
+                    cell_challenge(out, in.commitments[b], plan->ci.data() + cstart[j], plan->uniq_entry.data() + ustart[j], ustart[j + 1] - ustart[j],
+                                   in.cell_indices[b], in.cells[b], in.proofs[b], n, plan->off[b]);
                 } else {
                     ci.resize(n);
                     uniq.clear();
-                    cell_dedup(commitments + 48 * e, n, ci.data(), uniq);
-                    cell_challenge(r_be + 32 * j, commitments + 48 * e, ci.data(), uniq.data(), uniq.size(), cell_indices + e, cells + CELL_BYTES * e,
-                                   proofs + 48 * e, n);
+                    cell_dedup(in.commitments[b], n, ci.data(), uniq);
+                    cell_challenge(out, in.commitments[b], ci.data(), uniq.data(), uniq.size(), in.cell_indices[b], in.cells[b], in.proofs[b], n);
+                }
+                if (known && known[b].state) {
+                    memcpy(known[b].r_be, out, 32);
+                    known[b].state->store(2, std::memory_order_release);
                 }
             }
-        } catch (const std::bad_alloc&) {
+        } catch (const std::bad_alloc&) {  // (cell_dedup, before a claimed challenge is started: nothing is left at state 1)
             failed = true;
         }
         const auto now = std::chrono::steady_clock::now();
@@ -74,7 +117,8 @@ struct CellGroupHash {
         size_t bytes = 0;
         for (size_t j = 0; j < count; j++) {
             const size_t b = plan ? plan->slot_batch[j] : j;
-            bytes += (off[b + 1] - off[b]) * (CELL_BYTES + 112);
+            if (known && known[b].state && known[b].state->load(std::memory_order_relaxed) != 0) continue;
+            bytes += in.batch_sizes[b] * (CELL_BYTES + 112);
         }
         const long opt = KZG_HOST_THREADS_OPTION;
         const size_t nthr = std::min(std::min((size_t)(opt < 1 ? 1 : opt > 64 ? 64 : opt), count), bytes / (128 * 1024) + 1);
@@ -111,8 +155,9 @@ extern "C" KzgRet kzg_cell_batch_challenges(uint8_t* r_out, const uint8_t* commi
     std::vector<size_t> off(n_batches + 1, 0);
     for (size_t b = 0; b < n_batches; b++) off[b + 1] = off[b] + batch_sizes[b];
     if (off[n_batches] && (!commitments || !cell_indices || !cells || !proofs)) return fail(KZG_BADARGS, "null argument");
+    const CellGroupInArrays arrays(commitments, cell_indices, cells, proofs, batch_sizes, n_batches);
     CellGroupHash h;
-    h.r_be = r_out, h.commitments = commitments, h.cell_indices = cell_indices, h.cells = cells, h.proofs = proofs, h.off = off.data(), h.count = n_batches;
+    h.r_be = r_out, h.in = arrays.in, h.count = n_batches;
     h.start();
     h.finish();
     if (h.failed) return fail(KZG_MALLOC, "host buffers of the call");
@@ -150,66 +195,15 @@ struct CellGroupBufs {
 };
 CellState::~CellState() { delete group; }
 
-// ---------------------------------------------------------------- the entry point
-extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, const uint64_t* cell_indices,
-                                                    const uint8_t* cells, const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches,
-                                                    const KzgSettings* s) try {
-    if (!s || (n_batches && (!ok_out || !batch_sizes))) return fail(KZG_BADARGS, "null argument");
-    KzgRet rc = cells_ready(s);
-    if (rc != KZG_OK) return rc;
-    if (n_batches > CELL_GROUP_MAX_BATCHES) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batches: more than 4096 batches");
-    size_t total = 0;
-    if (!cell_group_sizes(&total, batch_sizes, n_batches)) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batches: more than 2^20 cells");
-    if (total && (!commitments || !cell_indices || !cells || !proofs)) return fail(KZG_BADARGS, "null argument");
-    if (n_batches == 0) return KZG_OK;
-    const auto t_call = std::chrono::steady_clock::now();
-    CellGroupPlan P;
-    cell_group_plan(P, commitments, cell_indices, batch_sizes, n_batches, cell_group_threshold());
-    for (size_t b = 0; b < n_batches; b++)
-        if (P.kind[b] == CELL_GROUP_BAD_INDEX && !err_out) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
-    for (size_t b = 0; b < n_batches; b++) {
-        ok_out[b] = P.kind[b] != CELL_GROUP_BAD_INDEX;  // (an empty batch is true; the others get their verdict below)
-        if (err_out) err_out[b] = P.kind[b] == CELL_GROUP_BAD_INDEX ? 1 : 0;
-    }
-    // the slots' hashes start now and run beside everything up to the first wait on the device
-    std::vector<uint8_t> r_be(32 * (size_t)P.G);
-    CellGroupHash hash;  // (declared after what its helper threads read and write: joined first)
-    hash.r_be = r_be.data(), hash.commitments = commitments, hash.cell_indices = cell_indices, hash.cells = cells, hash.proofs = proofs,
-    hash.off = P.off.data(), hash.plan = &P, hash.count = P.G;
-    if (P.G) hash.start();
-    // batches above T: the single call, one after another (it takes the handle's lock itself); its stage times are added below.
-    // It uses - and may regrow - the stage buffers the group is about to use: each of these calls has drained its stream before
-    // it returns, and the group sizes the buffers for itself only afterwards, under the lock
-    float t_large[8] = {};
-    for (size_t b = 0; b < n_batches; b++) {
-        if (P.kind[b] != CELL_GROUP_LARGE) continue;
-        const size_t e = P.off[b];
-        bool okb = false;
-        rc = kzg_verify_cell_kzg_proof_batch(&okb, commitments + 48 * e, cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, batch_sizes[b], s);
-        if (rc == KZG_BADARGS && err_out) {
-            err_out[b] = 1;
-            okb = false;
-        } else if (rc != KZG_OK) {
-            return rc;
-        }
-        ok_out[b] = okb;
-        for (int i = 1; i < 8; i++) t_large[i] += s->timings[i];
-    }
-    auto finish_timings = [&](double hash_ms, float msm, float pairing, float between, float decode) {
-        s->timings[0] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        s->timings[1] = (float)hash_ms + t_large[1];
-        s->timings[2] = msm + t_large[2];
-        s->timings[3] = pairing + t_large[3];
-        s->timings[4] = between + t_large[4];
-        s->timings[6] = decode + t_large[6];
-        s->timings[5] = s->timings[7] = 0.0f;
-    };
-    if (P.G == 0) {
-        std::lock_guard<std::mutex> lk(s->mu);
-        finish_timings(0.0, 0.f, 0.f, 0.f, 0.f);
-        return KZG_OK;
-    }
-
+// ---------------------------------------------------------------- one group on one handle
+// The GROUP slots of plan P over the batches `in`, on handle s whose lock the caller holds (the entry point below: the handle's own;
+// a leader of the small-call queue: its private lane).  hash: posted by the caller over the same plan, finished here.  ok_out [b]
+// and err_out [b] of the slots' batches are written (err_out null: the first refused slot fails the call, as the single call
+// does); why_out (optional) [b] = the reason of a refused slot.  stage_ms: MSM | pairing | r -> scalars | decode.
+static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why_out, const CellGroupIn& in, const CellGroupPlan& P, CellGroupHash& hash,
+                                const uint8_t* r_be, const KzgSettings* s, float stage_ms[4]) {
+    KzgRet rc = KZG_OK;
+    const size_t* const batch_sizes = in.batch_sizes;
     const uint32_t G = P.G, nG = P.nG, mtot = P.mtot, NP = cell_group_points(nG, mtot), nsc = cell_group_scalars(nG, mtot, G);
     const uint32_t max_terms = P.max_rl;
     const size_t terms = (size_t)2 * G * max_terms;
@@ -219,7 +213,6 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     const size_t h_pflag = up(48 * (size_t)NP), h_bad = h_pflag + up(4 * (size_t)NP), h_r = h_bad + up(4 * (size_t)nG), h_live = h_r + up(32 * (size_t)G),
                  h_out = h_live + up(4 * (size_t)G), h_bytes = h_out + sizeof(Fp) * 6 * G;
 
-    std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     CellState* cs = nullptr;
@@ -234,11 +227,12 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     // 1. decode: the points with their subgroup test and table rows, the cells with their canonical check - none of it needs r
     uint8_t* const hp = g.h_buf.p;
     for (uint32_t sl = 0; sl < G; sl++) {
-        const size_t e = P.off[P.slot_batch[sl]], n = batch_sizes[P.slot_batch[sl]];
-        memcpy(hp + 48 * (size_t)P.idx[P.o_cstart + sl], proofs + 48 * e, 48 * n);
+        const size_t b = P.slot_batch[sl];
+        memcpy(hp + 48 * (size_t)P.idx[P.o_cstart + sl], in.proofs[b], 48 * batch_sizes[b]);
+        for (uint32_t i = P.idx[P.o_ustart + sl]; i < P.idx[P.o_ustart + sl + 1]; i++)
+            memcpy(hp + 48 * ((size_t)nG + i), in.commitments[b] + 48 * ((size_t)P.uniq_entry[i] - P.off[b]), 48);
     }
-    for (uint32_t i = 0; i < mtot; i++) memcpy(hp + 48 * ((size_t)nG + i), commitments + 48 * (size_t)P.uniq_entry[i], 48);
-    memcpy(hp + 48 * ((size_t)nG + mtot), cs->mono, sizeof cs->mono);
+    memcpy(hp + 48 * ((size_t)nG + mtot), cs->t->mono, sizeof cs->t->mono);
     uint8_t* const skip = hp + 48 * (size_t)cell_group_skip_point(nG, mtot);
     memset(skip, 0, 48);
     skip[0] = 0xc0;  // the identity, compressed
@@ -248,7 +242,7 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     HIPCHK(hipGetLastError());
     uint32_t* const f_point = reinterpret_cast<uint32_t*>(hp + h_pflag);
     uint32_t* const f_cell = reinterpret_cast<uint32_t*>(hp + h_bad);
-    if ((rc = cells_decode(s, *cs, P, cells, f_cell)) != KZG_OK) return rc;
+    if ((rc = cells_decode(s, *cs, P, in.cells, f_cell)) != KZG_OK) return rc;
     HIPCHK(hipMemcpyAsync(f_point, g.d_pflag.p, 4 * (size_t)NP, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(s->ev[6], st));
     hash.finish();
@@ -272,9 +266,10 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
         if (why) {
             if (!err_out) return fail(KZG_BADARGS, why);
             err_out[P.slot_batch[sl]] = 1;
+            if (why_out) why_out[P.slot_batch[sl]] = why;
             memset(r_le + 32 * (size_t)sl, 0, 32);
         } else {
-            reverse32(r_le + 32 * (size_t)sl, r_be.data() + 32 * (size_t)sl);
+            reverse32(r_le + 32 * (size_t)sl, r_be + 32 * (size_t)sl);
         }
     }
 
@@ -322,8 +317,8 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     hipLaunchKernelGGL(k_jac_to_slp, dim3(G), dim3(64), 0, st, (const G1Jac*)g.d_ab.p, g.d_slp_in.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[4], st));
-    rc = pairing_latency_form(G) ? run_program2(s->t->verify2, g.d_slp_in.p, cs->d_lines29.p, g.d_slp_out.p, (int)G, st)
-                                 : run_program(s->t->verify, g.d_slp_in.p, cs->d_lines.p, g.d_slp_out.p, (int)G, st);
+    rc = pairing_latency_form(G) ? run_program2(s->t->verify2, g.d_slp_in.p, cs->t->d_lines29.p, g.d_slp_out.p, (int)G, st)
+                                 : run_program(s->t->verify, g.d_slp_in.p, cs->t->d_lines.p, g.d_slp_out.p, (int)G, st);
     if (rc != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[9], st));
     const uint32_t* const out = reinterpret_cast<const uint32_t*>(hp + h_out);
@@ -334,13 +329,279 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
         for (int i = 0; i < 72; i++) any |= out[72 * (size_t)sl + i];
         ok_out[P.slot_batch[sl]] = live[sl] && any == 0;
     }
-    float t_msm = 0.f, t_pair = 0.f, t_between = 0.f, t_decode = 0.f;
-    elapsed(&t_msm, s->ev[2], s->ev[3]);
-    elapsed(&t_pair, s->ev[4], s->ev[9]);
-    elapsed(&t_between, s->ev[7], s->ev[8]);
-    elapsed(&t_decode, s->ev[5], s->ev[6]);
-    finish_timings(hash.ms(), t_msm, t_pair, t_between, t_decode);
+    elapsed(&stage_ms[0], s->ev[2], s->ev[3]);
+    elapsed(&stage_ms[1], s->ev[4], s->ev[9]);
+    elapsed(&stage_ms[2], s->ev[7], s->ev[8]);
+    elapsed(&stage_ms[3], s->ev[5], s->ev[6]);
+    return KZG_OK;
+}
+// kzg_last_timings of a group call: total | hash | MSM | pairing | r -> scalars | - | decode | - (t_large: what the batches above T added)
+static void cell_group_timings(const KzgSettings* s, std::chrono::steady_clock::time_point t_call, double hash_ms, const float stage_ms[4], const float t_large[8]) {
+    s->timings[0] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    s->timings[1] = (float)hash_ms + t_large[1];
+    s->timings[2] = stage_ms[0] + t_large[2];
+    s->timings[3] = stage_ms[1] + t_large[3];
+    s->timings[4] = stage_ms[2] + t_large[4];
+    s->timings[6] = stage_ms[3] + t_large[6];
+    s->timings[5] = s->timings[7] = 0.0f;
+}
+
+// ---------------------------------------------------------------- the entry point
+extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, const uint64_t* cell_indices,
+                                                    const uint8_t* cells, const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches,
+                                                    const KzgSettings* s) try {
+    if (!s || (n_batches && (!ok_out || !batch_sizes))) return fail(KZG_BADARGS, "null argument");
+    KzgRet rc = cells_ready(s);
+    if (rc != KZG_OK) return rc;
+    if (n_batches > CELL_GROUP_MAX_BATCHES) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batches: more than 4096 batches");
+    size_t total = 0;
+    if (!cell_group_sizes(&total, batch_sizes, n_batches)) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batches: more than 2^20 cells");
+    if (total && (!commitments || !cell_indices || !cells || !proofs)) return fail(KZG_BADARGS, "null argument");
+    if (n_batches == 0) return KZG_OK;
+    const auto t_call = std::chrono::steady_clock::now();
+    const CellGroupInArrays arrays(commitments, cell_indices, cells, proofs, batch_sizes, n_batches);
+    CellGroupPlan P;
+    cell_group_plan(P, arrays.in.commitments, arrays.in.cell_indices, batch_sizes, n_batches, cell_group_threshold());
+    for (size_t b = 0; b < n_batches; b++)
+        if (P.kind[b] == CELL_GROUP_BAD_INDEX && !err_out) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
+    for (size_t b = 0; b < n_batches; b++) {
+        ok_out[b] = P.kind[b] != CELL_GROUP_BAD_INDEX;  // (an empty batch is true; the others get their verdict below)
+        if (err_out) err_out[b] = P.kind[b] == CELL_GROUP_BAD_INDEX ? 1 : 0;
+    }
+    // the slots' hashes start now and run beside everything up to the first wait on the device
+    std::vector<uint8_t> r_be(32 * (size_t)P.G);
+    CellGroupHash hash;  // (declared after what its helper threads read and write: joined first)
+    hash.r_be = r_be.data(), hash.in = arrays.in, hash.plan = &P, hash.count = P.G;
+    if (P.G) hash.start();
+    // batches above T: the single call, one after another (it takes the handle's lock itself); its stage times are added below.
+    // It uses - and may regrow - the stage buffers the group is about to use: each of these calls has drained its stream before
+    // it returns, and the group sizes the buffers for itself only afterwards, under the lock
+    float t_large[8] = {};
+    for (size_t b = 0; b < n_batches; b++) {
+        if (P.kind[b] != CELL_GROUP_LARGE) continue;
+        const size_t e = P.off[b];
+        bool okb = false;
+        rc = kzg_verify_cell_kzg_proof_batch(&okb, commitments + 48 * e, cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, batch_sizes[b], s);
+        if (rc == KZG_BADARGS && err_out) {
+            err_out[b] = 1;
+            okb = false;
+        } else if (rc != KZG_OK) {
+            return rc;
+        }
+        ok_out[b] = okb;
+        for (int i = 1; i < 8; i++) t_large[i] += s->timings[i];
+    }
+    float stage_ms[4] = {};
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (P.G && (rc = cell_group_locked(ok_out, err_out, nullptr, arrays.in, P, hash, r_be.data(), s, stage_ms)) != KZG_OK) return rc;
+    cell_group_timings(s, t_call, P.G ? hash.ms() : 0.0, stage_ms, t_large);
     return KZG_OK;
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
+}
+
+// ---------------------------------------------------------------- concurrent single calls: requests of the small-call queue
+// kzg_verify_cell_kzg_proof_batch from many threads on one handle (a PeerDAS node's gossip-validation threads, a column sidecar
+// each): every call of up to T cells is a request of kind CELLS (small_queue.hpp); a leader takes up to 128 of them - 128 x T cells
+// at most - and runs them as the slots of ONE group on its lane.  A slot's verdict and error flag are the single call's on that
+// request alone (a refused slot is masked out of the term tables: cell_group_plan, cell_group_locked), so one caller's BadArgs
+// never touches another's answer.  A launch of one request is cell_batch_locked - the direct path, on the lane.
+
+// what the owner of a queued request does instead of sleeping: its own transcript hash (one chain; the leader collects it)
+static bool small_cell_wait_work(SmallReq& r) {
+    int idle = 0;
+    if (r.r_state.load(std::memory_order_relaxed) != 0) return false;
+    std::vector<uint32_t> ci, uniq;
+    try {
+        ci.resize(r.n);
+        cell_dedup(r.c, r.n, ci.data(), uniq);
+    } catch (const std::bad_alloc&) {
+        return false;  // (the leader will hash it)
+    }
+    if (!r.r_state.compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return false;
+    cell_challenge(r.r_be, r.c, ci.data(), uniq.data(), uniq.size(), r.cell_indices, r.cells, r.p, r.n);
+    r.r_state.store(2, std::memory_order_release);
+    return true;
+}
+static void small_cell_refuse(SmallReq& r, const char* why) {
+    r.err[0] = 1;
+    r.ok[0] = false;
+    snprintf(r.msg, sizeof r.msg, "%s", why);
+}
+// the launch of one leader on lane L (capi_coalesce.hpp small_submit): requests of kind CELLS, m cells in all
+static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m) {
+    (void)m;
+    const KzgSettings* l = L.h;
+    const auto t_call = std::chrono::steady_clock::now();
+    const size_t B = batch.size();
+    if (B == 1) {  // nobody else was waiting: the single call as it was
+        SmallReq& r = *batch[0];
+        CellGroupPlan P;
+        cell_group_plan(P, r.c, r.cell_indices, &r.n, 1, CELL_MAX_CELLS);
+        if (P.kind[0] == CELL_GROUP_BAD_INDEX) {
+            small_cell_refuse(r, "cell index out of range (>= 128)");
+            return KZG_OK;
+        }
+        bool ok = false;
+        const KzgRet rc = cell_batch_locked(&ok, r.c, r.cell_indices, r.cells, r.p, r.n, P, t_call, l);
+        if (rc == KZG_BADARGS) {
+            const std::string why = g_err;
+            small_cell_refuse(r, why.c_str());
+            return KZG_OK;
+        }
+        if (rc != KZG_OK) return rc;
+        r.err[0] = 0;
+        r.ok[0] = ok;
+        return KZG_OK;
+    }
+    std::vector<const uint8_t*> c(B), ce(B), p(B);
+    std::vector<const uint64_t*> ix(B);
+    std::vector<size_t> sizes(B);
+    std::vector<CellKnownR> known(B);
+    std::vector<uint8_t> okerr(2 * B, 0);
+    std::vector<const char*> why(B, nullptr);
+    for (size_t b = 0; b < B; b++) {
+        SmallReq& r = *batch[b];
+        c[b] = r.c, ix[b] = r.cell_indices, ce[b] = r.cells, p[b] = r.p, sizes[b] = r.n;
+        known[b] = CellKnownR{&r.r_state, r.r_be};
+    }
+    const CellGroupIn in{c.data(), ix.data(), ce.data(), p.data(), sizes.data(), B};
+    bool* const ok = reinterpret_cast<bool*>(okerr.data());
+    uint8_t* const err = okerr.data() + B;
+    CellGroupPlan P;
+    cell_group_plan(P, in.commitments, in.cell_indices, in.batch_sizes, B, cell_group_threshold());
+    for (size_t b = 0; b < B; b++) {
+        if (P.kind[b] == CELL_GROUP_LARGE || P.kind[b] == CELL_GROUP_EMPTY) return fail(KZG_ERROR, "small-call queue: a cell request outside the group's range");
+        if (P.kind[b] == CELL_GROUP_BAD_INDEX) err[b] = 1, why[b] = "cell index out of range (>= 128)";
+    }
+    std::vector<uint8_t> r_be(32 * (size_t)P.G);
+    CellGroupHash hash;  // (declared after what its helper threads read and write: joined first)
+    hash.r_be = r_be.data(), hash.in = in, hash.known = known.data(), hash.plan = &P, hash.count = P.G;
+    float stage_ms[4] = {};
+    const float none[8] = {};
+    if (P.G) {
+        hash.start();
+        const KzgRet rc = cell_group_locked(ok, err, why.data(), in, P, hash, r_be.data(), l, stage_ms);
+        if (rc != KZG_OK) return rc;
+    }
+    cell_group_timings(l, t_call, P.G ? hash.ms() : 0.0, stage_ms, none);
+    for (size_t b = 0; b < B; b++) {
+        SmallReq& r = *batch[b];
+        if (err[b]) small_cell_refuse(r, why[b] ? why[b] : "invalid argument");
+        else r.err[0] = 0, r.ok[0] = ok[b];
+    }
+    return KZG_OK;
+}
+// one call as a request: returns when its launch is done
+static KzgRet small_cells(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n,
+                          const KzgSettings* s) {
+    SmallReq r;
+    bool verdict = false;
+    uint8_t err = 0, general = 0;
+    r.kind = SmallReq::CELLS;
+    r.n = n;
+    r.c = commitments;
+    r.cell_indices = cell_indices;
+    r.cells = cells;
+    r.p = proofs;
+    r.ok = &verdict;
+    r.err = &err;
+    r.general = &general;
+    r.wait_work = small_cell_wait_work;
+    const KzgRet rc = small_submit(s, r);
+    if (rc != KZG_OK) return rc;
+    if (err) return fail(KZG_BADARGS, r.msg);
+    *ok = verdict;
+    return KZG_OK;
+}
+
+// diagnostic: launches | requests | cells | the largest launch in requests - of the CELLS kind alone, since the last reset
+extern "C" KzgRet kzg_debug_cell_queue_stats(const KzgSettings* s, uint64_t out[4], int reset) {
+    if (!s || !out) return fail(KZG_BADARGS, "null argument");
+    memset(out, 0, 4 * sizeof(uint64_t));
+    if (!s->small) return KZG_OK;
+    SmallQueue& Q = *s->small;
+    std::lock_guard<SmallSpinLock> lk(Q.mu);
+    out[0] = Q.cell_launches;
+    out[1] = Q.cell_requests;
+    out[2] = Q.cell_items;
+    out[3] = Q.cell_max_requests;
+    if (reset) Q.cell_launches = Q.cell_requests = Q.cell_items = Q.cell_max_requests = 0;
+    return KZG_OK;
+}
+
+// measurement hook, after kzg_debug_concurrent_callers: T host threads inside the library (no interpreter lock, no ctypes) calling
+// kzg_verify_cell_kzg_proof_batch on ONE shared handle for `seconds`.  The calls: n_calls batches, batch after batch in the four
+// arrays, batch i of batch_sizes[i] cells; expect[i]: 0 false | 1 true | 2 Err(BadArgs).  Thread t takes calls t, t + T, ...
+// out: [0] calls completed, [1] elapsed seconds, [2] answers that differ from `expect`, [3] mean latency in ms, [4] the longest.
+extern "C" KzgRet kzg_debug_concurrent_cell_callers(double out[5], size_t threads, double seconds, const uint8_t* commitments, const uint64_t* cell_indices,
+                                                    const uint8_t* cells, const uint8_t* proofs, const size_t* batch_sizes, const uint8_t* expect,
+                                                    size_t n_calls, const KzgSettings* s) try {
+    if (!out || !s || !commitments || !cell_indices || !cells || !proofs || !batch_sizes || !expect || !threads || !n_calls)
+        return fail(KZG_BADARGS, "bad argument");
+    const CellGroupInArrays arrays(commitments, cell_indices, cells, proofs, batch_sizes, n_calls);
+    std::atomic<uint64_t> calls{0}, wrong{0};
+    std::atomic<bool> stop{false};
+    std::mutex go_mu;  // (the threads wait for the start asleep)
+    std::condition_variable go_cv;
+    bool go = false;
+    std::vector<double> lat_sum(threads, 0.0), lat_max(threads, 0.0);
+    auto body = [&](size_t t) {
+        {
+            std::unique_lock<std::mutex> lk(go_mu);
+            go_cv.wait(lk, [&] { return go; });
+        }
+        // (independent callers do not arrive in lock-step: a fixed pseudo-random offset below 2.5 ms per thread)
+        std::this_thread::sleep_for(std::chrono::microseconds((uint32_t)(t * 2654435761u) % 2500u));
+        for (size_t i = t % n_calls; !stop.load(std::memory_order_relaxed); i = (i + threads) % n_calls) {
+            const auto t0 = std::chrono::steady_clock::now();
+            bool ok = false;
+            const KzgRet rc = kzg_verify_cell_kzg_proof_batch(&ok, arrays.c[i], arrays.ix[i], arrays.ce[i], arrays.p[i], batch_sizes[i], s);
+            const int got = rc == KZG_BADARGS ? 2 : rc == KZG_OK ? (ok ? 1 : 0) : 3;
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            lat_sum[t] += ms;
+            lat_max[t] = std::max(lat_max[t], ms);
+            if (got != expect[i]) wrong.fetch_add(1, std::memory_order_relaxed);
+            calls.fetch_add(1, std::memory_order_relaxed);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        pool.reserve(threads);
+        for (size_t t = 0; t < threads; t++) pool.emplace_back(body, t);
+    } catch (...) {  // (no more threads to be had: the ones made leave at once)
+        stop.store(true);
+        {
+            std::lock_guard<std::mutex> lk(go_mu);
+            go = true;
+        }
+        go_cv.notify_all();
+        for (auto& th : pool) th.join();
+        return fail(KZG_ERROR, "kzg_debug_concurrent_cell_callers: could not start the threads");
+    }
+    std::this_thread::sleep_for(std::chrono::milliseconds(20));  // (every thread has reached its wait)
+    {
+        std::lock_guard<std::mutex> lk(go_mu);
+        go = true;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    go_cv.notify_all();
+    std::this_thread::sleep_for(std::chrono::duration<double>(seconds));
+    const uint64_t counted = calls.load();  // (calls completed inside the interval)
+    const double elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    stop.store(true);
+    for (auto& th : pool) th.join();
+    double ls = 0, lm = 0;
+    for (size_t t = 0; t < threads; t++) {
+        ls += lat_sum[t];
+        lm = std::max(lm, lat_max[t]);
+    }
+    out[0] = (double)counted;
+    out[1] = elapsed_s;
+    out[2] = (double)wrong.load();
+    out[3] = calls.load() ? ls / (double)calls.load() : 0.0;
+    out[4] = lm;
+    return KZG_OK;
+} catch (const std::exception& e) {
+    return fail(KZG_ERROR, std::string("kzg_debug_concurrent_cell_callers: ") + e.what());
 }

@@ -27,9 +27,9 @@ static void cell_u64be(uint8_t o[8], uint64_t v) {
 }
 // compute_verify_cell_kzg_proof_batch_challenge: SHA-256("RCKZGCBATCH__V1_" || u64be(4096) || u64be(64) || u64be(m) || u64be(n) ||
 // unique commitments || per cell: u64be(commitment index) || u64be(cell index) || cell || proof), read big-endian, mod r.  ci and uniq:
-// cell_dedup's (cell_group_plan.hpp); uniq[i] indexes `commitments`, which need not start where the batch does
+// cell_dedup's (cell_group_plan.hpp); uniq[i] - uniq_base indexes `commitments`, which need not start where the batch does
 static void cell_challenge(uint8_t r_be[32], const uint8_t* commitments, const uint32_t* ci, const uint32_t* uniq, size_t m,
-                           const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n) {
+                           const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n, size_t uniq_base = 0) {
     hostsha::Stream h;
     uint8_t hdr[48];
     memcpy(hdr, "RCKZGCBATCH__V1_", 16);
@@ -38,7 +38,7 @@ static void cell_challenge(uint8_t r_be[32], const uint8_t* commitments, const u
     cell_u64be(hdr + 32, (uint64_t)m);
     cell_u64be(hdr + 40, (uint64_t)n);
     h.update(hdr, 48);
-    for (size_t i = 0; i < m; i++) h.update(commitments + 48 * (size_t)uniq[i], 48);
+    for (size_t i = 0; i < m; i++) h.update(commitments + 48 * ((size_t)uniq[i] - uniq_base), 48);
     for (size_t k = 0; k < n; k++) {
         uint8_t ix[16];
         cell_u64be(ix, ci[k]);
@@ -89,14 +89,19 @@ struct CellStageBufs {
     }
 };
 struct CellGroupBufs;  // what is kzg_verify_cell_kzg_proof_batches' own (capi_cell_groups.hpp), made by its first call
-struct CellState {
-    CellStageBufs stage;
-    CellGroupBufs* group = nullptr;
-    ~CellState();
+// the set-up: derived once per handle, immutable afterwards - the lanes of the small-call queue read their parent's
+struct CellSetup {
     DevBuf<Fr> d_T;                             // w8192^e, e < 8192, Montgomery
     uint8_t mono[CELL_FE * 48] = {};            // [tau^i]G1, compressed
     DevBuf<Fp> d_lines;                         // prepared lines of g2_points[64] then G2, 8x32 Montgomery (VERIFY)
     DevBuf<uint32_t> d_lines29;                 // the same in the latency program's format (VERIFY2)
+};
+struct CellState {
+    CellStageBufs stage;
+    CellGroupBufs* group = nullptr;
+    ~CellState();
+    CellSetup own;                // empty on a lane
+    const CellSetup* t = &own;    // a lane (KzgSettings::cell_home): its parent's
 };
 static void cells_release(const KzgSettings* s) {
     delete s->cells;
@@ -114,9 +119,17 @@ static KzgRet cells_state(const KzgSettings* s, CellState** out) {
         return KZG_OK;
     }
     std::unique_ptr<CellState> c(new CellState());
+    if (s->cell_home) {  // a lane of the small-call queue: buffers of its own, the set-up of the handle it serves - never derived here
+        const CellState* const home = s->cell_home->cells;
+        if (!home) return fail(KZG_ERROR, "a lane ran a cell launch before its handle's cell set-up was made");
+        c->t = home->t;
+        s->cells = c.release();
+        *out = s->cells;
+        return KZG_OK;
+    }
     StreamDrain drain{s->s1};
-    HIPCHK(c->d_T.alloc(EXT_FE));
-    hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->d_T.p);
+    HIPCHK(c->own.d_T.alloc(EXT_FE));
+    hipLaunchKernelGGL(k_cell_roots, dim3(EXT_FE / 256), dim3(256), 0, s->s1, c->own.d_T.p);
     // [tau^i]G1 = sum_j w_j^i g1_points[j]: the commitments of 64 "blobs" over the Lagrange points, on the prover's MSM path
     ProverBufs* bp = nullptr;
     KzgRet rc = prover_bufs(s, &bp);
@@ -124,23 +137,34 @@ static KzgRet cells_state(const KzgSettings* s, CellState** out) {
     hipLaunchKernelGGL(k_cell_monomial_scalars, dim3(CELL_FE * FE_PER_BLOB / 256), dim3(256), 0, s->s1, (const Fr*)s->t->d_M.p, bp->d_sc.p);
     HIPCHK(hipGetLastError());
     if ((rc = setup_msm(s, *bp, CELL_FE)) != KZG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(c->mono, bp->d_out.p, sizeof c->mono, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipMemcpyAsync(c->own.mono, bp->d_out.p, sizeof c->own.mono, hipMemcpyDeviceToHost, s->s1));
     // the lines of (g2_points[64], G2): the PREP program on two instances, as kzg_pairings_verify runs it per call
     const size_t n_lines = (size_t)2 * s->t->prep.p.n_out;
     DevBuf<Fp> t_q;
     HIPCHK(t_q.alloc(8));
-    HIPCHK(c->d_lines.alloc(n_lines));
-    HIPCHK(c->d_lines29.alloc(16 * n_lines));
+    HIPCHK(c->own.d_lines.alloc(n_lines));
+    HIPCHK(c->own.d_lines29.alloc(16 * n_lines));
     HIPCHK(hipMemcpyAsync(t_q.p, s->t->d_g2.p + 4 * CELL_FE, sizeof(Fp) * 4, hipMemcpyDeviceToDevice, s->s1));
     hipLaunchKernelGGL(k_g2_generator, dim3(1), dim3(64), 0, s->s1, t_q.p + 4);
     HIPCHK(hipGetLastError());
-    if ((rc = run_program(s->t->prep, t_q.p, nullptr, c->d_lines.p, 2, s->s1)) != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s->s1, (const Fp*)c->d_lines.p, c->d_lines29.p, (int)n_lines);
+    if ((rc = run_program(s->t->prep, t_q.p, nullptr, c->own.d_lines.p, 2, s->s1)) != KZG_OK) return rc;
+    hipLaunchKernelGGL(k_fp_to_fp29mem, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s->s1, (const Fp*)c->own.d_lines.p, c->own.d_lines29.p, (int)n_lines);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s->s1));
     s->cells = c.release();
+    s->cells_built.store(true, std::memory_order_release);
     *out = s->cells;
     return KZG_OK;
+}
+// The set-up made before a call is queued: the launch of a leader runs on a lane, which only borrows it.  One atomic load per
+// call once it exists; the first call derives it under the handle's lock, as the direct path does.
+static KzgRet cells_setup_once(const KzgSettings* s) {
+    if (s->cells_built.load(std::memory_order_acquire)) return KZG_OK;
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);
+    CellState* cs = nullptr;
+    return cells_state(s, &cs);
 }
 
 // e(LL, g2_points[64]) == e(RL, G2) on the cached lines: kzg_pairings_verify's VERIFY step without its per-call PREP
@@ -154,8 +178,8 @@ static KzgRet cells_pairing(const KzgSettings* s, const CellState& c, const uint
     hipLaunchKernelGGL(k_aff_to_slp, dim3(1), dim3(64), 0, s->s1, w.d_points.p, w.d_pflag.p, w.d_slp_in.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[3], s->s1));
-    KzgRet rc = pairing_latency_form(1) ? run_program2(s->t->verify2, w.d_slp_in.p, c.d_lines29.p, w.d_slp_out.p, 1, s->s1)
-                                        : run_program(s->t->verify, w.d_slp_in.p, c.d_lines.p, w.d_slp_out.p, 1, s->s1);
+    KzgRet rc = pairing_latency_form(1) ? run_program2(s->t->verify2, w.d_slp_in.p, c.t->d_lines29.p, w.d_slp_out.p, 1, s->s1)
+                                        : run_program(s->t->verify, w.d_slp_in.p, c.t->d_lines.p, w.d_slp_out.p, 1, s->s1);
     if (rc != KZG_OK) return rc;
     HIPCHK(hipEventRecord(s->ev[4], s->s1));
     uint32_t* hf = reinterpret_cast<uint32_t*>(h + 128);  // [g1 flags 2 | out 72]
@@ -172,18 +196,19 @@ static KzgRet cells_pairing(const KzgSettings* s, const CellState& c, const uint
 
 // ---------------------------------------------------------------- the stage both entry points share
 // Before r: the plan's index words and the cells of its slots cross to the device, the cells are decoded with their canonical check
-// and the flags start back to h_bad [nG] (read them after the stream has drained).  `cells`: the caller's array, batch after batch.
-static KzgRet cells_decode(const KzgSettings* s, CellState& cs, const CellGroupPlan& P, const uint8_t* cells, uint32_t* h_bad) {
+// and the flags start back to h_bad [nG] (read them after the stream has drained).  cells[b]: the cells of batch b, where its
+// caller keeps them.
+static KzgRet cells_decode(const KzgSettings* s, CellState& cs, const CellGroupPlan& P, const uint8_t* const* cells, uint32_t* h_bad) {
     CellStageBufs& b = cs.stage;
     hipStream_t st = s->s1;
     const uint32_t* const cstart = P.idx.data() + P.o_cstart;
     HIPCHK(hipMemcpyAsync(b.d_idx.p, P.idx.data(), 4 * P.idx.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(b.d_bad.p, 0, 4 * (size_t)P.nG, st));
-    for (uint32_t sl = 0; sl < P.G;) {  // the cells of consecutive slots that are consecutive batches cross in one copy
+    for (uint32_t sl = 0; sl < P.G;) {  // the cells of consecutive slots that lie one behind the other (one array, batch after batch) cross in one copy
         uint32_t to = sl + 1;
-        while (to < P.G && P.slot_batch[to] == P.slot_batch[to - 1] + 1) to++;
-        const size_t e = P.off[P.slot_batch[sl]], c0 = cstart[sl], c1 = cstart[to];
-        HIPCHK(hipMemcpyAsync(b.d_cells.p + CELL_BYTES * c0, cells + CELL_BYTES * e, CELL_BYTES * (c1 - c0), hipMemcpyHostToDevice, st));
+        while (to < P.G && cells[P.slot_batch[to]] == cells[P.slot_batch[to - 1]] + CELL_BYTES * (size_t)(cstart[to] - cstart[to - 1])) to++;
+        const size_t c0 = cstart[sl], c1 = cstart[to];
+        HIPCHK(hipMemcpyAsync(b.d_cells.p + CELL_BYTES * c0, cells[P.slot_batch[sl]], CELL_BYTES * (c1 - c0), hipMemcpyHostToDevice, st));
         sl = to;
     }
     hipLaunchKernelGGL(k_cell_decode, dim3((unsigned)((CELL_FE * (size_t)P.nG + 255) / 256)), dim3(256), 0, st, (const uint8_t*)b.d_cells.p, b.d_vals.p, b.d_bad.p,
@@ -198,7 +223,7 @@ static KzgRet cells_scalars(const KzgSettings* s, CellState& cs, const CellGroup
     CellStageBufs& b = cs.stage;
     hipStream_t st = s->s1;
     const uint32_t* const ix = b.d_idx.p;
-    const Fr *T = cs.d_T.p, *rM = b.d_rM.p;
+    const Fr *T = cs.t->d_T.p, *rM = b.d_rM.p;
     HIPCHK(hipMemcpyAsync(b.d_r.p, r_le, 32 * (size_t)P.G, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_cell_powers, dim3((P.nG + 255) / 256), dim3(256), 0, st, (const Fr*)b.d_r.p, ix + P.o_cell_slot, ix + P.o_cstart, ix + P.o_cidx, T,
                        b.d_rM.p, b.d_sc.p, (int)P.nG);
@@ -212,24 +237,15 @@ static KzgRet cells_scalars(const KzgSettings* s, CellState& cs, const CellGroup
 }
 
 // ---------------------------------------------------------------- entry points
-extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
-                                                  const uint8_t* proofs, size_t n, const KzgSettings* s) try {
-    if (!ok || !s || (n && (!commitments || !cell_indices || !cells || !proofs))) return fail(KZG_BADARGS, "null argument");
-    KzgRet rc = cells_ready(s);
-    if (rc != KZG_OK) return rc;
-    if (n > CELL_MAX_CELLS) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batch: more than 2^20 cells");
-    if (n == 0) {
-        *ok = true;
-        return KZG_OK;
-    }
-    const auto t_call = std::chrono::steady_clock::now();
-    // r-independent host work: the plan of a group of this one batch.  No batch is above the threshold, so it is slot 0 of G = 1
-    CellGroupPlan P;
-    cell_group_plan(P, commitments, cell_indices, &n, 1, CELL_MAX_CELLS);
-    if (P.kind[0] == CELL_GROUP_BAD_INDEX) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
+static size_t cell_group_threshold();  // (capi_cell_groups.hpp, as is small_cells: the call as a request of the small-call queue)
+static KzgRet small_cells(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n,
+                          const KzgSettings* s);
+// One batch on handle s, whose lock the caller holds (a lane of the small-call queue is private to its leader): P = its plan as a
+// group of one slot, checked for cell indices >= 128.  May throw std::bad_alloc.
+static KzgRet cell_batch_locked(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n,
+                                const CellGroupPlan& P, std::chrono::steady_clock::time_point t_call, const KzgSettings* s) {
     const size_t m = P.mtot, N = n + m + CELL_FE;
-
-    std::lock_guard<std::mutex> lk(s->mu);
+    KzgRet rc = KZG_OK;
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     CellState* cs = nullptr;
@@ -263,14 +279,14 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     uint8_t* hp = w.h_buf.p;  // pinned, at least 128 N bytes (ws_reserve)
     memcpy(hp, proofs, 48 * n);
     for (size_t i = 0; i < m; i++) memcpy(hp + 48 * (n + i), commitments + 48 * (size_t)P.uniq_entry[i], 48);
-    memcpy(hp + 48 * (n + m), cs->mono, sizeof cs->mono);
+    memcpy(hp + 48 * (n + m), cs->t->mono, sizeof cs->t->mono);
     HIPCHK(hipEventRecord(s->ev[5], s->s1));
     HIPCHK(hipMemcpyAsync(w.d_bytes.p, hp, 48 * N, hipMemcpyHostToDevice, s->s1));
     const bool aff = msm_affine_enabled();
     g1_decode_tables(w.d_bytes.p, N, w.d_points.p, w.d_pflag.p, w.d_mult.p, w.d_jtmp.p, (int)N, aff, s->s1);
     HIPCHK(hipGetLastError());
     // the cells -> plain limbs with their canonical flags, and the index words
-    if ((rc = cells_decode(s, *cs, P, cells, h_bad.data())) != KZG_OK) return rc;
+    if ((rc = cells_decode(s, *cs, P, &cells, h_bad.data())) != KZG_OK) return rc;
     HIPCHK(hipMemcpyAsync(h_pflag.data(), w.d_pflag.p, 4 * N, hipMemcpyDeviceToHost, s->s1));
     HIPCHK(hipEventRecord(s->ev[6], s->s1));
     if (hasher.joinable()) hasher.join();
@@ -304,6 +320,33 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     s->timings[1] = (float)hash_ms;
     s->timings[5] = s->timings[7] = 0.0f;
     return KZG_OK;
+}
+
+extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                                                  const uint8_t* proofs, size_t n, const KzgSettings* s) try {
+    if (!ok || !s || (n && (!commitments || !cell_indices || !cells || !proofs))) return fail(KZG_BADARGS, "null argument");
+    KzgRet rc = cells_ready(s);
+    if (rc != KZG_OK) return rc;
+    if (n > CELL_MAX_CELLS) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batch: more than 2^20 cells");
+    if (n == 0) {
+        *ok = true;
+        return KZG_OK;
+    }
+    const auto t_call = std::chrono::steady_clock::now();
+    // Concurrent callers of one handle: a call of up to T cells becomes a request of the handle's small-call queue and rides -
+    // with whatever else is waiting - as a slot of one group launch on a private lane (capi_coalesce.hpp; small_cells,
+    // capi_cell_groups.hpp).  A lone caller's launch of one is the path below, on the lane.  Larger calls, and every call with
+    // option cell_coalesce=0, take the handle's own lock.
+    if (small_enabled(s) && s->small->cells_on && n <= cell_group_threshold()) {
+        if ((rc = cells_setup_once(s)) != KZG_OK) return rc;
+        return small_cells(ok, commitments, cell_indices, cells, proofs, n, s);
+    }
+    // r-independent host work: the plan of a group of this one batch.  No batch is above the threshold, so it is slot 0 of G = 1
+    CellGroupPlan P;
+    cell_group_plan(P, commitments, cell_indices, &n, 1, CELL_MAX_CELLS);
+    if (P.kind[0] == CELL_GROUP_BAD_INDEX) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
+    std::lock_guard<std::mutex> lk(s->mu);
+    return cell_batch_locked(ok, commitments, cell_indices, cells, proofs, n, P, t_call, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
 }
@@ -318,6 +361,6 @@ extern "C" KzgRet kzg_settings_g1_monomial_point(const KzgSettings* s, size_t i,
     select_streams(s, (size_t)-1);
     CellState* cs = nullptr;
     if ((rc = cells_state(s, &cs)) != KZG_OK) return rc;
-    memcpy(out, cs->mono + 48 * i, 48);
+    memcpy(out, cs->t->mono + 48 * i, 48);
     return KZG_OK;
 }

@@ -23,7 +23,11 @@
 //     keep arriving, 250 us at most: small_submit) - a closed loop of T callers then travels as ONE launch of T, and its rate
 //     is T / (the launch's 1.7-2 ms + the turn-around) instead of a stream of fragments that each wait for a lane;
 //   * a waiting blob caller hashes its own blobs meanwhile (host_only.hpp hostpool), so the host-side SHA-256 of T callers runs
-//     on T cores and the leader only collects the challenges.
+//     on T cores and the leader only collects the challenges;
+//   * a third kind of request is one kzg_verify_cell_kzg_proof_batch call of up to T = 256 cells: a launch carries up to 128
+//     of them (128 x T cells at most) as the slots of one cell group (capi_cell_groups.hpp small_run_cells), each with its own
+//     transcript - hashed by its owner while it waits - and its own pairing instance.  A multi-device handle has the cell
+//     set-up on its first device only, so these launches keep to that device's lanes (SmallQueue::cell_lane_stride).
 // Results are per request: a wrong proof, a non-canonical scalar, an undecodable or off-subgroup point in one caller's input
 // never changes another caller's answer (the instances share a launch, not a random linear combination).
 // z = tau (the pairing's G2 point is the identity: only for who knows the setup's secret, i.e. test rigs) is flagged per item;
@@ -149,12 +153,16 @@ static KzgRet small_lane_make(SmallLane& L, const SmallQueue& Q, const KzgSettin
     KzgRet rc = settings_lane(&L.h, home, Q.lane_priority);
     if (rc != KZG_OK) return rc;
     L.h->proof_two_streams = Q.lane_two_streams;
+    L.h->cell_home = home;  // cell launches: the lane's own stage and group buffers (grow-only, made by its first cell launch, freed
+                            // with it), the handle's set-up (capi_cells.hpp cells_state)
     ProofStreams ps{};
     ProofsLaunch pl{};
     if ((rc = proofs_reserve(ps, pl, SMALL_MAX_TUPLES, STAGE_CP, L.h)) != KZG_OK) return rc;
     if ((rc = ws_reserve(L.h, SMALL_MAX_TUPLES, 1, STAGE_NONE)) != KZG_OK) return rc;
     return ws_reserve(L.h, SMALL_MAX_BLOBS, 1, STAGE_BLOBS);
 }
+
+static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m);  // (capi_cell_groups.hpp)
 
 // Submit a request and return when it is done (small_queue.hpp small_submit_core); the launch a leader runs on its lane:
 static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
@@ -183,7 +191,7 @@ static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
         }
         if (rc == KZG_OK) {
             try {
-                rc = kind == SmallReq::PROOFS ? small_run_proofs(L, batch, m) : small_run_blobs(L, batch, m);
+                rc = kind == SmallReq::PROOFS ? small_run_proofs(L, batch, m) : kind == SmallReq::BLOBS ? small_run_blobs(L, batch, m) : small_run_cells(L, batch, m);
                 if (rc != KZG_OK) msg = g_err;
             } catch (const std::bad_alloc&) {
                 rc = KZG_MALLOC;

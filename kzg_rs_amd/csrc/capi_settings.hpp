@@ -124,6 +124,8 @@ struct KzgSettings {
     mutable uint64_t tcount = 0;
     mutable struct ProverBufs* prover = nullptr;  // the prover-side entry points' buffers, made by the first of those calls (capi_prover.hpp)
     mutable struct CellState* cells = nullptr;    // the cell-proof entry points' tables and buffers, made by the first of those calls (capi_cells.hpp)
+    mutable std::atomic<bool> cells_built{false};  // ... its set-up is derived (read without the lock by a call about to be queued: cells_setup_once)
+    const KzgSettings* cell_home = nullptr;       // a lane of the small-call queue: the handle whose cell set-up it reads (its CellState holds buffers alone)
     mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
     mutable struct CellRecoverState* cell_recover = nullptr;  // cell recovery's own buffers, made by its first call (capi_cell_recover.hpp)
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
@@ -262,6 +264,11 @@ static KzgRet settings_common(KzgSettings** out, const uint8_t tau_g2[96]) {
         s->small->linger_us = std::max(0L, std::min(2000L, opt_int("small_linger_us", 250)));
         s->small->linger_gap_us = std::max(1L, std::min(1000L, ab_int("small_linger_gap_us", 40)));
         s->small->cap_proofs = (size_t)std::max(1L, std::min(1024L, ab_int("small_cap_proofs", 1024)));  // (A/B: fewer tuples per launch; a request larger than the cap would never leave)
+        // concurrent kzg_verify_cell_kzg_proof_batch calls (option cell_coalesce=0: every call under the handle's own lock, as
+        // before); a launch carries up to 128 calls and 128 x T cells, the largest shape measured (profiles/cell_shared_stage_probes.txt)
+        s->small->cells_on = opt_flag("cell_coalesce", true);
+        s->small->cap_cell_requests = (size_t)std::max(1L, std::min(128L, ab_int("small_cap_cell_requests", 128)));
+        s->small->cap_cells = (size_t)std::max(1L, std::min(128L * (long)CELL_GROUP_MAX_CELLS, ab_int("small_cap_cells", 128L * (long)CELL_GROUP_MAX_CELLS)));
     }
     *out = s;
     return KZG_OK;

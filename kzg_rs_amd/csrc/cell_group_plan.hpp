@@ -98,8 +98,10 @@ struct CellGroupPlan {
     size_t o_cstart = 0, o_ustart = 0, o_colstart = 0, o_cell_slot = 0, o_cidx = 0, o_order = 0, o_col_start = 0, o_col_id = 0, o_wlist = 0, o_wstart = 0;
 };
 
-inline void cell_group_plan(CellGroupPlan& P, const uint8_t* commitments, const uint64_t* cell_indices, const size_t* batch_sizes, size_t n_batches,
-                            size_t threshold) {
+// The batches given one by one: commitments[b] / cell_indices[b] = the batch_sizes[b] entries of batch b, wherever they lie (the
+// requests of concurrent callers, capi_coalesce.hpp).  "Entry" e of the plan = off[b] + k, cell k of batch b, as if the arrays were one.
+inline void cell_group_plan(CellGroupPlan& P, const uint8_t* const* commitments, const uint64_t* const* cell_indices, const size_t* batch_sizes,
+                            size_t n_batches, size_t threshold) {
     P = CellGroupPlan();
     P.kind.assign(n_batches, CELL_GROUP_EMPTY);
     P.off.assign(n_batches + 1, 0);
@@ -108,7 +110,7 @@ inline void cell_group_plan(CellGroupPlan& P, const uint8_t* commitments, const 
         const size_t n = batch_sizes[b];
         if (n == 0) continue;
         bool bad = false;
-        for (size_t k = 0; k < n && !bad; k++) bad = cell_indices[P.off[b] + k] >= (uint64_t)CELL_GROUP_COLUMNS;
+        for (size_t k = 0; k < n && !bad; k++) bad = cell_indices[b][k] >= (uint64_t)CELL_GROUP_COLUMNS;
         P.kind[b] = bad ? CELL_GROUP_BAD_INDEX : n > threshold ? CELL_GROUP_LARGE : CELL_GROUP_GROUP;
         if (P.kind[b] == CELL_GROUP_GROUP) {
             P.slot_batch.push_back((uint32_t)b);
@@ -122,10 +124,10 @@ inline void cell_group_plan(CellGroupPlan& P, const uint8_t* commitments, const 
     P.ci.resize(nG);
     const std::vector<uint32_t>& ci = P.ci;
     for (uint32_t g = 0; g < G; g++) {
-        const size_t e0 = P.off[P.slot_batch[g]], n = batch_sizes[P.slot_batch[g]];
-        cell_dedup(commitments + 48 * e0, n, P.ci.data() + cstart[g], P.uniq_entry, e0);
+        const size_t b = P.slot_batch[g], e0 = P.off[b], n = batch_sizes[b];
+        cell_dedup(commitments[b], n, P.ci.data() + cstart[g], P.uniq_entry, e0);
         bool touched[CELL_GROUP_COLUMNS] = {};
-        for (size_t k = 0; k < n; k++) touched[cell_indices[e0 + k]] = true;
+        for (size_t k = 0; k < n; k++) touched[cell_indices[b][k]] = true;
         for (uint32_t c = 0; c < CELL_GROUP_COLUMNS; c++)
             if (touched[c]) col_id.push_back(c);
         cstart[g + 1] = cstart[g] + (uint32_t)n;
@@ -152,11 +154,11 @@ inline void cell_group_plan(CellGroupPlan& P, const uint8_t* commitments, const 
     for (uint32_t u = 0; u < Utot; u++) w[P.o_col_id + u] = col_id[u];
     // second pass: the two counting sorts of every slot
     for (uint32_t g = 0; g < G; g++) {
-        const size_t e0 = P.off[P.slot_batch[g]];
+        const uint64_t* const cix = cell_indices[P.slot_batch[g]];
         const uint32_t c0 = cstart[g], n = cstart[g + 1] - c0, u0 = ustart[g], m = ustart[g + 1] - u0, k0 = colstart[g], U = colstart[g + 1] - k0;
         uint32_t cnt[CELL_GROUP_COLUMNS + 1] = {};
         for (uint32_t k = 0; k < n; k++) {
-            const uint32_t c = (uint32_t)cell_indices[e0 + k];
+            const uint32_t c = (uint32_t)cix[k];
             w[P.o_cell_slot + c0 + k] = g;
             w[P.o_cidx + c0 + k] = c;
             cnt[c + 1]++;
@@ -172,6 +174,19 @@ inline void cell_group_plan(CellGroupPlan& P, const uint8_t* commitments, const 
     }
     w[P.o_col_start + Utot] = nG;
     w[P.o_wstart + mtot] = nG;
+}
+// ... and given as one array each, batch after batch (kzg_verify_cell_kzg_proof_batches' arguments)
+inline void cell_group_plan(CellGroupPlan& P, const uint8_t* commitments, const uint64_t* cell_indices, const size_t* batch_sizes, size_t n_batches,
+                            size_t threshold) {
+    std::vector<const uint8_t*> c(n_batches);
+    std::vector<const uint64_t*> ix(n_batches);
+    size_t off = 0;
+    for (size_t b = 0; b < n_batches; b++) {
+        c[b] = commitments + 48 * off;
+        ix[b] = cell_indices + off;
+        off += batch_sizes[b];
+    }
+    cell_group_plan(P, c.data(), ix.data(), batch_sizes, n_batches, threshold);
 }
 
 }  // namespace kzg

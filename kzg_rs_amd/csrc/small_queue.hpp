@@ -1,7 +1,8 @@
 // small_queue.hpp - the small-call queue of a settings handle: requests, lanes, waiting and waking, and the submit loop with the
 // launch itself left to the caller (capi_coalesce.hpp supplies the GPU launch).  Plain C++17 + Linux futexes, no HIP: part of the
 // translation unit kzg_capi.hip, and compiled on its own with g++ -fsanitize=thread by tests/test_small_queue_host.py
-// (tests/host/small_queue_main.cpp: hundreds of threads, a stand-in launch, every result checked, no lost wake-up, no race).
+// (tests/host/small_queue_main.cpp: hundreds of threads, a stand-in launch, every result checked, no lost wake-up, no race) and by
+// tests/test_small_queue_cells_host.py (tests/host/small_queue_cells_main.cpp: the same with the third request kind among them).
 #pragma once
 #include <linux/futex.h>
 #include <stdint.h>
@@ -24,15 +25,26 @@
 
 // One request = the small call of one host thread: n (commitment, z, y, proof) tuples, or n host blobs with their commitments
 // and proofs; every item gets its own pairing and the request gets its own results - what the entry point makes of them
-// (one verdict, a conjunction, a verdict per item) is the submitter's business.
+// (one verdict, a conjunction, a verdict per item) is the submitter's business.  The third kind is one call of the cell-proof
+// verifier: n cells with their commitments, cell indices and proofs, ONE verdict - the requests of a launch ride as the slots of a
+// group launch (capi_cell_groups.hpp), each with its own batch challenge.
 struct SmallReq {
-    enum Kind { PROOFS = 0, BLOBS = 1 };
+    enum Kind { PROOFS = 0, BLOBS = 1, CELLS = 2 };
     Kind kind = PROOFS;
     size_t n = 0;
     const uint8_t *c = nullptr, *p = nullptr;  // n x 48 bytes each
     const uint8_t *z = nullptr, *y = nullptr;  // PROOFS: n x 32 big-endian bytes each
     const uint8_t* blobs = nullptr;            // BLOBS: n x 131072 bytes
     hostpool::JobRef hash;                     // BLOBS: the challenges (the submitter's buffer behind hash->z_le), claimed blob by blob by whoever has time
+    // CELLS: c, p as above (a commitment and a proof per cell), n cell indices, n x 2048 bytes of cells; ok[0] / err[0] the call's
+    // verdict and its Err(BadArgs) (the reason in msg), general unused
+    const uint64_t* cell_indices = nullptr;
+    const uint8_t* cells = nullptr;
+    // ... and the call's batch challenge r, big-endian: whoever moves r_state from 0 to 1 computes it and then stores 2 - the
+    // owner while it waits (wait_work), or the leader of the launch for the requests whose owners have not come to it
+    uint8_t r_be[32] = {0};
+    std::atomic<int> r_state{0};
+    bool (*wait_work)(SmallReq&) = nullptr;  // what the owner can do instead of sleeping; false: nothing (left) to do
     // results.  PROOFS: per item.  BLOBS: [0] only - the conjunction over the request's blobs, any parse failure among them, any z = tau
     bool* ok = nullptr;
     uint8_t *err = nullptr, *general = nullptr;
@@ -89,7 +101,18 @@ struct SmallQueue {
     size_t last_done_items = 0;
     uint64_t launches = 0, requests = 0, items = 0, max_items = 0;  // since the last kzg_debug_small_queue_stats(reset)
     size_t cap_proofs = 1024, cap_blobs = 256;  // items per launch
+    // CELLS: two limits per launch - requests (the slots of a group launch) and cells in all - and counters of their own beside the
+    // queue's totals above (kzg_debug_cell_queue_stats): launches | requests | cells | the largest launch in requests
+    size_t cap_cell_requests = 128, cap_cells = (size_t)128 * 256;
+    bool cells_on = true;  // option cell_coalesce (read when the handle is made)
+    uint64_t cell_launches = 0, cell_requests = 0, cell_items = 0, cell_max_requests = 0;
+    // the lanes that may carry CELLS: lane i with i % cell_lane_stride == 0 (a multi-device handle deals its lanes to its devices
+    // in turn and has the cell set-up on the first one only; 1: every lane)
+    size_t cell_lane_stride = 1;
 };
+static bool small_lane_carries(const SmallQueue& Q, int li, SmallReq::Kind kind) {
+    return kind != SmallReq::CELLS || (size_t)li % Q.cell_lane_stride == 0;
+}
 
 
 // Waiting and waking.  Waiters sleep on 32-bit futex words - the queue's while their request is still in the queue, their
@@ -139,6 +162,30 @@ static int small_take_lane(SmallQueue& Q) {
     return -1;
 }
 
+// The CELLS requests of a launch on lane li, under the queue's lock: oldest first while requests <= cap_cell_requests and cells <=
+// cap_cells (`batch` has room for the whole queue: nothing here allocates).  The first one leaves whatever its size - a request
+// beyond cap_cells on its own (an A/B capacity below the routing threshold) travels alone.  Returns the cells taken.
+static size_t small_take_cells(SmallQueue& Q, int li, std::vector<SmallReq*>& batch) {
+    size_t m = 0;
+    for (auto it = Q.q.begin(); it != Q.q.end();) {
+        SmallReq* x = *it;
+        if (x->kind != SmallReq::CELLS) {
+            ++it;
+            continue;
+        }
+        if (!batch.empty() && (batch.size() >= Q.cap_cell_requests || m + x->n > Q.cap_cells)) break;
+        x->lane.store(li, std::memory_order_release);
+        x->taken.store(true, std::memory_order_relaxed);
+        m += x->n;
+        batch.push_back(x);
+        it = Q.q.erase(it);
+    }
+    Q.cell_launches++;
+    Q.cell_items += m;
+    Q.cell_max_requests = std::max<uint64_t>(Q.cell_max_requests, batch.size());
+    return m;
+}
+
 // (tests/host/small_queue_main.cpp defines this to stall a caller between its read of r.lane and its read of the word it will
 // sleep on - the window in which a leader can take the request)
 #ifndef SMALL_QUEUE_TEST_HOOK_BETWEEN_LOADS
@@ -176,6 +223,7 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
             if (!queued) {
                 Q.q.push_back(&r);
                 Q.requests++;
+                if (r.kind == SmallReq::CELLS) Q.cell_requests++;
                 queued = true;
                 Q.arrivals.fetch_add(1, std::memory_order_relaxed);
             }
@@ -184,7 +232,8 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
         }
         if (li < 0) {
             if (r.hash && r.hash->unclaimed()) hostpool::help(*r.hash);  // nothing to lead: hash the own blobs instead of sleeping
-            else small_sleep(word, seen);
+            else if (r.wait_work && r.wait_work(r)) {  // (CELLS: the own transcript)
+            } else small_sleep(word, seen);
             continue;
         }
         // ---- leader (holds the lock and lane li)
@@ -235,17 +284,37 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
                 continue;  // (another leader carries our request: wait for it)
             }
             kind = Q.q.front()->kind;
-            const size_t cap = kind == SmallReq::PROOFS ? Q.cap_proofs : Q.cap_blobs;
-            for (auto it = Q.q.begin(); it != Q.q.end();) {
-                SmallReq* x = *it;
-                if (x->kind == kind && m + x->n <= cap) {
-                    x->lane.store(li, std::memory_order_release);
-                    x->taken.store(true, std::memory_order_relaxed);
-                    m += x->n;
-                    batch.push_back(x);
-                    it = Q.q.erase(it);
-                    if (m == cap) break;
-                } else ++it;
+            if (!small_lane_carries(Q, li, kind)) {  // (a lane that cannot carry the oldest request's kind takes the oldest it can)
+                bool found = false;
+                for (SmallReq* x : Q.q)
+                    if (small_lane_carries(Q, li, x->kind)) {
+                        kind = x->kind;
+                        found = true;
+                        break;
+                    }
+                if (!found) {  // nothing for this lane: it goes back, and this caller waits like a follower - the lane that can
+                               // carry what is queued is busy (lanes are taken in index order) and wakes a caller when it is done
+                    L.busy = false;
+                    lk.unlock();
+                    small_sleep(word, seen);
+                    continue;
+                }
+            }
+            if (kind == SmallReq::CELLS) {
+                m = small_take_cells(Q, li, batch);
+            } else {
+                const size_t cap = kind == SmallReq::PROOFS ? Q.cap_proofs : Q.cap_blobs;
+                for (auto it = Q.q.begin(); it != Q.q.end();) {
+                    SmallReq* x = *it;
+                    if (x->kind == kind && m + x->n <= cap) {
+                        x->lane.store(li, std::memory_order_release);
+                        x->taken.store(true, std::memory_order_relaxed);
+                        m += x->n;
+                        batch.push_back(x);
+                        it = Q.q.erase(it);
+                        if (m == cap) break;
+                    } else ++it;
+                }
             }
         }
         if (batch.empty()) {  // (everything left while this thread lingered)
