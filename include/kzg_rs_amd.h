@@ -326,6 +326,28 @@ KzgRet kzg_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out,
  * before the proof chain is started.  The buffers (another ~85 MB for 64 blobs) stay on the handle. */
 KzgRet kzg_recover_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint64_t *cell_indices,
                                         const uint8_t *cells, size_t num_cells, size_t n, const KzgSettings *s);
+/* The same recovery for a caller that also holds the KZG proof of every given cell - a data column sidecar carries both - and has
+ * ALREADY VERIFIED those pairs.  cell_indices, cells, num_cells, n and cells_out: exactly as above (cells_out may be NULL).  proofs:
+ * n * num_cells * 48 bytes (host), proof k of blob b belongs to cell cell_indices[b * num_cells + k].  proofs_out (required): all 128
+ * proofs per blob; the given ones come out byte for byte as they went in, the missing ones are interpolated from the FIRST 64 given
+ * proofs of that blob, in list order; with num_cells == 128 nothing is interpolated.  A blob's 128 proofs are the values of a
+ * G1-valued polynomial of degree < 64 at the 128th roots of unity, so 64 of them determine the others: at most 64
+ * sums of 64 terms per blob over 64 points, against FK20's 128 fixed-base and 128 variable-base sums.  The FK20 table is neither
+ * built nor read.
+ * THE CALL TAKES NO COMMITMENT AND DOES NOT VERIFY THE GIVEN PROOFS.  Where every given (cell, proof) pair is one that
+ * kzg_verify_cell_kzg_proof_batch accepts for the blob's commitment, all outputs equal kzg_recover_cells_and_kzg_proofs' byte for
+ * byte.  With wrong but well-formed proofs the call returns KZG_OK and the missing proofs are the deterministic interpolation of what
+ * was given (the cells are unaffected): a caller that cannot vouch for the proofs verifies them first, or uses the call above.
+ * Errors: everything the call above refuses, with the same code, after the same host-side index checks and before anything is
+ * copied; KZG_BADARGS also for NULL proofs or proofs_out and for a given proof that is not a G1 point (decoded and subgroup-tested as
+ * kzg_g1_msm decodes its points; the identity 0xC0 00 .. 00 is allowed).  The verdict on cells and points is read before the sums are
+ * queued; n == 0 is KZG_OK; after an error the handle stays usable.  The handle's lock is taken; a multi-device handle runs the call
+ * on its first device; blobs are processed 64 per launch; two runs give the same bytes.  The time of the call
+ * (tools/prof/cell_recover_proofs_probe.py: 1, 6 and 64 blobs from 64 cells and proofs, beside the call above in the same run) is
+ * not yet measured on an MI355X. */
+KzgRet kzg_recover_cells_and_kzg_proofs_given_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint64_t *cell_indices,
+                                                     const uint8_t *cells, const uint8_t *proofs, size_t num_cells, size_t n,
+                                                     const KzgSettings *s);
 
 /* EIP-7594 cell proofs (not in the reference: c-kzg-4844's verify_cell_kzg_proof_batch, the consensus spec's
  * verify_cell_kzg_proof_batch_impl).  Cell k of the batch is (commitment k, cell index k, 64 big-endian field elements - the

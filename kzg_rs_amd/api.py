@@ -130,6 +130,7 @@ def lib():
         L.kzg_compute_cells.argtypes = [u8, u8, sz, vp]
         L.kzg_compute_cells_and_kzg_proofs.argtypes = [u8, u8, u8, sz, vp]
         L.kzg_recover_cells_and_kzg_proofs.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, sz, sz, vp]
+        L.kzg_recover_cells_and_kzg_proofs_given_proofs.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz, sz, vp]
         L.kzg_cell_batch_challenge.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz]
         L.kzg_verify_cell_kzg_proof_batches.argtypes = [bp, u8, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(C.c_size_t), sz, vp]
         L.kzg_cell_batch_challenges.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(C.c_size_t), sz]
@@ -823,6 +824,42 @@ def recover_cells_and_kzg_proofs(cell_indices, cells, kzg_settings):
     proofs = [[raw[48 * (CELLS_PER_EXT_BLOB * b + c): 48 * (CELLS_PER_EXT_BLOB * b + c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
               for b in range(n)]
     return _cells_of(out, n), proofs
+
+
+def recover_cells_and_kzg_proofs_given_proofs(cell_indices, cells, proofs, kzg_settings):
+    """recover_cells_and_kzg_proofs for a caller that also holds the KZG proof of every given cell and has verified those pairs:
+    proofs[b][k] (Bytes48 or bytes) belongs to cells[b][k].  The missing proofs are interpolated from the first 64 given ones of
+    the blob instead of being recomputed by FK20; the given ones come back as passed.  -> (cells, proofs), all 128 of each, per
+    blob.  The proofs are NOT checked against the cells (include/kzg_rs_amd.h): wrong but well-formed proofs give wrong missing
+    proofs and no error - verify first, or use recover_cells_and_kzg_proofs.  Length errors as there, and for proofs that differ
+    in number from the cells or are not 48 bytes long; a proof that is not a G1 point raises BadArgs."""
+    if len(cell_indices) != len(cells) or len(proofs) != len(cells):
+        raise InvalidBytesLength("cell_indices, cells and proofs differ in length: %d, %d and %d blobs" % (len(cell_indices), len(cells), len(proofs)))
+    n = len(cells)
+    data = [[c.data if isinstance(c, Cell) else bytes(c) for c in per] for per in cells]
+    given = [[p.data if isinstance(p, Bytes48) else bytes(p) for p in per] for per in proofs]
+    per = len(data[0]) if n else 0
+    for idx, cs, ps in zip(cell_indices, data, given):
+        if len(idx) != len(cs) or len(ps) != len(cs) or len(cs) != per:
+            raise InvalidBytesLength("every blob needs as many cell indices and proofs as cells, and the same number as the other blobs")
+        for c in cs:
+            if len(c) != BYTES_PER_CELL:
+                raise InvalidBytesLength("Invalid cell length: %d bytes, expected %d" % (len(c), BYTES_PER_CELL))
+        for p in ps:
+            if len(p) != 48:
+                raise InvalidBytesLength("Invalid proof length: %d bytes, expected 48" % len(p))
+    flat = [int(c) for idx in cell_indices for c in idx]
+    if any(not 0 <= c < 1 << 64 for c in flat):
+        raise KzgError("BadArgs", "cell index out of range")
+    out = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * max(n, 1))
+    pr = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(n, 1))
+    idx = (C.c_uint64 * max(len(flat), 1))(*flat)
+    _chk(lib().kzg_recover_cells_and_kzg_proofs_given_proofs(out, pr, idx, b"".join(c for cs in data for c in cs), b"".join(p for ps in given for p in ps), per, n,
+                                                             kzg_settings._h))
+    raw = pr.raw
+    all_proofs = [[raw[48 * (CELLS_PER_EXT_BLOB * b + c): 48 * (CELLS_PER_EXT_BLOB * b + c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
+                  for b in range(n)]
+    return _cells_of(out, n), all_proofs
 
 
 def g1_mul_generator(scalars, kzg_settings):

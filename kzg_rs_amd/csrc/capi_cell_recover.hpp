@@ -11,6 +11,16 @@
 //   proofs   the cell prover's chain, unchanged, on d_coef: k_fk20_tvec_dft -> ... -> k_fk20_compress
 // The coefficients and the proof chain's buffers are the cell prover's (CellProverState::reserve); what only recovery needs lives
 // in CellRecoverState beside it.  A call without proofs_out touches neither the FK20 table nor the chain.
+//
+// kzg_recover_cells_and_kzg_proofs_given_proofs is the same call up to the verdict; its proofs are not the chain's but the Lagrange
+// interpolation of the first 64 given proofs of each blob (recover_lagrange.hpp), and it never touches the FK20 table:
+//   copy     the given proofs, the first 64 of every blob in front (two strided copies), the others behind them
+//   decode   the shared decode pass (decompression, curve and subgroup test) over all of them, k_g1_ntt_load: the first 64 of a
+//            blob into d_H, where k_fk20_rows reads its input
+//   verdict  the cells' status words AND the proofs' flags are read before the sums are queued
+//   proofs   k_recover_proof_weights -> d_sc, k_fk20_rows over 64 points per blob, k_fk20_msm<Fk20Lagrange> on the grid
+//            (128 - num_cells, blobs) into d_P (zeroed: the identity pads a blob to 128), k_fk20_compress; the host places given
+//            and computed proofs into proofs_out
 
 struct CellRecoverState {
     size_t cap = 0;  // blobs
@@ -30,14 +40,31 @@ struct CellRecoverState {
         cap = m;
         return KZG_OK;
     }
+    // what the call with given proofs adds: their bytes and their decoded form (the decode pass's tables: MSM_CHUNKS rows of np points)
+    size_t cap_given = 0;  // proofs
+    DevBuf<uint8_t> d_pbytes, d_pmult;
+    DevBuf<G1Aff> d_ppoints;
+    DevBuf<uint32_t> d_pflag;
+    KzgRet reserve_given(size_t np) {
+        if (np <= cap_given) return KZG_OK;
+        cap_given = 0;
+        HIPCHK(d_pbytes.alloc(48 * np));
+        HIPCHK(d_pmult.alloc(MULT_ENTRY_BYTES * MSM_CHUNKS * np));
+        HIPCHK(d_ppoints.alloc(np));
+        HIPCHK(d_pflag.alloc(np));
+        cap_given = np;
+        return KZG_OK;
+    }
 };
 static void cell_recover_release(const KzgSettings* s) {
     delete s->cell_recover;
     s->cell_recover = nullptr;
 }
 
-static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, size_t per, size_t n,
-                               const KzgSettings* s) {
+// given: null (the proofs are the FK20 chain's on the recovered coefficients) or n * per proofs, one per given cell (the missing
+// proofs are interpolated from them)
+static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* given, size_t per,
+                               size_t n, const KzgSettings* s) {
     KzgRet rc = prover_ready(s);
     if (rc != KZG_OK) return rc;
     if (per < (size_t)RECOVER_N / 2 || per > (size_t)RECOVER_N) return fail(KZG_BADARGS, "between 64 and 128 cells per blob are needed");
@@ -56,13 +83,14 @@ static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const ui
     const size_t cap = std::min(n, PROVER_CHUNK);
     CellProverState* cp = nullptr;
     if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cp->reserve(cap, proofs_out != nullptr)) != KZG_OK) return rc;
-    if (proofs_out && (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
+    if (proofs_out && !given && (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
     if (!s->cell_recover) s->cell_recover = new CellRecoverState();
-    if ((rc = s->cell_recover->reserve(cap)) != KZG_OK) return rc;
+    if ((rc = s->cell_recover->reserve(cap)) != KZG_OK || (given && (rc = s->cell_recover->reserve_given(cap * per)) != KZG_OK)) return rc;
     CellProverState& c = *cp;
     CellRecoverState& r = *s->cell_recover;
     const Fr29Mem* W = c.d_W.p;
-    std::vector<uint32_t> st(PROVER_CHUNK);
+    std::vector<uint32_t> st(PROVER_CHUNK), pst(given ? cap * per : 0);
+    std::vector<uint8_t> computed(given ? (size_t)48 * FK20_K2 * cap : 0);
     StreamDrain drain{s->s1};  // (declared after the host buffers the copies read and write)
     auto verdict = [&st](size_t m) {  // after the stream has delivered the chunk's status words
         for (size_t b = 0; b < m; b++) {
@@ -91,7 +119,40 @@ static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const ui
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(cells_out + CELLS_BYTES * lo, r.d_out.p, CELLS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
         }
-        if (proofs_out) {
+        if (given) {
+            const size_t np = per * m, first = (size_t)LAGRANGE_K * m, rest = np - first;  // the first 64 of every blob, then the others
+            const uint8_t* src = given + 48 * per * lo;
+            HIPCHK(hipMemcpy2DAsync(r.d_pbytes.p, 48 * LAGRANGE_K, src, 48 * per, 48 * LAGRANGE_K, m, hipMemcpyHostToDevice, s->s1));
+            if (rest)
+                HIPCHK(hipMemcpy2DAsync(r.d_pbytes.p + 48 * first, 48 * (per - LAGRANGE_K), src + 48 * LAGRANGE_K, 48 * per, 48 * (per - LAGRANGE_K), m, hipMemcpyHostToDevice, s->s1));
+            g1_decode_tables(r.d_pbytes.p, np, r.d_ppoints.p, r.d_pflag.p, r.d_pmult.p, nullptr, (int)np, false, s->s1);
+            hipLaunchKernelGGL(k_g1_ntt_load, dim3((unsigned)((first + 255) / 256)), dim3(256), 0, s->s1, (const G1Aff*)r.d_ppoints.p, (const uint32_t*)r.d_pflag.p, c.d_H.p, (int)first, 0);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(pst.data(), r.d_pflag.p, 4 * np, hipMemcpyDeviceToHost, s->s1));
+            // the verdict on cells and proofs before the sums are queued
+            HIPCHK(hipStreamSynchronize(s->s1));
+            if ((rc = verdict(m)) != KZG_OK) return rc;
+            for (size_t i = 0; i < np; i++)
+                if (pst[i] == G1_INVALID) return fail(KZG_BADARGS, "a given proof is not a G1 point");
+            const unsigned missing = (unsigned)(RECOVER_N - per);
+            if (missing) {
+                HIPCHK(hipMemsetAsync(c.d_P.p, 0, sizeof(G1Jac29Mem) * FK20_K2 * m, s->s1));  // (Z = 0: the identity)
+                hipLaunchKernelGGL(k_recover_proof_weights, dim3(mb), dim3(RECOVER_N), 0, s->s1, (const uint8_t*)r.d_slot.p, W, c.d_sc.p);
+                hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(first / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)first);
+                hipLaunchKernelGGL(k_fk20_msm<Fk20Lagrange>, dim3(missing, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_sc.p, c.d_P.p);
+                hipLaunchKernelGGL(k_fk20_compress, dim3(mb), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(computed.data(), c.d_out.p, PROOFS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
+                HIPCHK(hipStreamSynchronize(s->s1));
+            }
+            for (size_t b = 0; b < m; b++) {  // proof c of a blob: the given one, or the next computed one (the missing cells in ascending order)
+                const uint8_t* sl = slot.data() + (size_t)RECOVER_N * (lo + b);
+                uint8_t* dst = proofs_out + PROOFS_BYTES * (lo + b);
+                size_t next = 0;
+                for (size_t cc = 0; cc < (size_t)RECOVER_N; cc++)
+                    memcpy(dst + 48 * cc, sl[cc] == RECOVER_MISSING ? computed.data() + PROOFS_BYTES * b + 48 * next++ : src + 48 * (per * b + sl[cc]), 48);
+            }
+        } else if (proofs_out) {
             // the verdict on the input first: a rejected blob (the adversarial case) must not cost the proof chain's 60 ms
             HIPCHK(hipStreamSynchronize(s->s1));
             if ((rc = verdict(m)) != KZG_OK) return rc;
@@ -103,7 +164,7 @@ static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const ui
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(proofs_out + PROOFS_BYTES * lo, c.d_out.p, PROOFS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
         }
-        HIPCHK(hipStreamSynchronize(s->s1));
+        HIPCHK(hipStreamSynchronize(s->s1));  // (the cells' copy; with given proofs the last wait was before the host placed them)
         if (!proofs_out && (rc = verdict(m)) != KZG_OK) return rc;
     }
     return KZG_OK;
@@ -114,7 +175,16 @@ extern "C" KzgRet kzg_recover_cells_and_kzg_proofs(uint8_t* cells_out, uint8_t* 
     if (!s) return fail(KZG_BADARGS, "null argument");
     if (n == 0) return KZG_OK;
     if ((!cells_out && !proofs_out) || !cell_indices || !cells) return fail(KZG_BADARGS, "null argument");
-    return cell_recover_run(cells_out, proofs_out, cell_indices, cells, num_cells, n, s);
+    return cell_recover_run(cells_out, proofs_out, cell_indices, cells, nullptr, num_cells, n, s);
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");
+}
+extern "C" KzgRet kzg_recover_cells_and_kzg_proofs_given_proofs(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells,
+                                                                const uint8_t* proofs, size_t num_cells, size_t n, const KzgSettings* s) try {
+    if (!s) return fail(KZG_BADARGS, "null argument");
+    if (n == 0) return KZG_OK;
+    if (!proofs_out || !cell_indices || !cells || !proofs) return fail(KZG_BADARGS, "null argument");
+    return cell_recover_run(cells_out, proofs_out, cell_indices, cells, proofs, num_cells, n, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");
 }

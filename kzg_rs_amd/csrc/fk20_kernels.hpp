@@ -198,6 +198,12 @@ struct Fk20Variable {  // the proof of cell `slot` of blob b, P[k] with k = brp7
     }
     __device__ static size_t scalar(int b, int slot, int t) { return (size_t)t; }
 };
+struct Fk20Lagrange {  // the slot-th missing proof of blob b from its first 64 given ones (recover_lagrange.hpp): term t = (given proof t, lambda[b][slot][t])
+    static constexpr int TERMS = 64;
+    __device__ static int out_slot(int slot) { return slot; }
+    __device__ static size_t point(int b, int slot, int t) { return (size_t)b * 64 + t; }
+    __device__ static size_t scalar(int b, int slot, int t) { return ((size_t)b * FK20_K2 + slot) * 64 + t; }
+};
 
 // One workgroup per (slot, blob): out[b * 128 + slot] = sum_t scalar_t * point_t over the rows 2^(8c) point (see the header
 // comment).  Lane d owns bucket d: it adds the rows whose digit is d in ascending (t, c) order - the inner search runs for all

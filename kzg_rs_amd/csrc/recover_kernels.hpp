@@ -6,9 +6,12 @@
 //   k_recover_poly        per (i, blob)           the three 128-point transforms: P_i's coefficients into the layout k_fk20_tvec_dft
 //                                                 reads, the zero test of the upper half, then P_i(y_c) h_c^i for all 128 cells
 //   k_recover_cells       per (cell, blob)        64-point forward DFT, big-endian bytes
+//   k_recover_proof_weights  per blob             (kzg_recover_cells_and_kzg_proofs_given_proofs) the interpolation weights of
+//                                                 recover_lagrange.hpp, the scalars of k_fk20_msm<Fk20Lagrange>
 // Sums run in the fixed order of the stages; the only atomic is the OR into the blob's status word.
 #pragma once
 #include "fk20_kernels.hpp"
+#include "recover_lagrange.hpp"
 #include "recover_ntt.hpp"
 
 namespace kzg {
@@ -149,6 +152,54 @@ __global__ __launch_bounds__(64) void k_recover_cells(const Fr29* __restrict__ e
     uint4* dst = reinterpret_cast<uint4*>(out + at * (CELL_FE * 32));
     dst[2 * t] = hi;
     dst[2 * t + 1] = lo;
+}
+
+__device__ __forceinline__ Fr fr29_inverse_canonical(const Fr29& a) {  // a: a plain residue below 100 r, not zero
+    Fr c;
+    cell_fr_canonical(c.l, a);
+    return FrF::from_mont(fr_inverse_mont(FrF::to_mont(c)));
+}
+
+// One workgroup of 128 lanes per blob: the interpolation weights of recover_lagrange.hpp from the blob's slot map.  K = the cells
+// with slot < 64 (the first 64 given ones, in list order), m = the missing cells in ascending order.  Lane c owns cell c: the
+// product Z_c over K, then one inversion (B_k for a cell of K) and, as lane d, the table entry I[d] = 1 / (w128^d - 1); after that
+// the 64 x (128 - per) weights are shared out over the lanes.  sc[(b * 128 + m) * 64 + k] = lambda_(m,k), plain canonical: the
+// scalars of output m are contiguous, as k_fk20_tvec_dft writes them.  No atomics.
+__global__ __launch_bounds__(RECOVER_N) void k_recover_proof_weights(const uint8_t* __restrict__ slot, const Fr29Mem* __restrict__ W, Fr* __restrict__ sc) {
+    __shared__ uint32_t zm[LAGRANGE_K * 9], bk[LAGRANGE_K * 9], inv[RECOVER_N * 9];
+    __shared__ uint8_t miss[RECOVER_N], kb[LAGRANGE_K], ma[LAGRANGE_K];
+    const int b = blockIdx.x, c = threadIdx.x;
+    const uint32_t sl = slot[(size_t)b * RECOVER_N + c], a = bitrev7((uint32_t)c);
+    miss[c] = sl == RECOVER_MISSING;
+    if (sl < (uint32_t)LAGRANGE_K) kb[sl] = (uint8_t)a;
+    __syncthreads();
+    int rank = 0, nmiss = 0;  // of cell c among the missing ones; the number of those (at most 64: the host has checked per >= 64)
+#pragma unroll 1
+    for (int j = 0; j < RECOVER_N; j++) {
+        rank += (j < c) & miss[j];
+        nmiss += miss[j];
+    }
+    if (miss[c]) ma[rank] = (uint8_t)a;
+    const Fr29 y = fr29_load9(W + lagrange_y_index(a, false));
+    Fr29 z = fr29_small(1u);
+#pragma unroll 1
+    for (int k = 0; k < LAGRANGE_K; k++) {
+        const uint32_t bb = kb[k];
+        if (bb != a) z = lagrange_prod_step(z, y, fr29_load9(W + lagrange_y_index(bb, false)));
+    }
+    if (miss[c]) ntt_put<LAGRANGE_K>(zm, rank, z);
+    if (sl < (uint32_t)LAGRANGE_K)
+        ntt_put<LAGRANGE_K>(bk, (int)sl, lagrange_given_entry(fr29_inverse_canonical(z).l, fr29_load9(W + lagrange_y_index(a, true))));
+    if (c) ntt_put<RECOVER_N>(inv, c, lagrange_inv_entry(fr29_inverse_canonical(lagrange_root_minus_one(fr29_load9(W + lagrange_y_index((uint32_t)c, false)))).l));
+    __syncthreads();
+    Fr* out = sc + (size_t)b * RECOVER_N * LAGRANGE_K;
+#pragma unroll 1
+    for (int e = c; e < nmiss * LAGRANGE_K; e += RECOVER_N) {
+        const int m = e / LAGRANGE_K, k = e % LAGRANGE_K;
+        Fr o;
+        cell_fr_canonical(o.l, lagrange_weight(ntt_get<LAGRANGE_K>(zm, m), ntt_get<LAGRANGE_K>(bk, k), ntt_get<RECOVER_N>(inv, (int)lagrange_delta(ma[m], kb[k]))));
+        out[e] = o;
+    }
 }
 
 }  // namespace kzg

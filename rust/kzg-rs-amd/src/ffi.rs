@@ -36,6 +36,7 @@ extern "C" {
     pub fn kzg_compute_cells(cells_out: *mut u8, blobs: *const u8, n: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_compute_cells_and_kzg_proofs(cells_out: *mut u8, proofs_out: *mut u8, blobs: *const u8, n: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_recover_cells_and_kzg_proofs(cells_out: *mut u8, proofs_out: *mut u8, cell_indices: *const u64, cells: *const u8, num_cells: usize, n: usize, s: *const RawSettings) -> c_int;
+    pub fn kzg_recover_cells_and_kzg_proofs_given_proofs(cells_out: *mut u8, proofs_out: *mut u8, cell_indices: *const u64, cells: *const u8, proofs: *const u8, num_cells: usize, n: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_verify_kzg_proof(ok: *mut bool, commitment: *const u8, z: *const u8, y: *const u8, proof: *const u8, s: *const RawSettings) -> c_int;
     pub fn kzg_verify_kzg_proof_batch(ok: *mut bool, commitments: *const u8, zs: *const u8, ys: *const u8, proofs: *const u8, n: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_verify_kzg_proofs(ok_out: *mut bool, err_out: *mut u8, commitments: *const u8, zs: *const u8, ys: *const u8, proofs: *const u8, n: usize, s: *const RawSettings) -> c_int;

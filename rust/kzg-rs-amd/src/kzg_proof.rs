@@ -204,4 +204,36 @@ impl KzgProof {
         let proofs: Result<Vec<Bytes48>, KzgError> = proofs.chunks_exact(48).map(Bytes48::from_slice).collect();
         Ok((out?, proofs?))
     }
+
+    /// The same recovery for a caller that also holds the KZG proof of every given cell and HAS VERIFIED those pairs
+    /// (`kzg_recover_cells_and_kzg_proofs_given_proofs`, include/kzg_rs_amd.h): the missing proofs are interpolated from the first 64
+    /// given ones instead of being recomputed by FK20.  The proofs are not checked against the cells: with wrong but well-formed
+    /// proofs the call succeeds and the missing proofs are wrong.  A given proof that is not a G1 point is `BadArgs`.
+    pub fn recover_cells_and_kzg_proofs_given_proofs(
+        cell_indices: &[u64],
+        cells: &[Cell],
+        proofs: &[Bytes48],
+        kzg_settings: &KzgSettings,
+    ) -> Result<(Vec<Cell>, Vec<Bytes48>), KzgError> {
+        if cell_indices.len() != cells.len() || proofs.len() != cells.len() {
+            return Err(KzgError::InvalidBytesLength("cell indices, cells and proofs differ in length".to_string()));
+        }
+        let mut out: Vec<u8> = alloc::vec![0u8; 128 * crate::dtypes::BYTES_PER_CELL];
+        let mut all: Vec<u8> = alloc::vec![0u8; 128 * 48];
+        ffi::check(unsafe {
+            ffi::kzg_recover_cells_and_kzg_proofs_given_proofs(
+                out.as_mut_ptr(),
+                all.as_mut_ptr(),
+                cell_indices.as_ptr(),
+                cells.as_ptr().cast::<u8>(),
+                proofs.as_ptr().cast::<u8>(),
+                cells.len(),
+                1,
+                kzg_settings.raw(),
+            )
+        })?;
+        let out: Result<Vec<Cell>, KzgError> = out.chunks_exact(crate::dtypes::BYTES_PER_CELL).map(Cell::from_slice).collect();
+        let all: Result<Vec<Bytes48>, KzgError> = all.chunks_exact(48).map(Bytes48::from_slice).collect();
+        Ok((out?, all?))
+    }
 }
