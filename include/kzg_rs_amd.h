@@ -411,6 +411,39 @@ KzgRet kzg_verify_cell_kzg_proof_batches(bool *ok_out, uint8_t *err_out, const u
  * host code - no handle, no device; nothing is validated; the batches are spread over host threads (KZG_OPTIONS host_threads). */
 KzgRet kzg_cell_batch_challenges(uint8_t *r_out, const uint8_t *commitments, const uint64_t *cell_indices,
                                  const uint8_t *cells, const uint8_t *proofs, const size_t *batch_sizes, size_t n_batches);
+/* Blobs against their 128 cell proofs each, a verdict per blob, WITHOUT computing a cell: the execution layer's Fulu check of a blob
+ * transaction's network wrapper (version 1) and of engine_getBlobsV2 answers, which carry per blob the blob, its commitment and its
+ * 128 cell proofs and no blob proof.  Inputs are host arrays: blobs n * 131072 bytes, commitments n * 48, cell_proofs n * 128 * 48
+ * (proof c of blob b at (128 b + c) * 48); n <= KZG_BLOB_CELL_MAX_BLOBS.  For valid input ok_out[b] is the verdict
+ * kzg_verify_cell_kzg_proof_batch gives on (commitment b x 128, cell indices 0..127, kzg_compute_cells(blob b), the proofs of b).
+ * err_out[b] (optional) = 1 and ok_out[b] = false where that call would return KZG_BADARGS - a field element >= r, a commitment or
+ * proof that is not a G1 point (the identity is allowed) - and the other blobs keep their own verdicts; without err_out any such
+ * blob fails the whole call with KZG_BADARGS.  Errors of the call, KZG_BADARGS: null pointers, settings the cell verifier refuses
+ * (no G1 points, fewer than 65 G2 points), n above KZG_BLOB_CELL_MAX_BLOBS; KZG_BAD_SETUP for an off-subgroup monomial point.
+ * n == 0 is KZG_OK.  After any error the handle stays usable.
+ * No cell is formed.  With a_i the blob polynomial's coefficients and g_c = h_c^64 = w128^brp7(c), the interpolant of cell c is
+ * p mod (X^64 - g_c), so the aggregated interpolant of the equation above has the coefficients I_i = sum_(j<64) a_(i+64j) s_j with
+ * s_j = sum_(c<128) r^c g_c^j: per blob one inverse 4 096-point transform (before r, beside the hash) and 8 192 + 4 096 field
+ * multiplications (csrc/blob_cell_interp.hpp).  Everything else is kzg_verify_cell_kzg_proof_batches' group with blob b as slot b:
+ * one point decode, one window-kernel launch over two sums per blob, one pairing instance per blob; blobs are processed in groups
+ * of at most 64.
+ * THE CHALLENGE IS NOT THE SPEC'S: the spec's transcript hashes the cells, which this call never forms.  Blob b gets
+ *     r_b = SHA-256("RCKZGBLOBCELLS_1" || u64be(4096) || u64be(64) || u64be(128) || commitment b || blob b || its 128 proofs) mod r
+ * (kzg_blob_cell_proofs_challenges), hashed on host threads (KZG_OPTIONS host_threads) while the device decodes.  The cells are a
+ * function of the blob, so this transcript fixes every coefficient of the polynomial in r that the pairing tests, as the spec's
+ * does: the equation holds whenever all 128 proofs are right, and could hold otherwise only if the hash-derived r_b were a root of
+ * a fixed non-zero polynomial of degree < 128 over Fr (probability < 2^-246, the argument made for small batches at
+ * kzg_verify_kzg_proof_batch) - so the verdict differs from the spec-challenge verdict with a probability below that.
+ * The handle's lock is taken; a multi-device handle runs the call on its first device.  kzg_last_timings afterwards holds the
+ * group call's slots, summed over the groups.  Two runs give the same bytes and verdicts: every device sum has a fixed order.
+ * Measured (profiles/blob_cell_verify_probe.json): not yet measured on an MI355X. */
+#define KZG_BLOB_CELL_MAX_BLOBS 8192
+KzgRet kzg_verify_blob_cell_kzg_proofs(bool *ok_out, uint8_t *err_out, const uint8_t *blobs, const uint8_t *commitments,
+                                       const uint8_t *cell_proofs, size_t n, const KzgSettings *s);
+/* The challenges r_b of the above alone: r_out = n x 32 big-endian bytes.  Pure host code - no handle, no device; nothing is
+ * validated; the blobs are spread over host threads (KZG_OPTIONS host_threads). */
+KzgRet kzg_blob_cell_proofs_challenges(uint8_t *r_out, const uint8_t *blobs, const uint8_t *commitments,
+                                       const uint8_t *cell_proofs, size_t n);
 /* [tau^i]G1, i < 64, compressed: derived from the handle's Lagrange points by the first cell call or the first call of this
  * accessor.  KZG_BADARGS for i >= 64 and for the settings the cell verifier refuses. */
 KzgRet kzg_settings_g1_monomial_point(const KzgSettings *s, size_t i, uint8_t out[48]);
@@ -514,6 +547,10 @@ KzgRet kzg_debug_cell_queue_stats(const KzgSettings *s, uint64_t out[4], int res
 KzgRet kzg_debug_concurrent_cell_callers(double out[5], size_t threads, double seconds, const uint8_t *commitments,
                                          const uint64_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
                                          const size_t *batch_sizes, const uint8_t *expect, size_t n_calls, const KzgSettings *s);
+/* Test hook: the two kernels of kzg_verify_blob_cell_kzg_proofs alone.  out[64 b + i] = coefficient I_i of blob b's aggregated
+ * interpolant under the challenge r_be + 32 b (32 big-endian bytes per blob, reduced mod r), as 32 big-endian bytes.  Host
+ * pointers; KZG_BADARGS for a field element >= r and for what the call itself refuses. */
+KzgRet kzg_debug_blob_cell_interp(uint8_t *out, const uint8_t *blobs, const uint8_t *r_be, size_t n, const KzgSettings *s);
 
 const char *kzg_last_error(void);
 

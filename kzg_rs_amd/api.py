@@ -134,6 +134,9 @@ def lib():
         L.kzg_cell_batch_challenge.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, sz]
         L.kzg_verify_cell_kzg_proof_batches.argtypes = [bp, u8, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(C.c_size_t), sz, vp]
         L.kzg_cell_batch_challenges.argtypes = [u8, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(C.c_size_t), sz]
+        L.kzg_verify_blob_cell_kzg_proofs.argtypes = [bp, u8, u8, u8, u8, sz, vp]
+        L.kzg_blob_cell_proofs_challenges.argtypes = [u8, u8, u8, u8, sz]
+        L.kzg_debug_blob_cell_interp.argtypes = [u8, u8, u8, sz, vp]
         L.kzg_settings_g1_monomial_point.argtypes = [vp, sz, u8]
         L.kzg_settings_g1_monomial_points.argtypes = [vp, sz, sz, u8]
         L.kzg_settings_precompute.argtypes = [vp, C.c_uint32]
@@ -794,6 +797,44 @@ def compute_cells_and_kzg_proofs(blobs, kzg_settings):
     proofs = [[raw[48 * (CELLS_PER_EXT_BLOB * b + c): 48 * (CELLS_PER_EXT_BLOB * b + c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
               for b in range(n)]
     return _cells_of(out, n), proofs
+
+
+def _blob_cell_args(blobs, commitments, cell_proofs):
+    data = _cell_prover_blobs(blobs)
+    n = len(data)
+    if len(commitments) != n or len(cell_proofs) != n:
+        raise InvalidBytesLength("blobs, commitments and cell_proofs differ in length: %d, %d and %d blobs" % (n, len(commitments), len(cell_proofs)))
+    raw = lambda x: x.data if isinstance(x, _BytesN) else bytes(x)
+    cm = [raw(c) for c in commitments]
+    pr = [[raw(p) for p in per] for per in cell_proofs]
+    if any(len(c) != 48 for c in cm):
+        raise InvalidBytesLength("commitments are 48 bytes each")
+    for per in pr:
+        if len(per) != CELLS_PER_EXT_BLOB or any(len(p) != 48 for p in per):
+            raise InvalidBytesLength("every blob needs %d cell proofs of 48 bytes" % CELLS_PER_EXT_BLOB)
+    return b"".join(data), b"".join(cm), b"".join(p for per in pr for p in per), n
+
+
+def verify_blob_cell_kzg_proofs(blobs, commitments, cell_proofs, kzg_settings, return_errors=False):
+    """Blobs against their 128 cell proofs each (kzg_verify_blob_cell_kzg_proofs; the Fulu check of a blob transaction's network
+    wrapper): blobs (Blob or bytes), commitments (Bytes48 or bytes) and cell_proofs (per blob a list of 128 Bytes48 or bytes), one
+    entry per blob.  -> a list of bool, the verdict verify_cell_kzg_proof_batch gives on that blob's cells, which are never
+    computed.  Lists of unequal length and items of the wrong size raise InvalidBytesLength before any device call; a blob with a
+    field element >= r or a point outside G1 raises BadArgs - or, with return_errors=True, is reported as "BadArgs" in its place
+    while the others keep their verdicts."""
+    bl, cm, pr, n = _blob_cell_args(blobs, commitments, cell_proofs)
+    ok = (C.c_bool * max(n, 1))()
+    err = (C.c_uint8 * max(n, 1))()
+    _chk(lib().kzg_verify_blob_cell_kzg_proofs(ok, C.cast(err, C.c_char_p) if return_errors else None, bl, cm, pr, n, kzg_settings._h))
+    return ["BadArgs" if return_errors and err[b] else bool(ok[b]) for b in range(n)]
+
+
+def blob_cell_proofs_challenges(blobs, commitments, cell_proofs):
+    """The challenges r_b of verify_blob_cell_kzg_proofs (host code, no device): a list of 32 big-endian bytes per blob."""
+    bl, cm, pr, n = _blob_cell_args(blobs, commitments, cell_proofs)
+    out = C.create_string_buffer(32 * max(n, 1))
+    _chk(lib().kzg_blob_cell_proofs_challenges(out, bl, cm, pr, n))
+    return [out.raw[32 * b: 32 * b + 32] for b in range(n)]
 
 
 def recover_cells_and_kzg_proofs(cell_indices, cells, kzg_settings):

@@ -64,6 +64,11 @@ struct CellGroupHash {
     CellGroupIn in;
     const CellKnownR* known = nullptr;
     const CellGroupPlan* plan = nullptr;
+    // slots that are not lists of cells (capi_blob_cells.hpp): slot_hash(out, slot_ctx, j) = the challenge of slot j, one chain of
+    // slot_bytes bytes; `in` and `known` are not read
+    void (*slot_hash)(uint8_t r_be[32], const void* ctx, size_t j) = nullptr;
+    const void* slot_ctx = nullptr;
+    size_t slot_bytes = 0;
     size_t count = 0;
     std::atomic<size_t> next{0};
     std::atomic<bool> failed{false};
@@ -81,8 +86,12 @@ struct CellGroupHash {
             for (;;) {
                 const size_t j = next.fetch_add(1, std::memory_order_relaxed);
                 if (j >= count) break;
-                const size_t b = plan ? plan->slot_batch[j] : j, n = in.batch_sizes[b];
                 uint8_t* const out = r_be + 32 * j;
+                if (slot_hash) {
+                    slot_hash(out, slot_ctx, j);
+                    continue;
+                }
+                const size_t b = plan ? plan->slot_batch[j] : j, n = in.batch_sizes[b];
                 int idle = 0;
                 if (known && known[b].state && !known[b].state->compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) {
                     // its owner has it, or is at it (one chain of at most T cells: well under a millisecond)
@@ -114,8 +123,8 @@ struct CellGroupHash {
     }
     // up to host_threads - 1 helpers, one per 128 KB of transcript at most (a thread costs more than a short chain)
     void start() {
-        size_t bytes = 0;
-        for (size_t j = 0; j < count; j++) {
+        size_t bytes = slot_hash ? count * slot_bytes : 0;
+        for (size_t j = 0; j < count && !slot_hash; j++) {
             const size_t b = plan ? plan->slot_batch[j] : j;
             if (known && known[b].state && known[b].state->load(std::memory_order_relaxed) != 0) continue;
             bytes += in.batch_sizes[b] * (CELL_BYTES + 112);
@@ -196,12 +205,27 @@ struct CellGroupBufs {
 CellState::~CellState() { delete group; }
 
 // ---------------------------------------------------------------- one group on one handle
+// The scalar stage of a group whose slots are not lists of cells (capi_blob_cells.hpp: whole blobs) - what stands in the place of
+// CellStageBufs::reserve, cells_decode and cells_scalars; everything else of cell_group_locked is shared.  The handle's lock is held
+// and every launch goes to s->s1.
+struct CellGroupStage {
+    const char* why_bad = nullptr;  // the reason of a slot with a flag set
+    // the stage's buffers for plan P; stage.d_idx, d_bad, d_r and d_sc among them
+    virtual KzgRet reserve(CellState& cs, const CellGroupPlan& P) = 0;
+    // before r: P.idx to stage.d_idx, the slots' data decoded with their canonical check; the flags start back to f_cell [nG] - a
+    // slot is refused when any word of its dense cells is set
+    virtual KzgRet decode(const KzgSettings* s, CellState& cs, const CellGroupPlan& P, uint32_t* f_cell) = 0;
+    // after r: r_le as for cells_scalars -> every scalar of stage.d_sc in the layout of cell_group_scalars
+    virtual KzgRet scalars(const KzgSettings* s, CellState& cs, const CellGroupPlan& P, const uint8_t* r_le) = 0;
+    virtual ~CellGroupStage() = default;
+};
 // The GROUP slots of plan P over the batches `in`, on handle s whose lock the caller holds (the entry point below: the handle's own;
 // a leader of the small-call queue: its private lane).  hash: posted by the caller over the same plan, finished here.  ok_out [b]
 // and err_out [b] of the slots' batches are written (err_out null: the first refused slot fails the call, as the single call
-// does); why_out (optional) [b] = the reason of a refused slot.  stage_ms: MSM | pairing | r -> scalars | decode.
+// does); why_out (optional) [b] = the reason of a refused slot.  stage_ms: MSM | pairing | r -> scalars | decode.  stage (optional):
+// the scalar stage of a caller that brings no cells - in.cells and in.cell_indices are not read then.
 static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why_out, const CellGroupIn& in, const CellGroupPlan& P, CellGroupHash& hash,
-                                const uint8_t* r_be, const KzgSettings* s, float stage_ms[4]) {
+                                const uint8_t* r_be, const KzgSettings* s, float stage_ms[4], CellGroupStage* stage = nullptr) {
     KzgRet rc = KZG_OK;
     const size_t* const batch_sizes = in.batch_sizes;
     const uint32_t G = P.G, nG = P.nG, mtot = P.mtot, NP = cell_group_points(nG, mtot), nsc = cell_group_scalars(nG, mtot, G);
@@ -219,7 +243,7 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
     if ((rc = cells_state(s, &cs)) != KZG_OK) return rc;
     if (!cs->group) cs->group = new CellGroupBufs();
     CellGroupBufs& g = *cs->group;
-    if ((rc = cs->stage.reserve(P)) != KZG_OK || (rc = g.reserve(G, NP, terms, h_bytes, aff)) != KZG_OK) return rc;
+    if ((rc = stage ? stage->reserve(*cs, P) : cs->stage.reserve(P)) != KZG_OK || (rc = g.reserve(G, NP, terms, h_bytes, aff)) != KZG_OK) return rc;
     CellStageBufs& sb = cs->stage;
     StreamDrain drain{s->s1};
     hipStream_t st = s->s1;
@@ -242,7 +266,7 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
     HIPCHK(hipGetLastError());
     uint32_t* const f_point = reinterpret_cast<uint32_t*>(hp + h_pflag);
     uint32_t* const f_cell = reinterpret_cast<uint32_t*>(hp + h_bad);
-    if ((rc = cells_decode(s, *cs, P, in.cells, f_cell)) != KZG_OK) return rc;
+    if ((rc = stage ? stage->decode(s, *cs, P, f_cell) : cells_decode(s, *cs, P, in.cells, f_cell)) != KZG_OK) return rc;
     HIPCHK(hipMemcpyAsync(f_point, g.d_pflag.p, 4 * (size_t)NP, hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(s->ev[6], st));
     hash.finish();
@@ -257,7 +281,7 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
         const uint32_t c0 = P.idx[P.o_cstart + sl], c1 = P.idx[P.o_cstart + sl + 1], u0 = P.idx[P.o_ustart + sl], u1 = P.idx[P.o_ustart + sl + 1];
         const char* why = nullptr;
         for (uint32_t q = c0; q < c1 && !why; q++)
-            if (f_cell[q]) why = "a cell holds a field element >= r";
+            if (f_cell[q]) why = stage ? stage->why_bad : "a cell holds a field element >= r";
         for (uint32_t q = c0; q < c1 && !why; q++)
             if (f_point[q] == G1_INVALID) why = "invalid proof (not a G1 point)";
         for (uint32_t i = u0; i < u1 && !why; i++)
@@ -277,7 +301,7 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
     const uint32_t* const ix = sb.d_idx.p;
     HIPCHK(hipEventRecord(s->ev[7], st));
     HIPCHK(hipMemcpyAsync(g.d_live.p, live, 4 * (size_t)G, hipMemcpyHostToDevice, st));
-    if ((rc = cells_scalars(s, *cs, P, r_le)) != KZG_OK) return rc;
+    if ((rc = stage ? stage->scalars(s, *cs, P, r_le) : cells_scalars(s, *cs, P, r_le)) != KZG_OK) return rc;
     hipLaunchKernelGGL(k_cell_terms, dim3((unsigned)((terms + 255) / 256)), dim3(256), 0, st, g.d_term_point.p, g.d_term_scalar.p, ix + P.o_cstart,
                        ix + P.o_ustart, (const uint32_t*)g.d_live.p, (int)G, (int)nG, (int)mtot, (int)max_terms);
     HIPCHK(hipGetLastError());

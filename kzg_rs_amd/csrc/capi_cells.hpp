@@ -89,6 +89,11 @@ struct CellStageBufs {
     }
 };
 struct CellGroupBufs;  // what is kzg_verify_cell_kzg_proof_batches' own (capi_cell_groups.hpp), made by its first call
+struct BlobCellBufs {  // what is kzg_verify_blob_cell_kzg_proofs' own (capi_blob_cells.hpp): empty until its first call
+    DevBuf<uint8_t> d_blobs;   // [G] x 131072 bytes as given
+    DevBuf<Fr> d_coef;         // [4096 G] the blob polynomials' coefficients, plain
+    DevBuf<uint8_t> d_interp;  // [64 G] x 32 bytes: kzg_debug_blob_cell_interp's output
+};
 // the set-up: derived once per handle, immutable afterwards - the lanes of the small-call queue read their parent's
 struct CellSetup {
     DevBuf<Fr> d_T;                             // w8192^e, e < 8192, Montgomery
@@ -99,6 +104,7 @@ struct CellSetup {
 struct CellState {
     CellStageBufs stage;
     CellGroupBufs* group = nullptr;
+    BlobCellBufs blob;
     ~CellState();
     CellSetup own;                // empty on a lane
     const CellSetup* t = &own;    // a lane (KzgSettings::cell_home): its parent's

@@ -157,6 +157,39 @@ impl KzgProof {
         Ok(ok)
     }
 
+    /// Blobs against their 128 cell proofs each, without computing a cell (not in kzg-rs; include/kzg_rs_amd.h): the Fulu check of
+    /// a blob transaction's network wrapper and of `engine_getBlobsV2` answers.  `cell_proofs` holds the 128 proofs of blob 0,
+    /// then those of blob 1, ...  Entry b is what `verify_cell_kzg_proof_batch` returns for blob b's commitment x 128, the cell
+    /// indices 0..127, its cells and its proofs: `Ok(verdict)`, or `BadArgs` for a non-canonical field element or a point
+    /// outside G1 - the other blobs keep their own results.  Slices whose lengths do not fit are `InvalidBytesLength`.
+    pub fn verify_blob_cell_kzg_proofs(
+        blobs: &[Blob],
+        commitments: &[Bytes48],
+        cell_proofs: &[Bytes48],
+        kzg_settings: &KzgSettings,
+    ) -> Result<Vec<Result<bool, KzgError>>, KzgError> {
+        let n = blobs.len();
+        if commitments.len() != n || cell_proofs.len() != 128 * n {
+            return Err(KzgError::InvalidBytesLength("every blob needs one commitment and 128 cell proofs".to_string()));
+        }
+        let mut ok = vec![false; n];
+        let mut err = vec![0u8; n];
+        ffi::check(unsafe {
+            ffi::kzg_verify_blob_cell_kzg_proofs(
+                ok.as_mut_ptr(),
+                err.as_mut_ptr(),
+                blobs.as_ptr().cast::<u8>(),
+                commitments.as_ptr().cast::<u8>(),
+                cell_proofs.as_ptr().cast::<u8>(),
+                n,
+                kzg_settings.raw(),
+            )
+        })?;
+        Ok((0..n)
+            .map(|b| if err[b] != 0 { Err(KzgError::BadArgs("a field element >= r or a point outside G1".to_string())) } else { Ok(ok[b]) })
+            .collect())
+    }
+
     /// c-kzg-4844's `compute_cells` (EIP-7594; not in kzg-rs): the 128 cells of every blob, blob after blob
     /// (include/kzg_rs_amd.h).  A field element >= r is `BadArgs`.
     pub fn compute_cells(blobs: &[Blob], kzg_settings: &KzgSettings) -> Result<Vec<Cell>, KzgError> {
