@@ -500,6 +500,38 @@ KzgRet kzg_g1_msm(uint8_t out[48], const uint8_t *points48, const uint8_t *scala
  * (random, or hash-derived as in the verifier): a million EQUAL scalars put every entry of a window into one bucket, which one
  * lane then adds one after the other - the sum is still exact, the call takes on the order of a second. */
 KzgRet kzg_g1_msm_setup(uint8_t out[48], const uint8_t *scalars, size_t n, const KzgSettings *s);
+/* PREPARED G1 point sets: hand n arbitrary points over once, then sum over them from scalars alone - the fixed-base form of
+ * kzg_g1_msm_setup (csrc/msm_fixed.hpp) over ANY points instead of the handle's 4 096.
+ * kzg_g1_points_prepare decodes and subgroup-tests points48 (n * 48 bytes compressed, host pointer) exactly as kzg_g1_msm does and
+ * builds, on the device, the affine rows 2^(16 v) P_j (v < 16) and 2^(16 v + 1) P_j (the rows of the digit 2^15); *out keeps them.
+ * The identity 0xC0 00 .. 00 is allowed and contributes nothing; any other invalid point is KZG_BADARGS (*out untouched, nothing
+ * kept).  n == 0 gives a valid empty set; n > KZG_G1_POINTS_MAX is KZG_BADARGS.  Device memory: 32 rows x 128 B + a 4-byte flag =
+ * 4 100 B per point for as long as the set lives (4 GB at 2^20 points), and ~6.5 KB per point of a 32 768-point slice (~215 MB at
+ * most) while it is built; an allocation the device refuses is KZG_MALLOC.  The set belongs to the handle's device (the first device
+ * of a multi-device handle) and to the handle `s`: it must be freed BEFORE the handle, is immutable, and any number of threads may
+ * sum over it (each call takes the handle's lock).  kzg_g1_points_prepare takes the handle's lock.
+ * kzg_g1_points_count: *n = the number of points.  kzg_g1_points_point: point i re-compressed from the set's row 0, as
+ * kzg_settings_g1_point does for the handle's points (i >= n: KZG_BADARGS).  kzg_g1_points_free(NULL) does nothing. */
+typedef struct KzgG1Points KzgG1Points;
+#define KZG_G1_POINTS_MAX ((size_t)1 << 20)
+/* KZG_G1_POINTS_API expands to nothing.  It marks the entry points that take a KzgG1Points: the Rust shim (rust/kzg-rs-amd) does not
+ * bind them, and its extern-block check translates every plain `KzgRet kzg_*(...)` declaration of this header into the Rust types it
+ * knows - a handle type it has no spelling for stays out of that table this way. */
+#define KZG_G1_POINTS_API
+KzgRet KZG_G1_POINTS_API kzg_g1_points_prepare(KzgG1Points **out, const uint8_t *points48, size_t n, const KzgSettings *s);
+KzgRet KZG_G1_POINTS_API kzg_g1_points_count(const KzgG1Points *p, size_t *n);
+KzgRet KZG_G1_POINTS_API kzg_g1_points_point(const KzgG1Points *p, size_t i, uint8_t out[48]);
+void KZG_G1_POINTS_API kzg_g1_points_free(KzgG1Points *p);
+/* out = sum_i scalars[i] * P_i over a prepared set: scalars n * 32 bytes big-endian (reduced mod r), host pointer; n must equal the
+ * set's count and `s` be the handle the set was prepared on (KZG_BADARGS otherwise); n == 0 gives the identity 0xC0 00 .. 00.
+ * Nothing is decoded and no row is built per call: 16 signed 16-bit digits per term, 16 bucket additions where kzg_g1_msm spends 32,
+ * on call buffers of the handle's own that grow with n (192 B per term, 48 KB per workgroup of the bucket pass: ~270 MB at 2^20
+ * terms).  The same call twice gives the same bytes.  The handle's lock is taken; kzg_last_timings [2] is the sum, [6] is 0.
+ * 2^20 distinct points: not yet measured on an MI355X (tools/prof/g1_points_probe.py; the rows of 2^20 points are 4 GB and
+ * stream from HBM, where kzg_g1_msm_setup's 16 MB stay in the last-level cache).  Like kzg_g1_msm_setup, the timing assumes scalars
+ * whose digits spread over the buckets (random, or hash-derived): a million EQUAL scalars put every entry of a window into one
+ * bucket, which one lane then adds one after the other - the sum is still exact, the call takes on the order of a second. */
+KzgRet KZG_G1_POINTS_API kzg_g1_msm_prepared(uint8_t out[48], const KzgG1Points *p, const uint8_t *scalars, size_t n, const KzgSettings *s);
 /* The group DFT over G1 (c-kzg-4844's g1_fft / g1_ifft): out[i] = sum_t w_n^(i t) points[t], n a power of two <= 4096, w_n the
  * n-th root of unity of kzg_settings_root_of_unity's table, natural order on both sides; inverse != 0: w_n^-1 and the factor
  * 1 / n.  points48 / out48: n * 48 bytes compressed, host pointers; the points are decoded and subgroup-tested as in kzg_g1_msm

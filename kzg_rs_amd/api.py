@@ -157,6 +157,12 @@ def lib():
         L.kzg_g1_decompress.argtypes = [u8, u8, u8, sz, vp]
         L.kzg_g1_msm.argtypes = [u8, u8, u8, sz, vp]
         L.kzg_g1_msm_setup.argtypes = [u8, u8, sz, vp]
+        L.kzg_g1_points_prepare.argtypes = [C.POINTER(vp), u8, sz, vp]
+        L.kzg_g1_points_count.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.kzg_g1_points_point.argtypes = [vp, sz, u8]
+        L.kzg_g1_points_free.argtypes = [vp]
+        L.kzg_g1_points_free.restype = None
+        L.kzg_g1_msm_prepared.argtypes = [u8, vp, u8, sz, vp]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -716,6 +722,73 @@ def g1_msm_setup(scalars, kzg_settings):
     out = C.create_string_buffer(48)
     _chk(lib().kzg_g1_msm_setup(out, bytes(raw), len(raw) // 32, kzg_settings._h))
     return out.raw
+
+
+G1_POINTS_MAX = 1 << 20
+
+
+class G1Points:
+    """A prepared G1 point set (kzg_g1_points_prepare): the points - a list of 48-byte compressed values, or one bytes-like object
+    of n x 48 - are decoded and subgroup-tested once and their fixed-base rows kept on the handle's device (4 KB per point);
+    msm(scalars) then sums over them from scalars alone (kzg_g1_msm_prepared).  The identity encoding is allowed; any other invalid
+    point raises KzgError.  The set keeps its handle alive and must be closed (or dropped) before the handle is freed."""
+
+    def __init__(self, points, kzg_settings):
+        raw = points if isinstance(points, (bytes, bytearray, memoryview)) else b"".join(points)
+        raw = bytes(raw)
+        if len(raw) % 48:
+            raise KzgError("InvalidBytesLength", "points: not a multiple of 48 bytes")
+        self._settings = kzg_settings
+        h = C.c_void_p()
+        _chk(lib().kzg_g1_points_prepare(C.byref(h), raw, len(raw) // 48, kzg_settings._h))
+        self._h = h
+
+    def __len__(self):
+        n = C.c_size_t(0)
+        _chk(lib().kzg_g1_points_count(self._h, C.byref(n)))
+        return n.value
+
+    def point(self, i):
+        """point i, re-compressed from the set's own row (kzg_g1_points_point)"""
+        out = C.create_string_buffer(48)
+        _chk(lib().kzg_g1_points_point(self._h, i, out))
+        return out.raw
+
+    def msm(self, scalars):
+        """sum_i scalars[i] * P_i: scalars = a list of 32-byte big-endian values, or one bytes-like object of n x 32"""
+        raw = scalars if isinstance(scalars, (bytes, bytearray, memoryview)) else b"".join(scalars)
+        raw = bytes(raw)
+        if len(raw) % 32:
+            raise KzgError("InvalidBytesLength", "scalars: not a multiple of 32 bytes")
+        out = C.create_string_buffer(48)
+        _chk(lib().kzg_g1_msm_prepared(out, self._h, raw, len(raw) // 32, self._settings._h))
+        return out.raw
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
+                lib().kzg_g1_points_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def g1_points_prepare(points, kzg_settings):
+    return G1Points(points, kzg_settings)
+
+
+def g1_msm_prepared(point_set, scalars):
+    return point_set.msm(scalars)
 
 
 def pairing_check(a, b, kzg_settings):

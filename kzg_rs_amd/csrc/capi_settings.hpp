@@ -128,6 +128,7 @@ struct KzgSettings {
     const KzgSettings* cell_home = nullptr;       // a lane of the small-call queue: the handle whose cell set-up it reads (its CellState holds buffers alone)
     mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
     mutable struct CellRecoverState* cell_recover = nullptr;  // cell recovery's own buffers, made by its first call (capi_cell_recover.hpp)
+    mutable struct G1PointsBufs* g1_points = nullptr;  // kzg_g1_msm_prepared's call buffers, made by its first call (capi_g1_points.hpp)
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the
     // last launch group, and summed over the groups finished since the last reset (kzg_kernel_stamp_totals)
@@ -576,6 +577,7 @@ static void prover_release(const KzgSettings* s);  // (capi_prover.hpp)
 static void cells_release(const KzgSettings* s);   // (capi_cells.hpp)
 static void cell_prover_release(const KzgSettings* s);  // (capi_cell_prover.hpp)
 static void cell_recover_release(const KzgSettings* s);  // (capi_cell_recover.hpp)
+static void g1_points_release(const KzgSettings* s);  // (capi_g1_points.hpp)
 extern "C" void kzg_settings_free(KzgSettings* s) {
     if (!s) return;
     int prev = -1;
@@ -595,6 +597,7 @@ extern "C" void kzg_settings_free(KzgSettings* s) {
     cells_release(s);
     cell_prover_release(s);
     cell_recover_release(s);
+    g1_points_release(s);
     s->own = SettingsTables();  // (a lane's is empty: it reads its parent's, which is freed after its lanes)
     for (auto& e : s->ev)
         if (e) (void)hipEventDestroy(e);

@@ -67,6 +67,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_pipeline.hpp"
 #include "capi_pieces.hpp"
 #include "capi_prover.hpp"
+#include "capi_g1_points.hpp"
 #include "capi_cells.hpp"
 #include "capi_cell_groups.hpp"
 #include "capi_cell_prover.hpp"

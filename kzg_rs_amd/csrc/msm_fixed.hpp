@@ -18,13 +18,13 @@
 //   (k_msm_bucket_fold, k_msm_bucket_sum_quads, k_msm_reduce_quads) as TWO "windows" 8 bits apart, joined by k_msm_combine_quad.
 // Part of the single translation unit kzg_capi.hip (after msm.hpp).
 #pragma once
+#include "fb_entry.hpp"  // FBM_WINDOWS, fb_digits, the entry formats FbEntry32 / FbEntry64
 
 namespace kzg {
 
-constexpr int FBM_WINDOWS = 16;           // 16-bit windows of a 255-bit scalar
 constexpr int FBM_PARTS = 128;            // |digit| >> 8 for |digit| <= 2^15 - 1 (a digit of exactly 2^15 travels as two entries of 2^14, below)
 constexpr int FBM_SLICE_ENTRIES = 12288;  // entries a workgroup sorts in LDS (48 KB: three workgroups per CU, like k_msm_window)
-constexpr uint32_t FBM_ENTRY_ROW_MASK = 0x1ffffu, FBM_ENTRY_NEG = 0x20000u;  // entry = low byte of |digit| << 24 | negative << 17 | row (v N + j; doubled rows from 16 N on)
+constexpr uint32_t FBM_ENTRY_ROW_MASK = FbEntry32::ROW_MASK, FBM_ENTRY_NEG = FbEntry32::NEG;  // the setup form's entry = low byte of |digit| << 24 | negative << 17 | row (v N + j; doubled rows from 16 N on)
 // device-side plan of one call: entries per partition | their exclusive scan (+ total) | first workgroup of
 // each partition (+ total workgroups) | then the scatter's cursors
 constexpr int FBM_PLAN_COUNT = 0, FBM_PLAN_OFF = FBM_PARTS, FBM_PLAN_BLK = 2 * FBM_PARTS + 1, FBM_PLAN_CUR = 3 * FBM_PARTS + 2, FBM_PLAN_WORDS = 4 * FBM_PARTS + 2;
@@ -38,24 +38,6 @@ __global__ __launch_bounds__(256) void k_scalars_reduce_be(const uint8_t* __rest
     v = FrF::reduce_once(v);
     v = FrF::reduce_once(v);
     out[i] = v;
-}
-
-// the 16 signed digits d_v in [-(2^15 - 1), 2^15] of a canonical scalar, least significant first: f(v, |d_v|, d_v < 0, doubled row) for every non-zero digit
-template <class F>
-__device__ __forceinline__ void fb_digits(const Fr& k, F&& f) {
-    uint32_t carry = 0;
-#pragma unroll
-    for (int v = 0; v < FBM_WINDOWS; v++) {
-        const uint32_t x = ((k.l[v >> 1] >> (16 * (v & 1))) & 0xffffu) + carry;
-        carry = x > 32768u ? 1u : 0u;
-        const uint32_t mag = carry ? 65536u - x : x;
-        // |d| = 2^15 (one digit in 65 536) would be the ONLY magnitude of a 129th partition: ~n / 4 096 entries in one bucket, added by
-        // one lane one after the other - at 2^20 terms a 4 ms straggler behind a 4 ms kernel (profiles/r6_fb_window_timeline.txt).
-        // It travels as 2^14 x the DOUBLED row 2^(16 v + 1) P_j instead (rows 16 N ..: one more row per window and point).
-        if (mag == 32768u) f(v, 16384u, false, true);
-        else if (mag) f(v, mag, carry != 0, false);
-    }
-    // (k < r < 2^255: the top window is below 2^15, so no carry leaves it)
 }
 
 constexpr int FBM_TERMS_PER_BLOCK = 1024;
@@ -92,8 +74,10 @@ __global__ __launch_bounds__(64) void k_fb_plan(uint32_t* __restrict__ plan, int
 }
 // pass 1c: the entries, partition by partition (order inside a partition: whatever the workgroups' reservations make it - a sum
 // does not care).  A workgroup counts its terms' entries per partition in LDS, reserves one run per partition, and fills the runs.
-__global__ __launch_bounds__(256) void k_fb_scatter(const Fr* __restrict__ scalars, const uint32_t* __restrict__ pflag, int n, int npoints,
-                                                    uint32_t* __restrict__ plan, uint32_t* __restrict__ entries) {
+// (EF: the entry format, fb_entry.hpp - k_fb_scatter writes the setup form's 4-byte entries, k_fbp_scatter a prepared set's 8-byte ones)
+template <class EF>
+__device__ __forceinline__ void fb_scatter_body(const Fr* __restrict__ scalars, const uint32_t* __restrict__ pflag, int n, int npoints,
+                                                uint32_t* __restrict__ plan, typename EF::Word* __restrict__ entries) {
     __shared__ uint32_t h[FBM_PARTS], base[FBM_PARTS];
     for (int i = threadIdx.x; i < FBM_PARTS; i += 256) h[i] = 0;
     __syncthreads();
@@ -115,9 +99,17 @@ __global__ __launch_bounds__(256) void k_fb_scatter(const Fr* __restrict__ scala
         const Fr k = scalars[t];
         fb_digits(k, [&](int v, uint32_t mag, bool neg, bool doubled) {
             const uint32_t p = mag >> 8, pos = base[p] + atomicAdd(&h[p], 1u);
-            entries[pos] = (mag & 255u) << 24 | (neg ? FBM_ENTRY_NEG : 0u) | (uint32_t)(((doubled ? FBM_WINDOWS : 0) + v) * npoints + j);
+            entries[pos] = EF::make(mag & 255u, neg, fb_row_index(v, doubled, npoints, j));
         });
     }
+}
+__global__ __launch_bounds__(256) void k_fb_scatter(const Fr* __restrict__ scalars, const uint32_t* __restrict__ pflag, int n, int npoints,
+                                                    uint32_t* __restrict__ plan, uint32_t* __restrict__ entries) {
+    fb_scatter_body<FbEntry32>(scalars, pflag, n, npoints, plan, entries);
+}
+__global__ __launch_bounds__(256) void k_fbp_scatter(const Fr* __restrict__ scalars, const uint32_t* __restrict__ pflag, int n, int npoints,
+                                                     uint32_t* __restrict__ plan, unsigned long long* __restrict__ entries) {
+    fb_scatter_body<FbEntry64>(scalars, pflag, n, npoints, plan, entries);
 }
 
 // table build, once per handle: jac[(v - 1) N + j] = 2^(16 v) P_j for v = 1 .. 15, jac[(15 + v) N + j] = 2^(16 v + 1) P_j for v = 0 .. 15
@@ -146,12 +138,71 @@ __global__ __launch_bounds__(64) void k_fb_build_rows(const G1Aff29Mem* __restri
     }
 }
 
+// table build of a PREPARED set (kzg_g1_points_prepare), one slice of m points [j0, j0 + m) of the set's npoints at a time: row0 = the
+// slice's decoded affine points, jac = what k_fb_build_rows made of them ([31][m]: jac row r becomes table row r + 1) -> the set's
+// affine rows[(r + 1) npoints + j0 + j] and rows[j0 + j] = P.  Lane j converts the 31 multiples of ITS point with one inversion
+// (Montgomery's trick, as k_mult_to_affine29: the prefix products are parked in the x slot of the output row until the backward sweep
+// overwrites it).  A flagged point (the identity) gets zero rows: no entry ever names them.
+__global__ __launch_bounds__(64) void k_fbp_rows_to_affine(const G1Aff29Mem* __restrict__ row0, const uint32_t* __restrict__ pflag, const G1Jac29Mem* __restrict__ jac,
+                                                           G1Aff29Mem* __restrict__ rows, int m, int npoints, int j0) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    constexpr int NR = 2 * FBM_WINDOWS - 1;
+    G1Aff29Mem* const col = rows + j0 + j;  // row r of this point: col[r * npoints]
+    if (pflag[j]) {
+        Fp29 z;
+#pragma unroll
+        for (int i = 0; i < 14; i++) z.l[i] = 0u;
+#pragma unroll 1
+        for (int r = 0; r <= NR; r++) g1a29_store(col[(size_t)r * npoints], z, z);
+        return;
+    }
+    {
+        const G1Aff29 a = g1a29_load(row0[j]);
+        g1a29_store(col[0], a.x, a.y);
+    }
+    Fp29 acc = fp29_const(cp29::FP29_ONE);
+#pragma unroll 1
+    for (int r = 0; r < NR; r++) {
+        fp29_store(col[(size_t)(r + 1) * npoints].x, acc);
+        acc = fp29_mul(acc, fp29_load(jac[(size_t)r * m + j].z));  // Z of 2^k P, P in G1 and not the identity: never 0 mod p
+    }
+    Fp29 inv = fp29_inverse(acc);
+#pragma unroll 1
+    for (int r = NR - 1; r >= 0; r--) {
+        G1Aff29Mem& o = col[(size_t)(r + 1) * npoints];
+        const G1Jac29Mem& q = jac[(size_t)r * m + j];
+        const Fp29 zi = fp29_mul(inv, fp29_load(o.x));  // 1 / Z_r
+        inv = fp29_mul(inv, fp29_load(q.z));
+        const Fp29 zi2 = fp29_sqr(zi), zi3 = fp29_mul(zi2, zi);
+        g1a29_store(o, fp29_mul(fp29_load(q.x), zi2), fp29_mul(fp29_load(q.y), zi3));  // < 2p
+    }
+}
+
+// table rows 0 (the points themselves) -> 48 compressed bytes each (flag != 0: the identity encoding): kzg_g1_points_point
+__global__ void k_fbp_row_compress(const G1Aff29Mem* __restrict__ row0, const uint32_t* __restrict__ pflag, uint8_t* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    G1Aff a;
+    a.x = FpF::zero();
+    a.y = FpF::zero();
+    const bool inf = pflag[i] != 0;
+    if (!inf) {
+        const G1Aff29 q = g1a29_load(row0[i]);
+        a.x = fp29_to_std(q.x);
+        a.y = fp29_to_std(q.y);
+    }
+    g1_compress(out + 48 * (size_t)i, a, inf);
+}
+
 // pass 2: workgroup blk = slice s of partition p: at most L entries, sorted by the low byte of the bucket number in LDS, one bucket
 // per lane (handed out by decreasing size), mixed additions of table rows with the digit's sign.  Leaves its 256 bucket sums in
 // save slot blk (point-major 48-word records: the format k_msm_bucket_fold reads).  Workgroups beyond the plan's total leave identities.
-__global__ __launch_bounds__(256, KZG_MSM_OCC) void k_fb_window(const uint32_t* __restrict__ entries, const uint32_t* __restrict__ plan,
-                                                                const G1Aff29Mem* __restrict__ rows, uint32_t* __restrict__ save, int L,
-                                                                unsigned long long* __restrict__ ktime) {
+// (EF: the entry format of `entries`; the sorted list keeps EF::lds(entry), 4 bytes, in either format)
+template <class EF>
+__device__ __forceinline__ void fb_window_body(const typename EF::Word* __restrict__ entries, const uint32_t* __restrict__ plan,
+                                               const G1Aff29Mem* __restrict__ rows, uint32_t* __restrict__ save, int L,
+                                               unsigned long long* __restrict__ ktime) {
     using CV = Curve29Aff;
     using Pt = typename CV::Pt;
     kstamp_in(ktime);
@@ -184,11 +235,11 @@ __global__ __launch_bounds__(256, KZG_MSM_OCC) void k_fb_window(const uint32_t* 
     const uint32_t c = plan[FBM_PLAN_OFF + p + 1] - plan[FBM_PLAN_OFF + p], ns = bstart[p + 1] - bstart[p], len = (c + ns - 1) / ns, sl = blk - bstart[p];
     const uint32_t e0 = plan[FBM_PLAN_OFF + p] + sl * len;
     const uint32_t m = sl * len < c ? min(len, c - sl * len) : 0u;
-    const uint32_t* const src = entries + e0;
+    const typename EF::Word* const src = entries + e0;
     cnt[tid] = 0;
     cur[tid] = 0;
     __syncthreads();
-    for (uint32_t t = tid; t < m; t += 256) atomicAdd(&cnt[src[t] >> 24], 1u);
+    for (uint32_t t = tid; t < m; t += 256) atomicAdd(&cnt[EF::low(src[t])], 1u);
     __syncthreads();
     if (tid == 0) {
         uint32_t s = 0;
@@ -200,8 +251,9 @@ __global__ __launch_bounds__(256, KZG_MSM_OCC) void k_fb_window(const uint32_t* 
     }
     __syncthreads();
     for (uint32_t t = tid; t < m; t += 256) {
-        const uint32_t e = src[t], dig = e >> 24;
-        fb_lst[off[dig] + atomicAdd(&cur[dig], 1u)] = e & (FBM_ENTRY_NEG | FBM_ENTRY_ROW_MASK);
+        const typename EF::Word e = src[t];
+        const uint32_t dig = EF::low(e);
+        fb_lst[off[dig] + atomicAdd(&cur[dig], 1u)] = EF::lds(e);
     }
     __threadfence_block();
     __syncthreads();
@@ -221,9 +273,9 @@ __global__ __launch_bounds__(256, KZG_MSM_OCC) void k_fb_window(const uint32_t* 
     // blk & 3 nor (blk >> 3) & 3 varies between the workgroups that share a CU: a multiplicative hash of the id does.
     const int bucket = cur[(tid + 64 * (int)((blk * 0x9E3779B1u) >> 30)) & 255];
     auto row_of = [&](uint32_t e) -> typename CV::Entry {
-        typename CV::Entry q = CV::load(rows[e & FBM_ENTRY_ROW_MASK]);
+        typename CV::Entry q = CV::load(rows[EF::lds_row(e)]);
         const Fp29 ny = fp29_neg<3>(q.y);  // rows hold y < 4p
-        const bool neg = (e & FBM_ENTRY_NEG) != 0;
+        const bool neg = EF::lds_neg(e);
 #pragma unroll
         for (int i = 0; i < 14; i++) q.y.l[i] = neg ? ny.l[i] : q.y.l[i];
         return q;
@@ -247,6 +299,17 @@ __global__ __launch_bounds__(256, KZG_MSM_OCC) void k_fb_window(const uint32_t* 
     for (uint32_t j = first; j < wr; j++) a = CV::add_entry(a, row_of(fb_lst[j]));  // rare
     put(bucket, a);
     kstamp_out(ktime);
+}
+__global__ __launch_bounds__(256, KZG_MSM_OCC) void k_fb_window(const uint32_t* __restrict__ entries, const uint32_t* __restrict__ plan,
+                                                                const G1Aff29Mem* __restrict__ rows, uint32_t* __restrict__ save, int L,
+                                                                unsigned long long* __restrict__ ktime) {
+    fb_window_body<FbEntry32>(entries, plan, rows, save, L, ktime);
+}
+// ... over a prepared set's rows (up to 32 x 2^20 of them: 8-byte entries)
+__global__ __launch_bounds__(256, KZG_MSM_OCC) void k_fbp_window(const unsigned long long* __restrict__ entries, const uint32_t* __restrict__ plan,
+                                                                 const G1Aff29Mem* __restrict__ rows, uint32_t* __restrict__ save, int L,
+                                                                 unsigned long long* __restrict__ ktime) {
+    fb_window_body<FbEntry64>(entries, plan, rows, save, L, ktime);
 }
 
 // R_p = the sum of everything partition p's workgroups accumulated (all 256 buckets of all its slices), as bucket p of a second
@@ -282,8 +345,10 @@ constexpr size_t fb_tail_bytes(int gp) { return 4 * ((size_t)MSM_FOLD_MAX_GROUPS
 inline unsigned fb_max_blocks(size_t n_entries, int L) { return (unsigned)(FBM_PARTS + (n_entries + (size_t)L - 1) / (size_t)L); }
 
 // Host side: scalars (canonical limbs, n of them) -> out_ab[0] = the sum (Jacobian, 12x32 form).  `entries`: 16 n words; `save`:
-// fb_max_blocks x 48 KB; `tmp`: fb_tail_bytes(gp); plan: FBM_PLAN_WORDS words.  Everything on `st`.
-inline hipError_t fb_msm_launch(const Fr* scalars, const uint32_t* pflag, int n, int npoints, const G1Aff29Mem* rows, uint32_t* plan, uint32_t* entries,
+// fb_max_blocks x 48 KB; `tmp`: fb_tail_bytes(gp); plan: FBM_PLAN_WORDS words.  Everything on `st`.  EF: the entry format (fb_entry.hpp) -
+// FbEntry32 over the setup's 4 096 points, FbEntry64 over a prepared set (`entries`: 16 n words of EF::Word either way).
+template <class EF = FbEntry32>
+inline hipError_t fb_msm_launch(const Fr* scalars, const uint32_t* pflag, int n, int npoints, const G1Aff29Mem* rows, uint32_t* plan, typename EF::Word* entries,
                                 uint32_t* save, uint8_t* tmp, G1Jac* out_ab, int L, int fold_per_min, unsigned long long* ktime, hipStream_t st,
                                 hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr) {
     const unsigned nb = (unsigned)((n + FBM_TERMS_PER_BLOCK - 1) / FBM_TERMS_PER_BLOCK);
@@ -291,10 +356,16 @@ inline hipError_t fb_msm_launch(const Fr* scalars, const uint32_t* pflag, int n,
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fb_count, dim3(nb), dim3(256), 0, st, scalars, pflag, n, npoints, plan);
     hipLaunchKernelGGL(k_fb_plan, dim3(1), dim3(64), 0, st, plan, L);
-    hipLaunchKernelGGL(k_fb_scatter, dim3(nb), dim3(256), 0, st, scalars, pflag, n, npoints, plan, entries);
     const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * n, L);
-    if ((e = DYN_LDS(k_fb_window, 4 * (size_t)L + 16)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fb_window, dim3(Z), dim3(256), 4 * (size_t)L + 16, st, (const uint32_t*)entries, (const uint32_t*)plan, rows, save, L, ktime);
+    if constexpr (EF::WIDE) {
+        hipLaunchKernelGGL(k_fbp_scatter, dim3(nb), dim3(256), 0, st, scalars, pflag, n, npoints, plan, entries);
+        if ((e = DYN_LDS(k_fbp_window, 4 * (size_t)L + 16)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_fbp_window, dim3(Z), dim3(256), 4 * (size_t)L + 16, st, (const unsigned long long*)entries, (const uint32_t*)plan, rows, save, L, ktime);
+    } else {
+        hipLaunchKernelGGL(k_fb_scatter, dim3(nb), dim3(256), 0, st, scalars, pflag, n, npoints, plan, entries);
+        if ((e = DYN_LDS(k_fb_window, 4 * (size_t)L + 16)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_fb_window, dim3(Z), dim3(256), 4 * (size_t)L + 16, st, (const uint32_t*)entries, (const uint32_t*)plan, rows, save, L, ktime);
+    }
     // C_l: every workgroup's bucket l, folded layer by layer (groups of `per` layers per thread, then a tree with four lanes per addition)
     const int per = std::max(fold_per_min, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS));
     int gp;
