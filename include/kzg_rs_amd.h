@@ -434,10 +434,24 @@ KzgRet kzg_cell_batch_challenges(uint8_t *r_out, const uint8_t *commitments, con
  * does: the equation holds whenever all 128 proofs are right, and could hold otherwise only if the hash-derived r_b were a root of
  * a fixed non-zero polynomial of degree < 128 over Fr (probability < 2^-246, the argument made for small batches at
  * kzg_verify_kzg_proof_batch) - so the verdict differs from the spec-challenge verdict with a probability below that.
- * The handle's lock is taken; a multi-device handle runs the call on its first device.  kzg_last_timings afterwards holds the
- * group call's slots, summed over the groups.  Two runs give the same bytes and verdicts: every device sum has a fixed order.
- * Measured (profiles/blob_cell_verify_probe.json): not yet measured on an MI355X. */
+ * Threads: call it from as many threads as you like on ONE shared handle (an execution client's transaction-pool threads, a blob
+ * transaction of 1 to 6 blobs each).  A call of 1 .. KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs does not take the handle's lock: it
+ * becomes a request of the handle's small-call queue (as kzg_verify_cell_kzg_proof_batch does), and the calls that wait while a
+ * launch is in flight leave TOGETHER - oldest first, up to 64 blobs in all - as the slots of one group on a private lane of the
+ * handle, every blob with its own challenge, sums and pairing instance.  ok_out, err_out and the return code are exactly the lone
+ * call's on the caller's own blobs: a wrong proof, a field element >= r or a point outside G1 in one caller's blobs never changes
+ * another caller's answer, and without err_out only the caller that brought the refused blob gets KZG_BADARGS (kzg_last_error on
+ * its thread: the reason of its first refused blob).  A caller that waits hashes its own challenges meanwhile.  A call that finds
+ * the handle idle runs at once and alone, on the path described above (no added wait); after it kzg_last_timings reports what it
+ * always did, after a shared launch the group call's slots for that launch.  Calls above KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs
+ * (an engine_getBlobsV2 answer), and every call on a handle made under KZG_OPTIONS blob_cell_coalesce=0 (or coalesce=0), run one at
+ * a time under the handle's lock as before.  A multi-device handle runs the call on its first device: the lanes that carry these
+ * launches are that device's.  kzg_last_timings after a locked call holds the group call's slots, summed over the groups.  Two
+ * runs give the same bytes and verdicts: every device sum has a fixed order.
+ * Measured (profiles/blob_cell_verify_probe.json, profiles/blob_cell_concurrent_probe.json): not yet measured on an
+ * MI355X. */
 #define KZG_BLOB_CELL_MAX_BLOBS 8192
+#define KZG_BLOB_CELL_COALESCE_MAX_BLOBS 16
 KzgRet kzg_verify_blob_cell_kzg_proofs(bool *ok_out, uint8_t *err_out, const uint8_t *blobs, const uint8_t *commitments,
                                        const uint8_t *cell_proofs, size_t n, const KzgSettings *s);
 /* The challenges r_b of the above alone: r_out = n x 32 big-endian bytes.  Pure host code - no handle, no device; nothing is
@@ -579,6 +593,18 @@ KzgRet kzg_debug_cell_queue_stats(const KzgSettings *s, uint64_t out[4], int res
 KzgRet kzg_debug_concurrent_cell_callers(double out[5], size_t threads, double seconds, const uint8_t *commitments,
                                          const uint64_t *cell_indices, const uint8_t *cells, const uint8_t *proofs,
                                          const size_t *batch_sizes, const uint8_t *expect, size_t n_calls, const KzgSettings *s);
+/* Diagnostic: the coalescing of concurrent kzg_verify_blob_cell_kzg_proofs calls on this handle since the last reset:
+ * out = { launches, calls carried (requests), blobs, the largest launch in calls }.  launches == requests: every call ran alone.
+ * All zero on a handle made with KZG_OPTIONS blob_cell_coalesce=0, and for calls above KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs. */
+KzgRet kzg_debug_blob_cell_queue_stats(const KzgSettings *s, uint64_t out[4], int reset);
+/* Measurement hook: `threads` host threads inside the library call kzg_verify_blob_cell_kzg_proofs on this one handle for
+ * `seconds`; the calls are n_calls slices of the three arrays, call after call, call i of call_sizes[i] blobs; expect[b] per blob =
+ * 0 false | 1 true | 2 refused.  A thread's calls pass err_out and omit it in turn: without it a call with a refused blob must
+ * return KZG_BADARGS, every other call its verdicts.  out = { calls completed, elapsed seconds, calls whose answer differs from
+ * expect, mean latency ms, longest latency ms }. */
+KzgRet kzg_debug_concurrent_blob_cell_callers(double out[5], size_t threads, double seconds, const uint8_t *blobs,
+                                              const uint8_t *commitments, const uint8_t *cell_proofs, const size_t *call_sizes,
+                                              const uint8_t *expect, size_t n_calls, const KzgSettings *s);
 /* Test hook: the two kernels of kzg_verify_blob_cell_kzg_proofs alone.  out[64 b + i] = coefficient I_i of blob b's aggregated
  * interpolant under the challenge r_be + 32 b (32 big-endian bytes per blob, reduced mod r), as 32 big-endian bytes.  Host
  * pointers; KZG_BADARGS for a field element >= r and for what the call itself refuses. */

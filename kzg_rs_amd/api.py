@@ -177,6 +177,8 @@ def lib():
         L.kzg_debug_concurrent_callers.argtypes = [C.POINTER(C.c_double), C.c_int, sz, C.c_double, u8, u8, u8, u8, u8, u8, sz, sz, vp]
         L.kzg_debug_cell_queue_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.kzg_debug_concurrent_cell_callers.argtypes = [C.POINTER(C.c_double), sz, C.c_double, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(sz), u8, sz, vp]
+        L.kzg_debug_blob_cell_queue_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.kzg_debug_concurrent_blob_cell_callers.argtypes = [C.POINTER(C.c_double), sz, C.c_double, u8, u8, u8, C.POINTER(sz), u8, sz, vp]
         _lib = L
     return _lib
 
@@ -323,11 +325,37 @@ class KzgSettings:
         _chk(lib().kzg_debug_cell_queue_stats(self._h, o, int(reset)))
         return dict(zip(("launches", "requests", "cells", "max_requests"), (int(x) for x in o)))
 
-    def concurrent_callers(self, kind, threads, seconds, c, p, expect, z=None, y=None, blobs=None, per_call=1):
+    def blob_cell_queue_stats(self, reset=False):
+        """Concurrent verify_blob_cell_kzg_proofs calls on this handle since the last reset (csrc/capi_blob_cells.hpp
+        small_run_blob_cells): {launches, requests (calls carried), blobs, max_requests (the largest launch, in calls)}.  All zero
+        with KZG_OPTIONS blob_cell_coalesce=0 and for calls above 16 blobs."""
+        o = (C.c_uint64 * 4)()
+        _chk(lib().kzg_debug_blob_cell_queue_stats(self._h, o, int(reset)))
+        return dict(zip(("launches", "requests", "blobs", "max_requests"), (int(x) for x in o)))
+
+    def concurrent_blob_cell_callers(self, threads, seconds, blobs, commitments, cell_proofs, call_sizes, expect):
+        """T host threads INSIDE the library calling verify_blob_cell_kzg_proofs on this one handle for `seconds`
+        (kzg_debug_concurrent_blob_cell_callers): call i is call_sizes[i] blobs of the three byte strings, call after call; expect
+        per BLOB (0 false / 1 true / 2 refused).  Returns {calls, seconds, calls_per_s, wrong, mean_ms, max_ms}."""
+        sizes = (C.c_size_t * len(call_sizes))(*call_sizes)
+        if sum(call_sizes) != len(expect) or len(blobs) != BYTES_PER_BLOB * len(expect) or len(commitments) != 48 * len(expect) \
+                or len(cell_proofs) != 48 * 128 * len(expect):
+            raise InvalidBytesLength("concurrent_blob_cell_callers: the arrays do not hold sum(call_sizes) blobs")
+        o = (C.c_double * 5)()
+        _chk(lib().kzg_debug_concurrent_blob_cell_callers(o, threads, float(seconds), bytes(blobs), bytes(commitments), bytes(cell_proofs), sizes,
+                                                         bytes(expect), len(call_sizes), self._h))
+        return {"calls": int(o[0]), "seconds": o[1], "calls_per_s": o[0] / o[1] if o[1] else 0.0, "wrong": int(o[2]), "mean_ms": o[3], "max_ms": o[4]}
+
+    def concurrent_callers(self, kind, threads, seconds, c, p, expect, z=None, y=None, blobs=None, per_call=1, call_sizes=None):
         """T host threads INSIDE the library (no interpreter lock) calling the public small entry points on this one handle for
         `seconds`, every answer checked against `expect` (0 false / 1 true / 2 Err): kind "proof" = verify_kzg_proof per tuple,
         "blobs" = verify_blob_kzg_proof_batch of per_call blobs (expect per call), "proofs" = kzg_verify_kzg_proofs of per_call
-        tuples (expect per tuple).  Returns {calls, seconds, calls_per_s, wrong, mean_ms, max_ms}."""
+        tuples (expect per tuple), "blob_cells" = verify_blob_cell_kzg_proofs of call_sizes[i] blobs (default: per_call each; c the
+        commitments, p the cell proofs, expect per blob: concurrent_blob_cell_callers).
+        Returns {calls, seconds, calls_per_s, wrong, mean_ms, max_ms}."""
+        if kind == "blob_cells":
+            sizes = list(call_sizes) if call_sizes is not None else [per_call] * (len(expect) // per_call)
+            return self.concurrent_blob_cell_callers(threads, seconds, blobs, c, p, sizes, expect)
         k = {"proof": 0, "blobs": 1, "proofs": 2}[kind]
         n_items = len(c) // 48
         o = (C.c_double * 5)()

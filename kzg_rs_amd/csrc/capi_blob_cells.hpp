@@ -16,6 +16,13 @@
 //   device  k_blob_cell_scalars: r^c, r^c g_c, sum r^c, -I_i into the shared scalar layout
 // The spec's transcript hashes the cells, which are never formed here; the cells are a function of the blob, so this transcript fixes
 // every coefficient of the polynomial in r that the pairing tests as the spec's does (kzg_rs_amd.h).
+//
+// Concurrent callers of one handle (transaction-pool threads, a blob transaction of 1 to 6 blobs each): a call of up to
+// KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs is a request of the small-call queue's fourth kind (small_queue.hpp BLOB_CELLS).  A leader
+// takes what is queued, oldest first, up to 64 blobs, and runs it as ONE group on its lane (small_run_blob_cells below): the blobs of
+// the requests are the group's slots, one behind the other, each with its own challenge, status word, two sums and pairing instance
+// - so a request's verdicts, error flags and return code are the lone call's on its own blobs.  A launch of one request is
+// blob_cell_call_locked, the code the handle's lock guards, on the lane.
 
 constexpr size_t BLOB_CELL_MAX_BLOBS = 8192;   // blobs per call (2^20 cell proofs)
 constexpr size_t BLOB_CELL_GROUP = 64;         // blobs per group of launches
@@ -82,7 +89,8 @@ static void blob_cell_plan(CellGroupPlan& P, size_t G) {
 
 // ---------------------------------------------------------------- the scalar stage
 struct BlobCellStage : CellGroupStage {
-    const uint8_t* blobs = nullptr;  // the group's blobs (host)
+    const uint8_t* blobs = nullptr;  // the group's blobs (host), one behind the other
+    const uint8_t* const* slot_blobs = nullptr;  // ... or (a launch of several callers' requests) the blob of slot g where its caller keeps it
     const Fr29Mem* W = nullptr;      // the twiddle table of the handle's cell prover state
     BlobCellStage() { why_bad = "a blob holds a field element >= r"; }
     KzgRet reserve(CellState& cs, const CellGroupPlan& P) override {
@@ -101,7 +109,13 @@ struct BlobCellStage : CellGroupStage {
         hipStream_t st = s->s1;
         HIPCHK(hipMemcpyAsync(b.d_idx.p, P.idx.data(), 4 * P.idx.size(), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(b.d_bad.p, 0, 4 * (size_t)P.nG, st));
-        HIPCHK(hipMemcpyAsync(cs.blob.d_blobs.p, blobs, (size_t)BLOB_BYTES * P.G, hipMemcpyHostToDevice, st));
+        if (!slot_blobs) HIPCHK(hipMemcpyAsync(cs.blob.d_blobs.p, blobs, (size_t)BLOB_BYTES * P.G, hipMemcpyHostToDevice, st));
+        for (uint32_t g = 0; slot_blobs && g < P.G;) {  // the blobs of one request lie one behind the other: one copy
+            uint32_t to = g + 1;
+            while (to < P.G && slot_blobs[to] == slot_blobs[to - 1] + BLOB_BYTES) to++;
+            HIPCHK(hipMemcpyAsync(cs.blob.d_blobs.p + (size_t)BLOB_BYTES * g, slot_blobs[g], (size_t)BLOB_BYTES * (to - g), hipMemcpyHostToDevice, st));
+            g = to;
+        }
         hipLaunchKernelGGL(k_blob_cell_coef, dim3(P.G), dim3(CELL_NTT_THREADS), CELL_NTT_LDS, st, (const uint8_t*)cs.blob.d_blobs.p, W, cs.blob.d_coef.p, b.d_bad.p,
                            (int)CELLS_PER_EXT_BLOB);
         HIPCHK(hipGetLastError());
@@ -116,10 +130,17 @@ struct BlobCellStage : CellGroupStage {
         return KZG_OK;
     }
 };
-// the caller holds the handle's lock: the plain stream pair selected, the twiddle table made, the transform's LDS granted
+// the caller holds the handle's lock (a lane of the small-call queue is private to its leader): the plain stream pair selected, the
+// twiddle table made, the transform's LDS granted
 static KzgRet blob_cell_stage_ready(const KzgSettings* s, BlobCellStage& stage) {
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);
+    if (s->cell_home) {  // a lane: the table of the handle it serves (blob_cell_setup_once has run before anything was queued)
+        if (!s->cell_home->blob_cells_built.load(std::memory_order_acquire)) return fail(KZG_ERROR, "a lane ran a blob-cell launch before its handle's twiddle table was made");
+        if (DYN_LDS(k_blob_cell_coef, CELL_NTT_LDS) != hipSuccess) return fail(KZG_ERROR, "k_blob_cell_coef: the device refuses 144 KB of LDS per workgroup");
+        stage.W = s->cell_home->blob_cell_W;
+        return KZG_OK;
+    }
     CellProverState* cp = nullptr;
     const KzgRet rc = cell_prover_state(s, &cp);
     if (rc != KZG_OK) return rc;
@@ -129,19 +150,11 @@ static KzgRet blob_cell_stage_ready(const KzgSettings* s, BlobCellStage& stage) 
 }
 
 // ---------------------------------------------------------------- the entry point
-extern "C" KzgRet kzg_verify_blob_cell_kzg_proofs(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments,
-                                                  const uint8_t* cell_proofs, size_t n, const KzgSettings* s) try {
-    if (!s || (n && (!ok_out || !blobs || !commitments || !cell_proofs))) return fail(KZG_BADARGS, "null argument");
-    KzgRet rc = cells_ready(s);
-    if (rc != KZG_OK) return rc;
-    if (n > BLOB_CELL_MAX_BLOBS) return fail(KZG_BADARGS, "kzg_verify_blob_cell_kzg_proofs: more than 8192 blobs");
-    if (n == 0) return KZG_OK;
-    const auto t_call = std::chrono::steady_clock::now();
-    for (size_t b = 0; b < n; b++) {
-        ok_out[b] = false;
-        if (err_out) err_out[b] = 0;
-    }
-    std::lock_guard<std::mutex> lk(s->mu);
+// The call on handle s, whose lock the caller holds (a lane of the small-call queue is private to its leader); ok_out and err_out
+// start cleared.  why_out (optional) [b] = the reason of a blob with err_out set.  May throw std::bad_alloc.
+static KzgRet blob_cell_call_locked(bool* ok_out, uint8_t* err_out, const char** why_out, const uint8_t* blobs, const uint8_t* commitments,
+                                    const uint8_t* cell_proofs, size_t n, std::chrono::steady_clock::time_point t_call, const KzgSettings* s) {
+    KzgRet rc = KZG_OK;
     BlobCellStage stage;
     if ((rc = blob_cell_stage_ready(s, stage)) != KZG_OK) return rc;
     const std::vector<size_t> sizes(std::min(n, BLOB_CELL_GROUP), (size_t)CELLS_PER_EXT_BLOB);
@@ -163,14 +176,291 @@ extern "C" KzgRet kzg_verify_blob_cell_kzg_proofs(bool* ok_out, uint8_t* err_out
         hash.start();
         stage.blobs = hin.blobs;
         float stage_ms[4] = {};
-        if ((rc = cell_group_locked(ok_out + lo, err_out ? err_out + lo : nullptr, nullptr, in, P, hash, r_be.data(), s, stage_ms, &stage)) != KZG_OK) return rc;
+        if ((rc = cell_group_locked(ok_out + lo, err_out ? err_out + lo : nullptr, why_out ? why_out + lo : nullptr, in, P, hash, r_be.data(), s, stage_ms, &stage)) != KZG_OK)
+            return rc;
         for (int i = 0; i < 4; i++) total_ms[i] += stage_ms[i];
         hash_ms += hash.ms();
     }
     cell_group_timings(s, t_call, hash_ms, total_ms, none);
     return KZG_OK;
+}
+static KzgRet blob_cell_setup_once(const KzgSettings* s);
+static KzgRet small_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments, const uint8_t* cell_proofs, size_t n,
+                               const KzgSettings* s);
+extern "C" KzgRet kzg_verify_blob_cell_kzg_proofs(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments,
+                                                  const uint8_t* cell_proofs, size_t n, const KzgSettings* s) try {
+    if (!s || (n && (!ok_out || !blobs || !commitments || !cell_proofs))) return fail(KZG_BADARGS, "null argument");
+    KzgRet rc = cells_ready(s);
+    if (rc != KZG_OK) return rc;
+    if (n > BLOB_CELL_MAX_BLOBS) return fail(KZG_BADARGS, "kzg_verify_blob_cell_kzg_proofs: more than 8192 blobs");
+    if (n == 0) return KZG_OK;
+    const auto t_call = std::chrono::steady_clock::now();
+    for (size_t b = 0; b < n; b++) {
+        ok_out[b] = false;
+        if (err_out) err_out[b] = 0;
+    }
+    // Concurrent callers of one handle: a call of up to KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs becomes a request of the handle's
+    // small-call queue and rides - with whatever else is waiting - as slots of one group on a private lane (small_blob_cells
+    // below).  A lone caller's launch of one is blob_cell_call_locked, on the lane.  Larger calls, and every call with option
+    // blob_cell_coalesce=0, take the handle's own lock.
+    if (small_enabled(s) && small_blob_cells_queued(*s->small, n)) {
+        if ((rc = cells_setup_once(s)) != KZG_OK || (rc = blob_cell_setup_once(s)) != KZG_OK) return rc;
+        return small_blob_cells(ok_out, err_out, blobs, commitments, cell_proofs, n, s);
+    }
+    std::lock_guard<std::mutex> lk(s->mu);
+    return blob_cell_call_locked(ok_out, err_out, nullptr, blobs, commitments, cell_proofs, n, t_call, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
+}
+
+// ---------------------------------------------------------------- concurrent calls: requests of the small-call queue
+// What a lane borrows from the handle it serves, made before the first request is queued: the twiddle table (the cell prover's
+// state, under the handle's lock as the direct path makes it).  One atomic load per call once it exists.
+static KzgRet blob_cell_setup_once(const KzgSettings* s) {
+    if (s->blob_cells_built.load(std::memory_order_acquire)) return KZG_OK;
+    std::lock_guard<std::mutex> lk(s->mu);
+    BlobCellStage stage;
+    const KzgRet rc = blob_cell_stage_ready(s, stage);
+    if (rc != KZG_OK) return rc;
+    s->blob_cell_W = stage.W;
+    s->blob_cells_built.store(true, std::memory_order_release);
+    return KZG_OK;
+}
+// The challenge of blob b of request r, by whoever comes first; false: somebody else has it, or has had it
+static bool small_blob_cell_hash_one(SmallReq& r, size_t b) {
+    int idle = 0;
+    if (r.blob_r_state[b].load(std::memory_order_relaxed) != 0 || !r.blob_r_state[b].compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return false;
+    blob_cell_challenge(r.blob_r + 32 * b, r.blobs + (size_t)BLOB_BYTES * b, r.c + 48 * b, r.p + BLOB_CELL_PROOFS_BYTES * b);
+    r.blob_r_state[b].store(2, std::memory_order_release);
+    return true;
+}
+// what the owner of a queued request does instead of sleeping: one more of its own blobs' challenges (the leader collects them)
+static bool small_blob_cell_wait_work(SmallReq& r) {
+    for (size_t b = 0; b < r.n; b++)
+        if (small_blob_cell_hash_one(r, b)) return true;
+    return false;
+}
+// slot g of a launch = blob `b` of request `r`
+struct BlobCellSlot {
+    SmallReq* r;
+    size_t b;
+};
+static void small_blob_cell_slot_hash(uint8_t r_be[32], const void* ctx, size_t g) {
+    const BlobCellSlot& sl = static_cast<const BlobCellSlot*>(ctx)[g];
+    // (a blob its owner is at: one chain of 137 KB, ~0.1 ms)
+    if (!small_blob_cell_hash_one(*sl.r, sl.b))
+        while (sl.r->blob_r_state[sl.b].load(std::memory_order_acquire) != 2) std::this_thread::yield();
+    memcpy(r_be, sl.r->blob_r + 32 * sl.b, 32);
+}
+// A lane's buffers for the largest launch, made by its first launch of this kind: a buffer that grew with the launches would free
+// and allocate device memory in the middle of the traffic (capi_coalesce.hpp small_lane_make).  Released with the lane.
+static KzgRet blob_cell_lane_reserve(const KzgSettings* l) {
+    HIPCHK(hipSetDevice(l->device));
+    select_streams(l, (size_t)-1);
+    CellState* cs = nullptr;
+    KzgRet rc = cells_state(l, &cs);
+    if (rc != KZG_OK) return rc;
+    if (cs->blob.d_coef.cap >= (size_t)FE_PER_BLOB * BLOB_CELL_GROUP) return KZG_OK;
+    CellGroupPlan P;
+    blob_cell_plan(P, BLOB_CELL_GROUP);
+    BlobCellStage stage;
+    if (!cs->group) cs->group = new CellGroupBufs();
+    const uint32_t NP = cell_group_points(P.nG, P.mtot);
+    auto up = [](size_t x) { return (x + 63) & ~(size_t)63; };
+    const size_t h_bytes = up(48 * (size_t)NP) + up(4 * (size_t)NP) + up(4 * (size_t)P.nG) + up(32 * (size_t)P.G) + up(4 * (size_t)P.G) + sizeof(Fp) * 6 * P.G;
+    if ((rc = stage.reserve(*cs, P)) != KZG_OK || (rc = cs->group->reserve(P.G, NP, (size_t)2 * P.G * P.max_rl, h_bytes, msm_affine_enabled())) != KZG_OK) return rc;
+    return msm_save_reserve(l, MSM_WINDOWS / MSM_CHUNKS, MSM_CHUNKS / msm_chunks_per_block(P.G), 2 * P.G);
+}
+// the launch of one leader on lane L (capi_coalesce.hpp small_submit): requests of kind BLOB_CELLS, m blobs in all (m <= 64)
+static KzgRet small_run_blob_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m) {
+    const KzgSettings* l = L.h;
+    const auto t_call = std::chrono::steady_clock::now();
+    KzgRet rc = blob_cell_lane_reserve(l);
+    if (rc != KZG_OK) return rc;
+    if (m == 0 || m > BLOB_CELL_GROUP) return fail(KZG_ERROR, "small-call queue: a blob-cell launch outside the group's range");
+    std::vector<const char*> why(m, nullptr);
+    auto refuse = [](SmallReq& r, const char* const* w) {  // the message of the first blob refused
+        for (size_t b = 0; b < r.n; b++)
+            if (r.err[b]) {
+                snprintf(r.msg, sizeof r.msg, "%s", w[b] ? w[b] : "invalid argument");
+                return;
+            }
+    };
+    if (batch.size() == 1) {  // nobody else was waiting: the call as it was (its owner has hashed nothing: it found a lane at once)
+        SmallReq& r = *batch[0];
+        if ((rc = blob_cell_call_locked(r.ok, r.err, why.data(), r.blobs, r.c, r.p, r.n, t_call, l)) != KZG_OK) return rc;
+        refuse(r, why.data());
+        return KZG_OK;
+    }
+    std::vector<const uint8_t*> c(m), p(m), bl(m);
+    std::vector<BlobCellSlot> slots(m);
+    std::vector<uint8_t> okerr(2 * m, 0), r_be(32 * m);
+    const std::vector<size_t> sizes(m, (size_t)CELLS_PER_EXT_BLOB);
+    size_t g = 0, pending = 0;
+    for (SmallReq* r : batch)
+        for (size_t b = 0; b < r->n; b++, g++) {
+            c[g] = r->c + 48 * b, p[g] = r->p + BLOB_CELL_PROOFS_BYTES * b, bl[g] = r->blobs + (size_t)BLOB_BYTES * b;
+            slots[g] = BlobCellSlot{r, b};
+            pending += r->blob_r_state[b].load(std::memory_order_relaxed) == 0;
+        }
+    if (g != m) return fail(KZG_ERROR, "small-call queue: a blob-cell launch whose requests do not add up");
+    bool* const ok = reinterpret_cast<bool*>(okerr.data());
+    uint8_t* const err = okerr.data() + m;
+    CellGroupPlan P;
+    blob_cell_plan(P, m);
+    BlobCellStage stage;
+    if ((rc = blob_cell_stage_ready(l, stage)) != KZG_OK) return rc;
+    stage.slot_blobs = bl.data();
+    const CellGroupIn in{c.data(), nullptr, nullptr, p.data(), sizes.data(), m};
+    CellGroupHash hash;  // (declared after what its helper threads read and write: joined first)
+    hash.r_be = r_be.data(), hash.count = m;
+    hash.slot_hash = small_blob_cell_slot_hash, hash.slot_ctx = slots.data(), hash.slot_bytes = (size_t)BLOB_BYTES + BLOB_CELL_PROOFS_BYTES + 88;
+    hash.slot_pending = pending;
+    hash.start();
+    float stage_ms[4] = {};
+    const float none[8] = {};
+    if ((rc = cell_group_locked(ok, err, why.data(), in, P, hash, r_be.data(), l, stage_ms, &stage)) != KZG_OK) return rc;
+    cell_group_timings(l, t_call, hash.ms(), stage_ms, none);
+    g = 0;
+    for (SmallReq* r : batch) {
+        for (size_t b = 0; b < r->n; b++) r->ok[b] = ok[g + b], r->err[b] = err[g + b];
+        refuse(*r, why.data() + g);
+        g += r->n;
+    }
+    return KZG_OK;
+}
+// one call as a request: returns when its launch is done.  The results land in buffers of the request's own and reach the
+// caller's as the lone call leaves them: without err_out a refused blob is the call's KZG_BADARGS and ok_out stays cleared.
+static KzgRet small_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments, const uint8_t* cell_proofs, size_t n,
+                               const KzgSettings* s) {
+    enum : size_t { N = KZG_BLOB_CELL_COALESCE_MAX_BLOBS };  // (blobs of a request at most)
+    SmallReq r;
+    bool ok[N] = {};
+    uint8_t err[N] = {}, r_be[32 * N];
+    std::atomic<int> r_state[N];
+    for (auto& x : r_state) x.store(0, std::memory_order_relaxed);
+    r.kind = SmallReq::BLOB_CELLS;
+    r.n = n;
+    r.blobs = blobs;
+    r.c = commitments;
+    r.p = cell_proofs;
+    r.ok = ok;
+    r.err = err;
+    r.blob_r = r_be;
+    r.blob_r_state = r_state;
+    r.wait_work = small_blob_cell_wait_work;
+    const KzgRet rc = small_submit(s, r);
+    if (rc != KZG_OK) return rc;
+    for (size_t b = 0; b < n && !err_out; b++)
+        if (err[b]) return fail(KZG_BADARGS, r.msg);
+    for (size_t b = 0; b < n; b++) {
+        ok_out[b] = ok[b];
+        if (err_out) err_out[b] = err[b];
+    }
+    return KZG_OK;
+}
+
+// diagnostic: launches | requests | blobs | the largest launch in requests - of the BLOB_CELLS kind alone, since the last reset
+extern "C" KzgRet kzg_debug_blob_cell_queue_stats(const KzgSettings* s, uint64_t out[4], int reset) {
+    if (!s || !out) return fail(KZG_BADARGS, "null argument");
+    memset(out, 0, 4 * sizeof(uint64_t));
+    if (!s->small) return KZG_OK;
+    SmallQueue& Q = *s->small;
+    std::lock_guard<SmallSpinLock> lk(Q.mu);
+    out[0] = Q.blob_cell_launches;
+    out[1] = Q.blob_cell_requests;
+    out[2] = Q.blob_cell_items;
+    out[3] = Q.blob_cell_max_requests;
+    if (reset) Q.blob_cell_launches = Q.blob_cell_requests = Q.blob_cell_items = Q.blob_cell_max_requests = 0;
+    return KZG_OK;
+}
+
+// measurement hook, after kzg_debug_concurrent_cell_callers: T host threads inside the library (no interpreter lock, no ctypes)
+// calling kzg_verify_blob_cell_kzg_proofs on ONE shared handle for `seconds`.  The calls: n_calls slices of the three arrays, call
+// after call, call i of call_sizes[i] blobs; expect[b] per blob: 0 false | 1 true | 2 refused.  Thread t takes calls t, t + T, ...;
+// its calls pass err_out and every second one of them does not - that one must return KZG_BADARGS exactly when a blob of the call
+// is refused, and the call's verdicts otherwise.  A call that differs in any blob or in its return code counts once in out[2].
+// out: [0] calls completed, [1] elapsed seconds, [2] answers that differ from `expect`, [3] mean latency in ms, [4] the longest.
+extern "C" KzgRet kzg_debug_concurrent_blob_cell_callers(double out[5], size_t threads, double seconds, const uint8_t* blobs, const uint8_t* commitments,
+                                                         const uint8_t* cell_proofs, const size_t* call_sizes, const uint8_t* expect, size_t n_calls,
+                                                         const KzgSettings* s) try {
+    if (!out || !s || !blobs || !commitments || !cell_proofs || !call_sizes || !expect || !threads || !n_calls) return fail(KZG_BADARGS, "bad argument");
+    std::vector<size_t> off(n_calls + 1, 0);
+    size_t longest = 0;
+    for (size_t i = 0; i < n_calls; i++) off[i + 1] = off[i] + call_sizes[i], longest = std::max(longest, call_sizes[i]);
+    std::atomic<uint64_t> calls{0}, wrong{0};
+    std::atomic<bool> stop{false};
+    std::mutex go_mu;  // (the threads wait for the start asleep)
+    std::condition_variable go_cv;
+    bool go = false;
+    std::vector<double> lat_sum(threads, 0.0), lat_max(threads, 0.0);
+    auto body = [&](size_t t) {
+        std::vector<uint8_t> oks(longest + 1), errs(longest + 1);
+        {
+            std::unique_lock<std::mutex> lk(go_mu);
+            go_cv.wait(lk, [&] { return go; });
+        }
+        // (independent callers do not arrive in lock-step: a fixed pseudo-random offset below 2.5 ms per thread)
+        std::this_thread::sleep_for(std::chrono::microseconds((uint32_t)(t * 2654435761u) % 2500u));
+        uint64_t round = 0;
+        for (size_t i = t % n_calls; !stop.load(std::memory_order_relaxed); i = (i + threads) % n_calls, round++) {
+            const size_t e = off[i], n = call_sizes[i];
+            const bool with_err = (round & 1) == 0;
+            const auto t0 = std::chrono::steady_clock::now();
+            const KzgRet rc = kzg_verify_blob_cell_kzg_proofs(reinterpret_cast<bool*>(oks.data()), with_err ? errs.data() : nullptr, blobs + (size_t)BLOB_BYTES * e,
+                                                              commitments + 48 * e, cell_proofs + BLOB_CELL_PROOFS_BYTES * e, n, s);
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            bool refused = false, bad = false;
+            for (size_t b = 0; b < n; b++) refused |= expect[e + b] == 2;
+            if (!with_err && refused) bad = rc != KZG_BADARGS;
+            else if (rc != KZG_OK) bad = true;
+            else
+                for (size_t b = 0; b < n; b++) bad |= ((with_err && errs[b]) ? 2 : oks[b] ? 1 : 0) != expect[e + b];
+            lat_sum[t] += ms;
+            lat_max[t] = std::max(lat_max[t], ms);
+            if (bad) wrong.fetch_add(1, std::memory_order_relaxed);
+            calls.fetch_add(1, std::memory_order_relaxed);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        pool.reserve(threads);
+        for (size_t t = 0; t < threads; t++) pool.emplace_back(body, t);
+    } catch (...) {  // (no more threads to be had: the ones made leave at once)
+        stop.store(true);
+        {
+            std::lock_guard<std::mutex> lk(go_mu);
+            go = true;
+        }
+        go_cv.notify_all();
+        for (auto& th : pool) th.join();
+        return fail(KZG_ERROR, "kzg_debug_concurrent_blob_cell_callers: could not start the threads");
+    }
+    std::this_thread::sleep_for(std::chrono::milliseconds(20));  // (every thread has reached its wait)
+    {
+        std::lock_guard<std::mutex> lk(go_mu);
+        go = true;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    go_cv.notify_all();
+    std::this_thread::sleep_for(std::chrono::duration<double>(seconds));
+    const uint64_t counted = calls.load();  // (calls completed inside the interval)
+    const double elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    stop.store(true);
+    for (auto& th : pool) th.join();
+    double ls = 0, lm = 0;
+    for (size_t t = 0; t < threads; t++) {
+        ls += lat_sum[t];
+        lm = std::max(lm, lat_max[t]);
+    }
+    out[0] = (double)counted;
+    out[1] = elapsed_s;
+    out[2] = (double)wrong.load();
+    out[3] = calls.load() ? ls / (double)calls.load() : 0.0;
+    out[4] = lm;
+    return KZG_OK;
+} catch (const std::exception& e) {
+    return fail(KZG_ERROR, std::string("kzg_debug_concurrent_blob_cell_callers: ") + e.what());
 }
 
 // test hook (tests/test_gpu_blob_cells.py): the two kernels alone.  out[64 b + i] = I_i of blob b under the challenge r_be + 32 b

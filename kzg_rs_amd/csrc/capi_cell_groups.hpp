@@ -69,6 +69,7 @@ struct CellGroupHash {
     void (*slot_hash)(uint8_t r_be[32], const void* ctx, size_t j) = nullptr;
     const void* slot_ctx = nullptr;
     size_t slot_bytes = 0;
+    size_t slot_pending = (size_t)-1;  // ... of which at most this many are still to be hashed (the others are only collected): sizes the helpers
     size_t count = 0;
     std::atomic<size_t> next{0};
     std::atomic<bool> failed{false};
@@ -123,7 +124,7 @@ struct CellGroupHash {
     }
     // up to host_threads - 1 helpers, one per 128 KB of transcript at most (a thread costs more than a short chain)
     void start() {
-        size_t bytes = slot_hash ? count * slot_bytes : 0;
+        size_t bytes = slot_hash ? std::min(count, slot_pending) * slot_bytes : 0;
         for (size_t j = 0; j < count && !slot_hash; j++) {
             const size_t b = plan ? plan->slot_batch[j] : j;
             if (known && known[b].state && known[b].state->load(std::memory_order_relaxed) != 0) continue;

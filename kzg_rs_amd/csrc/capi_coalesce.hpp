@@ -28,6 +28,9 @@
 //     of them (128 x T cells at most) as the slots of one cell group (capi_cell_groups.hpp small_run_cells), each with its own
 //     transcript - hashed by its owner while it waits - and its own pairing instance.  A multi-device handle has the cell
 //     set-up on its first device only, so these launches keep to that device's lanes (SmallQueue::cell_lane_stride).
+//   * a fourth kind is one kzg_verify_blob_cell_kzg_proofs call of up to 16 blobs (a blob transaction's): a launch carries up to 64
+//     blobs as the slots of one blob-cell group (capi_blob_cells.hpp small_run_blob_cells), every blob with its own challenge -
+//     hashed by its owner while it waits - its own two sums and pairing instance; on the cell set-up's device, like the third kind.
 // Results are per request: a wrong proof, a non-canonical scalar, an undecodable or off-subgroup point in one caller's input
 // never changes another caller's answer (the instances share a launch, not a random linear combination).
 // z = tau (the pairing's G2 point is the identity: only for who knows the setup's secret, i.e. test rigs) is flagged per item;
@@ -163,6 +166,7 @@ static KzgRet small_lane_make(SmallLane& L, const SmallQueue& Q, const KzgSettin
 }
 
 static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m);  // (capi_cell_groups.hpp)
+static KzgRet small_run_blob_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m);  // (capi_blob_cells.hpp)
 
 // Submit a request and return when it is done (small_queue.hpp small_submit_core); the launch a leader runs on its lane:
 static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
@@ -191,7 +195,8 @@ static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
         }
         if (rc == KZG_OK) {
             try {
-                rc = kind == SmallReq::PROOFS ? small_run_proofs(L, batch, m) : kind == SmallReq::BLOBS ? small_run_blobs(L, batch, m) : small_run_cells(L, batch, m);
+                rc = kind == SmallReq::PROOFS ? small_run_proofs(L, batch, m) : kind == SmallReq::BLOBS ? small_run_blobs(L, batch, m)
+                   : kind == SmallReq::CELLS ? small_run_cells(L, batch, m) : small_run_blob_cells(L, batch, m);
                 if (rc != KZG_OK) msg = g_err;
             } catch (const std::bad_alloc&) {
                 rc = KZG_MALLOC;

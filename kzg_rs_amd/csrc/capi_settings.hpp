@@ -126,6 +126,10 @@ struct KzgSettings {
     mutable struct CellState* cells = nullptr;    // the cell-proof entry points' tables and buffers, made by the first of those calls (capi_cells.hpp)
     mutable std::atomic<bool> cells_built{false};  // ... its set-up is derived (read without the lock by a call about to be queued: cells_setup_once)
     const KzgSettings* cell_home = nullptr;       // a lane of the small-call queue: the handle whose cell set-up it reads (its CellState holds buffers alone)
+    // kzg_verify_blob_cell_kzg_proofs as a request of the small-call queue: the twiddle table of the cell prover's state and the
+    // transform's LDS grant, made before the first such call is queued (blob_cell_setup_once) - a lane reads them through cell_home
+    mutable std::atomic<bool> blob_cells_built{false};
+    mutable const Fr29Mem* blob_cell_W = nullptr;
     mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
     mutable struct CellRecoverState* cell_recover = nullptr;  // cell recovery's own buffers, made by its first call (capi_cell_recover.hpp)
     mutable struct G1PointsBufs* g1_points = nullptr;  // kzg_g1_msm_prepared's call buffers, made by its first call (capi_g1_points.hpp)
@@ -270,6 +274,9 @@ static KzgRet settings_common(KzgSettings** out, const uint8_t tau_g2[96]) {
         s->small->cells_on = opt_flag("cell_coalesce", true);
         s->small->cap_cell_requests = (size_t)std::max(1L, std::min(128L, ab_int("small_cap_cell_requests", 128)));
         s->small->cap_cells = (size_t)std::max(1L, std::min(128L * (long)CELL_GROUP_MAX_CELLS, ab_int("small_cap_cells", 128L * (long)CELL_GROUP_MAX_CELLS)));
+        // concurrent kzg_verify_blob_cell_kzg_proofs calls of up to KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs (option blob_cell_coalesce=0:
+        // every call under the handle's own lock, as before); a launch carries up to 64 blobs, that call's group size
+        s->small->blob_cells_on = opt_flag("blob_cell_coalesce", true);
     }
     *out = s;
     return KZG_OK;

@@ -1,8 +1,9 @@
 // small_queue.hpp - the small-call queue of a settings handle: requests, lanes, waiting and waking, and the submit loop with the
 // launch itself left to the caller (capi_coalesce.hpp supplies the GPU launch).  Plain C++17 + Linux futexes, no HIP: part of the
 // translation unit kzg_capi.hip, and compiled on its own with g++ -fsanitize=thread by tests/test_small_queue_host.py
-// (tests/host/small_queue_main.cpp: hundreds of threads, a stand-in launch, every result checked, no lost wake-up, no race) and by
-// tests/test_small_queue_cells_host.py (tests/host/small_queue_cells_main.cpp: the same with the third request kind among them).
+// (tests/host/small_queue_main.cpp: hundreds of threads, a stand-in launch, every result checked, no lost wake-up, no race), by
+// tests/test_small_queue_cells_host.py (tests/host/small_queue_cells_main.cpp: the same with the third request kind among them) and
+// by tests/test_small_queue_blob_cells_host.py (tests/host/small_queue_blob_cells_main.cpp: the fourth kind).
 #pragma once
 #include <linux/futex.h>
 #include <stdint.h>
@@ -27,9 +28,11 @@
 // and proofs; every item gets its own pairing and the request gets its own results - what the entry point makes of them
 // (one verdict, a conjunction, a verdict per item) is the submitter's business.  The third kind is one call of the cell-proof
 // verifier: n cells with their commitments, cell indices and proofs, ONE verdict - the requests of a launch ride as the slots of a
-// group launch (capi_cell_groups.hpp), each with its own batch challenge.
+// group launch (capi_cell_groups.hpp), each with its own batch challenge.  The fourth kind is one call of
+// kzg_verify_blob_cell_kzg_proofs: n <= KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs with their commitments and 128 cell proofs each, a
+// verdict and an error flag PER BLOB - the blobs of a launch's requests are the slots of one blob-cell group (capi_blob_cells.hpp).
 struct SmallReq {
-    enum Kind { PROOFS = 0, BLOBS = 1, CELLS = 2 };
+    enum Kind { PROOFS = 0, BLOBS = 1, CELLS = 2, BLOB_CELLS = 3 };
     Kind kind = PROOFS;
     size_t n = 0;
     const uint8_t *c = nullptr, *p = nullptr;  // n x 48 bytes each
@@ -45,6 +48,11 @@ struct SmallReq {
     uint8_t r_be[32] = {0};
     std::atomic<int> r_state{0};
     bool (*wait_work)(SmallReq&) = nullptr;  // what the owner can do instead of sleeping; false: nothing (left) to do
+    // BLOB_CELLS: blobs n x 131072 bytes, c n x 48, p n x 128 x 48; ok[b] / err[b] per blob, msg the reason of the first blob with
+    // err set.  The challenges, one per blob, in the submitter's buffers: blob_r_state[b] moves 0 -> 1 -> 2 like r_state, so the
+    // owner (wait_work) and the leader share the blobs between them and none is hashed twice
+    uint8_t* blob_r = nullptr;                  // n x 32 big-endian bytes
+    std::atomic<int>* blob_r_state = nullptr;   // n words
     // results.  PROOFS: per item.  BLOBS: [0] only - the conjunction over the request's blobs, any parse failure among them, any z = tau
     bool* ok = nullptr;
     uint8_t *err = nullptr, *general = nullptr;
@@ -108,11 +116,20 @@ struct SmallQueue {
     uint64_t cell_launches = 0, cell_requests = 0, cell_items = 0, cell_max_requests = 0;
     // the lanes that may carry CELLS: lane i with i % cell_lane_stride == 0 (a multi-device handle deals its lanes to its devices
     // in turn and has the cell set-up on the first one only; 1: every lane)
+    // (BLOB_CELLS run on the cell set-up too: the same rule)
     size_t cell_lane_stride = 1;
+    // BLOB_CELLS: one limit per launch - blobs in all, the group size of kzg_verify_blob_cell_kzg_proofs - and counters of their own
+    // (kzg_debug_blob_cell_queue_stats): launches | requests | blobs | the largest launch in requests
+    size_t cap_blob_cell_blobs = 64;
+    bool blob_cells_on = true;  // option blob_cell_coalesce (read when the handle is made)
+    uint64_t blob_cell_launches = 0, blob_cell_requests = 0, blob_cell_items = 0, blob_cell_max_requests = 0;
 };
 static bool small_lane_carries(const SmallQueue& Q, int li, SmallReq::Kind kind) {
-    return kind != SmallReq::CELLS || (size_t)li % Q.cell_lane_stride == 0;
+    return (kind != SmallReq::CELLS && kind != SmallReq::BLOB_CELLS) || (size_t)li % Q.cell_lane_stride == 0;
 }
+// which kzg_verify_blob_cell_kzg_proofs calls become requests: up to KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs (a blob transaction
+// carries at most 6; an engine_getBlobsV2 answer is larger and keeps the handle's lock) on a queue with the kind switched on
+static bool small_blob_cells_queued(const SmallQueue& Q, size_t n) { return Q.blob_cells_on && n >= 1 && n <= (size_t)KZG_BLOB_CELL_COALESCE_MAX_BLOBS; }
 
 
 // Waiting and waking.  Waiters sleep on 32-bit futex words - the queue's while their request is still in the queue, their
@@ -186,6 +203,30 @@ static size_t small_take_cells(SmallQueue& Q, int li, std::vector<SmallReq*>& ba
     return m;
 }
 
+// The BLOB_CELLS requests of a launch on lane li, under the queue's lock: oldest first while the blobs in all stay at or below
+// cap_blob_cell_blobs; the first one that does not fit ends the launch (it leads the next one: nobody is overtaken).  A request
+// holds at most KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs, so the oldest always leaves.  Returns the blobs taken.
+static size_t small_take_blob_cells(SmallQueue& Q, int li, std::vector<SmallReq*>& batch) {
+    size_t m = 0;
+    for (auto it = Q.q.begin(); it != Q.q.end();) {
+        SmallReq* x = *it;
+        if (x->kind != SmallReq::BLOB_CELLS) {
+            ++it;
+            continue;
+        }
+        if (!batch.empty() && m + x->n > Q.cap_blob_cell_blobs) break;
+        x->lane.store(li, std::memory_order_release);
+        x->taken.store(true, std::memory_order_relaxed);
+        m += x->n;
+        batch.push_back(x);
+        it = Q.q.erase(it);
+    }
+    Q.blob_cell_launches++;
+    Q.blob_cell_items += m;
+    Q.blob_cell_max_requests = std::max<uint64_t>(Q.blob_cell_max_requests, batch.size());
+    return m;
+}
+
 // (tests/host/small_queue_main.cpp defines this to stall a caller between its read of r.lane and its read of the word it will
 // sleep on - the window in which a leader can take the request)
 #ifndef SMALL_QUEUE_TEST_HOOK_BETWEEN_LOADS
@@ -224,6 +265,7 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
                 Q.q.push_back(&r);
                 Q.requests++;
                 if (r.kind == SmallReq::CELLS) Q.cell_requests++;
+                if (r.kind == SmallReq::BLOB_CELLS) Q.blob_cell_requests++;
                 queued = true;
                 Q.arrivals.fetch_add(1, std::memory_order_relaxed);
             }
@@ -232,7 +274,7 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
         }
         if (li < 0) {
             if (r.hash && r.hash->unclaimed()) hostpool::help(*r.hash);  // nothing to lead: hash the own blobs instead of sleeping
-            else if (r.wait_work && r.wait_work(r)) {  // (CELLS: the own transcript)
+            else if (r.wait_work && r.wait_work(r)) {  // (CELLS: the own transcript; BLOB_CELLS: one more of the own blobs' challenges)
             } else small_sleep(word, seen);
             continue;
         }
@@ -302,6 +344,8 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
             }
             if (kind == SmallReq::CELLS) {
                 m = small_take_cells(Q, li, batch);
+            } else if (kind == SmallReq::BLOB_CELLS) {
+                m = small_take_blob_cells(Q, li, batch);
             } else {
                 const size_t cap = kind == SmallReq::PROOFS ? Q.cap_proofs : Q.cap_blobs;
                 for (auto it = Q.q.begin(); it != Q.q.end();) {
