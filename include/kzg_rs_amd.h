@@ -298,8 +298,8 @@ KzgRet kzg_compute_blob_kzg_proof(uint8_t *proofs_out, const uint8_t *blobs, con
  * 128 sums of 64 terms over a table derived from the Lagrange points, then the inverse DFT - truncate - DFT of the 128 results
  * as one circulant product (128 sums of 65 terms).  Blobs are processed 64 per launch.  The identity proof is 0xC0 00 .. 00.
  * KZG_BADARGS for a field element >= r (no output is promised) or settings without G1 points, KZG_BAD_SETUP for an off-subgroup
- * set-up point; n == 0 is KZG_OK.  No G2 point is read.  The handle's lock is taken; a multi-device handle runs the call on its
- * first device.  The first proof call on a handle derives the FK20 table, unless kzg_settings_precompute did so before: 8 192 points
+ * set-up point; n == 0 is KZG_OK.  No G2 point is read.  The handle's lock is taken; a multi-device handle deals the blobs over its devices, ceil(n / D) consecutive blobs per shard, each shard under its own lock writing its blobs' outputs in place (MULTI-DEVICE CELL CALLS below).
+ * The first proof call on a handle (on a shard of a multi-device handle: the first proof range dealt to it) derives the FK20 table, unless kzg_settings_precompute did so before: 8 192 points
  * x 32 rows = 48 MB kept on the handle, made by group DFTs over G1 (csrc/g1_ntt.hpp): one 4 096-point transform of the Lagrange
  * points gives the monomial points (12 stages of 2 048 butterflies), 64 transforms of 128 of those the table (7 stages of 4 096
  * butterflies).  That call takes a time not yet measured on an MI355X (KZG_OPTIONS fk20_table=msm, the earlier derivation by 8 192 MSMs: 1.24 s when it was the only form) against 6.2 ms
@@ -319,8 +319,8 @@ KzgRet kzg_compute_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out,
  * coefficients.  KZG_BADARGS (no output is promised; the handle stays usable) for num_cells outside 64..128, an index >= 128, indices
  * that are not strictly ascending, a field element >= r, settings without G1 points, and cells that are not the evaluations of one
  * polynomial of degree < 4096 (an exact test, which 64 cells always pass); KZG_BAD_SETUP for an off-subgroup set-up point; n == 0 is
- * KZG_OK.  The index lists are checked on the host before anything is copied.  The handle's lock is taken; a multi-device handle
- * runs the call on its first device; blobs are processed 64 per launch.  Measured from 64 cells (DESIGN.md 4b,
+ * KZG_OK.  The index lists are checked on the host before anything is copied.  The handle's lock is taken; a multi-device handle deals the blobs over its devices, ceil(n / D) consecutive blobs per shard, each shard under its own lock writing its blobs' outputs in place (MULTI-DEVICE CELL CALLS below);
+ * blobs are processed 64 per launch.  Measured from 64 cells (DESIGN.md 4b,
  * profiles/cell_recover_probe.json): 6.5 ms for one blob, 9.9 ms for six, 62.5 ms for 64 with proofs - 0.3 ms more than
  * kzg_compute_cells_and_kzg_proofs on the same blobs - and 0.5 / 0.6 / 1.1 ms with proofs_out == NULL.  Bad input is rejected
  * before the proof chain is started.  The buffers (another ~85 MB for 64 blobs) stay on the handle. */
@@ -341,8 +341,8 @@ KzgRet kzg_recover_cells_and_kzg_proofs(uint8_t *cells_out, uint8_t *proofs_out,
  * Errors: everything the call above refuses, with the same code, after the same host-side index checks and before anything is
  * copied; KZG_BADARGS also for NULL proofs or proofs_out and for a given proof that is not a G1 point (decoded and subgroup-tested as
  * kzg_g1_msm decodes its points; the identity 0xC0 00 .. 00 is allowed).  The verdict on cells and points is read before the sums are
- * queued; n == 0 is KZG_OK; after an error the handle stays usable.  The handle's lock is taken; a multi-device handle runs the call
- * on its first device; blobs are processed 64 per launch; two runs give the same bytes.  The time of the call
+ * queued; n == 0 is KZG_OK; after an error the handle stays usable.  The handle's lock is taken; a multi-device handle deals the blobs over its devices, ceil(n / D) consecutive blobs per shard, each shard under its own lock writing its blobs' outputs in place (MULTI-DEVICE CELL CALLS below);
+ * blobs are processed 64 per launch; two runs give the same bytes.  The time of the call
  * (tools/prof/cell_recover_proofs_probe.py: 1, 6 and 64 blobs from 64 cells and proofs, beside the call above in the same run) is
  * not yet measured on an MI355X. */
 KzgRet kzg_recover_cells_and_kzg_proofs_given_proofs(uint8_t *cells_out, uint8_t *proofs_out, const uint64_t *cell_indices,
@@ -375,8 +375,10 @@ KzgRet kzg_recover_cells_and_kzg_proofs_given_proofs(uint8_t *cells_out, uint8_t
  * once and alone, on the path described above (no added wait); after it kzg_last_timings reports what it always did, after a
  * shared launch the group call's slots for that launch.  Calls above T, and every call on a handle made under KZG_OPTIONS
  * cell_coalesce=0 (or coalesce=0), run one at a time under the handle's lock as before.  A multi-device handle deals the lanes
- * of its queue to its devices in turn, but the cell set-up (the 64 monomial points, the lines of g2_points[64]) exists on its
- * first device only: cell launches keep to the first device's lanes, and calls above T run there too. */
+ * of its queue to its devices in turn and every shard has a cell set-up of its own (the 64 monomial points, the lines of
+ * g2_points[64], derived on that device the first time it is given cell work): a queued call runs on the shard of the lane that
+ * leads its launch.  ONE batch is one transcript and one pairing and is not cut: a call that is not queued - above T, or with
+ * cell_coalesce=0 - stays on the handle's first device.  Many batches spread: kzg_verify_cell_kzg_proof_batches. */
 KzgRet kzg_verify_cell_kzg_proof_batch(bool *ok, const uint8_t *commitments, const uint64_t *cell_indices,
                                        const uint8_t *cells, const uint8_t *proofs, size_t n, const KzgSettings *s);
 /* The batch challenge r of the above alone, as 32 big-endian bytes: host code, no device and no settings needed; inputs are
@@ -398,8 +400,9 @@ KzgRet kzg_cell_batch_challenge(uint8_t r_out[32], const uint8_t *commitments, c
  * on host threads (KZG_OPTIONS host_threads) meanwhile, one segmented launch each for the powers of r_b, the column sums and the
  * term tables, one window-kernel launch over 2 n_batches sums (a longer list than 2 T + 64 terms does not fit the kernel's LDS
  * list) and one pairing program with an instance per batch.  Batches above T run through kzg_verify_cell_kzg_proof_batch one after
- * another inside the call; the contract is the same on both sides of T.  The handle's lock is taken; a multi-device handle runs
- * the call on its first device.  kzg_last_timings afterwards holds the single call's slots, [1] being the wall clock of the
+ * another inside the call; the contract is the same on both sides of T.  The handle's lock is taken; a multi-device handle deals
+ * whole batches over its devices in contiguous ranges balanced by cell count, at most one range per shard (a batch above T counts
+ * with its size and runs on its shard's single-batch path; MULTI-DEVICE CELL CALLS below).  kzg_last_timings afterwards holds the single call's slots, [1] being the wall clock of the
  * parallel hashing.  Two runs of a group give the same bytes: every device sum has a fixed order.  Measured (DESIGN.md 4b,
  * profiles/cell_group_probe.json): not yet measured on an MI355X. */
 #define KZG_CELL_GROUP_MAX_CELLS 256
@@ -445,8 +448,9 @@ KzgRet kzg_cell_batch_challenges(uint8_t *r_out, const uint8_t *commitments, con
  * the handle idle runs at once and alone, on the path described above (no added wait); after it kzg_last_timings reports what it
  * always did, after a shared launch the group call's slots for that launch.  Calls above KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs
  * (an engine_getBlobsV2 answer), and every call on a handle made under KZG_OPTIONS blob_cell_coalesce=0 (or coalesce=0), run one at
- * a time under the handle's lock as before.  A multi-device handle runs the call on its first device: the lanes that carry these
- * launches are that device's.  kzg_last_timings after a locked call holds the group call's slots, summed over the groups.  Two
+ * a time under the handle's lock as before.  A multi-device handle runs a queued call on the shard of the lane that leads its
+ * launch (lanes on every device carry them, each with its own shard's set-up) and deals a call under the lock over its devices by
+ * blob, ceil(n / D) consecutive blobs per shard (MULTI-DEVICE CELL CALLS below).  kzg_last_timings after a locked call holds the group call's slots, summed over the groups.  Two
  * runs give the same bytes and verdicts: every device sum has a fixed order.
  * Measured (profiles/blob_cell_verify_probe.json, profiles/blob_cell_concurrent_probe.json): not yet measured on an
  * MI355X. */
@@ -472,7 +476,27 @@ KzgRet kzg_settings_g1_monomial_points(const KzgSettings *s, size_t first, size_
  * KZG_PRECOMPUTE_CELL_VERIFY (the 64 monomial points and the lines of g2_points[64] of kzg_verify_cell_kzg_proof_batch) and
  * KZG_PRECOMPUTE_CELL_PROOFS (the twiddles, the circulant and the FK20 table of kzg_compute_cells_and_kzg_proofs and
  * kzg_recover_cells_and_kzg_proofs).  Idempotent; what == 0 is KZG_OK; unknown bits are KZG_BADARGS; settings the family refuses
- * are refused here with the family's error. */
+ * are refused here with the family's error.  On a multi-device handle the requested families are built on EVERY shard, one after
+ * the other, each on its own device.
+ *
+ * MULTI-DEVICE CELL CALLS.  A handle made by kzg_settings_load_trusted_setup(_devices) over D devices holds the full trusted setup
+ * on every shard: the parsed file is decoded once per device into that device's own MSM tables, fixed-base plan and subgroup
+ * verdict; the cell set-up and the prover state (twiddles, circulant, monomial points, FK20 table) are derived per shard, on its
+ * own device and under its own once-flag, the first time that shard is given such work (or by kzg_settings_precompute); nothing is
+ * copied between devices, and a device may appear in the list more than once.  Device memory PER DEVICE: the setup tables (the
+ * Lagrange points and their MSM rows, ~4 MB, and the verification tables every shard always had), the grow-only call buffers of the
+ * work it is given, and 48 MB more once the shard has proved (its FK20 table).  A handle made by kzg_settings_from_tau_g2_devices
+ * holds [tau]G2 alone on every shard and the cell family refuses it, as before.
+ * The calls named above cut their units - batches or blobs - into contiguous ranges, at most one per shard; with fewer units than
+ * shards the trailing shards get nothing and derive nothing.  Each range runs the single-device call's own code on its shard, from a
+ * host thread of its own, and the caller's current device is restored.  The contract is the single-device call's, item for item:
+ * ok_out, err_out and the output bytes are what a single-device handle gives on the same input; without err_out the return code and
+ * kzg_last_error() are those of the lowest-indexed refused unit, whichever shard saw it (what a call refuses on the host before it
+ * copies anything - an index list of a recovery - is refused for the whole call first); after an error on one shard the other
+ * shards' ranges are still run to their end and drained before the call returns, so that nothing writes to the caller's memory or
+ * the handle's buffers afterwards; the handle stays usable.  kzg_last_timings after a dealt verification call: [0] the call's host
+ * wall clock, [1..7] the largest value over the shards that ran.  Speed on more than one device: not yet measured (no multi-GPU
+ * node was available; what the dealing costs on one device listed three times: tools/prof/cell_multidevice_probe.py). */
 #define KZG_PRECOMPUTE_CELL_VERIFY 1u
 #define KZG_PRECOMPUTE_CELL_PROOFS 2u
 KzgRet kzg_settings_precompute(const KzgSettings *s, uint32_t what);
@@ -597,6 +621,11 @@ KzgRet kzg_debug_concurrent_cell_callers(double out[5], size_t threads, double s
  * out = { launches, calls carried (requests), blobs, the largest launch in calls }.  launches == requests: every call ran alone.
  * All zero on a handle made with KZG_OPTIONS blob_cell_coalesce=0, and for calls above KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs. */
 KzgRet kzg_debug_blob_cell_queue_stats(const KzgSettings *s, uint64_t out[4], int reset);
+/* Diagnostic: the EIP-7594 cell work each shard of the handle has run since the last reset.  For shard k (device k of the handle's
+ * list; a single-device handle is one shard) out[4 k .. 4 k + 3] = { cell-family launches run on it - ranges under its lock and
+ * coalesced launches led by its lanes -, cells verified, blobs verified against their cell proofs, blobs proved or recovered }.
+ * cap: the words `out` holds; shards beyond it are not written (and still reset). */
+KzgRet kzg_debug_cell_shard_stats(const KzgSettings *s, uint64_t *out, size_t cap, int reset);
 /* Measurement hook: `threads` host threads inside the library call kzg_verify_blob_cell_kzg_proofs on this one handle for
  * `seconds`; the calls are n_calls slices of the three arrays, call after call, call i of call_sizes[i] blobs; expect[b] per blob =
  * 0 false | 1 true | 2 refused.  A thread's calls pass err_out and omit it in turn: without it a call with a refused blob must

@@ -179,6 +179,7 @@ def lib():
         L.kzg_debug_concurrent_cell_callers.argtypes = [C.POINTER(C.c_double), sz, C.c_double, u8, C.POINTER(C.c_uint64), u8, u8, C.POINTER(sz), u8, sz, vp]
         L.kzg_debug_blob_cell_queue_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.kzg_debug_concurrent_blob_cell_callers.argtypes = [C.POINTER(C.c_double), sz, C.c_double, u8, u8, u8, C.POINTER(sz), u8, sz, vp]
+        L.kzg_debug_cell_shard_stats.argtypes = [vp, C.POINTER(C.c_uint64), sz, C.c_int]
         _lib = L
     return _lib
 
@@ -332,6 +333,15 @@ class KzgSettings:
         o = (C.c_uint64 * 4)()
         _chk(lib().kzg_debug_blob_cell_queue_stats(self._h, o, int(reset)))
         return dict(zip(("launches", "requests", "blobs", "max_requests"), (int(x) for x in o)))
+
+    def cell_shard_stats(self, reset=False):
+        """The EIP-7594 cell work each shard of this handle has run since the last reset (kzg_debug_cell_shard_stats): one dict per
+        device of the handle's list, {launches (ranges under the shard's lock and coalesced launches led by its lanes), cells
+        (verified), blobs_verified (against their cell proofs), blobs_proved (proved or recovered)}."""
+        d = len(self.devices()[0])
+        o = (C.c_uint64 * (4 * d))()
+        _chk(lib().kzg_debug_cell_shard_stats(self._h, o, 4 * d, int(reset)))
+        return [dict(zip(("launches", "cells", "blobs_verified", "blobs_proved"), (int(x) for x in o[4 * k: 4 * k + 4]))) for k in range(d)]
 
     def concurrent_blob_cell_callers(self, threads, seconds, blobs, commitments, cell_proofs, call_sizes, expect):
         """T host threads INSIDE the library calling verify_blob_cell_kzg_proofs on this one handle for `seconds`

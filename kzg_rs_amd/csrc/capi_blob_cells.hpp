@@ -184,6 +184,17 @@ static KzgRet blob_cell_call_locked(bool* ok_out, uint8_t* err_out, const char**
     cell_group_timings(s, t_call, hash_ms, total_ms, none);
     return KZG_OK;
 }
+// the call that is not queued, under the lock of handle s - the handle a caller holds, or one shard of it with that shard's range of
+// the blobs (capi_cell_multi.hpp: cell_multi_blob_cells)
+static KzgRet blob_cell_call_direct(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments, const uint8_t* cell_proofs, size_t n,
+                                    std::chrono::steady_clock::time_point t_call, const KzgSettings* s) {
+    std::lock_guard<std::mutex> lk(s->mu);
+    const KzgRet rc = blob_cell_call_locked(ok_out, err_out, nullptr, blobs, commitments, cell_proofs, n, t_call, s);
+    cell_stats_add(s, 1, 0, n, 0);
+    return rc;
+}
+static KzgRet cell_multi_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments, const uint8_t* cell_proofs, size_t n,
+                                    const KzgSettings* s);
 static KzgRet blob_cell_setup_once(const KzgSettings* s);
 static KzgRet small_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments, const uint8_t* cell_proofs, size_t n,
                                const KzgSettings* s);
@@ -207,8 +218,8 @@ extern "C" KzgRet kzg_verify_blob_cell_kzg_proofs(bool* ok_out, uint8_t* err_out
         if ((rc = cells_setup_once(s)) != KZG_OK || (rc = blob_cell_setup_once(s)) != KZG_OK) return rc;
         return small_blob_cells(ok_out, err_out, blobs, commitments, cell_proofs, n, s);
     }
-    std::lock_guard<std::mutex> lk(s->mu);
-    return blob_cell_call_locked(ok_out, err_out, nullptr, blobs, commitments, cell_proofs, n, t_call, s);
+    if (s->multi) return cell_multi_blob_cells(ok_out, err_out, blobs, commitments, cell_proofs, n, s);
+    return blob_cell_call_direct(ok_out, err_out, blobs, commitments, cell_proofs, n, t_call, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
 }
@@ -278,6 +289,7 @@ static KzgRet small_run_blob_cells(SmallLane& L, std::vector<SmallReq*>& batch, 
     KzgRet rc = blob_cell_lane_reserve(l);
     if (rc != KZG_OK) return rc;
     if (m == 0 || m > BLOB_CELL_GROUP) return fail(KZG_ERROR, "small-call queue: a blob-cell launch outside the group's range");
+    cell_stats_add(l, 1, 0, m, 0);
     std::vector<const char*> why(m, nullptr);
     auto refuse = [](SmallReq& r, const char* const* w) {  // the message of the first blob refused
         for (size_t b = 0; b < r.n; b++)

@@ -372,6 +372,10 @@ static void cell_group_timings(const KzgSettings* s, std::chrono::steady_clock::
 }
 
 // ---------------------------------------------------------------- the entry point
+static KzgRet cell_batches_run(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                               const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches, const KzgSettings* s);
+static KzgRet cell_multi_batches(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                                 const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches, const KzgSettings* s);  // (capi_cell_multi.hpp)
 extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, const uint64_t* cell_indices,
                                                     const uint8_t* cells, const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches,
                                                     const KzgSettings* s) try {
@@ -383,6 +387,18 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     if (!cell_group_sizes(&total, batch_sizes, n_batches)) return fail(KZG_BADARGS, "kzg_verify_cell_kzg_proof_batches: more than 2^20 cells");
     if (total && (!commitments || !cell_indices || !cells || !proofs)) return fail(KZG_BADARGS, "null argument");
     if (n_batches == 0) return KZG_OK;
+    if (s->multi) return cell_multi_batches(ok_out, err_out, commitments, cell_indices, cells, proofs, batch_sizes, n_batches, s);
+    return cell_batches_run(ok_out, err_out, commitments, cell_indices, cells, proofs, batch_sizes, n_batches, s);
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
+}
+// The checked call on handle s, whose lock it takes itself - the handle a caller holds, or one shard of it with that shard's range
+// of the batches (capi_cell_multi.hpp).  May throw std::bad_alloc.
+static KzgRet cell_batches_run(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                               const uint8_t* proofs, const size_t* batch_sizes, size_t n_batches, const KzgSettings* s) {
+    KzgRet rc = KZG_OK;
+    size_t total = 0;
+    for (size_t b = 0; b < n_batches; b++) total += batch_sizes[b];
     const auto t_call = std::chrono::steady_clock::now();
     const CellGroupInArrays arrays(commitments, cell_indices, cells, proofs, batch_sizes, n_batches);
     CellGroupPlan P;
@@ -406,7 +422,8 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
         if (P.kind[b] != CELL_GROUP_LARGE) continue;
         const size_t e = P.off[b];
         bool okb = false;
-        rc = kzg_verify_cell_kzg_proof_batch(&okb, commitments + 48 * e, cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, batch_sizes[b], s);
+        rc = cell_batch_direct(&okb, commitments + 48 * e, cell_indices + e, cells + CELL_BYTES * e, proofs + 48 * e, batch_sizes[b],
+                               std::chrono::steady_clock::now(), s);
         if (rc == KZG_BADARGS && err_out) {
             err_out[b] = 1;
             okb = false;
@@ -420,9 +437,8 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batches(bool* ok_out, uint8_t* err_o
     std::lock_guard<std::mutex> lk(s->mu);
     if (P.G && (rc = cell_group_locked(ok_out, err_out, nullptr, arrays.in, P, hash, r_be.data(), s, stage_ms)) != KZG_OK) return rc;
     cell_group_timings(s, t_call, P.G ? hash.ms() : 0.0, stage_ms, t_large);
+    cell_stats_add(s, 1, total, 0, 0);
     return KZG_OK;
-} catch (const std::bad_alloc&) {
-    return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
 }
 
 // ---------------------------------------------------------------- concurrent single calls: requests of the small-call queue
@@ -455,10 +471,10 @@ static void small_cell_refuse(SmallReq& r, const char* why) {
 }
 // the launch of one leader on lane L (capi_coalesce.hpp small_submit): requests of kind CELLS, m cells in all
 static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m) {
-    (void)m;
     const KzgSettings* l = L.h;
     const auto t_call = std::chrono::steady_clock::now();
     const size_t B = batch.size();
+    cell_stats_add(l, 1, m, 0, 0);
     if (B == 1) {  // nobody else was waiting: the single call as it was
         SmallReq& r = *batch[0];
         CellGroupPlan P;

@@ -197,17 +197,22 @@ static KzgRet cell_prover_run(uint8_t* cells_out, uint8_t* proofs_out, const uin
         for (size_t b = 0; b < m; b++)
             if (st[b]) return fail(KZG_BADARGS, "a blob holds a field element >= r");
     }
+    cell_stats_add(s, 1, 0, 0, n);
     return KZG_OK;
 }
+// a multi-device handle: the blobs dealt over its shards, each running cell_prover_run on its range (capi_cell_multi.hpp)
+static KzgRet cell_multi_prover(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n, const KzgSettings* s);
 
 extern "C" KzgRet kzg_compute_cells(uint8_t* cells_out, const uint8_t* blobs, size_t n, const KzgSettings* s) try {
     if (!s || (n && (!cells_out || !blobs))) return fail(KZG_BADARGS, "null argument");
+    if (s->multi) return cell_multi_prover(cells_out, nullptr, blobs, n, s);
     return cell_prover_run(cells_out, nullptr, blobs, n, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");
 }
 extern "C" KzgRet kzg_compute_cells_and_kzg_proofs(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n, const KzgSettings* s) try {
     if (!s || (n && (!proofs_out || !blobs))) return fail(KZG_BADARGS, "null argument");
+    if (s->multi) return cell_multi_prover(cells_out, proofs_out, blobs, n, s);
     return cell_prover_run(cells_out, proofs_out, blobs, n, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");

@@ -61,22 +61,37 @@ static void cell_recover_release(const KzgSettings* s) {
     s->cell_recover = nullptr;
 }
 
-// given: null (the proofs are the FK20 chain's on the recovered coefficients) or n * per proofs, one per given cell (the missing
-// proofs are interpolated from them)
-static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* given, size_t per,
-                               size_t n, const KzgSettings* s) {
+// What is refused before anything is copied, in the order of the blobs; cidx / slot (optional): the index lists as bytes and, per
+// blob, the map cell -> slot.  A multi-device handle runs it over the WHOLE call before the blobs are dealt, so that such a refusal
+// is the same one whichever shard holds the blob (capi_cell_multi.hpp).
+static KzgRet cell_recover_check(std::vector<uint8_t>& cidx, std::vector<uint8_t>& slot, const uint64_t* cell_indices, size_t per, size_t n,
+                                 const KzgSettings* s, bool fill = true) {
     KzgRet rc = prover_ready(s);
     if (rc != KZG_OK) return rc;
     if (per < (size_t)RECOVER_N / 2 || per > (size_t)RECOVER_N) return fail(KZG_BADARGS, "between 64 and 128 cells per blob are needed");
-    std::vector<uint8_t> cidx(n * per), slot(n * RECOVER_N, RECOVER_MISSING);
+    if (fill) {
+        cidx.assign(n * per, 0);
+        slot.assign(n * RECOVER_N, RECOVER_MISSING);
+    }
     for (size_t b = 0; b < n; b++)
         for (size_t k = 0; k < per; k++) {
             const uint64_t c = cell_indices[b * per + k];
             if (c >= (uint64_t)RECOVER_N) return fail(KZG_BADARGS, "cell index out of range");
             if (k && c <= cell_indices[b * per + k - 1]) return fail(KZG_BADARGS, "a blob's cell indices are not strictly ascending");
-            cidx[b * per + k] = (uint8_t)c;
-            slot[b * RECOVER_N + c] = (uint8_t)k;
+            if (fill) {
+                cidx[b * per + k] = (uint8_t)c;
+                slot[b * RECOVER_N + c] = (uint8_t)k;
+            }
         }
+    return KZG_OK;
+}
+// given: null (the proofs are the FK20 chain's on the recovered coefficients) or n * per proofs, one per given cell (the missing
+// proofs are interpolated from them)
+static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* given, size_t per,
+                               size_t n, const KzgSettings* s) {
+    std::vector<uint8_t> cidx, slot;
+    KzgRet rc = cell_recover_check(cidx, slot, cell_indices, per, n, s);
+    if (rc != KZG_OK) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
@@ -167,14 +182,19 @@ static KzgRet cell_recover_run(uint8_t* cells_out, uint8_t* proofs_out, const ui
         HIPCHK(hipStreamSynchronize(s->s1));  // (the cells' copy; with given proofs the last wait was before the host placed them)
         if (!proofs_out && (rc = verdict(m)) != KZG_OK) return rc;
     }
+    cell_stats_add(s, 1, 0, 0, n);
     return KZG_OK;
 }
+// a multi-device handle: the blobs dealt over its shards, each running cell_recover_run on its range (capi_cell_multi.hpp)
+static KzgRet cell_multi_recover(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* given,
+                                 size_t per, size_t n, const KzgSettings* s);
 
 extern "C" KzgRet kzg_recover_cells_and_kzg_proofs(uint8_t* cells_out, uint8_t* proofs_out, const uint64_t* cell_indices, const uint8_t* cells, size_t num_cells,
                                                    size_t n, const KzgSettings* s) try {
     if (!s) return fail(KZG_BADARGS, "null argument");
     if (n == 0) return KZG_OK;
     if ((!cells_out && !proofs_out) || !cell_indices || !cells) return fail(KZG_BADARGS, "null argument");
+    if (s->multi) return cell_multi_recover(cells_out, proofs_out, cell_indices, cells, nullptr, num_cells, n, s);
     return cell_recover_run(cells_out, proofs_out, cell_indices, cells, nullptr, num_cells, n, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");
@@ -184,6 +204,7 @@ extern "C" KzgRet kzg_recover_cells_and_kzg_proofs_given_proofs(uint8_t* cells_o
     if (!s) return fail(KZG_BADARGS, "null argument");
     if (n == 0) return KZG_OK;
     if (!proofs_out || !cell_indices || !cells || !proofs) return fail(KZG_BADARGS, "null argument");
+    if (s->multi) return cell_multi_recover(cells_out, proofs_out, cell_indices, cells, proofs, num_cells, n, s);
     return cell_recover_run(cells_out, proofs_out, cell_indices, cells, proofs, num_cells, n, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");

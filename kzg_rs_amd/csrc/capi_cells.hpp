@@ -16,7 +16,9 @@
 //   device  two sums over the one set of decoded tables (g1_msm_core): LL over the proofs, RL over all N = n + m + 64 points
 //   device  one pairing against the prepared lines of (g2_points[64], G2), made with the monomial table and kept on the handle
 // The hash stays on the host: a GPU lane runs SHA-256 at ~1.4 us per 64-byte block, a SHA-NI core at ~1.5 GB/s, and the chain
-// has no parallelism to give the GPU.  A multi-device handle runs on its first device, as the prover entry points do.
+// has no parallelism to give the GPU.  One batch is one transcript and one pairing: on a multi-device handle a call that is not
+// queued runs on the first device (a queued one on the shard of the lane that leads it); the calls of MANY units are dealt over
+// the shards (capi_cell_multi.hpp).
 
 constexpr size_t CELL_BYTES = (size_t)CELL_FE * 32;   // BYTES_PER_CELL
 constexpr size_t CELL_MAX_CELLS = (size_t)1 << 20;    // 8 192 blobs x 128 cells per call
@@ -112,6 +114,14 @@ struct CellState {
 static void cells_release(const KzgSettings* s) {
     delete s->cells;
     s->cells = nullptr;
+}
+// the counters of kzg_debug_cell_shard_stats, on the shard that ran the work (a lane of the small-call queue: the shard it lives on)
+static void cell_stats_add(const KzgSettings* s, uint64_t launches, uint64_t cells, uint64_t blobs_verified, uint64_t blobs_proved) {
+    const KzgSettings* const h = s->cell_home ? s->cell_home : s;
+    h->cell_stats[0].fetch_add(launches, std::memory_order_relaxed);
+    h->cell_stats[1].fetch_add(cells, std::memory_order_relaxed);
+    h->cell_stats[2].fetch_add(blobs_verified, std::memory_order_relaxed);
+    h->cell_stats[3].fetch_add(blobs_proved, std::memory_order_relaxed);
 }
 static KzgRet cells_ready(const KzgSettings* s) {
     if (!s->t->d_g1.p) return fail(KZG_BADARGS, "cell proofs need the G1 points of a trusted-setup file; these settings hold [tau]G2 alone");
@@ -328,6 +338,18 @@ static KzgRet cell_batch_locked(bool* ok, const uint8_t* commitments, const uint
     return KZG_OK;
 }
 
+// One batch under the lock of handle s - the handle a caller holds, or one shard of it (capi_cell_multi.hpp): the path of a call
+// that is not queued, and of a batch above T inside kzg_verify_cell_kzg_proof_batches.  May throw std::bad_alloc.
+static KzgRet cell_batch_direct(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs, size_t n,
+                                std::chrono::steady_clock::time_point t_call, const KzgSettings* s) {
+    // r-independent host work: the plan of a group of this one batch.  No batch is above the threshold, so it is slot 0 of G = 1
+    CellGroupPlan P;
+    cell_group_plan(P, commitments, cell_indices, &n, 1, CELL_MAX_CELLS);
+    if (P.kind[0] == CELL_GROUP_BAD_INDEX) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
+    std::lock_guard<std::mutex> lk(s->mu);
+    return cell_batch_locked(ok, commitments, cell_indices, cells, proofs, n, P, t_call, s);
+}
+
 extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
                                                   const uint8_t* proofs, size_t n, const KzgSettings* s) try {
     if (!ok || !s || (n && (!commitments || !cell_indices || !cells || !proofs))) return fail(KZG_BADARGS, "null argument");
@@ -347,12 +369,9 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
         if ((rc = cells_setup_once(s)) != KZG_OK) return rc;
         return small_cells(ok, commitments, cell_indices, cells, proofs, n, s);
     }
-    // r-independent host work: the plan of a group of this one batch.  No batch is above the threshold, so it is slot 0 of G = 1
-    CellGroupPlan P;
-    cell_group_plan(P, commitments, cell_indices, &n, 1, CELL_MAX_CELLS);
-    if (P.kind[0] == CELL_GROUP_BAD_INDEX) return fail(KZG_BADARGS, "cell index out of range (>= 128)");
-    std::lock_guard<std::mutex> lk(s->mu);
-    return cell_batch_locked(ok, commitments, cell_indices, cells, proofs, n, P, t_call, s);
+    rc = cell_batch_direct(ok, commitments, cell_indices, cells, proofs, n, t_call, s);
+    cell_stats_add(s, 1, n, 0, 0);
+    return rc;
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
 }

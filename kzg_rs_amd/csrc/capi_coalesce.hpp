@@ -26,11 +26,11 @@
 //     on T cores and the leader only collects the challenges;
 //   * a third kind of request is one kzg_verify_cell_kzg_proof_batch call of up to T = 256 cells: a launch carries up to 128
 //     of them (128 x T cells at most) as the slots of one cell group (capi_cell_groups.hpp small_run_cells), each with its own
-//     transcript - hashed by its owner while it waits - and its own pairing instance.  A multi-device handle has the cell
-//     set-up on its first device only, so these launches keep to that device's lanes (SmallQueue::cell_lane_stride).
+//     transcript - hashed by its owner while it waits - and its own pairing instance.  On a multi-device handle every shard
+//     has a cell set-up of its own (derived on first use), and a lane leads these launches on the shard it lives on.
 //   * a fourth kind is one kzg_verify_blob_cell_kzg_proofs call of up to 16 blobs (a blob transaction's): a launch carries up to 64
 //     blobs as the slots of one blob-cell group (capi_blob_cells.hpp small_run_blob_cells), every blob with its own challenge -
-//     hashed by its owner while it waits - its own two sums and pairing instance; on the cell set-up's device, like the third kind.
+//     hashed by its owner while it waits - its own two sums and pairing instance; on every shard, like the third kind.
 // Results are per request: a wrong proof, a non-canonical scalar, an undecodable or off-subgroup point in one caller's input
 // never changes another caller's answer (the instances share a launch, not a random linear combination).
 // z = tau (the pairing's G2 point is the identity: only for who knows the setup's secret, i.e. test rigs) is flagged per item;
@@ -167,6 +167,8 @@ static KzgRet small_lane_make(SmallLane& L, const SmallQueue& Q, const KzgSettin
 
 static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m);  // (capi_cell_groups.hpp)
 static KzgRet small_run_blob_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m);  // (capi_blob_cells.hpp)
+static KzgRet cells_setup_once(const KzgSettings* s);      // (capi_cells.hpp)
+static KzgRet blob_cell_setup_once(const KzgSettings* s);  // (capi_blob_cells.hpp)
 
 // Submit a request and return when it is done (small_queue.hpp small_submit_core); the launch a leader runs on its lane:
 static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
@@ -192,6 +194,12 @@ static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
                 if (L.h) kzg_settings_free(L.h);
                 L.h = nullptr;
             }
+        }
+        // a cell launch borrows the set-up of the shard the lane lives on: the first shard's exists (made before the request was
+        // queued); another shard derives its own, once, on its own device, before its first lane leads (one atomic load afterwards)
+        if (rc == KZG_OK && shard != 0 && (kind == SmallReq::CELLS || kind == SmallReq::BLOB_CELLS)) {
+            if ((rc = cells_setup_once(home)) == KZG_OK && kind == SmallReq::BLOB_CELLS) rc = blob_cell_setup_once(home);
+            if (rc != KZG_OK) msg = g_err;
         }
         if (rc == KZG_OK) {
             try {

@@ -87,15 +87,8 @@ extern "C" KzgRet kzg_settings_g1_monomial_points(const KzgSettings* s, size_t f
     return fail(KZG_MALLOC, "host buffers of the call");
 }
 
-// What the first cell verification (KZG_PRECOMPUTE_CELL_VERIFY) or the first cell proof call (KZG_PRECOMPUTE_CELL_PROOFS) of a
-// handle would build, built now.  Idempotent.
-extern "C" KzgRet kzg_settings_precompute(const KzgSettings* s, unsigned what) try {
-    if (!s) return fail(KZG_BADARGS, "null argument");
-    if (what & ~(unsigned)(KZG_PRECOMPUTE_CELL_VERIFY | KZG_PRECOMPUTE_CELL_PROOFS)) return fail(KZG_BADARGS, "kzg_settings_precompute: unknown flag");
-    if (!what) return KZG_OK;
-    KzgRet rc;
-    if ((what & KZG_PRECOMPUTE_CELL_VERIFY) && (rc = cells_ready(s)) != KZG_OK) return rc;
-    if ((what & KZG_PRECOMPUTE_CELL_PROOFS) && (rc = prover_ready(s)) != KZG_OK) return rc;
+static KzgRet precompute_shard(const KzgSettings* s, unsigned what) {
+    KzgRet rc = KZG_OK;
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);
@@ -108,6 +101,26 @@ extern "C" KzgRet kzg_settings_precompute(const KzgSettings* s, unsigned what) t
         if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cp->reserve(1, true)) != KZG_OK || (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
     }
     return KZG_OK;
+}
+// What the first cell verification (KZG_PRECOMPUTE_CELL_VERIFY) or the first cell proof call (KZG_PRECOMPUTE_CELL_PROOFS) of a
+// handle would build, built now - on every shard of a multi-device handle.  Idempotent.
+extern "C" KzgRet kzg_settings_precompute(const KzgSettings* s, unsigned what) try {
+    if (!s) return fail(KZG_BADARGS, "null argument");
+    if (what & ~(unsigned)(KZG_PRECOMPUTE_CELL_VERIFY | KZG_PRECOMPUTE_CELL_PROOFS)) return fail(KZG_BADARGS, "kzg_settings_precompute: unknown flag");
+    if (!what) return KZG_OK;
+    KzgRet rc = KZG_OK;
+    if ((what & KZG_PRECOMPUTE_CELL_VERIFY) && (rc = cells_ready(s)) != KZG_OK) return rc;
+    if ((what & KZG_PRECOMPUTE_CELL_PROOFS) && (rc = prover_ready(s)) != KZG_OK) return rc;
+    // every shard of the handle, each on its own device and under its own lock (a single-device handle is its one shard)
+    int prev = -1;
+    if (s->multi && hipGetDevice(&prev) != hipSuccess) prev = -1;
+    for (size_t k = 0; k < shard_count(s) && rc == KZG_OK; k++) rc = precompute_shard(shard_of(s, k), what);
+    if (prev >= 0) {
+        const std::string msg = g_err;
+        (void)hipSetDevice(prev);
+        g_err = msg;
+    }
+    return rc;
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");
 }

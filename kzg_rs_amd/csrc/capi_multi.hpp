@@ -247,7 +247,7 @@ static KzgRet multi_build(KzgSettings* s, const uint8_t tau_g2[96], const std::v
     }
     s->note = "exchange: " + m->exchange_note;
     if (s->small) s->small->max_lanes = std::min<size_t>(SMALL_LANES_MAX, s->small->max_lanes * D);  // small calls: the same number of lanes on every device (lane i on shard i mod D)
-    if (s->small) s->small->cell_lane_stride = D;  // ... but the cell set-up exists on the first device alone: cell launches keep to its lanes
+    // (cell launches too: a lane borrows the cell set-up of the shard it lives on, derived by that shard on first use - small_submit)
     HIPCHK(hipSetDevice(s->device));
     return KZG_OK;
 }

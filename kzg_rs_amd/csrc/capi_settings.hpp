@@ -133,6 +133,10 @@ struct KzgSettings {
     mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
     mutable struct CellRecoverState* cell_recover = nullptr;  // cell recovery's own buffers, made by its first call (capi_cell_recover.hpp)
     mutable struct G1PointsBufs* g1_points = nullptr;  // kzg_g1_msm_prepared's call buffers, made by its first call (capi_g1_points.hpp)
+    // the EIP-7594 cell work this shard has run since the last reset (kzg_debug_cell_shard_stats, capi_cell_multi.hpp): launches
+    // (locked ranges and coalesced launches) | cells verified | blobs verified against cell proofs | blobs proved or recovered.
+    // A lane of the small-call queue counts on the shard it lives on (cell_home)
+    mutable std::atomic<uint64_t> cell_stats[4] = {};
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the
     // last launch group, and summed over the groups finished since the last reset (kzg_kernel_stamp_totals)
@@ -528,9 +532,15 @@ static KzgRet load_trusted_setup_on(KzgSettings** out, const char* txt, size_t l
     if (rc != KZG_OK) return rc;
     int prev = 0;
     (void)hipGetDevice(&prev);
-    (void)hipSetDevice(s->device);  // the full point tables live on shard 0 only (verification does not read them)
-    memcpy(s->g1_first, first, sizeof first);
-    rc = settings_load_points(s, g1b, g2b, (int)n1, (size_t)n2);
+    // the full point tables on EVERY shard (blob verification does not read them; the EIP-7594 cell family runs on every device
+    // of the handle, capi_cell_multi.hpp): each peer decodes the parsed bytes on its own device into tables, a fixed-base plan and
+    // a subgroup verdict of its own - nothing is copied between devices
+    for (size_t k = 0; k <= s->peers.size() && rc == KZG_OK; k++) {
+        KzgSettings* const c = k == 0 ? s : s->peers[k - 1];
+        (void)hipSetDevice(c->device);
+        memcpy(c->g1_first, first, sizeof first);
+        rc = settings_load_points(c, g1b, g2b, (int)n1, (size_t)n2);
+    }
     (void)hipSetDevice(prev);
     if (rc != KZG_OK) {  // any failure below settings_common releases the whole handle (and keeps the first message)
         const std::string msg = g_err;

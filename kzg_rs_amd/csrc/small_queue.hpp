@@ -114,8 +114,9 @@ struct SmallQueue {
     size_t cap_cell_requests = 128, cap_cells = (size_t)128 * 256;
     bool cells_on = true;  // option cell_coalesce (read when the handle is made)
     uint64_t cell_launches = 0, cell_requests = 0, cell_items = 0, cell_max_requests = 0;
-    // the lanes that may carry CELLS: lane i with i % cell_lane_stride == 0 (a multi-device handle deals its lanes to its devices
-    // in turn and has the cell set-up on the first one only; 1: every lane)
+    // the lanes that may carry CELLS: lane i with i % cell_lane_stride == 0; 1: every lane, which is what every handle uses - each
+    // shard of a multi-device handle has a cell set-up of its own.  (The stride remains for a queue whose cell set-up is on some
+    // lanes' device only: tests/host/small_queue_cells_main.cpp drives it.)
     // (BLOB_CELLS run on the cell set-up too: the same rule)
     size_t cell_lane_stride = 1;
     // BLOB_CELLS: one limit per launch - blobs in all, the group size of kzg_verify_blob_cell_kzg_proofs - and counters of their own

@@ -35,6 +35,7 @@ extern "C" {
     pub fn kzg_cell_batch_challenges(r_out: *mut u8, commitments: *const u8, cell_indices: *const u64, cells: *const u8, proofs: *const u8, batch_sizes: *const usize, n_batches: usize) -> c_int;
     pub fn kzg_verify_blob_cell_kzg_proofs(ok_out: *mut bool, err_out: *mut u8, blobs: *const u8, commitments: *const u8, cell_proofs: *const u8, n: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_debug_blob_cell_queue_stats(s: *const RawSettings, out: *mut u64, reset: c_int) -> c_int;
+    pub fn kzg_debug_cell_shard_stats(s: *const RawSettings, out: *mut u64, cap: usize, reset: c_int) -> c_int;
     pub fn kzg_debug_concurrent_blob_cell_callers(out: *mut f64, threads: usize, seconds: f64, blobs: *const u8, commitments: *const u8, cell_proofs: *const u8, call_sizes: *const usize, expect: *const u8, n_calls: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_blob_cell_proofs_challenges(r_out: *mut u8, blobs: *const u8, commitments: *const u8, cell_proofs: *const u8, n: usize) -> c_int;
     pub fn kzg_compute_cells(cells_out: *mut u8, blobs: *const u8, n: usize, s: *const RawSettings) -> c_int;
