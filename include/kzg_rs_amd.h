@@ -414,6 +414,43 @@ KzgRet kzg_verify_cell_kzg_proof_batches(bool *ok_out, uint8_t *err_out, const u
  * host code - no handle, no device; nothing is validated; the batches are spread over host threads (KZG_OPTIONS host_threads). */
 KzgRet kzg_cell_batch_challenges(uint8_t *r_out, const uint8_t *commitments, const uint64_t *cell_indices,
                                  const uint8_t *cells, const uint8_t *proofs, const size_t *batch_sizes, size_t n_batches);
+/* The column sidecars of ONE block in one call, a verdict each, the block's commitments given ONCE (the consensus spec's
+ * verify_data_column_sidecar_kzg_proofs for every sidecar of a slot).  commitments: n_blobs * 48 bytes, the block's; sidecar j is the
+ * column index column_indices[j], the n_blobs cells at cells + j * n_blobs * 2048 and the n_blobs proofs at proofs + j * n_blobs * 48
+ * (cell and proof k belong to commitment k); host pointers.  For every j, ok_out[j] and err_out[j] are exactly what
+ * kzg_verify_cell_kzg_proof_batch returns on (the n_blobs commitments, column_indices[j] repeated n_blobs times, the cells of j, the
+ * proofs of j): r_j is that batch's spec challenge (kzg_data_column_sidecar_challenges) - its transcript lists the distinct
+ * commitments in first-seen order and indexes every cell by its commitment's place in that list; equal commitments in a block (two
+ * equal blobs, several zero blobs) are legal and fold into one point with a summed weight.  err_out[j] (optional) = 1 and
+ * ok_out[j] = false where the single call would return KZG_BADARGS: a column index >= 128, a field element >= r or a proof that is
+ * not a G1 point refuses that sidecar alone, a commitment that is not a G1 point refuses every sidecar; the identity is allowed
+ * everywhere.  With err_out == NULL the lowest-indexed refused sidecar fails the whole call with KZG_BADARGS and its reason in
+ * kzg_last_error().  Errors of the call, KZG_BADARGS: null pointers, settings the cell verifier refuses, n_sidecars above
+ * KZG_CELL_GROUP_MAX_BATCHES, n_sidecars * n_blobs above 2^20; KZG_BAD_SETUP for an off-subgroup monomial point.  n_sidecars == 0 is
+ * KZG_OK; n_blobs == 0 makes every sidecar true.  After any error the handle stays usable; two runs give the same bytes.
+ * Against kzg_verify_cell_kzg_proof_batches on the expanded arrays (the commitments repeated per sidecar, the column index repeated
+ * per cell), which treats every batch as a stranger: the block's commitments are deduplicated once on the host (m' distinct ones),
+ * uploaded, decompressed, subgroup-tested and given their MSM table rows ONCE per call - S * n_blobs + m' + 65 points go through the
+ * decode instead of S * n_blobs + S * m' + 65 - and output 1 of every sidecar's pair of sums points at the same m' rows with its own
+ * m' weights; the scalars between r and the sums come from one kernel with a wavefront per sidecar (the shape is uniform: no
+ * counting sorts, no index words per cell); the window-kernel launch over 2 S sums, the combine, the S pairing instances and the
+ * flag folding are the group call's.  Blocks of up to KZG_CELL_GROUP_MAX_CELLS blobs ride that group; larger ones run sidecar after
+ * sidecar through kzg_verify_cell_kzg_proof_batch's path inside the call, with the same contract.  The handle's lock is taken (the
+ * call is not carried by the small-call queue); a multi-device handle deals whole sidecars over its devices, ceil(n_sidecars / D)
+ * consecutive ones per shard, and every shard decodes the block's commitments itself (MULTI-DEVICE CELL CALLS below; counted in
+ * kzg_debug_cell_shard_stats as cell-family launches and cells verified).  kzg_last_timings afterwards holds the group call's slots.
+ * Measured (tools/prof/data_column_probe.py, profiles/data_column_probe.json), median wall clock beside the group call on
+ * the expanded arrays in the same run: 128 sidecars x 6 / 21 / 72 blobs 7.57 / 7.80 / 8.28 ms against 7.64 / 7.95 / 8.84 ms, 8 x 72
+ * 5.65 against 5.67 ms; the decode slot [6] at 128 x 72 2.719 against 2.789 ms. */
+KzgRet kzg_verify_data_column_sidecars(bool *ok_out, uint8_t *err_out, const uint8_t *commitments, size_t n_blobs,
+                                       const uint64_t *column_indices, const uint8_t *cells, const uint8_t *proofs,
+                                       size_t n_sidecars, const KzgSettings *s);
+/* The challenges r_j of the above alone: r_out = n_sidecars x 32 big-endian bytes, r_j = kzg_cell_batch_challenge on sidecar j's
+ * expansion, streamed from the compact arguments (the expansion is never formed).  Pure host code - no handle, no device; nothing
+ * is validated; the sidecars are spread over host threads (KZG_OPTIONS host_threads). */
+KzgRet kzg_data_column_sidecar_challenges(uint8_t *r_out, const uint8_t *commitments, size_t n_blobs,
+                                          const uint64_t *column_indices, const uint8_t *cells, const uint8_t *proofs,
+                                          size_t n_sidecars);
 /* Blobs against their 128 cell proofs each, a verdict per blob, WITHOUT computing a cell: the execution layer's Fulu check of a blob
  * transaction's network wrapper (version 1) and of engine_getBlobsV2 answers, which carry per blob the blob, its commitment and its
  * 128 cell proofs and no blob proof.  Inputs are host arrays: blobs n * 131072 bytes, commitments n * 48, cell_proofs n * 128 * 48
@@ -487,7 +524,7 @@ KzgRet kzg_settings_g1_monomial_points(const KzgSettings *s, size_t first, size_
  * Lagrange points and their MSM rows, ~4 MB, and the verification tables every shard always had), the grow-only call buffers of the
  * work it is given, and 48 MB more once the shard has proved (its FK20 table).  A handle made by kzg_settings_from_tau_g2_devices
  * holds [tau]G2 alone on every shard and the cell family refuses it, as before.
- * The calls named above cut their units - batches or blobs - into contiguous ranges, at most one per shard; with fewer units than
+ * The calls named above cut their units - batches, sidecars or blobs - into contiguous ranges, at most one per shard; with fewer units than
  * shards the trailing shards get nothing and derive nothing.  Each range runs the single-device call's own code on its shard, from a
  * host thread of its own, and the caller's current device is restored.  The contract is the single-device call's, item for item:
  * ok_out, err_out and the output bytes are what a single-device handle gives on the same input; without err_out the return code and
@@ -621,6 +658,11 @@ KzgRet kzg_debug_concurrent_cell_callers(double out[5], size_t threads, double s
  * out = { launches, calls carried (requests), blobs, the largest launch in calls }.  launches == requests: every call ran alone.
  * All zero on a handle made with KZG_OPTIONS blob_cell_coalesce=0, and for calls above KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs. */
 KzgRet kzg_debug_blob_cell_queue_stats(const KzgSettings *s, uint64_t out[4], int reset);
+/* Diagnostic: kzg_verify_data_column_sidecars on this handle since the last reset, summed over its shards: out = { calls (a shard
+ * counts the range it was dealt as a call), sidecars, G1 points that went through the decode (the 64 monomial points and the
+ * identity of every group included), commitments decoded }.  One call of S sidecars over m blobs with m' distinct commitments on one
+ * device: { 1, S, S m + m' + 65, m' } - the commitments are decoded once per call and per shard, not once per sidecar. */
+KzgRet kzg_debug_data_column_stats(const KzgSettings *s, uint64_t out[4], int reset);
 /* Diagnostic: the EIP-7594 cell work each shard of the handle has run since the last reset.  For shard k (device k of the handle's
  * list; a single-device handle is one shard) out[4 k .. 4 k + 3] = { cell-family launches run on it - ranges under its lock and
  * coalesced launches led by its lanes -, cells verified, blobs verified against their cell proofs, blobs proved or recovered }.

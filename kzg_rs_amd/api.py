@@ -180,6 +180,9 @@ def lib():
         L.kzg_debug_blob_cell_queue_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.kzg_debug_concurrent_blob_cell_callers.argtypes = [C.POINTER(C.c_double), sz, C.c_double, u8, u8, u8, C.POINTER(sz), u8, sz, vp]
         L.kzg_debug_cell_shard_stats.argtypes = [vp, C.POINTER(C.c_uint64), sz, C.c_int]
+        L.kzg_verify_data_column_sidecars.argtypes = [bp, u8, u8, sz, C.POINTER(C.c_uint64), u8, u8, sz, vp]
+        L.kzg_data_column_sidecar_challenges.argtypes = [u8, u8, sz, C.POINTER(C.c_uint64), u8, u8, sz]
+        L.kzg_debug_data_column_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         _lib = L
     return _lib
 
@@ -333,6 +336,13 @@ class KzgSettings:
         o = (C.c_uint64 * 4)()
         _chk(lib().kzg_debug_blob_cell_queue_stats(self._h, o, int(reset)))
         return dict(zip(("launches", "requests", "blobs", "max_requests"), (int(x) for x in o)))
+
+    def data_column_stats(self, reset=False):
+        """kzg_debug_data_column_stats: (calls, sidecars, G1 points decoded, commitments decoded) of verify_data_column_sidecars on
+        this handle since the last reset, summed over its shards."""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().kzg_debug_data_column_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(x) for x in out)
 
     def cell_shard_stats(self, reset=False):
         """The EIP-7594 cell work each shard of this handle has run since the last reset (kzg_debug_cell_shard_stats): one dict per
@@ -586,6 +596,47 @@ def cell_batch_challenge(commitments, cell_indices, cells, proofs):
     out = C.create_string_buffer(32)
     _chk(lib().kzg_cell_batch_challenge(out, *_cell_args(commitments, cell_indices, cells, proofs)))
     return out.raw
+
+
+def _data_column_args(commitments, column_indices, cells, proofs):
+    m, S = len(commitments), len(column_indices)
+    if len(cells) != S or len(proofs) != S:
+        raise InvalidBytesLength("column_indices, cells and proofs must have one entry per sidecar")
+    raw = lambda x: x.data if isinstance(x, _BytesN) else bytes(x)
+    side = lambda xs: raw(xs) if isinstance(xs, (bytes, bytearray, memoryview, _BytesN)) else b"".join(raw(x) for x in xs)
+    cm = b"".join(raw(x) for x in commitments)
+    ce, pr = [side(x) for x in cells], [side(x) for x in proofs]
+    if len(cm) != 48 * m or any(len(x) != 48 * m for x in pr):
+        raise InvalidBytesLength("commitments and proofs are 48 bytes each, one proof per commitment in every sidecar")
+    if any(len(x) != BYTES_PER_CELL * m for x in ce):
+        raise InvalidBytesLength("cells are %d bytes each, one cell per commitment in every sidecar" % BYTES_PER_CELL)
+    if any(not 0 <= int(c) < 2 ** 64 for c in column_indices):
+        raise BadArgs("cell index out of range")
+    idx = (C.c_uint64 * max(S, 1))(*[int(c) for c in column_indices])
+    return cm, m, idx, b"".join(ce), b"".join(pr), S
+
+
+def verify_data_column_sidecars(commitments, column_indices, cells, proofs, kzg_settings, return_errors=True):
+    """The column sidecars of one block through one call (kzg_verify_data_column_sidecars; the consensus spec's
+    verify_data_column_sidecar_kzg_proofs for every sidecar of a slot): `commitments` is the block's list of Bytes48, given once;
+    sidecar j is column_indices[j], cells[j] and proofs[j] - lists of one Cell / Bytes48 per commitment (or their bytes joined).
+    Items of the wrong size or count raise InvalidBytesLength before any device call.  -> (verdicts, errors): sidecar j's verdict is
+    verify_cell_kzg_proof_batch's on (commitments, [column_indices[j]] * m, cells[j], proofs[j]); errors[j] is True where that call
+    would raise BadArgs (its verdict is False then).  With return_errors=False such a sidecar raises BadArgs, the lowest-indexed
+    one's, and errors is all False."""
+    cm, m, idx, ce, pr, S = _data_column_args(commitments, column_indices, cells, proofs)
+    ok = (C.c_bool * max(S, 1))()
+    err = (C.c_uint8 * max(S, 1))()
+    _chk(lib().kzg_verify_data_column_sidecars(ok, C.cast(err, C.c_char_p) if return_errors else None, cm, m, idx, ce, pr, S, kzg_settings._h))
+    return [bool(ok[j]) for j in range(S)], [bool(err[j]) for j in range(S)]
+
+
+def data_column_sidecar_challenges(commitments, column_indices, cells, proofs):
+    """The challenges r_j of verify_data_column_sidecars (host code, no device): a list of 32 big-endian bytes per sidecar."""
+    cm, m, idx, ce, pr, S = _data_column_args(commitments, column_indices, cells, proofs)
+    out = C.create_string_buffer(32 * max(S, 1))
+    _chk(lib().kzg_data_column_sidecar_challenges(out, cm, m, idx, ce, pr, S))
+    return [out.raw[32 * j: 32 * j + 32] for j in range(S)]
 
 
 def _cell_group_args(batches):

@@ -211,6 +211,9 @@ CellState::~CellState() { delete group; }
 // and every launch goes to s->s1.
 struct CellGroupStage {
     const char* why_bad = nullptr;  // the reason of a slot with a flag set
+    // the slots share ONE list of commitments (capi_data_columns.hpp, data_column_plan.hpp): dense commitments 0 .. mtot - 1 are
+    // every slot's, taken from the first slot's batch, weighed per slot; points, scalars and term tables have that plan's layout
+    bool shared_commitments = false;
     // the stage's buffers for plan P; stage.d_idx, d_bad, d_r and d_sc among them
     virtual KzgRet reserve(CellState& cs, const CellGroupPlan& P) = 0;
     // before r: P.idx to stage.d_idx, the slots' data decoded with their canonical check; the flags start back to f_cell [nG] - a
@@ -229,7 +232,9 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
                                 const uint8_t* r_be, const KzgSettings* s, float stage_ms[4], CellGroupStage* stage = nullptr) {
     KzgRet rc = KZG_OK;
     const size_t* const batch_sizes = in.batch_sizes;
-    const uint32_t G = P.G, nG = P.nG, mtot = P.mtot, NP = cell_group_points(nG, mtot), nsc = cell_group_scalars(nG, mtot, G);
+    const bool shared = stage && stage->shared_commitments;  // (one more point layout with the same NP and SKIP; more scalars)
+    const uint32_t G = P.G, nG = P.nG, mtot = P.mtot, NP = cell_group_points(nG, mtot);
+    const uint32_t nsc = shared ? data_column_scalars(G, P.max_ll, mtot) : cell_group_scalars(nG, mtot, G);
     const uint32_t max_terms = P.max_rl;
     const size_t terms = (size_t)2 * G * max_terms;
     const bool aff = msm_affine_enabled();
@@ -254,9 +259,10 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
     for (uint32_t sl = 0; sl < G; sl++) {
         const size_t b = P.slot_batch[sl];
         memcpy(hp + 48 * (size_t)P.idx[P.o_cstart + sl], in.proofs[b], 48 * batch_sizes[b]);
-        for (uint32_t i = P.idx[P.o_ustart + sl]; i < P.idx[P.o_ustart + sl + 1]; i++)
+        for (uint32_t i = shared ? 0u : P.idx[P.o_ustart + sl]; !shared && i < P.idx[P.o_ustart + sl + 1]; i++)
             memcpy(hp + 48 * ((size_t)nG + i), in.commitments[b] + 48 * ((size_t)P.uniq_entry[i] - P.off[b]), 48);
     }
+    for (uint32_t i = 0; i < mtot && shared; i++) memcpy(hp + 48 * ((size_t)nG + i), in.commitments[P.slot_batch[0]] + 48 * (size_t)P.uniq_entry[i], 48);
     memcpy(hp + 48 * ((size_t)nG + mtot), cs->t->mono, sizeof cs->t->mono);
     uint8_t* const skip = hp + 48 * (size_t)cell_group_skip_point(nG, mtot);
     memset(skip, 0, 48);
@@ -279,7 +285,8 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
     uint32_t* const live = reinterpret_cast<uint32_t*>(hp + h_live);
     uint8_t* const r_le = hp + h_r;
     for (uint32_t sl = 0; sl < G; sl++) {
-        const uint32_t c0 = P.idx[P.o_cstart + sl], c1 = P.idx[P.o_cstart + sl + 1], u0 = P.idx[P.o_ustart + sl], u1 = P.idx[P.o_ustart + sl + 1];
+        const uint32_t c0 = P.idx[P.o_cstart + sl], c1 = P.idx[P.o_cstart + sl + 1];
+        const uint32_t u0 = shared ? 0u : P.idx[P.o_ustart + sl], u1 = shared ? mtot : P.idx[P.o_ustart + sl + 1];
         const char* why = nullptr;
         for (uint32_t q = c0; q < c1 && !why; q++)
             if (f_cell[q]) why = stage ? stage->why_bad : "a cell holds a field element >= r";
@@ -303,8 +310,12 @@ static KzgRet cell_group_locked(bool* ok_out, uint8_t* err_out, const char** why
     HIPCHK(hipEventRecord(s->ev[7], st));
     HIPCHK(hipMemcpyAsync(g.d_live.p, live, 4 * (size_t)G, hipMemcpyHostToDevice, st));
     if ((rc = stage ? stage->scalars(s, *cs, P, r_le) : cells_scalars(s, *cs, P, r_le)) != KZG_OK) return rc;
-    hipLaunchKernelGGL(k_cell_terms, dim3((unsigned)((terms + 255) / 256)), dim3(256), 0, st, g.d_term_point.p, g.d_term_scalar.p, ix + P.o_cstart,
-                       ix + P.o_ustart, (const uint32_t*)g.d_live.p, (int)G, (int)nG, (int)mtot, (int)max_terms);
+    if (shared)
+        hipLaunchKernelGGL(k_data_column_terms, dim3((unsigned)((terms + 255) / 256)), dim3(256), 0, st, g.d_term_point.p, g.d_term_scalar.p,
+                           (const uint32_t*)g.d_live.p, (int)G, (int)P.max_ll, (int)mtot, (int)max_terms);
+    else
+        hipLaunchKernelGGL(k_cell_terms, dim3((unsigned)((terms + 255) / 256)), dim3(256), 0, st, g.d_term_point.p, g.d_term_scalar.p, ix + P.o_cstart,
+                           ix + P.o_ustart, (const uint32_t*)g.d_live.p, (int)G, (int)nG, (int)mtot, (int)max_terms);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[8], st));
 

@@ -105,6 +105,18 @@ static KzgRet cell_multi_batches(bool* ok_out, uint8_t* err_out, const uint8_t* 
     });
 }
 
+// kzg_verify_data_column_sidecars: whole sidecars - all of one weight, n_blobs cells - ceil(n / D) consecutive ones per shard; every
+// shard gets the block's commitments and decodes them itself, once
+static KzgRet cell_multi_data_columns(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, size_t n_blobs, const uint64_t* column_indices,
+                                      const uint8_t* cells, const uint8_t* proofs, size_t n_sidecars, const KzgSettings* s) {
+    std::vector<CellShardRange> ranges;
+    cell_shard_ranges_even(ranges, n_sidecars, shard_count(s));
+    return cell_multi_deal(s, ranges, true, [&](const KzgSettings* c, size_t lo, size_t hi) {
+        return data_columns_run(ok_out + lo, err_out ? err_out + lo : nullptr, commitments, n_blobs, column_indices + lo, cells + CELL_BYTES * n_blobs * lo,
+                                proofs + 48 * n_blobs * lo, hi - lo, c);
+    });
+}
+
 // kzg_verify_blob_cell_kzg_proofs, the call that is not queued: by blob, ceil(n / D) per shard (the caller has cleared ok_out / err_out)
 static KzgRet cell_multi_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments, const uint8_t* cell_proofs, size_t n,
                                     const KzgSettings* s) {
@@ -153,6 +165,19 @@ extern "C" KzgRet kzg_debug_cell_shard_stats(const KzgSettings* s, uint64_t* out
             const uint64_t v = reset ? c->cell_stats[i].exchange(0, std::memory_order_relaxed) : c->cell_stats[i].load(std::memory_order_relaxed);
             if (4 * k + i < cap) out[4 * k + i] = v;
         }
+    }
+    return KZG_OK;
+}
+
+// diagnostic (include/kzg_rs_amd.h): calls | sidecars | G1 points decoded | commitments decoded by kzg_verify_data_column_sidecars,
+// summed over the shards (a shard counts the range it ran as a call)
+extern "C" KzgRet kzg_debug_data_column_stats(const KzgSettings* s, uint64_t out[4], int reset) {
+    if (!s || !out) return fail(KZG_BADARGS, "null argument");
+    memset(out, 0, 4 * sizeof(uint64_t));
+    for (size_t k = 0; k < shard_count(s); k++) {
+        const KzgSettings* const c = shard_of(s, k);
+        for (size_t i = 0; i < 4; i++)
+            out[i] += reset ? c->data_column_stats[i].exchange(0, std::memory_order_relaxed) : c->data_column_stats[i].load(std::memory_order_relaxed);
     }
     return KZG_OK;
 }

@@ -12,6 +12,7 @@
 // wavefront per column.
 #pragma once
 #include "cell_group_plan.hpp"
+#include "data_column_plan.hpp"
 #include "fr_kernels.hpp"
 
 namespace kzg {
@@ -155,6 +156,69 @@ __global__ void k_cell_terms(uint32_t* __restrict__ term_point, uint32_t* __rest
     const uint32_t bo = (uint32_t)(e / max_terms), t = (uint32_t)(e % max_terms), g = bo >> 1;
     const CellGroupTerm tm = cell_group_term(bo & 1, t, g, cstart[g], cstart[g + 1] - cstart[g], ustart[g], ustart[g + 1] - ustart[g], (uint32_t)nG,
                                              (uint32_t)mtot, live[g] != 0);
+    term_point[e] = tm.point;
+    term_scalar[e] = tm.scalar;
+}
+
+// ---------------------------------------------------------------- the uniform group: a block's column sidecars (data_column_plan.hpp)
+// S slots of exactly m cells and one column each over m' shared commitments: no (slot, column) or (slot, commitment) lists, the
+// slot is the block index and cell k of every slot is commitment ci[k].
+
+// The r -> scalars stage in one launch, one wavefront per slot g (column col[g] < 128, cells [g m, (g + 1) m) of vals):
+//   r_g^k for k < m, kept in LDS (Montgomery); sc[g m + k] = r_g^k and sc[S m + g m + k] = r_g^k g_c, g_c = h_c^64
+//   sc[2 S m + g m' + i] = w_i, the sum of r_g^k over the cells of distinct commitment i in ascending k (wlist[wstart[i] ..
+//   wstart[i + 1]), the same list for every slot)
+//   agg[j] = sum over k, ascending, of r_g^k cell_k[j], then k_cell_column_ifft's six stages on it, and
+//   sc[2 S m + S m' + 64 g + i] = -I_i = -(A[i] h_c^(-i) / 64): the column's interpolant IS the slot's (it touches no other)
+// all plain.  m <= CELL_GROUP_MAX_CELLS (the caller's threshold): the powers fill at most 8 KB of LDS.
+__global__ __launch_bounds__(64) void k_data_column_scalars(const Fr* __restrict__ r, const uint32_t* __restrict__ col, const uint32_t* __restrict__ wlist,
+                                                            const uint32_t* __restrict__ wstart, const Fr* __restrict__ vals, const Fr* __restrict__ T,
+                                                            Fr* __restrict__ sc, int S, int m, int mp) {
+    __shared__ Fr rk[CELL_GROUP_MAX_CELLS];
+    __shared__ Fr a[CELL_FE];
+    const uint32_t g = blockIdx.x, j = threadIdx.x, nG = (uint32_t)S * (uint32_t)m;
+    const size_t c0 = (size_t)g * m;
+    const uint32_t c = col[g] & (CELLS_PER_EXT_BLOB - 1);  // (validated on the host)
+    const Fr rM = FrF::to_mont(r[g]);
+    const Fr gc = FrF::from_mont(T[CELL_FE * bitrev7(c)]);  // h_c^64 = w8192^(64 brp7(c)), plain
+    for (uint32_t k = j; k < (uint32_t)m; k += CELL_FE) {
+        const Fr p = fr_pow_small(rM, k);
+        rk[k] = p;
+        sc[c0 + k] = FrF::from_mont(p);
+        sc[(size_t)nG + c0 + k] = FrF::mul(p, gc);
+    }
+    __syncthreads();
+    for (uint32_t i = j; i < (uint32_t)mp; i += CELL_FE) {
+        Fr w = FrF::zero();
+        for (uint32_t q = wstart[i]; q < wstart[i + 1]; q++) w = FrF::add(w, rk[wlist[q]]);
+        sc[(size_t)2 * nG + (size_t)g * mp + i] = FrF::from_mont(w);
+    }
+    Fr acc = FrF::zero();
+    for (uint32_t k = 0; k < (uint32_t)m; k++) acc = FrF::add(acc, FrF::mul(rk[k], vals[(c0 + k) * CELL_FE + j]));
+    a[j] = acc;
+    __syncthreads();
+    for (int half = 1; half < CELL_FE; half <<= 1) {
+        if (j < CELL_FE / 2) {
+            const int gr = j / half, kk = j % half, i0 = 2 * half * gr + kk, i1 = i0 + half;
+            const Fr tw = T[(EXT_FE - kk * (EXT_FE / (2 * half))) & (EXT_FE - 1)];  // w_(2 half)^(-kk)
+            const Fr x = a[i0], y = FrF::mul(tw, a[i1]);
+            a[i0] = FrF::add(x, y);
+            a[i1] = FrF::sub(x, y);
+        }
+        __syncthreads();
+    }
+    const uint32_t e = (bitrev7(c) * j) & (EXT_FE - 1);                                 // h_c^i = w8192^(brp7(c) i)
+    const Fr s = FrF::mul(FrF::to_mont(cell_inv64()), T[(EXT_FE - e) & (EXT_FE - 1)]);  // h_c^(-i) / 64, Montgomery
+    sc[(size_t)2 * nG + (size_t)S * mp + (size_t)g * CELL_FE + j] = FrF::neg(FrF::mul(s, a[j]));
+}
+
+// The term tables [2 S][max_terms] of the uniform group (data_column_term); live[g] == 0 masks slot g out: all its terms on SKIP
+__global__ void k_data_column_terms(uint32_t* __restrict__ term_point, uint32_t* __restrict__ term_scalar, const uint32_t* __restrict__ live, int S, int m,
+                                    int mp, int max_terms) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)2 * S * max_terms) return;
+    const uint32_t bo = (uint32_t)(e / max_terms), t = (uint32_t)(e % max_terms), g = bo >> 1;
+    const CellGroupTerm tm = data_column_term(bo & 1, t, g, (uint32_t)S, (uint32_t)m, (uint32_t)mp, live[g] != 0);
     term_point[e] = tm.point;
     term_scalar[e] = tm.scalar;
 }

@@ -73,6 +73,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_cell_prover.hpp"
 #include "capi_cell_recover.hpp"
 #include "capi_blob_cells.hpp"
+#include "capi_data_columns.hpp"
 #include "capi_cell_multi.hpp"
 #include "capi_g1_ntt.hpp"
 #include "capi_debug.hpp"
