@@ -451,6 +451,48 @@ KzgRet kzg_verify_data_column_sidecars(bool *ok_out, uint8_t *err_out, const uin
 KzgRet kzg_data_column_sidecar_challenges(uint8_t *r_out, const uint8_t *commitments, size_t n_blobs,
                                           const uint64_t *column_indices, const uint8_t *cells, const uint8_t *proofs,
                                           size_t n_sidecars);
+/* The PRODUCING side of a block's data column sidecars, in the layout kzg_verify_data_column_sidecars takes: a node that holds 64 or
+ * more verified sidecars of a block rebuilds the others.  Given sidecar j is column column_indices[j] (strictly ascending,
+ * 64 <= n_given <= 128), its n_blobs cells are at cells + j * n_blobs * 2048 and its n_blobs proofs at proofs + j * n_blobs * 48; host
+ * pointers.  proofs may be NULL: the missing proofs then come from the FK20 chain on the recovered coefficients, as in
+ * kzg_recover_cells_and_kzg_proofs; otherwise they are interpolated from the FIRST 64 given sidecars' proofs, as in
+ * kzg_recover_cells_and_kzg_proofs_given_proofs, and the FK20 table is neither built nor read.
+ * THE CALL TAKES NO COMMITMENT AND DOES NOT VERIFY THE GIVEN PROOFS: with wrong but well-formed proofs it returns KZG_OK and the
+ * missing proofs are the deterministic interpolation of what was given (the cells are unaffected) - verify the sidecars first
+ * (kzg_verify_data_column_sidecars), or pass proofs == NULL.
+ * Only the 128 - n_given MISSING columns are written, in ascending column order: missing column q goes to cells_out + q * n_blobs *
+ * 2048 and proofs_out + q * n_blobs * 48.  Either output may be NULL, not both; proofs_out is never required, and with proofs != NULL
+ * and proofs_out == NULL the given proofs are still decoded and checked.  n_given == 128 writes nothing and still validates.  The
+ * bytes written equal, cell for cell and proof for proof, what the blob-major call (..._given_proofs when proofs != NULL, else the
+ * plain one) gives for the same blobs when every blob carries the list column_indices.  Refusals, codes and their order are that
+ * call's: the index list is checked on the host before anything is copied (the count, then index after index its range and its
+ * order); KZG_BADARGS also for a field element >= r, for cells of a blob that are not the evaluations of one polynomial of degree
+ * < 4096, for a given proof that is not a G1 point (any of them, also beyond the first 64; the identity is allowed) and for
+ * settings without G1 points; KZG_BAD_SETUP for an off-subgroup set-up point.  n_blobs == 0 is KZG_OK after the index check.  After
+ * an error the handle stays usable and no output is promised; two runs give the same bytes.
+ * Against the blob-major route (gather the sidecars into per-blob lists, repeat the index list n_blobs times, recover, scatter the
+ * missing columns back): 64 blobs (a chunk) go up as ONE pitched copy of the cells and one of the proofs, straight from the
+ * caller's arrays; the vanishing polynomial of the missing columns and the 64 x (128 - n_given) interpolation weights depend on the
+ * index list alone and are computed ONCE per call (one workgroup each) instead of once per blob and chunk; only the missing columns
+ * get their forward transform, and they come down as one pitched copy into the caller's arrays: half the device-to-host bytes or
+ * less.  The handle's lock is taken; a multi-device handle deals the blobs over its devices, ceil(n_blobs / D) consecutive blobs per
+ * shard, each shard with its own set-up of the index list, which is refused for the whole call first (MULTI-DEVICE CELL CALLS
+ * below; counted in kzg_debug_cell_shard_stats as blobs proved or recovered).  Time of the call beside that route
+ * (tools/prof/data_column_recover_probe.py, profiles/data_column_recover_probe.json; 64 given sidecars x 6 / 21 / 72 blobs, median wall
+ * clock, both sides from and to column-major host arrays in one run): with the proofs given 7.52 / 11.68 / 28.33 ms against 7.65 /
+ * 12.01 / 31.29 ms, by FK20 10.35 / 23.98 / 72.73 ms against 10.31 / 24.30 / 74.85 ms. */
+KzgRet kzg_recover_data_column_sidecars(uint8_t *cells_out, uint8_t *proofs_out, const uint64_t *column_indices,
+                                        size_t n_given, const uint8_t *cells, const uint8_t *proofs, size_t n_blobs,
+                                        const KzgSettings *s);
+/* All 128 sidecars of a block from its blobs (n_blobs * 131072 bytes, host): kzg_compute_cells_and_kzg_proofs' bytes exactly,
+ * transposed - sidecar c goes to cells_out + c * n_blobs * 2048 and proofs_out + c * n_blobs * 48.  cells_out may be NULL and
+ * proofs_out may be NULL, not both; without proofs_out neither the FK20 table nor the chain is touched.  Errors are that call's
+ * (KZG_BADARGS for a field element >= r or settings without G1 points, KZG_BAD_SETUP); n_blobs == 0 is KZG_OK.  Cells 64..127 are
+ * written column-major on the device and come down as one pitched copy per 64 blobs; cells 0..63 are the blobs' own bytes, placed
+ * by the host meanwhile.  Multi-device handles deal the blobs as above.  Time of the call beside kzg_compute_cells_and_kzg_proofs
+ * and a host transposition (the same probe, 6 / 21 / 72 blobs): 9.89 / 23.77 / 73.07 ms against 9.91 / 24.02 / 73.78 ms. */
+KzgRet kzg_compute_data_column_sidecars(uint8_t *cells_out, uint8_t *proofs_out, const uint8_t *blobs, size_t n_blobs,
+                                        const KzgSettings *s);
 /* Blobs against their 128 cell proofs each, a verdict per blob, WITHOUT computing a cell: the execution layer's Fulu check of a blob
  * transaction's network wrapper (version 1) and of engine_getBlobsV2 answers, which carry per blob the blob, its commitment and its
  * 128 cell proofs and no blob proof.  Inputs are host arrays: blobs n * 131072 bytes, commitments n * 48, cell_proofs n * 128 * 48
@@ -663,6 +705,11 @@ KzgRet kzg_debug_blob_cell_queue_stats(const KzgSettings *s, uint64_t out[4], in
  * identity of every group included), commitments decoded }.  One call of S sidecars over m blobs with m' distinct commitments on one
  * device: { 1, S, S m + m' + 65, m' } - the commitments are decoded once per call and per shard, not once per sidecar. */
 KzgRet kzg_debug_data_column_stats(const KzgSettings *s, uint64_t out[4], int reset);
+/* Diagnostic: kzg_recover_data_column_sidecars on this handle since the last reset, summed over its shards: out = { ranges run (a
+ * single-device call is one; a shard counts the range it was dealt), blobs, columns written (per range), index-list set-ups (the
+ * launches of the vanishing-polynomial and weight kernels: once per range) }.  One single-device call of n blobs, whatever n:
+ * { 1, n, 128 - n_given, 1 }.  The blob-major recoveries and kzg_compute_data_column_sidecars do not count here. */
+KzgRet kzg_debug_data_column_recover_stats(const KzgSettings *s, uint64_t out[4], int reset);
 /* Diagnostic: the EIP-7594 cell work each shard of the handle has run since the last reset.  For shard k (device k of the handle's
  * list; a single-device handle is one shard) out[4 k .. 4 k + 3] = { cell-family launches run on it - ranges under its lock and
  * coalesced launches led by its lanes -, cells verified, blobs verified against their cell proofs, blobs proved or recovered }.

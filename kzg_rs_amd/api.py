@@ -183,6 +183,9 @@ def lib():
         L.kzg_verify_data_column_sidecars.argtypes = [bp, u8, u8, sz, C.POINTER(C.c_uint64), u8, u8, sz, vp]
         L.kzg_data_column_sidecar_challenges.argtypes = [u8, u8, sz, C.POINTER(C.c_uint64), u8, u8, sz]
         L.kzg_debug_data_column_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.kzg_recover_data_column_sidecars.argtypes = [u8, u8, C.POINTER(C.c_uint64), sz, u8, u8, sz, vp]
+        L.kzg_compute_data_column_sidecars.argtypes = [u8, u8, u8, sz, vp]
+        L.kzg_debug_data_column_recover_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         _lib = L
     return _lib
 
@@ -342,6 +345,13 @@ class KzgSettings:
         this handle since the last reset, summed over its shards."""
         out = (C.c_uint64 * 4)()
         _chk(lib().kzg_debug_data_column_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(x) for x in out)
+
+    def data_column_recover_stats(self, reset=False):
+        """kzg_debug_data_column_recover_stats: (ranges run, blobs, columns written, index-list set-ups) of
+        recover_data_column_sidecars on this handle since the last reset, summed over its shards."""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().kzg_debug_data_column_recover_stats(self._h, out, 1 if reset else 0))
         return tuple(int(x) for x in out)
 
     def cell_shard_stats(self, reset=False):
@@ -1063,6 +1073,62 @@ def recover_cells_and_kzg_proofs_given_proofs(cell_indices, cells, proofs, kzg_s
     all_proofs = [[raw[48 * (CELLS_PER_EXT_BLOB * b + c): 48 * (CELLS_PER_EXT_BLOB * b + c + 1)] for c in range(CELLS_PER_EXT_BLOB)]
                   for b in range(n)]
     return _cells_of(out, n), all_proofs
+
+
+def _sidecar_rows(rows, item, what):
+    """per sidecar a list of items (or their bytes joined) -> (the rows joined, items per row)"""
+    raw = lambda x: x.data if isinstance(x, _BytesN) else bytes(x)
+    data = [raw(r) if isinstance(r, (bytes, bytearray, memoryview, _BytesN)) else b"".join(raw(x) for x in r) for r in rows]
+    m = len(data[0]) // item if data else 0
+    if any(len(r) != item * m for r in data):
+        raise InvalidBytesLength("%s are %d bytes each, the same number in every sidecar" % (what, item))
+    return b"".join(data), m
+
+
+def recover_data_column_sidecars(column_indices, cells, proofs, kzg_settings):
+    """The missing column sidecars of one block from 64 or more of them (kzg_recover_data_column_sidecars): given sidecar j is
+    column column_indices[j] (strictly ascending), cells[j] and proofs[j] its lists of one Cell / Bytes48 per blob (or their bytes
+    joined).  proofs may be None: the missing proofs are then recomputed by FK20; otherwise they are interpolated from the first 64
+    given sidecars' proofs, which are NOT checked against the cells (include/kzg_rs_amd.h) - verify the sidecars first.
+    -> {column: (cells, proofs)} for every column that was not given, each a list with one Cell / one 48-byte string per blob.
+    Rows of the wrong size or count raise InvalidBytesLength before any device call; everything else that is wrong with the
+    input raises BadArgs."""
+    S = len(column_indices)
+    if len(cells) != S or (proofs is not None and len(proofs) != S):
+        raise InvalidBytesLength("column_indices, cells and proofs must have one entry per sidecar")
+    if any(not 0 <= int(c) < 1 << 64 for c in column_indices):
+        raise KzgError("BadArgs", "column index out of range")
+    ce, m = _sidecar_rows(cells, BYTES_PER_CELL, "cells")
+    pr = None
+    if proofs is not None:
+        pr, mp = _sidecar_rows(proofs, 48, "proofs")
+        if mp != m:
+            raise InvalidBytesLength("every sidecar needs as many proofs as cells")
+    idx = (C.c_uint64 * max(S, 1))(*[int(c) for c in column_indices])
+    out = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * max(m, 1))
+    po = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(m, 1))
+    _chk(lib().kzg_recover_data_column_sidecars(out, po, idx, S, ce, pr, m, kzg_settings._h))
+    given = set(int(c) for c in column_indices)
+    oc, op = out.raw, po.raw
+    res = {}
+    for q, col in enumerate(c for c in range(CELLS_PER_EXT_BLOB) if c not in given):
+        res[col] = ([Cell(oc[BYTES_PER_CELL * (q * m + b): BYTES_PER_CELL * (q * m + b + 1)]) for b in range(m)],
+                    [op[48 * (q * m + b): 48 * (q * m + b + 1)] for b in range(m)])
+    return res
+
+
+def compute_data_column_sidecars(blobs, kzg_settings):
+    """All 128 column sidecars of a block from its blobs (kzg_compute_data_column_sidecars): -> (cells, proofs), cells[c] the list
+    of column c's Cells, one per blob, and proofs[c] its 48-byte proofs: compute_cells_and_kzg_proofs, transposed on the device.
+    Errors as compute_cells."""
+    data = _cell_prover_blobs(blobs)
+    m = len(data)
+    out = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL * max(m, 1))
+    po = C.create_string_buffer(48 * CELLS_PER_EXT_BLOB * max(m, 1))
+    _chk(lib().kzg_compute_data_column_sidecars(out, po, b"".join(data), m, kzg_settings._h))
+    oc, op = out.raw, po.raw
+    return ([[Cell(oc[BYTES_PER_CELL * (c * m + b): BYTES_PER_CELL * (c * m + b + 1)]) for b in range(m)] for c in range(CELLS_PER_EXT_BLOB)],
+            [[op[48 * (c * m + b): 48 * (c * m + b + 1)] for b in range(m)] for c in range(CELLS_PER_EXT_BLOB)])
 
 
 def g1_mul_generator(scalars, kzg_settings):

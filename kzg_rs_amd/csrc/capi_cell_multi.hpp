@@ -6,9 +6,10 @@
 // trusted setup (capi_settings.hpp load_trusted_setup_on) and derives its own cell set-up and prover state on its own device, under
 // its own lock, the first time it is given such work; a shard that gets nothing derives nothing.
 //   * the calls under a lock (kzg_verify_cell_kzg_proof_batches; kzg_verify_blob_cell_kzg_proofs when it is not queued;
-//     kzg_compute_cells[_and_kzg_proofs]; both recoveries): cut into contiguous ranges, at most one per shard
-//     (cell_shard_ranges.hpp), each range the single-device body on its shard - cell_batches_run, blob_cell_call_direct,
-//     cell_prover_run, cell_recover_run: the very functions a single-device handle runs - from a host thread of its own, under that
+//     kzg_compute_cells[_and_kzg_proofs]; both recoveries; the two data column sidecar producers): cut into contiguous ranges, at
+//     most one per shard (cell_shard_ranges.hpp), each range the single-device body on its shard - cell_batches_run,
+//     blob_cell_call_direct, cell_prover_run, cell_recover_run, data_column_recover_run, data_column_compute_run: the very
+//     functions a single-device handle runs - from a host thread of its own, under that
 //     shard's lock, writing straight into the caller's arrays at its units' offsets;
 //   * the queued calls (capi_coalesce.hpp): lanes on every shard lead cell launches, each with the set-up of the shard it lives on.
 // A lone kzg_verify_cell_kzg_proof_batch is one transcript and one pairing: it is not cut.
@@ -156,6 +157,28 @@ static KzgRet cell_multi_recover(uint8_t* cells_out, uint8_t* proofs_out, const 
     });
 }
 
+// kzg_recover_data_column_sidecars: by blob, ceil(n_blobs / D) per shard, each shard on its blobs' part of every row of the caller's
+// column-major arrays (the row pitch stays the call's n_blobs) and with its own once-per-range set-up of the index list, which the
+// entry point has checked for the whole call
+static KzgRet cell_multi_data_column_recover(uint8_t* cells_out, uint8_t* proofs_out, const DataColumnRecoverPlan& P, const uint8_t* cells, const uint8_t* given,
+                                             size_t n_blobs, const KzgSettings* s) {
+    std::vector<CellShardRange> ranges;
+    cell_shard_ranges_even(ranges, n_blobs, shard_count(s));
+    return cell_multi_deal(s, ranges, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
+        return data_column_recover_run(cells_out ? cells_out + DC_CELL_BYTES * lo : nullptr, proofs_out ? proofs_out + DC_PROOF_BYTES * lo : nullptr, P,
+                                       cells + DC_CELL_BYTES * lo, given ? given + DC_PROOF_BYTES * lo : nullptr, hi - lo, n_blobs, c);
+    });
+}
+// kzg_compute_data_column_sidecars: the same dealing; the blobs themselves are blob-major
+static KzgRet cell_multi_data_column_compute(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n_blobs, const KzgSettings* s) {
+    std::vector<CellShardRange> ranges;
+    cell_shard_ranges_even(ranges, n_blobs, shard_count(s));
+    return cell_multi_deal(s, ranges, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
+        return data_column_compute_run(cells_out ? cells_out + DC_CELL_BYTES * lo : nullptr, proofs_out ? proofs_out + DC_PROOF_BYTES * lo : nullptr,
+                                       blobs + (size_t)BLOB_BYTES * lo, hi - lo, n_blobs, c);
+    });
+}
+
 // diagnostic (include/kzg_rs_amd.h): out[4 k .. 4 k + 3] = the cell work shard k has run since the last reset
 extern "C" KzgRet kzg_debug_cell_shard_stats(const KzgSettings* s, uint64_t* out, size_t cap, int reset) {
     if (!s || (cap && !out)) return fail(KZG_BADARGS, "null argument");
@@ -178,6 +201,19 @@ extern "C" KzgRet kzg_debug_data_column_stats(const KzgSettings* s, uint64_t out
         const KzgSettings* const c = shard_of(s, k);
         for (size_t i = 0; i < 4; i++)
             out[i] += reset ? c->data_column_stats[i].exchange(0, std::memory_order_relaxed) : c->data_column_stats[i].load(std::memory_order_relaxed);
+    }
+    return KZG_OK;
+}
+
+// diagnostic (include/kzg_rs_amd.h): ranges run | blobs | columns written | index-list set-ups of kzg_recover_data_column_sidecars,
+// summed over the shards
+extern "C" KzgRet kzg_debug_data_column_recover_stats(const KzgSettings* s, uint64_t out[4], int reset) {
+    if (!s || !out) return fail(KZG_BADARGS, "null argument");
+    memset(out, 0, 4 * sizeof(uint64_t));
+    for (size_t k = 0; k < shard_count(s); k++) {
+        const KzgSettings* const c = shard_of(s, k);
+        for (size_t i = 0; i < 4; i++)
+            out[i] += reset ? c->data_column_recover_stats[i].exchange(0, std::memory_order_relaxed) : c->data_column_recover_stats[i].load(std::memory_order_relaxed);
     }
     return KZG_OK;
 }

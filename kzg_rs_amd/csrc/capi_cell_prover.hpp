@@ -19,7 +19,7 @@
 struct CellProverCallBufs {  // what CellProverState::reserve rebuilds as a whole
     size_t cap = 0;                // blobs the call buffers hold
     bool cap_proofs = false;       // ... with the proof path's buffers
-    DevBuf<uint8_t> d_blobs, d_ext, d_out;
+    DevBuf<uint8_t> d_blobs, d_ext, d_out, d_colout;  // (d_colout: the proofs by column, capi_data_column_recover.hpp)
     DevBuf<Fr> d_coef, d_sc;
     DevBuf<G1Jac29Mem> d_H, d_Hrows, d_P;
     DevBuf<uint32_t> d_status;
@@ -47,6 +47,7 @@ struct CellProverState : CellProverCallBufs {
             HIPCHK(d_Hrows.alloc(FK20_K2 * FK20_ROWS * c));
             HIPCHK(d_P.alloc(FK20_K2 * c));
             HIPCHK(d_out.alloc((size_t)48 * FK20_K2 * c));
+            HIPCHK(d_colout.alloc((size_t)48 * FK20_K2 * c));
         }
         cap = c;
         cap_proofs = pr;

@@ -24,7 +24,7 @@
 
 struct CellRecoverState {
     size_t cap = 0;  // blobs
-    DevBuf<uint8_t> d_cells, d_cidx, d_slot, d_out;
+    DevBuf<uint8_t> d_cells, d_cidx, d_slot, d_out, d_cols;  // (d_cols: a block's missing columns, capi_data_column_recover.hpp)
     DevBuf<Fr29> d_u, d_zev, d_invz, d_ev;
     KzgRet reserve(size_t m) {
         if (m <= cap) return KZG_OK;
@@ -32,6 +32,7 @@ struct CellRecoverState {
         HIPCHK(d_cells.alloc((size_t)RECOVER_N * CELL_FE * 32 * m));
         HIPCHK(d_cidx.alloc((size_t)RECOVER_N * m));
         HIPCHK(d_slot.alloc((size_t)RECOVER_N * m));
+        HIPCHK(d_cols.alloc((size_t)RECOVER_N));
         HIPCHK(d_out.alloc((size_t)RECOVER_N * CELL_FE * 32 * m));
         HIPCHK(d_u.alloc((size_t)RECOVER_N * CELL_FE * m));
         HIPCHK(d_zev.alloc((size_t)RECOVER_N * m));

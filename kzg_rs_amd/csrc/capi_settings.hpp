@@ -139,6 +139,8 @@ struct KzgSettings {
     mutable std::atomic<uint64_t> cell_stats[4] = {};
     // kzg_debug_data_column_stats (capi_data_columns.hpp): calls run on this shard | sidecars | G1 points decoded | commitments decoded
     mutable std::atomic<uint64_t> data_column_stats[4] = {};
+    // kzg_debug_data_column_recover_stats (capi_data_column_recover.hpp): ranges run on this shard | blobs | columns written | index-list set-ups
+    mutable std::atomic<uint64_t> data_column_recover_stats[4] = {};
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the
     // last launch group, and summed over the groups finished since the last reset (kzg_kernel_stamp_totals)

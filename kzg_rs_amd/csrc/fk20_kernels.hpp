@@ -70,20 +70,18 @@ __device__ __forceinline__ void ntt_stages(uint32_t* s, int t, const Fr29Mem* __
     }
 }
 
-// One workgroup per blob.  blobs: n x 131072 big-endian bytes.  coef[b][i] = the blob polynomial's coefficient i (plain canonical
-// limbs; kept for the proofs), ext[b][j] = entry j of the extended blob's second half (32 big-endian bytes: cells 64..127 back
-// to back), status[b] |= 1 when a field element is >= r (the caller zeroes status).
-__global__ __launch_bounds__(CELL_NTT_THREADS) void k_cell_ntt(const uint8_t* __restrict__ blobs, const Fr29Mem* __restrict__ W, Fr* __restrict__ coef,
-                                                               uint8_t* __restrict__ ext, uint32_t* __restrict__ status) {
-    extern __shared__ uint32_t ntt_s[];
+// The work of one workgroup of k_cell_ntt on one blob.  src: the blob's 131072 big-endian bytes; coef[i] = the blob polynomial's
+// coefficient i (plain canonical limbs; kept for the proofs); entry j of the extended blob's second half (32 big-endian bytes)
+// goes to dst(j); *status |= 1 when a field element is >= r.  ntt_s: the workgroup's CELL_NTT_LDS bytes.
+template <class DST>
+__device__ __forceinline__ void cell_ntt_body(uint32_t* ntt_s, int t, const uint4* __restrict__ src, const Fr29Mem* __restrict__ W, Fr* __restrict__ coef,
+                                              uint32_t* __restrict__ status, DST dst) {
     constexpr int N = FE_PER_BLOB, Q = N / CELL_NTT_THREADS;
-    const int b = blockIdx.x, t = threadIdx.x;
-    const uint4* src = reinterpret_cast<const uint4*>(blobs + (size_t)BLOB_BYTES * b);
 #pragma unroll 1
     for (int q = 0; q < Q; q++) {
         const int i = t + CELL_NTT_THREADS * q;
         const Fr v = fr_from_be_words(src[2 * i], src[2 * i + 1]);
-        if (FrF::geq_mod(v)) atomicOr(&status[b], 1u);
+        if (FrF::geq_mod(v)) atomicOr(status, 1u);
         ntt_put<N>(ntt_s, i, fr29_from_words(v.l));  // (the blob's order IS the bit-reversed order a DIT transform reads)
     }
     __syncthreads();
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(CELL_NTT_THREADS) void k_cell_ntt(const uint8_t* __
         const Fr29 c = cell_ntt_scale(ntt_get<N>(ntt_s, i));
         Fr a;
         cell_fr_canonical(a.l, c);
-        coef[(size_t)b * N + i] = a;
+        coef[i] = a;
         tw[q] = fr29_mul(c, fr29_load9(W + i));  // a_i w8192^i
     }
     __syncthreads();
@@ -103,7 +101,6 @@ __global__ __launch_bounds__(CELL_NTT_THREADS) void k_cell_ntt(const uint8_t* __
     for (int q = 0; q < Q; q++) ntt_put<N>(ntt_s, (int)bitrev12((uint32_t)(t + CELL_NTT_THREADS * q)), tw[q]);
     __syncthreads();
     ntt_stages<N, CELL_NTT_THREADS>(ntt_s, t, W, false);
-    uint4* dst = reinterpret_cast<uint4*>(ext + (size_t)BLOB_BYTES * b);
 #pragma unroll 1
     for (int q = 0; q < Q; q++) {
         const int j = t + CELL_NTT_THREADS * q;
@@ -111,9 +108,22 @@ __global__ __launch_bounds__(CELL_NTT_THREADS) void k_cell_ntt(const uint8_t* __
         cell_fr_canonical(a.l, ntt_get<N>(ntt_s, (int)bitrev12((uint32_t)j)));  // entry j = p(w8192 w4096^brp12(j))
         uint4 hi, lo;
         fr_to_be_words(hi, lo, a);
-        dst[2 * j] = hi;
-        dst[2 * j + 1] = lo;
+        uint4* const d = dst(j);
+        d[0] = hi;
+        d[1] = lo;
     }
+}
+
+// One workgroup per blob.  blobs: n x 131072 big-endian bytes.  coef[b][i] = the blob polynomial's coefficient i (plain canonical
+// limbs; kept for the proofs), ext[b][j] = entry j of the extended blob's second half (32 big-endian bytes: cells 64..127 back
+// to back), status[b] |= 1 when a field element is >= r (the caller zeroes status).
+__global__ __launch_bounds__(CELL_NTT_THREADS) void k_cell_ntt(const uint8_t* __restrict__ blobs, const Fr29Mem* __restrict__ W, Fr* __restrict__ coef,
+                                                               uint8_t* __restrict__ ext, uint32_t* __restrict__ status) {
+    extern __shared__ uint32_t ntt_s[];
+    const int b = blockIdx.x;
+    uint4* const out = reinterpret_cast<uint4*>(ext + (size_t)BLOB_BYTES * b);
+    cell_ntt_body(ntt_s, (int)threadIdx.x, reinterpret_cast<const uint4*>(blobs + (size_t)BLOB_BYTES * b), W, coef + (size_t)b * FE_PER_BLOB, status + b,
+                  [out](int j) { return out + 2 * j; });
 }
 
 // One wavefront per (i, blob): the 128-point forward DFT of t_i; sc[(b * 128 + k) * 64 + i] = t^_i[k] (plain canonical): the
@@ -203,6 +213,15 @@ struct Fk20Lagrange {  // the slot-th missing proof of blob b from its first 64 
     __device__ static int out_slot(int slot) { return slot; }
     __device__ static size_t point(int b, int slot, int t) { return (size_t)b * 64 + t; }
     __device__ static size_t scalar(int b, int slot, int t) { return ((size_t)b * FK20_K2 + slot) * 64 + t; }
+};
+
+// Fk20Lagrange for the blobs of ONE block (data_column_recover_kernels.hpp): every blob carries the same index list, so the weights
+// lambda[slot][t] exist once, and the given proofs lie column-major - proof t of blob b at t * m + b, m = the blobs of the launch
+struct Fk20LagrangeShared {
+    static constexpr int TERMS = 64;
+    __device__ static int out_slot(int slot) { return slot; }
+    __device__ static size_t point(int b, int slot, int t) { return (size_t)t * gridDim.y + b; }
+    __device__ static size_t scalar(int b, int slot, int t) { return (size_t)slot * 64 + t; }
 };
 
 // One workgroup per (slot, blob): out[b * 128 + slot] = sum_t scalar_t * point_t over the rows 2^(8c) point (see the header

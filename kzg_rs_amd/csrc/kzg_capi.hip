@@ -30,6 +30,7 @@
 #include "fk20_kernels.hpp"
 #include "g1_ntt.hpp"
 #include "recover_kernels.hpp"
+#include "data_column_recover_kernels.hpp"
 #include "blob_cell_kernels.hpp"
 
 using namespace kzg;
@@ -74,6 +75,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_cell_recover.hpp"
 #include "capi_blob_cells.hpp"
 #include "capi_data_columns.hpp"
+#include "capi_data_column_recover.hpp"
 #include "capi_cell_multi.hpp"
 #include "capi_g1_ntt.hpp"
 #include "capi_debug.hpp"

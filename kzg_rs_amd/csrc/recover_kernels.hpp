@@ -28,22 +28,28 @@ __device__ __forceinline__ Fr29 fr29_ld(const Fr29* p) {
     return r;
 }
 
-// One wavefront per (slot, blob).  cells: the given cells, blob after blob, `per` each, 2048 big-endian bytes; cidx[b * per + slot]
-// = the cell's index (validated on the host).  u[(b * per + slot) * 64 + i] = 64 P_i(y_c) (product output); status[b] |= 1 when a
-// field element is >= r.  Entry j of a cell is the value at h_c w64^brp6(j): the order a decimation-in-time transform reads.
-__global__ __launch_bounds__(64) void k_recover_cell_idft(const uint8_t* __restrict__ cells, const uint8_t* __restrict__ cidx, int per,
-                                                          const Fr29Mem* __restrict__ W, Fr29* __restrict__ u, uint32_t* __restrict__ status) {
-    __shared__ uint32_t s[CELL_FE * 9];
-    const int slot = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-    const size_t at = (size_t)b * per + slot;
-    const uint4* src = reinterpret_cast<const uint4*>(cells + at * (CELL_FE * 32));
+// One wavefront on one given cell (the body of k_recover_cell_idft).  src: the cell's 2048 big-endian bytes, cell: its index
+// (validated on the host); u[i] = 64 P_i(y_c) (product output); *status |= 1 when a field element is >= r.  Entry j of a cell is
+// the value at h_c w64^brp6(j): the order a decimation-in-time transform reads.  s: CELL_FE * 9 words of LDS.
+__device__ __forceinline__ void recover_cell_idft_body(uint32_t* s, int t, const uint4* __restrict__ src, uint32_t cell, const Fr29Mem* __restrict__ W,
+                                                       Fr29* __restrict__ u, uint32_t* __restrict__ status) {
     const Fr v = fr_from_be_words(src[2 * t], src[2 * t + 1]);
-    if (FrF::geq_mod(v)) atomicOr(&status[b], RECOVER_BAD_ELEMENT);
+    if (FrF::geq_mod(v)) atomicOr(status, RECOVER_BAD_ELEMENT);
     ntt_put<CELL_FE>(s, t, fr29_from_words(v.l));
     __syncthreads();
     ntt_stages<CELL_FE, 64>(s, t, W, true);
-    const uint32_t k = bitrev7((uint32_t)cidx[at] & (RECOVER_N - 1));
-    u[at * CELL_FE + t] = recover_mul(ntt_get<CELL_FE>(s, t), fr29_load9(W + recover_pow_index(k, (uint32_t)t, true)));
+    const uint32_t k = bitrev7(cell & (RECOVER_N - 1));
+    u[t] = recover_mul(ntt_get<CELL_FE>(s, t), fr29_load9(W + recover_pow_index(k, (uint32_t)t, true)));
+}
+
+// One wavefront per (slot, blob).  cells: the given cells, blob after blob, `per` each, 2048 big-endian bytes; cidx[b * per + slot]
+// = the cell's index.  u[(b * per + slot) * 64 + i], status[b]: see the body.
+__global__ __launch_bounds__(64) void k_recover_cell_idft(const uint8_t* __restrict__ cells, const uint8_t* __restrict__ cidx, int per,
+                                                          const Fr29Mem* __restrict__ W, Fr29* __restrict__ u, uint32_t* __restrict__ status) {
+    __shared__ uint32_t s[CELL_FE * 9];
+    const int slot = blockIdx.x, b = blockIdx.y;
+    const size_t at = (size_t)b * per + slot;
+    recover_cell_idft_body(s, (int)threadIdx.x, reinterpret_cast<const uint4*>(cells + at * (CELL_FE * 32)), (uint32_t)cidx[at], W, u + at * CELL_FE, status + b);
 }
 
 // One workgroup of 128 lanes per blob.  slot[b][c] = the position of cell c among the blob's given cells, or RECOVER_MISSING.
@@ -95,20 +101,18 @@ __device__ __forceinline__ void recover_pointwise(uint32_t* s, int t, ENTRY entr
     __syncthreads();
 }
 
-// One wavefront per (i, blob).  coef[b][64 k + i] = P_i[k], k < 64 (plain canonical limbs: what k_fk20_tvec_dft reads);
-// status[b] |= 2 when a coefficient P_i[k], k >= 64, is not zero; ev[(b * 128 + c) * 64 + i] = P_i(y_c) h_c^i (product output).
-__global__ __launch_bounds__(64) void k_recover_poly(const Fr29* __restrict__ u, const uint8_t* __restrict__ slot, int per, const Fr29* __restrict__ zev,
-                                                     const Fr29* __restrict__ invz, const Fr29Mem* __restrict__ W, Fr* __restrict__ coef,
-                                                     Fr29* __restrict__ ev, uint32_t* __restrict__ status) {
-    __shared__ uint32_t s[RECOVER_N * 9];
-    const int i = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-    const Fr29* zb = zev + (size_t)b * RECOVER_N;
-    const Fr29* ib = invz + (size_t)b * RECOVER_N;
+// One wavefront on problem i of one blob (the body of k_recover_poly).  u: the blob's u_c[.] (slot * 64 + i), slot: its map cell ->
+// slot, zev / invz: k_recover_vanishing's 128 entries each for that map; coef[64 k + i] = P_i[k], k < 64 (plain canonical limbs:
+// what k_fk20_tvec_dft reads); *status |= 2 when a coefficient P_i[k], k >= 64, is not zero; ev[c * 64 + i] = P_i(y_c) h_c^i
+// (product output).  s: RECOVER_N * 9 words of LDS.
+__device__ __forceinline__ void recover_poly_body(uint32_t* s, int i, int t, const Fr29* __restrict__ u, const uint8_t* __restrict__ slot,
+                                                  const Fr29* __restrict__ zb, const Fr29* __restrict__ ib, const Fr29Mem* __restrict__ W, Fr* __restrict__ coef,
+                                                  Fr29* __restrict__ ev, uint32_t* __restrict__ status) {
 #pragma unroll 1
     for (int c = t; c < RECOVER_N; c += 64) {  // (position c of the bit-reversed input is k = brp7(c): cell c)
-        const uint32_t sl = slot[(size_t)b * RECOVER_N + c];
+        const uint32_t sl = slot[c];
         Fr29 e = fr29_small(0u);
-        if (sl != RECOVER_MISSING) e = recover_mul(fr29_ld(u + ((size_t)b * per + sl) * CELL_FE + i), fr29_ld(zb + c));
+        if (sl != RECOVER_MISSING) e = recover_mul(fr29_ld(u + (size_t)sl * CELL_FE + i), fr29_ld(zb + c));
         ntt_put<RECOVER_N>(s, c, e);
     }
     __syncthreads();
@@ -122,8 +126,8 @@ __global__ __launch_bounds__(64) void k_recover_poly(const Fr29* __restrict__ u,
     Fr a, z;
     cell_fr_canonical(a.l, lo);
     cell_fr_canonical(z.l, hi);
-    if (!recover_is_zero(z.l)) atomicOr(&status[b], RECOVER_INCONSISTENT);
-    coef[(size_t)b * FE_PER_BLOB + CELL_FE * t + i] = a;
+    if (!recover_is_zero(z.l)) atomicOr(status, RECOVER_INCONSISTENT);
+    coef[CELL_FE * t + i] = a;
     __syncthreads();
     // P_i on <w128>: the forward transform of the lower half, the upper half zero
     ntt_put<RECOVER_N>(s, (int)bitrev7((uint32_t)t), lo);
@@ -132,26 +136,38 @@ __global__ __launch_bounds__(64) void k_recover_poly(const Fr29* __restrict__ u,
     ntt_stages<RECOVER_N, 64>(s, t, W, false);
 #pragma unroll 1
     for (int k = t; k < RECOVER_N; k += 64)
-        ev[((size_t)b * RECOVER_N + bitrev7((uint32_t)k)) * CELL_FE + i] =
-            recover_mul(ntt_get<RECOVER_N>(s, k), fr29_load9(W + recover_pow_index((uint32_t)k, (uint32_t)i, false)));
+        ev[(size_t)bitrev7((uint32_t)k) * CELL_FE + i] = recover_mul(ntt_get<RECOVER_N>(s, k), fr29_load9(W + recover_pow_index((uint32_t)k, (uint32_t)i, false)));
 }
 
-// One wavefront per (cell, blob): P(h_c w64^t) = sum_i (P_i(y_c) h_c^i) w64^(i t); entry j of the cell is t = brp6(j).
-// out: b x 128 x 2048 big-endian bytes.
-__global__ __launch_bounds__(64) void k_recover_cells(const Fr29* __restrict__ ev, const Fr29Mem* __restrict__ W, uint8_t* __restrict__ out) {
-    __shared__ uint32_t s[CELL_FE * 9];
-    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
-    const size_t at = (size_t)b * RECOVER_N + c;
-    ntt_put<CELL_FE>(s, (int)bitrev6((uint32_t)t), fr29_ld(ev + at * CELL_FE + t));
+// One wavefront per (i, blob), every blob with its own slot map, zev and invz: coef[b][.], status[b], ev[(b * 128 + c) * 64 + i].
+__global__ __launch_bounds__(64) void k_recover_poly(const Fr29* __restrict__ u, const uint8_t* __restrict__ slot, int per, const Fr29* __restrict__ zev,
+                                                     const Fr29* __restrict__ invz, const Fr29Mem* __restrict__ W, Fr* __restrict__ coef,
+                                                     Fr29* __restrict__ ev, uint32_t* __restrict__ status) {
+    __shared__ uint32_t s[RECOVER_N * 9];
+    const int b = blockIdx.y;
+    recover_poly_body(s, (int)blockIdx.x, (int)threadIdx.x, u + (size_t)b * per * CELL_FE, slot + (size_t)b * RECOVER_N, zev + (size_t)b * RECOVER_N,
+                      invz + (size_t)b * RECOVER_N, W, coef + (size_t)b * FE_PER_BLOB, ev + (size_t)b * RECOVER_N * CELL_FE, status + b);
+}
+
+// One wavefront on one cell (the body of k_recover_cells): P(h_c w64^t) = sum_i (P_i(y_c) h_c^i) w64^(i t); entry j of the cell is
+// t = brp6(j).  ev: the cell's 64 entries of k_recover_poly's output, dst: its 2048 big-endian bytes.  s: CELL_FE * 9 words of LDS.
+__device__ __forceinline__ void recover_cells_body(uint32_t* s, int t, const Fr29* __restrict__ ev, const Fr29Mem* __restrict__ W, uint4* __restrict__ dst) {
+    ntt_put<CELL_FE>(s, (int)bitrev6((uint32_t)t), fr29_ld(ev + t));
     __syncthreads();
     ntt_stages<CELL_FE, 64>(s, t, W, false);
     Fr a;
     cell_fr_canonical(a.l, ntt_get<CELL_FE>(s, (int)bitrev6((uint32_t)t)));
     uint4 hi, lo;
     fr_to_be_words(hi, lo, a);
-    uint4* dst = reinterpret_cast<uint4*>(out + at * (CELL_FE * 32));
     dst[2 * t] = hi;
     dst[2 * t + 1] = lo;
+}
+
+// One wavefront per (cell, blob).  out: b x 128 x 2048 big-endian bytes.
+__global__ __launch_bounds__(64) void k_recover_cells(const Fr29* __restrict__ ev, const Fr29Mem* __restrict__ W, uint8_t* __restrict__ out) {
+    __shared__ uint32_t s[CELL_FE * 9];
+    const size_t at = (size_t)blockIdx.y * RECOVER_N + blockIdx.x;
+    recover_cells_body(s, (int)threadIdx.x, ev + at * CELL_FE, W, reinterpret_cast<uint4*>(out + at * (CELL_FE * 32)));
 }
 
 __device__ __forceinline__ Fr fr29_inverse_canonical(const Fr29& a) {  // a: a plain residue below 100 r, not zero
