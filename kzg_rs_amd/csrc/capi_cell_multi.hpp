@@ -106,13 +106,19 @@ static KzgRet cell_multi_batches(bool* ok_out, uint8_t* err_out, const uint8_t* 
     });
 }
 
+// The same dealing by count: n units of one weight, ceil(n / D) consecutive ones per shard (cell_shard_ranges_even)
+template <class Body>
+static KzgRet cell_multi_even(const KzgSettings* s, size_t n, bool timings, Body&& body) {
+    std::vector<CellShardRange> ranges;
+    cell_shard_ranges_even(ranges, n, shard_count(s));
+    return cell_multi_deal(s, ranges, timings, body);
+}
+
 // kzg_verify_data_column_sidecars: whole sidecars - all of one weight, n_blobs cells - ceil(n / D) consecutive ones per shard; every
 // shard gets the block's commitments and decodes them itself, once
 static KzgRet cell_multi_data_columns(bool* ok_out, uint8_t* err_out, const uint8_t* commitments, size_t n_blobs, const uint64_t* column_indices,
                                       const uint8_t* cells, const uint8_t* proofs, size_t n_sidecars, const KzgSettings* s) {
-    std::vector<CellShardRange> ranges;
-    cell_shard_ranges_even(ranges, n_sidecars, shard_count(s));
-    return cell_multi_deal(s, ranges, true, [&](const KzgSettings* c, size_t lo, size_t hi) {
+    return cell_multi_even(s, n_sidecars, true, [&](const KzgSettings* c, size_t lo, size_t hi) {
         return data_columns_run(ok_out + lo, err_out ? err_out + lo : nullptr, commitments, n_blobs, column_indices + lo, cells + CELL_BYTES * n_blobs * lo,
                                 proofs + 48 * n_blobs * lo, hi - lo, c);
     });
@@ -121,9 +127,7 @@ static KzgRet cell_multi_data_columns(bool* ok_out, uint8_t* err_out, const uint
 // kzg_verify_blob_cell_kzg_proofs, the call that is not queued: by blob, ceil(n / D) per shard (the caller has cleared ok_out / err_out)
 static KzgRet cell_multi_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* blobs, const uint8_t* commitments, const uint8_t* cell_proofs, size_t n,
                                     const KzgSettings* s) {
-    std::vector<CellShardRange> ranges;
-    cell_shard_ranges_even(ranges, n, shard_count(s));
-    return cell_multi_deal(s, ranges, true, [&](const KzgSettings* c, size_t lo, size_t hi) {
+    return cell_multi_even(s, n, true, [&](const KzgSettings* c, size_t lo, size_t hi) {
         return blob_cell_call_direct(ok_out + lo, err_out ? err_out + lo : nullptr, blobs + (size_t)BLOB_BYTES * lo, commitments + 48 * lo,
                                      cell_proofs + BLOB_CELL_PROOFS_BYTES * lo, hi - lo, std::chrono::steady_clock::now(), c);
     });
@@ -133,9 +137,7 @@ static KzgRet cell_multi_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_
 // its first proof range (or by kzg_settings_precompute).  These calls record no timings.
 static KzgRet cell_multi_prover(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n, const KzgSettings* s) {
     if (n == 0) return cell_prover_run(cells_out, proofs_out, blobs, n, s);
-    std::vector<CellShardRange> ranges;
-    cell_shard_ranges_even(ranges, n, shard_count(s));
-    return cell_multi_deal(s, ranges, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
+    return cell_multi_even(s, n, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
         return cell_prover_run(cells_out ? cells_out + 2 * (size_t)BLOB_BYTES * lo : nullptr, proofs_out ? proofs_out + (size_t)48 * FK20_K2 * lo : nullptr,
                                blobs + (size_t)BLOB_BYTES * lo, hi - lo, c);
     });
@@ -148,10 +150,8 @@ static KzgRet cell_multi_recover(uint8_t* cells_out, uint8_t* proofs_out, const 
     std::vector<uint8_t> none_a, none_b;
     const KzgRet rc = cell_recover_check(none_a, none_b, cell_indices, per, n, s, /*fill=*/false);
     if (rc != KZG_OK) return rc;
-    std::vector<CellShardRange> ranges;
-    cell_shard_ranges_even(ranges, n, shard_count(s));
     constexpr size_t CELLS_BYTES = CELL_BYTES * RECOVER_N, PROOFS_BYTES = (size_t)48 * FK20_K2;
-    return cell_multi_deal(s, ranges, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
+    return cell_multi_even(s, n, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
         return cell_recover_run(cells_out ? cells_out + CELLS_BYTES * lo : nullptr, proofs_out ? proofs_out + PROOFS_BYTES * lo : nullptr, cell_indices + per * lo,
                                 cells + CELL_BYTES * per * lo, given ? given + 48 * per * lo : nullptr, per, hi - lo, c);
     });
@@ -162,18 +162,14 @@ static KzgRet cell_multi_recover(uint8_t* cells_out, uint8_t* proofs_out, const 
 // entry point has checked for the whole call
 static KzgRet cell_multi_data_column_recover(uint8_t* cells_out, uint8_t* proofs_out, const DataColumnRecoverPlan& P, const uint8_t* cells, const uint8_t* given,
                                              size_t n_blobs, const KzgSettings* s) {
-    std::vector<CellShardRange> ranges;
-    cell_shard_ranges_even(ranges, n_blobs, shard_count(s));
-    return cell_multi_deal(s, ranges, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
+    return cell_multi_even(s, n_blobs, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
         return data_column_recover_run(cells_out ? cells_out + DC_CELL_BYTES * lo : nullptr, proofs_out ? proofs_out + DC_PROOF_BYTES * lo : nullptr, P,
                                        cells + DC_CELL_BYTES * lo, given ? given + DC_PROOF_BYTES * lo : nullptr, hi - lo, n_blobs, c);
     });
 }
 // kzg_compute_data_column_sidecars: the same dealing; the blobs themselves are blob-major
 static KzgRet cell_multi_data_column_compute(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n_blobs, const KzgSettings* s) {
-    std::vector<CellShardRange> ranges;
-    cell_shard_ranges_even(ranges, n_blobs, shard_count(s));
-    return cell_multi_deal(s, ranges, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
+    return cell_multi_even(s, n_blobs, false, [&](const KzgSettings* c, size_t lo, size_t hi) {
         return data_column_compute_run(cells_out ? cells_out + DC_CELL_BYTES * lo : nullptr, proofs_out ? proofs_out + DC_PROOF_BYTES * lo : nullptr,
                                        blobs + (size_t)BLOB_BYTES * lo, hi - lo, n_blobs, c);
     });
@@ -183,11 +179,10 @@ static KzgRet cell_multi_data_column_compute(uint8_t* cells_out, uint8_t* proofs
 extern "C" KzgRet kzg_debug_cell_shard_stats(const KzgSettings* s, uint64_t* out, size_t cap, int reset) {
     if (!s || (cap && !out)) return fail(KZG_BADARGS, "null argument");
     for (size_t k = 0; k < shard_count(s); k++) {
-        const KzgSettings* const c = shard_of(s, k);
-        for (size_t i = 0; i < 4; i++) {
-            const uint64_t v = reset ? c->cell_stats[i].exchange(0, std::memory_order_relaxed) : c->cell_stats[i].load(std::memory_order_relaxed);
-            if (4 * k + i < cap) out[4 * k + i] = v;
-        }
+        uint64_t v[4] = {};
+        stats_take(shard_of(s, k)->cell_stats, reset, v);
+        for (size_t i = 0; i < 4; i++)
+            if (4 * k + i < cap) out[4 * k + i] = v[i];
     }
     return KZG_OK;
 }
@@ -197,11 +192,7 @@ extern "C" KzgRet kzg_debug_cell_shard_stats(const KzgSettings* s, uint64_t* out
 extern "C" KzgRet kzg_debug_data_column_stats(const KzgSettings* s, uint64_t out[4], int reset) {
     if (!s || !out) return fail(KZG_BADARGS, "null argument");
     memset(out, 0, 4 * sizeof(uint64_t));
-    for (size_t k = 0; k < shard_count(s); k++) {
-        const KzgSettings* const c = shard_of(s, k);
-        for (size_t i = 0; i < 4; i++)
-            out[i] += reset ? c->data_column_stats[i].exchange(0, std::memory_order_relaxed) : c->data_column_stats[i].load(std::memory_order_relaxed);
-    }
+    for (size_t k = 0; k < shard_count(s); k++) stats_take(shard_of(s, k)->data_column_stats, reset, out);
     return KZG_OK;
 }
 
@@ -210,10 +201,6 @@ extern "C" KzgRet kzg_debug_data_column_stats(const KzgSettings* s, uint64_t out
 extern "C" KzgRet kzg_debug_data_column_recover_stats(const KzgSettings* s, uint64_t out[4], int reset) {
     if (!s || !out) return fail(KZG_BADARGS, "null argument");
     memset(out, 0, 4 * sizeof(uint64_t));
-    for (size_t k = 0; k < shard_count(s); k++) {
-        const KzgSettings* const c = shard_of(s, k);
-        for (size_t i = 0; i < 4; i++)
-            out[i] += reset ? c->data_column_recover_stats[i].exchange(0, std::memory_order_relaxed) : c->data_column_recover_stats[i].load(std::memory_order_relaxed);
-    }
+    for (size_t k = 0; k < shard_count(s); k++) stats_take(shard_of(s, k)->data_column_recover_stats, reset, out);
     return KZG_OK;
 }

@@ -6,8 +6,8 @@
 //   copy     the blobs to the device; cells 0..63 of a blob are its own bytes and never leave the host
 //   cells    k_cell_ntt: canonical check, inverse transform (coefficients, kept on the device), twist, forward transform:
 //            cells 64..127
-//   proofs   k_fk20_tvec_dft -> k_fk20_msm<Fixed> over the handle's FK20 table -> k_fk20_rows -> k_fk20_msm<Variable> ->
-//            k_fk20_compress
+//   proofs   fk20_chain, which the recoveries and the column-major producers queue too: k_fk20_tvec_dft -> k_fk20_msm<Fixed> over
+//            the handle's FK20 table -> k_fk20_rows -> k_fk20_msm<Variable> -> k_fk20_compress
 // The FK20 table (8 192 points x 32 rows of 192 bytes = 48 MB on the handle) is made by the first proof call, or ahead of it by
 // kzg_settings_precompute, with group DFTs over G1 (g1_ntt.hpp): the 4 096 monomial points [tau^i]G1 are ONE forward transform of
 // the Lagrange points (12 stages of 2 048 butterflies), the table's 8 192 points 64 forward transforms of 128 monomial points
@@ -159,15 +159,34 @@ static KzgRet cell_prover_tables(const KzgSettings* s, CellProverState& c) {
     return KZG_OK;
 }
 
+// The opening of a producer call; the caller holds the handle's lock and has checked prover_ready.  The device is set, the plain
+// stream pair selected; the state holds buffers for `cap` blobs, with the proof path's if `proofs`, and the FK20 table if `table`.
+static KzgRet cell_producer_open(const KzgSettings* s, size_t cap, bool proofs, bool table, CellProverState** out) {
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
+    KzgRet rc = cell_prover_state(s, out);
+    if (rc != KZG_OK || (rc = (*out)->reserve(cap, proofs)) != KZG_OK) return rc;
+    return table ? cell_prover_tables(s, **out) : KZG_OK;
+}
+// The FK20 proof chain of m blobs, queued on the main stream: c.d_coef -> 128 compressed proofs each in c.d_out.  The caller holds
+// the handle's lock; c is reserved for m blobs with the proof buffers and holds the table.  Nothing is waited for.
+static KzgRet fk20_chain(const KzgSettings* s, CellProverState& c, size_t m) {
+    const unsigned mb = (unsigned)m;
+    hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, mb), dim3(64), 0, s->s1, (const Fr*)c.d_coef.p, (const Fr29Mem*)c.d_W.p, c.d_sc.p);
+    hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X.p, (const Fr*)c.d_sc.p, c.d_H.p);
+    hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)(m * FK20_K2));
+    hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_circ.p, c.d_P.p);
+    hipLaunchKernelGGL(k_fk20_compress, dim3(mb), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
+    HIPCHK(hipGetLastError());
+    return KZG_OK;
+}
+
 static KzgRet cell_prover_run(uint8_t* cells_out, uint8_t* proofs_out, const uint8_t* blobs, size_t n, const KzgSettings* s) {
     KzgRet rc = prover_ready(s);
     if (rc != KZG_OK || n == 0) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
-    HIPCHK(hipSetDevice(s->device));
-    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     CellProverState* cp = nullptr;
-    if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cp->reserve(std::min(n, PROVER_CHUNK), proofs_out != nullptr)) != KZG_OK) return rc;
-    if (proofs_out && (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
+    if ((rc = cell_producer_open(s, std::min(n, PROVER_CHUNK), proofs_out != nullptr, proofs_out != nullptr, &cp)) != KZG_OK) return rc;
     CellProverState& c = *cp;
     if (DYN_LDS(k_cell_ntt, CELL_NTT_LDS) != hipSuccess) return fail(KZG_ERROR, "k_cell_ntt: the device refuses 144 KB of LDS per workgroup");
     std::vector<uint32_t> st(PROVER_CHUNK);
@@ -184,12 +203,7 @@ static KzgRet cell_prover_run(uint8_t* cells_out, uint8_t* proofs_out, const uin
         if (cells_out)
             HIPCHK(hipMemcpy2DAsync(cells_out + CELLS_BYTES * lo + EXT_BYTES, CELLS_BYTES, c.d_ext.p, EXT_BYTES, EXT_BYTES, m, hipMemcpyDeviceToHost, s->s1));
         if (proofs_out) {
-            hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, (unsigned)m), dim3(64), 0, s->s1, (const Fr*)c.d_coef.p, (const Fr29Mem*)c.d_W.p, c.d_sc.p);
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X.p, (const Fr*)c.d_sc.p, c.d_H.p);
-            hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)(m * FK20_K2));
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_circ.p, c.d_P.p);
-            hipLaunchKernelGGL(k_fk20_compress, dim3((unsigned)m), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
-            HIPCHK(hipGetLastError());
+            if ((rc = fk20_chain(s, c, m)) != KZG_OK) return rc;
             HIPCHK(hipMemcpyAsync(proofs_out + PROOFS_BYTES * lo, c.d_out.p, PROOFS_BYTES * m, hipMemcpyDeviceToHost, s->s1));
         }
         if (cells_out)  // cells 0..63 of a blob are the blob (the host copies them while the device works)

@@ -118,10 +118,7 @@ static void cells_release(const KzgSettings* s) {
 // the counters of kzg_debug_cell_shard_stats, on the shard that ran the work (a lane of the small-call queue: the shard it lives on)
 static void cell_stats_add(const KzgSettings* s, uint64_t launches, uint64_t cells, uint64_t blobs_verified, uint64_t blobs_proved) {
     const KzgSettings* const h = s->cell_home ? s->cell_home : s;
-    h->cell_stats[0].fetch_add(launches, std::memory_order_relaxed);
-    h->cell_stats[1].fetch_add(cells, std::memory_order_relaxed);
-    h->cell_stats[2].fetch_add(blobs_verified, std::memory_order_relaxed);
-    h->cell_stats[3].fetch_add(blobs_proved, std::memory_order_relaxed);
+    stats_add(h->cell_stats, launches, cells, blobs_verified, blobs_proved);
 }
 static KzgRet cells_ready(const KzgSettings* s) {
     if (!s->t->d_g1.p) return fail(KZG_BADARGS, "cell proofs need the G1 points of a trusted-setup file; these settings hold [tau]G2 alone");

@@ -11,17 +11,17 @@
 //   chunk    PROVER_CHUNK blobs: ONE pitched copy of the given cells (width m * 2048, height n_given, pitch n_blobs * 2048), one of
 //            the given proofs; k_dc_recover_cell_idft -> k_dc_recover_poly (the cell prover's d_coef) -> k_dc_recover_cells over the
 //            missing columns only, [q][b] -> ONE pitched copy into the caller's cells_out
-//   proofs   given:  the shared decode pass over the chunk's proofs as they lie, the first 64 sidecars' (the array's front) into
-//                    d_H -> k_fk20_rows -> k_fk20_msm<Fk20LagrangeShared> -> k_fk20_compress
-//            plain:  the cell prover's chain on d_coef, unchanged
+//   proofs   given:  recover_given_decode over the chunk's proofs as they lie, the first 64 sidecars' (the array's front) into d_H ->
+//                    lagrange_sums<Fk20LagrangeShared> -> k_fk20_compress
+//            plain:  the cell prover's chain on d_coef: fk20_chain (capi_cell_prover.hpp)
 //            either: k_dc_proofs_by_column picks the missing columns, [q][b] -> one pitched copy into proofs_out
-// The verdicts are read where cell_recover_run reads them: before the sums or the chain are queued.
+// The verdicts are read where cell_recover_run reads them: before the sums or the chain are queued; the opening, the verdicts, the
+// decode and the sums are that file's functions.
 // Compute is cell_prover_run with k_dc_cell_ntt writing cells 64..127 column-major and k_dc_proofs_by_column turning the proofs.
 #include "data_column_recover_plan.hpp"
 
 static void data_column_recover_stats_add(const KzgSettings* s, uint64_t ranges, uint64_t blobs, uint64_t columns, uint64_t setups) {
-    const uint64_t v[4] = {ranges, blobs, columns, setups};
-    for (int i = 0; i < 4; i++) s->data_column_recover_stats[i].fetch_add(v[i], std::memory_order_relaxed);
+    stats_add(s->data_column_recover_stats, ranges, blobs, columns, setups);
 }
 
 // what is refused on the host before anything is copied, with cell_recover_check's codes and words, in its order
@@ -46,26 +46,15 @@ static KzgRet data_column_recover_run(uint8_t* cells_out, uint8_t* proofs_out, c
     const size_t per = P.n_given, nmiss = P.n_missing;
     const bool sums = given && proofs_out && nmiss, chain = !given && proofs_out && nmiss;
     std::lock_guard<std::mutex> lk(s->mu);
-    HIPCHK(hipSetDevice(s->device));
-    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     const size_t cap = std::min(n, PROVER_CHUNK);
     CellProverState* cp = nullptr;
-    if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cp->reserve(cap, sums || chain)) != KZG_OK) return rc;
-    if (chain && (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
-    if (!s->cell_recover) s->cell_recover = new CellRecoverState();
-    if ((rc = s->cell_recover->reserve(cap)) != KZG_OK || (given && (rc = s->cell_recover->reserve_given(cap * per)) != KZG_OK)) return rc;
+    CellRecoverState* rp = nullptr;
+    if ((rc = cell_recover_open(s, cap, sums || chain, chain, given ? cap * per : 0, &cp, &rp)) != KZG_OK) return rc;
     CellProverState& c = *cp;
-    CellRecoverState& r = *s->cell_recover;
+    CellRecoverState& r = *rp;
     const Fr29Mem* W = c.d_W.p;
     std::vector<uint32_t> st(PROVER_CHUNK), pst(given ? cap * per : 0);
     StreamDrain drain{s->s1};  // (declared after the host buffers the copies read and write)
-    auto verdict = [&st](size_t m) {  // after the stream has delivered the chunk's status words
-        for (size_t b = 0; b < m; b++) {
-            if (st[b] & RECOVER_BAD_ELEMENT) return fail(KZG_BADARGS, "a cell holds a field element >= r");
-            if (st[b] & RECOVER_INCONSISTENT) return fail(KZG_BADARGS, "a blob's cells are not the evaluations of one polynomial of degree < 4096");
-        }
-        return KZG_OK;
-    };
     // once per range: the lists, the vanishing polynomial and the weights of the index list
     HIPCHK(hipMemcpyAsync(r.d_cidx.p, P.cidx, DC_COLUMNS, hipMemcpyHostToDevice, s->s1));
     HIPCHK(hipMemcpyAsync(r.d_slot.p, P.slot, DC_COLUMNS, hipMemcpyHostToDevice, s->s1));
@@ -94,43 +83,29 @@ static KzgRet data_column_recover_run(uint8_t* cells_out, uint8_t* proofs_out, c
         if (given) {
             const size_t np = per * m, first = (size_t)LAGRANGE_K * m;  // the first 64 sidecars' proofs are the front of the array
             HIPCHK(hipMemcpy2DAsync(r.d_pbytes.p, vp.width, given + vp.offset, vp.pitch, vp.width, per, hipMemcpyHostToDevice, s->s1));
-            g1_decode_tables(r.d_pbytes.p, np, r.d_ppoints.p, r.d_pflag.p, r.d_pmult.p, nullptr, (int)np, false, s->s1);
-            if (sums)
-                hipLaunchKernelGGL(k_g1_ntt_load, dim3((unsigned)((first + 255) / 256)), dim3(256), 0, s->s1, (const G1Aff*)r.d_ppoints.p, (const uint32_t*)r.d_pflag.p, c.d_H.p,
-                                   (int)first, 0);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(pst.data(), r.d_pflag.p, 4 * np, hipMemcpyDeviceToHost, s->s1));
-            // the verdict on cells and proofs before the sums are queued
+            if ((rc = recover_given_decode(s, c, r, np, sums ? first : 0, pst.data())) != KZG_OK) return rc;
+            // the verdict on cells and proofs before the sums are queued; a bad cell wins over a bad proof
             HIPCHK(hipStreamSynchronize(s->s1));
-            if ((rc = verdict(m)) != KZG_OK) return rc;
+            if ((rc = recover_verdict(st.data(), m)) != KZG_OK || (rc = recover_given_verdict(pst.data(), np)) != KZG_OK) return rc;
             judged = true;
-            for (size_t i = 0; i < np; i++)
-                if (pst[i] == G1_INVALID) return fail(KZG_BADARGS, "a given proof is not a G1 point");
             if (sums) {
-                HIPCHK(hipMemsetAsync(c.d_P.p, 0, sizeof(G1Jac29Mem) * FK20_K2 * m, s->s1));  // (Z = 0: the identity)
-                hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(first / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)first);
-                hipLaunchKernelGGL(k_fk20_msm<Fk20LagrangeShared>, dim3((unsigned)nmiss, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_sc.p,
-                                   c.d_P.p);
+                if ((rc = lagrange_sums<Fk20LagrangeShared>(s, c, first, nmiss, m)) != KZG_OK) return rc;
+                hipLaunchKernelGGL(k_fk20_compress, dim3(mb), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
             }
         } else if (chain) {
             // the verdict on the input first: a rejected blob (the adversarial case) must not cost the proof chain's 60 ms
             HIPCHK(hipStreamSynchronize(s->s1));
-            if ((rc = verdict(m)) != KZG_OK) return rc;
+            if ((rc = recover_verdict(st.data(), m)) != KZG_OK || (rc = fk20_chain(s, c, m)) != KZG_OK) return rc;
             judged = true;
-            hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, mb), dim3(64), 0, s->s1, (const Fr*)c.d_coef.p, W, c.d_sc.p);
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X.p, (const Fr*)c.d_sc.p, c.d_H.p);
-            hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)(m * FK20_K2));
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, mb), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_circ.p, c.d_P.p);
         }
         if (sums || chain) {  // the interpolated proofs are outputs 0 .. nmiss - 1 of a blob, the chain's are all 128 by column
-            hipLaunchKernelGGL(k_fk20_compress, dim3(mb), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
             hipLaunchKernelGGL(k_dc_proofs_by_column, dim3((unsigned)((nmiss * m * 12 + 255) / 256)), dim3(256), 0, s->s1, (const uint32_t*)c.d_out.p,
                                sums ? (const uint8_t*)nullptr : (const uint8_t*)r.d_cols.p, (int)nmiss, (int)m, (uint32_t*)c.d_colout.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpy2DAsync(proofs_out + vp.offset, vp.pitch, c.d_colout.p, vp.width, vp.width, nmiss, hipMemcpyDeviceToHost, s->s1));
         }
         HIPCHK(hipStreamSynchronize(s->s1));
-        if (!judged && (rc = verdict(m)) != KZG_OK) return rc;
+        if (!judged && (rc = recover_verdict(st.data(), m)) != KZG_OK) return rc;
     }
     cell_stats_add(s, 1, 0, 0, n);
     data_column_recover_stats_add(s, 1, n, nmiss, 1);
@@ -143,11 +118,8 @@ static KzgRet data_column_compute_run(uint8_t* cells_out, uint8_t* proofs_out, c
     KzgRet rc = prover_ready(s);
     if (rc != KZG_OK) return rc;
     std::lock_guard<std::mutex> lk(s->mu);
-    HIPCHK(hipSetDevice(s->device));
-    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     CellProverState* cp = nullptr;
-    if ((rc = cell_prover_state(s, &cp)) != KZG_OK || (rc = cp->reserve(std::min(n, PROVER_CHUNK), proofs_out != nullptr)) != KZG_OK) return rc;
-    if (proofs_out && (rc = cell_prover_tables(s, *cp)) != KZG_OK) return rc;
+    if ((rc = cell_producer_open(s, std::min(n, PROVER_CHUNK), proofs_out != nullptr, proofs_out != nullptr, &cp)) != KZG_OK) return rc;
     CellProverState& c = *cp;
     if (DYN_LDS(k_dc_cell_ntt, CELL_NTT_LDS) != hipSuccess) return fail(KZG_ERROR, "k_dc_cell_ntt: the device refuses 144 KB of LDS per workgroup");
     std::vector<uint32_t> st(PROVER_CHUNK);
@@ -165,11 +137,7 @@ static KzgRet data_column_compute_run(uint8_t* cells_out, uint8_t* proofs_out, c
         if (cells_out)
             HIPCHK(hipMemcpy2DAsync(cells_out + HALF * pitch * DC_CELL_BYTES + vc.offset, vc.pitch, c.d_ext.p, vc.width, vc.width, HALF, hipMemcpyDeviceToHost, s->s1));
         if (proofs_out) {
-            hipLaunchKernelGGL(k_fk20_tvec_dft, dim3(CELL_FE, (unsigned)m), dim3(64), 0, s->s1, (const Fr*)c.d_coef.p, (const Fr29Mem*)c.d_W.p, c.d_sc.p);
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Fixed>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_X.p, (const Fr*)c.d_sc.p, c.d_H.p);
-            hipLaunchKernelGGL(k_fk20_rows, dim3((unsigned)(m * FK20_K2 / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)c.d_H.p, c.d_Hrows.p, (int)(m * FK20_K2));
-            hipLaunchKernelGGL(k_fk20_msm<Fk20Variable>, dim3(FK20_K2, (unsigned)m), dim3(256), 0, s->s1, (const G1Jac29Mem*)c.d_Hrows.p, (const Fr*)c.d_circ.p, c.d_P.p);
-            hipLaunchKernelGGL(k_fk20_compress, dim3((unsigned)m), dim3(FK20_K2), 0, s->s1, (const G1Jac29Mem*)c.d_P.p, c.d_out.p);
+            if ((rc = fk20_chain(s, c, m)) != KZG_OK) return rc;
             hipLaunchKernelGGL(k_dc_proofs_by_column, dim3((unsigned)((FK20_K2 * m * 12 + 255) / 256)), dim3(256), 0, s->s1, (const uint32_t*)c.d_out.p, (const uint8_t*)nullptr,
                                FK20_K2, (int)m, (uint32_t*)c.d_colout.p);
             HIPCHK(hipGetLastError());

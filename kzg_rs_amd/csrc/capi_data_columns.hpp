@@ -105,8 +105,7 @@ struct DataColumnStage : CellGroupStage {
 };
 
 static void data_column_stats_add(const KzgSettings* s, uint64_t calls, uint64_t sidecars, uint64_t points, uint64_t commitments) {
-    const uint64_t v[4] = {calls, sidecars, points, commitments};
-    for (int i = 0; i < 4; i++) s->data_column_stats[i].fetch_add(v[i], std::memory_order_relaxed);
+    stats_add(s->data_column_stats, calls, sidecars, points, commitments);
 }
 
 // ---------------------------------------------------------------- the entry point

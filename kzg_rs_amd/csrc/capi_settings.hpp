@@ -166,6 +166,14 @@ struct KzgSettings {
 };
 static void multi_free(KzgSettings* s);
 static void small_free(KzgSettings* s);
+// a handle's four-counter diagnostics: add to one set; add one set to sum[0..3], zeroing it if `reset`
+static void stats_add(std::atomic<uint64_t> (&ctr)[4], uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+    const uint64_t v[4] = {a, b, c, d};
+    for (int i = 0; i < 4; i++) ctr[i].fetch_add(v[i], std::memory_order_relaxed);
+}
+static void stats_take(std::atomic<uint64_t> (&ctr)[4], int reset, uint64_t* sum) {
+    for (int i = 0; i < 4; i++) sum[i] += reset ? ctr[i].exchange(0, std::memory_order_relaxed) : ctr[i].load(std::memory_order_relaxed);
+}
 
 static KzgRet upload_program(DevProgram& dp, const unsigned char* begin, const unsigned char* end) {
     size_t len = (size_t)(end - begin);

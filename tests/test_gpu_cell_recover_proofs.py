@@ -208,6 +208,31 @@ def test_the_plain_recoverys_refusals_come_back_with_its_codes(env):
     assert ref["cells"].flags.writeable is False
 
 
+def test_a_bad_cell_wins_over_a_bad_proof_of_the_same_chunk(env):
+    """one wait delivers the cells' status words and the proofs' flags; the cells are judged first, whichever blob holds which"""
+    L = env["api"].lib()
+    idx = sorted(random.Random(70).sample(range(128), 70))
+    ce, pr = given(env, [13, 14], [idx, idx])
+    kc, kp = 2048 * (70 * 1 + 9) + 32 * 5, 48 * (70 * 0 + 17)   # a cell of blob 1, a proof of blob 0
+    bad_ce = ce[:kc] + M.R.to_bytes(32, "big") + ce[kc + 32:]
+    bad_pr = pr[:kp] + G.off_subgroup_g1() + pr[kp + 48:]
+    assert call(env, [idx, idx], ce, bad_pr)[0] == BAD and b"not a G1 point" in L.kzg_last_error()
+    assert call(env, [idx, idx], bad_ce, bad_pr)[0] == BAD and b">= r" in L.kzg_last_error()
+    check_good_call(env)
+
+
+def test_a_refusal_in_the_second_chunk(env):
+    """the bad element in the one blob behind the first full chunk: the verdict reads that chunk's status words"""
+    L = env["api"].lib()
+    ids = list(range(CHUNK + 1))
+    idxs = [rand64(1000 + b) for b in ids]
+    ce, pr = given(env, ids, idxs)
+    k = 2048 * (64 * CHUNK + 9) + 32 * 5
+    bad = ce[:k] + M.R.to_bytes(32, "big") + ce[k + 32:]
+    assert call(env, idxs, bad, pr)[0] == BAD and b">= r" in L.kzg_last_error()
+    check_good_call(env)
+
+
 def test_unverified_proofs_are_interpolated_as_given(env):
     """the contract: the call does not verify.  Two given proofs swapped: KZG_OK, right cells, the given proofs back as passed, and
     an output the cell verifier rejects; the unswapped input makes it accept."""

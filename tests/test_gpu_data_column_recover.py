@@ -245,6 +245,32 @@ def test_refusals_leave_the_handle_usable(env):
     assert env["ref"]["cells"].flags.writeable is False
 
 
+def test_a_bad_cell_wins_over_a_bad_proof_of_the_same_chunk(env):
+    """one wait delivers the cells' status words and the proofs' flags; the cells are judged first, whichever blob holds which"""
+    L = env["api"].lib()
+    c70, ids = columns(70), [17, 18]
+    ce, pr = sidecars(env, ids, c70)
+    kc, kp = 2048 * (2 * 9 + 1) + 32 * 5, 48 * (2 * 17 + 0)   # a cell of blob 1, a proof of blob 0
+    bad_ce = ce[:kc] + M.R.to_bytes(32, "big") + ce[kc + 32:]
+    bad_pr = pr[:kp] + G.off_subgroup_g1() + pr[kp + 48:]
+    assert recover(env, c70, ce, bad_pr, 2)[0] == BAD and b"not a G1 point" in L.kzg_last_error()
+    for want_proofs in (True, False):
+        assert recover(env, c70, bad_ce, bad_pr, 2, want_proofs=want_proofs)[0] == BAD and b">= r" in L.kzg_last_error()
+        check_good_call(env)
+
+
+@pytest.mark.parametrize("with_proofs", [True, False], ids=["given-proofs", "fk20"])
+def test_a_refusal_in_the_second_chunk(env, with_proofs):
+    """the bad element in the one blob behind the first full chunk: the verdict reads that chunk's status words"""
+    L = env["api"].lib()
+    cols, n = columns("64-random"), CHUNK + 1
+    ce, pr = sidecars(env, list(range(n)), cols)
+    k = 2048 * (n * 9 + CHUNK) + 32 * 5
+    bad = ce[:k] + M.R.to_bytes(32, "big") + ce[k + 32:]
+    assert recover(env, cols, bad, pr if with_proofs else None, n)[0] == BAD and b">= r" in L.kzg_last_error()
+    check_good_call(env)
+
+
 def test_unverified_proofs_are_interpolated_as_given(env):
     """the contract: the call does not verify.  Two proofs of one blob swapped between two given sidecars: KZG_OK, right cells, and
     interpolated proofs kzg_verify_data_column_sidecars rejects on the rebuilt sidecars; the unswapped input makes it accept all 128."""
