@@ -649,6 +649,43 @@ void KZG_G1_POINTS_API kzg_g1_points_free(KzgG1Points *p);
  * whose digits spread over the buckets (random, or hash-derived): a million EQUAL scalars put every entry of a window into one
  * bucket, which one lane then adds one after the other - the sum is still exact, the call takes on the order of a second. */
 KzgRet KZG_G1_POINTS_API kzg_g1_msm_prepared(uint8_t out[48], const KzgG1Points *p, const uint8_t *scalars, size_t n, const KzgSettings *s);
+/* COEFFICIENT-FORM POLYNOMIALS over a prepared set whose points are a monomial SRS, P_i = [tau^i]G1 (csrc/capi_poly.hpp): commit and
+ * open for any degree below the set's count, where kzg_blob_to_kzg_commitment / kzg_compute_kzg_proof know one shape, 4 096 evaluations
+ * over the handle's own points.  kzg_verify_kzg_proof reads [tau]G2 alone, so on a handle of the same tau (kzg_settings_from_tau_g2)
+ * it verifies these openings whatever their degree.
+ * coeffs: n_polys * n_coeffs * 32 bytes, big-endian, lowest degree first, host pointer.  n_coeffs may be smaller than the set's count
+ * (the higher points get no term); larger is KZG_BADARGS.
+ * kzg_poly_commit_prepared: commitments_out[k] = sum_i coeffs[k][i] * P_i, 48 bytes each.
+ * kzg_poly_compute_kzg_proofs_prepared: zs = n_polys * n_points * 32 bytes big-endian, n_points evaluation points PER polynomial; for
+ * polynomial k and its point j, ys_out[k * n_points + j] = p_k(z_kj) (32 bytes big-endian canonical; ys_out may be NULL) and
+ * proofs_out[k * n_points + j] = sum_i q_i * P_i (48 bytes), q = (p_k - y) / (X - z_kj).  The quotient is formed on the device
+ * (csrc/poly_quotient_kernels.hpp: a suffix scan of H_i = a_i + z H_(i+1) in three launches - tile sums, tile carries, apply) and
+ * written as the limbs the fixed-base sum reads; nothing returns to the host in between.  One upload of a polynomial serves all its
+ * points; each (polynomial, point) pair then takes one sum of kzg_g1_msm_prepared's kind, one after another.
+ * n_coeffs == 0 is the zero polynomial: the identity 0xC0 00 .. 00 as commitment and proof, y = 0.  n_coeffs == 1: y = a_0 and the
+ * identity as proof.  n_polys == 0 or n_points == 0: KZG_OK, nothing written.
+ * KZG_BADARGS, with no output promised and the handle usable afterwards: a null pointer; `s` is not the handle the set was prepared
+ * on; n_coeffs above the set's count; more than KZG_POLY_MAX_OPENINGS openings (n_polys * n_points; n_polys of a commit call); a
+ * coefficient or a z that is >= r (kzg_compute_kzg_proof's conventions).  The pairs of a call are cut into chunks of at most 2^23
+ * quotient scalars (256 MB); the verdict on a chunk's elements is read before any of its sums is queued, so a call of one chunk has
+ * queued no sum when it refuses.  The same call twice gives the same bytes.  The handle's lock is taken; the call runs on the set's
+ * device (the first device of a multi-device handle).  kzg_last_timings afterwards: [2] the sums, [4] the quotient launches (the
+ * commit: its decode), [6] the copies.  One opening of 2^20 coefficients from host memory: 6.36 ms (6.13 - 6.47) where
+ * kzg_g1_msm_prepared over the same set takes 6.21 ms (5.99 - 6.33): the sum 5.25 ms, the quotient launches 0.15 ms, the copies
+ * 0.65 ms; 2^16: 1.83 against 1.65 ms, 2^12: 1.20 against 1.02 ms, the quotient launches 0.10 ms at both
+ * (tools/prof/poly_open_probe.py, profiles/poly_open_probe.json). */
+KzgRet KZG_G1_POINTS_API kzg_poly_commit_prepared(uint8_t *commitments_out, const KzgG1Points *p, const uint8_t *coeffs,
+                                                  size_t n_coeffs, size_t n_polys, const KzgSettings *s);
+KzgRet KZG_G1_POINTS_API kzg_poly_compute_kzg_proofs_prepared(uint8_t *proofs_out, uint8_t *ys_out, const KzgG1Points *p,
+                                                              const uint8_t *coeffs, size_t n_coeffs, const uint8_t *zs,
+                                                              size_t n_points, size_t n_polys, const KzgSettings *s);
+#define KZG_POLY_MAX_OPENINGS 4096   /* n_polys * n_points, and n_polys of a commit call */
+/* test hook: the device stage alone - q_out[pair][i], i < n_coeffs (the last one 0), and ys_out[pair], 32 big-endian bytes each;
+ * n_coeffs <= 2^20, the same limit on the pairs and the same refusals of elements >= r; any handle serves (ys_out may be NULL) */
+KzgRet kzg_debug_poly_quotients(uint8_t *q_out, uint8_t *ys_out, const uint8_t *coeffs, size_t n_coeffs, const uint8_t *zs,
+                                size_t n_points, size_t n_polys, const KzgSettings *s);
+/* test hook: out = { coefficients per lane, per wavefront, per workgroup tile, scalars per chunk of pairs } (csrc/poly_quotient_plan.hpp) */
+KzgRet kzg_debug_poly_quotient_tiles(size_t out[4]);
 /* The group DFT over G1 (c-kzg-4844's g1_fft / g1_ifft): out[i] = sum_t w_n^(i t) points[t], n a power of two <= 4096, w_n the
  * n-th root of unity of kzg_settings_root_of_unity's table, natural order on both sides; inverse != 0: w_n^-1 and the factor
  * 1 / n.  points48 / out48: n * 48 bytes compressed, host pointers; the points are decoded and subgroup-tested as in kzg_g1_msm

@@ -163,6 +163,10 @@ def lib():
         L.kzg_g1_points_free.argtypes = [vp]
         L.kzg_g1_points_free.restype = None
         L.kzg_g1_msm_prepared.argtypes = [u8, vp, u8, sz, vp]
+        L.kzg_poly_commit_prepared.argtypes = [u8, vp, u8, sz, sz, vp]
+        L.kzg_poly_compute_kzg_proofs_prepared.argtypes = [u8, u8, vp, u8, sz, u8, sz, sz, vp]
+        L.kzg_debug_poly_quotients.argtypes = [u8, u8, u8, sz, u8, sz, sz, vp]
+        L.kzg_debug_poly_quotient_tiles.argtypes = [C.POINTER(C.c_size_t)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -863,6 +867,32 @@ class G1Points:
         _chk(lib().kzg_g1_msm_prepared(out, self._h, raw, len(raw) // 32, self._settings._h))
         return out.raw
 
+    def commit(self, polys):
+        """commitments of coefficient-form polynomials over the set as a monomial SRS (kzg_poly_commit_prepared): polys = a list of
+        polynomials of EQUAL length, each a list of 32-byte big-endian coefficients (lowest degree first) or one bytes-like object of
+        n_coeffs x 32; at most POLY_MAX_OPENINGS of them -> a list of 48-byte commitments"""
+        raw, n_coeffs = _poly_rows(polys)
+        out = C.create_string_buffer(48 * max(len(polys), 1))
+        _chk(lib().kzg_poly_commit_prepared(out, self._h, raw, n_coeffs, len(polys), self._settings._h))
+        return [out.raw[48 * k: 48 * k + 48] for k in range(len(polys))]
+
+    def open(self, polys, zs):
+        """openings of coefficient-form polynomials (kzg_poly_compute_kzg_proofs_prepared): zs[k] = the evaluation points of polys[k], a
+        list of 32-byte big-endian values, the same number for every polynomial -> (proofs, ys), proofs[k][j] and ys[k][j] for polynomial
+        k at zs[k][j]; a coefficient or a point that is not below r raises KzgError"""
+        raw, n_coeffs = _poly_rows(polys)
+        if len(zs) != len(polys) or any(len(row) != len(zs[0]) for row in zs):
+            raise KzgError("InvalidBytesLength", "zs: one row of equally many points per polynomial")
+        n_points = len(zs[0]) if zs else 0
+        zraw = b"".join(bytes(z) for row in zs for z in row)
+        if len(zraw) != 32 * n_points * len(polys):
+            raise KzgError("InvalidBytesLength", "zs: 32 bytes per point")
+        n = n_points * len(polys)
+        proofs, ys = C.create_string_buffer(48 * max(n, 1)), C.create_string_buffer(32 * max(n, 1))
+        _chk(lib().kzg_poly_compute_kzg_proofs_prepared(proofs, ys, self._h, raw, n_coeffs, zraw, n_points, len(polys), self._settings._h))
+        cut = lambda buf, w: [[buf.raw[w * (k * n_points + j): w * (k * n_points + j + 1)] for j in range(n_points)] for k in range(len(polys))]
+        return cut(proofs, 48), cut(ys, 32)
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
@@ -888,6 +918,25 @@ def g1_points_prepare(points, kzg_settings):
 
 def g1_msm_prepared(point_set, scalars):
     return point_set.msm(scalars)
+
+
+POLY_MAX_OPENINGS = 4096
+
+
+def _poly_rows(polys):
+    """polynomials of equal length -> (their coefficients as one bytes object, n_coeffs)"""
+    rows = [bytes(p) if isinstance(p, (bytes, bytearray, memoryview)) else b"".join(bytes(a) for a in p) for p in polys]
+    if any(len(r) % 32 or len(r) != len(rows[0]) for r in rows):
+        raise KzgError("InvalidBytesLength", "polys: equally many 32-byte coefficients per polynomial")
+    return b"".join(rows), (len(rows[0]) // 32 if rows else 0)
+
+
+def poly_commit_prepared(point_set, polys):
+    return point_set.commit(polys)
+
+
+def poly_compute_kzg_proofs_prepared(point_set, polys, zs):
+    return point_set.open(polys, zs)
 
 
 def pairing_check(a, b, kzg_settings):

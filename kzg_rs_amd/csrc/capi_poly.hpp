@@ -1,0 +1,238 @@
+// capi_poly.hpp - coefficient-form polynomials over a prepared G1 point set (capi_g1_points.hpp): kzg_poly_commit_prepared commits,
+// kzg_poly_compute_kzg_proofs_prepared opens - y = p(z) and the proof [q(tau)] of q = (p - y) / (X - z) - so that a caller who holds a
+// monomial SRS of up to 2^20 points gets commit -> open -> kzg_verify_kzg_proof from this library alone.
+// Part of the single translation unit kzg_capi.hip; not a stand-alone header (host code only).
+//
+// The pairs (polynomial, point) of a call are cut into chunks (poly_quotient_plan.hpp).  Per chunk: the coefficients of its polynomials
+// go up once into G1PointsBufs::d_stage, the three launches of poly_quotient_kernels.hpp write every pair's quotient into
+// G1PointsBufs::d_scalars - the limbs k_scalars_reduce_be leaves there for kzg_g1_msm_prepared - the refusal flag is read, and then
+// each pair gets ONE fixed-base sum, fb_msm_launch<FbEntry64>, one after another on the buffers of the prepared path.  A sum takes
+// n_coeffs - 1 TERMS over the set's points (fb_msm_launch keeps the two counts apart: term t uses point t), so a polynomial shorter
+// than the set needs no zero padding.  The commit is the same with k_poly_decode in place of the scan and n_coeffs terms.
+// The verdict on a chunk's coefficients and points is read before any of ITS sums is queued; a call of one chunk - every call whose
+// pairs x n_coeffs stay within 2^23 - has queued nothing when it refuses.
+
+struct PolyBufs {
+    DevBuf<uint8_t> d_zs, d_ys, d_out;  // per pair of a chunk: z as given | y, 32 big-endian bytes | the sums, compressed
+    DevBuf<Fr> d_tsum, d_carry;         // [pair][tile]
+    DevBuf<uint32_t> d_flag;
+    DevBuf<G1Jac> d_sums;               // per pair
+    KzgRet reserve(size_t n_coeffs, size_t pairs) {
+        HIPCHK(d_zs.grow(32 * pairs));
+        HIPCHK(d_ys.grow(32 * pairs));
+        HIPCHK(d_out.grow(48 * pairs));
+        HIPCHK(d_tsum.grow(pq_tile_scalars(n_coeffs, pairs)));
+        HIPCHK(d_carry.grow(pq_tile_scalars(n_coeffs, pairs)));
+        HIPCHK(d_flag.grow(1));
+        HIPCHK(d_sums.grow(pairs));
+        return KZG_OK;
+    }
+};
+static void poly_release(const KzgSettings* s) {
+    delete s->poly;
+    s->poly = nullptr;
+}
+
+// what one call asks for; zs == nullptr: the commit (a "pair" is a polynomial, n_points = 1)
+struct PolyCall {
+    const uint8_t* coeffs;
+    size_t n_coeffs;
+    const uint8_t* zs;
+    size_t n_points, n_polys;
+    size_t pairs() const { return n_points * n_polys; }
+};
+static_assert(PQ_MAX_OPENINGS == KZG_POLY_MAX_OPENINGS && PQ_MAX_COEFFS == KZG_G1_POINTS_MAX, "the plan's limits are the header's");
+
+// the handle's buffers for a call whose chunks hold at most `chunk` pairs (all growth before anything is queued: grow() keeps no contents)
+static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk, G1PointsBufs** b_out, PolyBufs** pb_out) {
+    if (!s->g1_points) s->g1_points = new (std::nothrow) G1PointsBufs();
+    if (!s->poly) s->poly = new (std::nothrow) PolyBufs();
+    if (!s->g1_points || !s->poly) return fail(KZG_MALLOC, "host buffers of the call");
+    size_t polys = 0;  // the most polynomials a chunk names
+    for (size_t k = 0; k < pq_chunks(c.pairs(), chunk); k++) {
+        const size_t lo = pq_chunk_lo(k, chunk), m = pq_chunk_size(c.pairs(), k, chunk);
+        polys = std::max(polys, pq_poly_end(lo, m, c.n_points) - pq_poly_first(lo, c.n_points));
+    }
+    HIPCHK(s->g1_points->d_stage.grow(pq_stage_bytes(c.n_coeffs, polys)));
+    HIPCHK(s->g1_points->d_scalars.grow(pq_quotient_scalars(c.n_coeffs, chunk)));
+    *b_out = s->g1_points;
+    *pb_out = s->poly;
+    return s->poly->reserve(c.n_coeffs, chunk);
+}
+
+// Pairs [lo, lo + m) of the call: upload (the coefficients only if the chunk before did not leave the same polynomials there), the
+// stage's launches, the verdict.  On KZG_OK the chunk's quotients (the commit: its coefficients) are in b.d_scalars, [pair][n_coeffs],
+// and its y in pb.d_ys.  ms: [0] copies [1] the launches, added to.
+struct PolyStaged {
+    size_t first = 1, end = 0;  // the polynomials in d_stage
+};
+static KzgRet poly_stage(const KzgSettings* s, G1PointsBufs& b, PolyBufs& pb, const PolyCall& c, size_t lo, size_t m, PolyStaged& staged, float ms[2]) {
+    const size_t n = c.n_coeffs, k0 = pq_poly_first(lo, c.n_points), k1 = pq_poly_end(lo, m, c.n_points);
+    hipStream_t st = s->s1;
+    HIPCHK(hipEventRecord(s->ev[0], st));
+    if (staged.first != k0 || staged.end != k1) {
+        HIPCHK(hipMemcpyAsync(b.d_stage.p, c.coeffs + 32 * n * k0, pq_stage_bytes(n, k1 - k0), hipMemcpyHostToDevice, st));
+        staged.first = k0, staged.end = k1;
+    }
+    if (c.zs) HIPCHK(hipMemcpyAsync(pb.d_zs.p, c.zs + 32 * lo, 32 * m, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(pb.d_flag.p, 0, 4, st));
+    HIPCHK(hipEventRecord(s->ev[1], st));
+    HIPCHK(hipEventRecord(s->ev[4], st));
+    if (c.zs) {
+        const PqGrid gt = pq_grid_tiles(n, m), gc = pq_grid_carries(m);
+        hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n,
+                           (int)c.n_points, (int)lo, (int)k0);
+        hipLaunchKernelGGL(k_poly_tile_carries, dim3(gc.x, gc.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_tsum.p, pb.d_carry.p, (int)gt.x);
+        hipLaunchKernelGGL(k_poly_apply, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_carry.p, b.d_scalars.p,
+                           pb.d_ys.p, (int)n, (int)c.n_points, (int)lo, (int)k0);
+    } else {
+        const PqGrid gd = pq_grid_decode(n, m);
+        hipLaunchKernelGGL(k_poly_decode, dim3(gd.x, gd.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, b.d_scalars.p, pb.d_flag.p, (int)n);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[5], st));
+    uint32_t flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, pb.d_flag.p, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float t = 0.f;
+    elapsed(&t, s->ev[0], s->ev[1]);
+    ms[0] += t;
+    elapsed(&t, s->ev[4], s->ev[5]);
+    ms[1] += t;
+    if (flag & PQ_BAD_COEFF) return fail(KZG_BADARGS, "a coefficient is not below r");
+    if (flag & PQ_BAD_Z) return fail(KZG_BADARGS, "an evaluation point is not below r");
+    return KZG_OK;
+}
+
+static void poly_identities(uint8_t* out48, size_t n) {
+    memset(out48, 0, 48 * n);
+    for (size_t i = 0; i < n; i++) out48[48 * i] = 0xC0;
+}
+
+// both entry points: sums_out pairs x 48, ys_out pairs x 32 or nullptr
+static KzgRet poly_run(uint8_t* sums_out, uint8_t* ys_out, const KzgG1Points* p, const PolyCall& c, const KzgSettings* s, const char* who) {
+    if (!s || !p) return fail(KZG_BADARGS, "null argument");
+    if (p->owner != s) return fail(KZG_BADARGS, std::string(who) + ": the point set was prepared on another handle");
+    if (c.n_coeffs > p->n) return fail(KZG_BADARGS, std::string(who) + ": more coefficients than the set has points");
+    if (c.n_polys == 0 || c.n_points == 0) return KZG_OK;
+    if (c.n_polys > KZG_POLY_MAX_OPENINGS || c.n_points > KZG_POLY_MAX_OPENINGS || c.pairs() > KZG_POLY_MAX_OPENINGS)
+        return fail(KZG_BADARGS, std::string(who) + ": more than 4096 openings");
+    const size_t pairs = c.pairs(), n = c.n_coeffs;
+    if (!sums_out || (n && !c.coeffs)) return fail(KZG_BADARGS, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->timings[2] = s->timings[4] = s->timings[6] = 0.0f;
+    if (n == 0) {  // the zero polynomial
+        poly_identities(sums_out, pairs);
+        if (ys_out) memset(ys_out, 0, 32 * pairs);
+        return KZG_OK;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
+    const size_t terms = c.zs ? n - 1 : n;  // of a pair's sum (the quotient's last coefficient is 0)
+    const size_t chunk = std::min(pairs, pq_chunk_pairs(n, c.n_points));
+    G1PointsBufs* bp = nullptr;
+    PolyBufs* pbp = nullptr;
+    KzgRet rc = poly_buffers(s, c, chunk, &bp, &pbp);
+    if (rc != KZG_OK) return rc;
+    G1PointsBufs& b = *bp;
+    PolyBufs& pb = *pbp;
+    const int L = FBM_SLICE_ENTRIES, fold_per = 11;
+    if (terms) {
+        const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * terms, L);
+        int gp = 0;
+        (void)msm_large_tail_groups(Z, std::max(fold_per, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
+        if ((rc = b.reserve(terms, Z, gp)) != KZG_OK) return rc;
+    }
+    // Nothing of the call stays in flight when an error path leaves, on either stream (kzg_g1_msm_prepared: the side stream runs
+    // k_fb_rowsum on the save area and the tail the next call reuses; declared in this order, it is joined first)
+    StreamDrain drain{s->s1};
+    StreamDrain join_side{s->s2 != s->s1 ? s->s2 : nullptr};
+    PolyStaged staged;
+    float ms[2] = {0.f, 0.f}, ms_sum = 0.f;
+    for (size_t k = 0; k < pq_chunks(pairs, chunk); k++) {
+        const size_t lo = pq_chunk_lo(k, chunk), m = pq_chunk_size(pairs, k, chunk);
+        if ((rc = poly_stage(s, b, pb, c, lo, m, staged, ms)) != KZG_OK) return rc;
+        if (!terms) {  // constants: every quotient is 0
+            poly_identities(sums_out + 48 * lo, m);
+        } else {
+            HIPCHK(hipEventRecord(s->ev[2], s->s1));
+            for (size_t q = 0; q < m; q++)
+                HIPCHK(fb_msm_launch<FbEntry64>(b.d_scalars.p + q * n, p->pflag.p, (int)terms, (int)p->n, p->rows.p, b.d_plan.p, b.d_entries.p, b.d_save.p, b.d_tail.p, pb.d_sums.p + q, L,
+                                                fold_per, nullptr, s->s1, s->s2, s->ev[7], s->ev[8]));
+            HIPCHK(hipEventRecord(s->ev[3], s->s1));
+            hipLaunchKernelGGL(k_jac_compress_n, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const G1Jac*)pb.d_sums.p, pb.d_out.p, (int)m);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(s->ev[9], s->s1));
+        if (terms) HIPCHK(hipMemcpyAsync(sums_out + 48 * lo, pb.d_out.p, 48 * m, hipMemcpyDeviceToHost, s->s1));
+        if (ys_out && c.zs) HIPCHK(hipMemcpyAsync(ys_out + 32 * lo, pb.d_ys.p, 32 * m, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipEventRecord(s->ev[10], s->s1));
+        HIPCHK(hipStreamSynchronize(s->s1));  // (the main stream waited for the side stream's event: nothing is left there)
+        float t = 0.f;
+        if (terms) {
+            elapsed(&t, s->ev[2], s->ev[3]);
+            ms_sum += t;
+        }
+        elapsed(&t, s->ev[9], s->ev[10]);
+        ms[0] += t;
+    }
+    join_side.st = nullptr;
+    s->timings[2] = ms_sum, s->timings[4] = ms[1], s->timings[6] = ms[0];
+    return KZG_OK;
+}
+
+extern "C" KzgRet kzg_poly_commit_prepared(uint8_t* commitments_out, const KzgG1Points* p, const uint8_t* coeffs, size_t n_coeffs, size_t n_polys, const KzgSettings* s) {
+    return poly_run(commitments_out, nullptr, p, PolyCall{coeffs, n_coeffs, nullptr, 1, n_polys}, s, "kzg_poly_commit_prepared");
+}
+
+extern "C" KzgRet kzg_poly_compute_kzg_proofs_prepared(uint8_t* proofs_out, uint8_t* ys_out, const KzgG1Points* p, const uint8_t* coeffs, size_t n_coeffs, const uint8_t* zs,
+                                                       size_t n_points, size_t n_polys, const KzgSettings* s) {
+    if (n_points && n_polys && !zs) return fail(KZG_BADARGS, "null argument");
+    return poly_run(proofs_out, ys_out, p, PolyCall{coeffs, n_coeffs, zs, n_points, n_polys}, s, "kzg_poly_compute_kzg_proofs_prepared");
+}
+
+// test hook (tests/test_gpu_poly_open.py): the device stage alone
+extern "C" KzgRet kzg_debug_poly_quotients(uint8_t* q_out, uint8_t* ys_out, const uint8_t* coeffs, size_t n_coeffs, const uint8_t* zs, size_t n_points, size_t n_polys,
+                                           const KzgSettings* s) try {
+    const PolyCall c{coeffs, n_coeffs, zs, n_points, n_polys};
+    if (!s) return fail(KZG_BADARGS, "null argument");
+    if (n_polys == 0 || n_points == 0) return KZG_OK;
+    if (n_coeffs > PQ_MAX_COEFFS || n_polys > PQ_MAX_OPENINGS || n_points > PQ_MAX_OPENINGS || c.pairs() > PQ_MAX_OPENINGS) return fail(KZG_BADARGS, "bad argument");
+    const size_t pairs = c.pairs(), n = n_coeffs;
+    if (!zs || (n && (!coeffs || !q_out))) return fail(KZG_BADARGS, "null argument");
+    if (n == 0) {
+        if (ys_out) memset(ys_out, 0, 32 * pairs);
+        return KZG_OK;
+    }
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);
+    const size_t chunk = std::min(pairs, pq_chunk_pairs(n, n_points));
+    G1PointsBufs* b = nullptr;
+    PolyBufs* pb = nullptr;
+    KzgRet rc = poly_buffers(s, c, chunk, &b, &pb);
+    if (rc != KZG_OK) return rc;
+    std::vector<uint8_t> limbs(32 * n * chunk);
+    StreamDrain drain{s->s1};
+    PolyStaged staged;
+    float ms[2] = {0.f, 0.f};
+    for (size_t k = 0; k < pq_chunks(pairs, chunk); k++) {
+        const size_t lo = pq_chunk_lo(k, chunk), m = pq_chunk_size(pairs, k, chunk);
+        if ((rc = poly_stage(s, *b, *pb, c, lo, m, staged, ms)) != KZG_OK) return rc;
+        HIPCHK(hipMemcpyAsync(limbs.data(), b->d_scalars.p, 32 * n * m, hipMemcpyDeviceToHost, s->s1));
+        if (ys_out) HIPCHK(hipMemcpyAsync(ys_out + 32 * lo, pb->d_ys.p, 32 * m, hipMemcpyDeviceToHost, s->s1));
+        HIPCHK(hipStreamSynchronize(s->s1));
+        for (size_t i = 0; i < n * m; i++)  // little-endian limbs -> big-endian bytes
+            for (int j = 0; j < 32; j++) q_out[32 * (n * lo + i) + j] = limbs[32 * i + 31 - j];
+    }
+    s->timings[4] = ms[1], s->timings[6] = ms[0];
+    return KZG_OK;
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
+}
+
+extern "C" KzgRet kzg_debug_poly_quotient_tiles(size_t out[4]) {
+    if (!out) return fail(KZG_BADARGS, "null argument");
+    out[0] = PQ_LANE, out[1] = PQ_WAVE, out[2] = PQ_TILE, out[3] = PQ_CHUNK_SCALARS;
+    return KZG_OK;
+}

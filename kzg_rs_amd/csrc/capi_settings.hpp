@@ -133,6 +133,7 @@ struct KzgSettings {
     mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
     mutable struct CellRecoverState* cell_recover = nullptr;  // cell recovery's own buffers, made by its first call (capi_cell_recover.hpp)
     mutable struct G1PointsBufs* g1_points = nullptr;  // kzg_g1_msm_prepared's call buffers, made by its first call (capi_g1_points.hpp)
+    mutable struct PolyBufs* poly = nullptr;  // the quotient stage's buffers of the coefficient-form openings, made by their first call (capi_poly.hpp)
     // the EIP-7594 cell work this shard has run since the last reset (kzg_debug_cell_shard_stats, capi_cell_multi.hpp): launches
     // (locked ranges and coalesced launches) | cells verified | blobs verified against cell proofs | blobs proved or recovered.
     // A lane of the small-call queue counts on the shard it lives on (cell_home)
@@ -607,6 +608,7 @@ static void cells_release(const KzgSettings* s);   // (capi_cells.hpp)
 static void cell_prover_release(const KzgSettings* s);  // (capi_cell_prover.hpp)
 static void cell_recover_release(const KzgSettings* s);  // (capi_cell_recover.hpp)
 static void g1_points_release(const KzgSettings* s);  // (capi_g1_points.hpp)
+static void poly_release(const KzgSettings* s);  // (capi_poly.hpp)
 extern "C" void kzg_settings_free(KzgSettings* s) {
     if (!s) return;
     int prev = -1;
@@ -627,6 +629,7 @@ extern "C" void kzg_settings_free(KzgSettings* s) {
     cell_prover_release(s);
     cell_recover_release(s);
     g1_points_release(s);
+    poly_release(s);
     s->own = SettingsTables();  // (a lane's is empty: it reads its parent's, which is freed after its lanes)
     for (auto& e : s->ev)
         if (e) (void)hipEventDestroy(e);

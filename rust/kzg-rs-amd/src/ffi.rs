@@ -50,6 +50,8 @@ extern "C" {
     pub fn kzg_pairings_verify(ok: *mut bool, a1: *const u8, a2: *const u8, b1: *const u8, b2: *const u8, s: *const RawSettings) -> c_int;
     pub fn kzg_g1_msm(out: *mut u8, points48: *const u8, scalars: *const u8, n: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_g1_msm_setup(out: *mut u8, scalars: *const u8, n: usize, s: *const RawSettings) -> c_int;
+    pub fn kzg_debug_poly_quotients(q_out: *mut u8, ys_out: *mut u8, coeffs: *const u8, n_coeffs: usize, zs: *const u8, n_points: usize, n_polys: usize, s: *const RawSettings) -> c_int;
+    pub fn kzg_debug_poly_quotient_tiles(out: *mut usize) -> c_int;
     pub fn kzg_last_error() -> *const c_char;
 }
 
