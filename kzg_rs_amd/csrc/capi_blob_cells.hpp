@@ -239,15 +239,11 @@ static KzgRet blob_cell_setup_once(const KzgSettings* s) {
 }
 // The challenge of blob b of request r, by whoever comes first; false: somebody else has it, or has had it
 static bool small_blob_cell_hash_one(SmallReq& r, size_t b) {
-    int idle = 0;
-    if (r.blob_r_state[b].load(std::memory_order_relaxed) != 0 || !r.blob_r_state[b].compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return false;
-    blob_cell_challenge(r.blob_r + 32 * b, r.blobs + (size_t)BLOB_BYTES * b, r.c + 48 * b, r.p + BLOB_CELL_PROOFS_BYTES * b);
-    r.blob_r_state[b].store(2, std::memory_order_release);
-    return true;
+    return small_claim(r, b, [&](uint8_t* out) { blob_cell_challenge(out, r.blobs + (size_t)BLOB_BYTES * b, r.c + 48 * b, r.p + BLOB_CELL_PROOFS_BYTES * b); });
 }
 // what the owner of a queued request does instead of sleeping: one more of its own blobs' challenges (the leader collects them)
 static bool small_blob_cell_wait_work(SmallReq& r) {
-    for (size_t b = 0; b < r.n; b++)
+    for (size_t b = 0; b < r.n_chal; b++)
         if (small_blob_cell_hash_one(r, b)) return true;
     return false;
 }
@@ -259,9 +255,8 @@ struct BlobCellSlot {
 static void small_blob_cell_slot_hash(uint8_t r_be[32], const void* ctx, size_t g) {
     const BlobCellSlot& sl = static_cast<const BlobCellSlot*>(ctx)[g];
     // (a blob its owner is at: one chain of 137 KB, ~0.1 ms)
-    if (!small_blob_cell_hash_one(*sl.r, sl.b))
-        while (sl.r->blob_r_state[sl.b].load(std::memory_order_acquire) != 2) std::this_thread::yield();
-    memcpy(r_be, sl.r->blob_r + 32 * sl.b, 32);
+    if (!small_blob_cell_hash_one(*sl.r, sl.b)) small_await(*sl.r, sl.b);
+    memcpy(r_be, sl.r->chal + 32 * sl.b, 32);
 }
 // A lane's buffers for the largest launch, made by its first launch of this kind: a buffer that grew with the launches would free
 // and allocate device memory in the middle of the traffic (capi_coalesce.hpp small_lane_make).  Released with the lane.
@@ -313,7 +308,7 @@ static KzgRet small_run_blob_cells(SmallLane& L, std::vector<SmallReq*>& batch, 
         for (size_t b = 0; b < r->n; b++, g++) {
             c[g] = r->c + 48 * b, p[g] = r->p + BLOB_CELL_PROOFS_BYTES * b, bl[g] = r->blobs + (size_t)BLOB_BYTES * b;
             slots[g] = BlobCellSlot{r, b};
-            pending += r->blob_r_state[b].load(std::memory_order_relaxed) == 0;
+            pending += r->chal_state[b].load(std::memory_order_relaxed) == 0;
         }
     if (g != m) return fail(KZG_ERROR, "small-call queue: a blob-cell launch whose requests do not add up");
     bool* const ok = reinterpret_cast<bool*>(okerr.data());
@@ -358,8 +353,7 @@ static KzgRet small_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* bl
     r.p = cell_proofs;
     r.ok = ok;
     r.err = err;
-    r.blob_r = r_be;
-    r.blob_r_state = r_state;
+    r.chal = r_be, r.chal_state = r_state, r.n_chal = n;
     r.wait_work = small_blob_cell_wait_work;
     const KzgRet rc = small_submit(s, r);
     if (rc != KZG_OK) return rc;
@@ -373,21 +367,9 @@ static KzgRet small_blob_cells(bool* ok_out, uint8_t* err_out, const uint8_t* bl
 }
 
 // diagnostic: launches | requests | blobs | the largest launch in requests - of the BLOB_CELLS kind alone, since the last reset
-extern "C" KzgRet kzg_debug_blob_cell_queue_stats(const KzgSettings* s, uint64_t out[4], int reset) {
-    if (!s || !out) return fail(KZG_BADARGS, "null argument");
-    memset(out, 0, 4 * sizeof(uint64_t));
-    if (!s->small) return KZG_OK;
-    SmallQueue& Q = *s->small;
-    std::lock_guard<SmallSpinLock> lk(Q.mu);
-    out[0] = Q.blob_cell_launches;
-    out[1] = Q.blob_cell_requests;
-    out[2] = Q.blob_cell_items;
-    out[3] = Q.blob_cell_max_requests;
-    if (reset) Q.blob_cell_launches = Q.blob_cell_requests = Q.blob_cell_items = Q.blob_cell_max_requests = 0;
-    return KZG_OK;
-}
+extern "C" KzgRet kzg_debug_blob_cell_queue_stats(const KzgSettings* s, uint64_t out[4], int reset) { return small_kind_stats(s, SmallReq::BLOB_CELLS, out, reset); }
 
-// measurement hook, after kzg_debug_concurrent_cell_callers: T host threads inside the library (no interpreter lock, no ctypes)
+// measurement hook, after kzg_debug_concurrent_cell_callers (capi_coalesce.hpp concurrent_run): T host threads inside the library
 // calling kzg_verify_blob_cell_kzg_proofs on ONE shared handle for `seconds`.  The calls: n_calls slices of the three arrays, call
 // after call, call i of call_sizes[i] blobs; expect[b] per blob: 0 false | 1 true | 2 refused.  Thread t takes calls t, t + T, ...;
 // its calls pass err_out and every second one of them does not - that one must return KZG_BADARGS exactly when a blob of the call
@@ -398,79 +380,21 @@ extern "C" KzgRet kzg_debug_concurrent_blob_cell_callers(double out[5], size_t t
                                                          const KzgSettings* s) try {
     if (!out || !s || !blobs || !commitments || !cell_proofs || !call_sizes || !expect || !threads || !n_calls) return fail(KZG_BADARGS, "bad argument");
     std::vector<size_t> off(n_calls + 1, 0);
-    size_t longest = 0;
-    for (size_t i = 0; i < n_calls; i++) off[i + 1] = off[i] + call_sizes[i], longest = std::max(longest, call_sizes[i]);
-    std::atomic<uint64_t> calls{0}, wrong{0};
-    std::atomic<bool> stop{false};
-    std::mutex go_mu;  // (the threads wait for the start asleep)
-    std::condition_variable go_cv;
-    bool go = false;
-    std::vector<double> lat_sum(threads, 0.0), lat_max(threads, 0.0);
-    auto body = [&](size_t t) {
-        std::vector<uint8_t> oks(longest + 1), errs(longest + 1);
-        {
-            std::unique_lock<std::mutex> lk(go_mu);
-            go_cv.wait(lk, [&] { return go; });
-        }
-        // (independent callers do not arrive in lock-step: a fixed pseudo-random offset below 2.5 ms per thread)
-        std::this_thread::sleep_for(std::chrono::microseconds((uint32_t)(t * 2654435761u) % 2500u));
-        uint64_t round = 0;
-        for (size_t i = t % n_calls; !stop.load(std::memory_order_relaxed); i = (i + threads) % n_calls, round++) {
-            const size_t e = off[i], n = call_sizes[i];
-            const bool with_err = (round & 1) == 0;
-            const auto t0 = std::chrono::steady_clock::now();
-            const KzgRet rc = kzg_verify_blob_cell_kzg_proofs(reinterpret_cast<bool*>(oks.data()), with_err ? errs.data() : nullptr, blobs + (size_t)BLOB_BYTES * e,
-                                                              commitments + 48 * e, cell_proofs + BLOB_CELL_PROOFS_BYTES * e, n, s);
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            bool refused = false, bad = false;
-            for (size_t b = 0; b < n; b++) refused |= expect[e + b] == 2;
-            if (!with_err && refused) bad = rc != KZG_BADARGS;
-            else if (rc != KZG_OK) bad = true;
-            else
-                for (size_t b = 0; b < n; b++) bad |= ((with_err && errs[b]) ? 2 : oks[b] ? 1 : 0) != expect[e + b];
-            lat_sum[t] += ms;
-            lat_max[t] = std::max(lat_max[t], ms);
-            if (bad) wrong.fetch_add(1, std::memory_order_relaxed);
-            calls.fetch_add(1, std::memory_order_relaxed);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        pool.reserve(threads);
-        for (size_t t = 0; t < threads; t++) pool.emplace_back(body, t);
-    } catch (...) {  // (no more threads to be had: the ones made leave at once)
-        stop.store(true);
-        {
-            std::lock_guard<std::mutex> lk(go_mu);
-            go = true;
-        }
-        go_cv.notify_all();
-        for (auto& th : pool) th.join();
-        return fail(KZG_ERROR, "kzg_debug_concurrent_blob_cell_callers: could not start the threads");
-    }
-    std::this_thread::sleep_for(std::chrono::milliseconds(20));  // (every thread has reached its wait)
-    {
-        std::lock_guard<std::mutex> lk(go_mu);
-        go = true;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    go_cv.notify_all();
-    std::this_thread::sleep_for(std::chrono::duration<double>(seconds));
-    const uint64_t counted = calls.load();  // (calls completed inside the interval)
-    const double elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    stop.store(true);
-    for (auto& th : pool) th.join();
-    double ls = 0, lm = 0;
-    for (size_t t = 0; t < threads; t++) {
-        ls += lat_sum[t];
-        lm = std::max(lm, lat_max[t]);
-    }
-    out[0] = (double)counted;
-    out[1] = elapsed_s;
-    out[2] = (double)wrong.load();
-    out[3] = calls.load() ? ls / (double)calls.load() : 0.0;
-    out[4] = lm;
-    return KZG_OK;
+    for (size_t i = 0; i < n_calls; i++) off[i + 1] = off[i] + call_sizes[i];
+    return concurrent_run(out, "kzg_debug_concurrent_blob_cell_callers", threads, seconds, n_calls, [&](size_t i, ConcurrentScratch& sc) -> uint64_t {
+        const size_t e = off[i], n = call_sizes[i];
+        const bool with_err = (sc.round & 1) == 0;
+        sc.oks.resize(n + 1), sc.errs.resize(n + 1);
+        const KzgRet rc = kzg_verify_blob_cell_kzg_proofs(reinterpret_cast<bool*>(sc.oks.data()), with_err ? sc.errs.data() : nullptr, blobs + (size_t)BLOB_BYTES * e,
+                                                          commitments + 48 * e, cell_proofs + BLOB_CELL_PROOFS_BYTES * e, n, s);
+        bool refused = false, bad = false;
+        for (size_t b = 0; b < n; b++) refused |= expect[e + b] == 2;
+        if (!with_err && refused) bad = rc != KZG_BADARGS;
+        else if (rc != KZG_OK) bad = true;
+        else
+            for (size_t b = 0; b < n; b++) bad |= ((with_err && sc.errs[b]) ? 2 : sc.oks[b] ? 1 : 0) != expect[e + b];
+        return bad;
+    });
 } catch (const std::exception& e) {
     return fail(KZG_ERROR, std::string("kzg_debug_concurrent_blob_cell_callers: ") + e.what());
 }

@@ -50,19 +50,14 @@ struct CellGroupInArrays {
         in = CellGroupIn{c.data(), ix.data(), ce.data(), p.data(), batch_sizes, n_batches};
     }
 };
-// A challenge that may exist already: the owner of a queued request computes its own while it waits (small_cell_wait_work).
-// state 0: nobody has started - whoever moves it to 1 computes r_be and then stores 2.
-struct CellKnownR {
-    std::atomic<int>* state = nullptr;
-    uint8_t* r_be = nullptr;
-};
 // r_be + 32 j = the single call's r of slot j of `plan` - its dedup is the plan's - or, without a plan, of batch j, deduplicated
 // here; hashed by whoever calls work(): the batches are claimed from a counter, so the poster and any number of helper threads
-// share them.  known (optional, per batch): challenges computed beforehand, or being computed - those are collected, not hashed again.
+// share them.  known (optional, per batch, with a plan): the queued request the batch is - its owner computes its challenge while it
+// waits (small_cell_wait_work), so the challenge is claimed first (small_queue.hpp small_claim) and, when the owner has it, collected.
 struct CellGroupHash {
     uint8_t* r_be = nullptr;
     CellGroupIn in;
-    const CellKnownR* known = nullptr;
+    SmallReq* const* known = nullptr;
     const CellGroupPlan* plan = nullptr;
     // slots that are not lists of cells (capi_blob_cells.hpp): slot_hash(out, slot_ctx, j) = the challenge of slot j, one chain of
     // slot_bytes bytes; `in` and `known` are not read
@@ -93,29 +88,27 @@ struct CellGroupHash {
                     continue;
                 }
                 const size_t b = plan ? plan->slot_batch[j] : j, n = in.batch_sizes[b];
-                int idle = 0;
-                if (known && known[b].state && !known[b].state->compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) {
-                    // its owner has it, or is at it (one chain of at most T cells: well under a millisecond)
-                    while (known[b].state->load(std::memory_order_acquire) != 2) std::this_thread::yield();
-                    memcpy(out, known[b].r_be, 32);
-                    continue;
-                }
                 if (plan) {
-                    const uint32_t *cstart = plan->idx.data() + plan->o_cstart, *ustart = plan->idx.data() + plan->o_ustart;
-                    cell_challenge(out, in.commitments[b], plan->ci.data() + cstart[j], plan->uniq_entry.data() + ustart[j], ustart[j + 1] - ustart[j],
-                                   in.cell_indices[b], in.cells[b], in.proofs[b], n, plan->off[b]);
+                    auto hash = [&](uint8_t* r) {
+                        const uint32_t *cstart = plan->idx.data() + plan->o_cstart, *ustart = plan->idx.data() + plan->o_ustart;
+                        cell_challenge(r, in.commitments[b], plan->ci.data() + cstart[j], plan->uniq_entry.data() + ustart[j], ustart[j + 1] - ustart[j],
+                                       in.cell_indices[b], in.cells[b], in.proofs[b], n, plan->off[b]);
+                    };
+                    if (!known) {
+                        hash(out);
+                        continue;
+                    }
+                    // (its owner has it, or is at it: one chain of at most T cells)
+                    if (!small_claim(*known[b], 0, hash)) small_await(*known[b], 0);
+                    memcpy(out, known[b]->chal, 32);
                 } else {
                     ci.resize(n);
                     uniq.clear();
                     cell_dedup(in.commitments[b], n, ci.data(), uniq);
                     cell_challenge(out, in.commitments[b], ci.data(), uniq.data(), uniq.size(), in.cell_indices[b], in.cells[b], in.proofs[b], n);
                 }
-                if (known && known[b].state) {
-                    memcpy(known[b].r_be, out, 32);
-                    known[b].state->store(2, std::memory_order_release);
-                }
             }
-        } catch (const std::bad_alloc&) {  // (cell_dedup, before a claimed challenge is started: nothing is left at state 1)
+        } catch (const std::bad_alloc&) {  // (cell_dedup, where no challenge is claimed: nothing is left at state 1)
             failed = true;
         }
         const auto now = std::chrono::steady_clock::now();
@@ -127,7 +120,7 @@ struct CellGroupHash {
         size_t bytes = slot_hash ? std::min(count, slot_pending) * slot_bytes : 0;
         for (size_t j = 0; j < count && !slot_hash; j++) {
             const size_t b = plan ? plan->slot_batch[j] : j;
-            if (known && known[b].state && known[b].state->load(std::memory_order_relaxed) != 0) continue;
+            if (known && known[b]->chal_state[0].load(std::memory_order_relaxed) != 0) continue;
             bytes += in.batch_sizes[b] * (CELL_BYTES + 112);
         }
         const long opt = KZG_HOST_THREADS_OPTION;
@@ -461,8 +454,7 @@ static KzgRet cell_batches_run(bool* ok_out, uint8_t* err_out, const uint8_t* co
 
 // what the owner of a queued request does instead of sleeping: its own transcript hash (one chain; the leader collects it)
 static bool small_cell_wait_work(SmallReq& r) {
-    int idle = 0;
-    if (r.r_state.load(std::memory_order_relaxed) != 0) return false;
+    if (r.chal_state[0].load(std::memory_order_relaxed) != 0) return false;
     std::vector<uint32_t> ci, uniq;
     try {
         ci.resize(r.n);
@@ -470,10 +462,7 @@ static bool small_cell_wait_work(SmallReq& r) {
     } catch (const std::bad_alloc&) {
         return false;  // (the leader will hash it)
     }
-    if (!r.r_state.compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return false;
-    cell_challenge(r.r_be, r.c, ci.data(), uniq.data(), uniq.size(), r.cell_indices, r.cells, r.p, r.n);
-    r.r_state.store(2, std::memory_order_release);
-    return true;
+    return small_claim(r, 0, [&](uint8_t* out) { cell_challenge(out, r.c, ci.data(), uniq.data(), uniq.size(), r.cell_indices, r.cells, r.p, r.n); });
 }
 static void small_cell_refuse(SmallReq& r, const char* why) {
     r.err[0] = 1;
@@ -509,13 +498,11 @@ static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_
     std::vector<const uint8_t*> c(B), ce(B), p(B);
     std::vector<const uint64_t*> ix(B);
     std::vector<size_t> sizes(B);
-    std::vector<CellKnownR> known(B);
     std::vector<uint8_t> okerr(2 * B, 0);
     std::vector<const char*> why(B, nullptr);
     for (size_t b = 0; b < B; b++) {
         SmallReq& r = *batch[b];
         c[b] = r.c, ix[b] = r.cell_indices, ce[b] = r.cells, p[b] = r.p, sizes[b] = r.n;
-        known[b] = CellKnownR{&r.r_state, r.r_be};
     }
     const CellGroupIn in{c.data(), ix.data(), ce.data(), p.data(), sizes.data(), B};
     bool* const ok = reinterpret_cast<bool*>(okerr.data());
@@ -528,7 +515,7 @@ static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_
     }
     std::vector<uint8_t> r_be(32 * (size_t)P.G);
     CellGroupHash hash;  // (declared after what its helper threads read and write: joined first)
-    hash.r_be = r_be.data(), hash.in = in, hash.known = known.data(), hash.plan = &P, hash.count = P.G;
+    hash.r_be = r_be.data(), hash.in = in, hash.known = batch.data(), hash.plan = &P, hash.count = P.G;
     float stage_ms[4] = {};
     const float none[8] = {};
     if (P.G) {
@@ -549,7 +536,8 @@ static KzgRet small_cells(bool* ok, const uint8_t* commitments, const uint64_t* 
                           const KzgSettings* s) {
     SmallReq r;
     bool verdict = false;
-    uint8_t err = 0, general = 0;
+    uint8_t err = 0, general = 0, r_be[32];
+    std::atomic<int> r_state{0};
     r.kind = SmallReq::CELLS;
     r.n = n;
     r.c = commitments;
@@ -559,6 +547,7 @@ static KzgRet small_cells(bool* ok, const uint8_t* commitments, const uint64_t* 
     r.ok = &verdict;
     r.err = &err;
     r.general = &general;
+    r.chal = r_be, r.chal_state = &r_state, r.n_chal = 1;
     r.wait_work = small_cell_wait_work;
     const KzgRet rc = small_submit(s, r);
     if (rc != KZG_OK) return rc;
@@ -568,21 +557,9 @@ static KzgRet small_cells(bool* ok, const uint8_t* commitments, const uint64_t* 
 }
 
 // diagnostic: launches | requests | cells | the largest launch in requests - of the CELLS kind alone, since the last reset
-extern "C" KzgRet kzg_debug_cell_queue_stats(const KzgSettings* s, uint64_t out[4], int reset) {
-    if (!s || !out) return fail(KZG_BADARGS, "null argument");
-    memset(out, 0, 4 * sizeof(uint64_t));
-    if (!s->small) return KZG_OK;
-    SmallQueue& Q = *s->small;
-    std::lock_guard<SmallSpinLock> lk(Q.mu);
-    out[0] = Q.cell_launches;
-    out[1] = Q.cell_requests;
-    out[2] = Q.cell_items;
-    out[3] = Q.cell_max_requests;
-    if (reset) Q.cell_launches = Q.cell_requests = Q.cell_items = Q.cell_max_requests = 0;
-    return KZG_OK;
-}
+extern "C" KzgRet kzg_debug_cell_queue_stats(const KzgSettings* s, uint64_t out[4], int reset) { return small_kind_stats(s, SmallReq::CELLS, out, reset); }
 
-// measurement hook, after kzg_debug_concurrent_callers: T host threads inside the library (no interpreter lock, no ctypes) calling
+// measurement hook, after kzg_debug_concurrent_callers (capi_coalesce.hpp concurrent_run): T host threads inside the library calling
 // kzg_verify_cell_kzg_proof_batch on ONE shared handle for `seconds`.  The calls: n_calls batches, batch after batch in the four
 // arrays, batch i of batch_sizes[i] cells; expect[i]: 0 false | 1 true | 2 Err(BadArgs).  Thread t takes calls t, t + T, ...
 // out: [0] calls completed, [1] elapsed seconds, [2] answers that differ from `expect`, [3] mean latency in ms, [4] the longest.
@@ -592,68 +569,11 @@ extern "C" KzgRet kzg_debug_concurrent_cell_callers(double out[5], size_t thread
     if (!out || !s || !commitments || !cell_indices || !cells || !proofs || !batch_sizes || !expect || !threads || !n_calls)
         return fail(KZG_BADARGS, "bad argument");
     const CellGroupInArrays arrays(commitments, cell_indices, cells, proofs, batch_sizes, n_calls);
-    std::atomic<uint64_t> calls{0}, wrong{0};
-    std::atomic<bool> stop{false};
-    std::mutex go_mu;  // (the threads wait for the start asleep)
-    std::condition_variable go_cv;
-    bool go = false;
-    std::vector<double> lat_sum(threads, 0.0), lat_max(threads, 0.0);
-    auto body = [&](size_t t) {
-        {
-            std::unique_lock<std::mutex> lk(go_mu);
-            go_cv.wait(lk, [&] { return go; });
-        }
-        // (independent callers do not arrive in lock-step: a fixed pseudo-random offset below 2.5 ms per thread)
-        std::this_thread::sleep_for(std::chrono::microseconds((uint32_t)(t * 2654435761u) % 2500u));
-        for (size_t i = t % n_calls; !stop.load(std::memory_order_relaxed); i = (i + threads) % n_calls) {
-            const auto t0 = std::chrono::steady_clock::now();
-            bool ok = false;
-            const KzgRet rc = kzg_verify_cell_kzg_proof_batch(&ok, arrays.c[i], arrays.ix[i], arrays.ce[i], arrays.p[i], batch_sizes[i], s);
-            const int got = rc == KZG_BADARGS ? 2 : rc == KZG_OK ? (ok ? 1 : 0) : 3;
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            lat_sum[t] += ms;
-            lat_max[t] = std::max(lat_max[t], ms);
-            if (got != expect[i]) wrong.fetch_add(1, std::memory_order_relaxed);
-            calls.fetch_add(1, std::memory_order_relaxed);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        pool.reserve(threads);
-        for (size_t t = 0; t < threads; t++) pool.emplace_back(body, t);
-    } catch (...) {  // (no more threads to be had: the ones made leave at once)
-        stop.store(true);
-        {
-            std::lock_guard<std::mutex> lk(go_mu);
-            go = true;
-        }
-        go_cv.notify_all();
-        for (auto& th : pool) th.join();
-        return fail(KZG_ERROR, "kzg_debug_concurrent_cell_callers: could not start the threads");
-    }
-    std::this_thread::sleep_for(std::chrono::milliseconds(20));  // (every thread has reached its wait)
-    {
-        std::lock_guard<std::mutex> lk(go_mu);
-        go = true;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    go_cv.notify_all();
-    std::this_thread::sleep_for(std::chrono::duration<double>(seconds));
-    const uint64_t counted = calls.load();  // (calls completed inside the interval)
-    const double elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    stop.store(true);
-    for (auto& th : pool) th.join();
-    double ls = 0, lm = 0;
-    for (size_t t = 0; t < threads; t++) {
-        ls += lat_sum[t];
-        lm = std::max(lm, lat_max[t]);
-    }
-    out[0] = (double)counted;
-    out[1] = elapsed_s;
-    out[2] = (double)wrong.load();
-    out[3] = calls.load() ? ls / (double)calls.load() : 0.0;
-    out[4] = lm;
-    return KZG_OK;
+    return concurrent_run(out, "kzg_debug_concurrent_cell_callers", threads, seconds, n_calls, [&](size_t i, ConcurrentScratch&) -> uint64_t {
+        bool ok = false;
+        const KzgRet rc = kzg_verify_cell_kzg_proof_batch(&ok, arrays.c[i], arrays.ix[i], arrays.ce[i], arrays.p[i], batch_sizes[i], s);
+        return (rc == KZG_BADARGS ? 2 : rc == KZG_OK ? (ok ? 1 : 0) : 3) != expect[i];
+    });
 } catch (const std::exception& e) {
     return fail(KZG_ERROR, std::string("kzg_debug_concurrent_cell_callers: ") + e.what());
 }

@@ -362,7 +362,7 @@ extern "C" KzgRet kzg_verify_cell_kzg_proof_batch(bool* ok, const uint8_t* commi
     // with whatever else is waiting - as a slot of one group launch on a private lane (capi_coalesce.hpp; small_cells,
     // capi_cell_groups.hpp).  A lone caller's launch of one is the path below, on the lane.  Larger calls, and every call with
     // option cell_coalesce=0, take the handle's own lock.
-    if (small_enabled(s) && s->small->cells_on && n <= cell_group_threshold()) {
+    if (small_enabled(s) && s->small->rule[SmallReq::CELLS].on && n <= cell_group_threshold()) {
         if ((rc = cells_setup_once(s)) != KZG_OK) return rc;
         return small_cells(ok, commitments, cell_indices, cells, proofs, n, s);
     }

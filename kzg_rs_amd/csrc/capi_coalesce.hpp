@@ -24,22 +24,26 @@
 //     is T / (the launch's 1.7-2 ms + the turn-around) instead of a stream of fragments that each wait for a lane;
 //   * a waiting blob caller hashes its own blobs meanwhile (host_only.hpp hostpool), so the host-side SHA-256 of T callers runs
 //     on T cores and the leader only collects the challenges;
-//   * a third kind of request is one kzg_verify_cell_kzg_proof_batch call of up to T = 256 cells: a launch carries up to 128
-//     of them (128 x T cells at most) as the slots of one cell group (capi_cell_groups.hpp small_run_cells), each with its own
-//     transcript - hashed by its owner while it waits - and its own pairing instance.  On a multi-device handle every shard
-//     has a cell set-up of its own (derived on first use), and a lane leads these launches on the shard it lives on.
-//   * a fourth kind is one kzg_verify_blob_cell_kzg_proofs call of up to 16 blobs (a blob transaction's): a launch carries up to 64
+//   * the kinds of request are rows of tables: what a launch of a kind may carry in SmallQueue::rule (small_queue.hpp), what
+//     runs it in small_kind_run below, its counters in SmallQueue::stats (small_kind_stats).  Beside PROOFS and BLOBS:
+//     CELLS is one kzg_verify_cell_kzg_proof_batch call of up to T = 256 cells: a launch carries up to 128 of them (128 x T cells
+//     at most) as the slots of one cell group (capi_cell_groups.hpp small_run_cells), each with its own transcript - hashed by
+//     its owner while it waits - and its own pairing instance.  On a multi-device handle every shard has a cell set-up of its
+//     own (derived on first use), and a lane leads these launches on the shard it lives on.
+//     BLOB_CELLS is one kzg_verify_blob_cell_kzg_proofs call of up to 16 blobs (a blob transaction's): a launch carries up to 64
 //     blobs as the slots of one blob-cell group (capi_blob_cells.hpp small_run_blob_cells), every blob with its own challenge -
-//     hashed by its owner while it waits - its own two sums and pairing instance; on every shard, like the third kind.
+//     hashed by its owner while it waits - its own two sums and pairing instance; on every shard, like CELLS.
 // Results are per request: a wrong proof, a non-canonical scalar, an undecodable or off-subgroup point in one caller's input
 // never changes another caller's answer (the instances share a launch, not a random linear combination).
 // z = tau (the pairing's G2 point is the identity: only for who knows the setup's secret, i.e. test rigs) is flagged per item;
 // its owner decides it through the general path under the handle's own lock, as before.
 
-constexpr size_t SMALL_MAX_TUPLES = PROOFS_CHUNK;  // proof tuples per launch (SmallQueue::cap_proofs)
-constexpr size_t SMALL_MAX_BLOBS = 256;            // blobs per launch (= the range of the one-pairing-per-blob form; SmallQueue::cap_blobs)
+constexpr size_t SMALL_MAX_TUPLES = PROOFS_CHUNK;  // proof tuples per launch: what a lane is sized for
+constexpr size_t SMALL_MAX_BLOBS = 256;            // blobs per launch (= the range of the one-pairing-per-blob form)
 
-static_assert(SMALL_MAX_TUPLES == 1024 && SMALL_MAX_BLOBS == 256, "SmallQueue::cap_proofs / cap_blobs (small_queue.hpp) are these");
+static_assert(SMALL_RULE_DEFAULTS[SmallReq::PROOFS].cap_items == SMALL_MAX_TUPLES && SMALL_RULE_DEFAULTS[SmallReq::BLOBS].cap_items == SMALL_MAX_BLOBS &&
+                  SMALL_RULE_DEFAULTS[SmallReq::CELLS].cap_items == SMALL_RULE_DEFAULTS[SmallReq::CELLS].cap_requests * CELL_GROUP_MAX_CELLS,
+              "the rules' defaults (small_queue.hpp) against what a lane and a cell group hold");
 static void small_free(KzgSettings* s) {
     if (!s->small) return;
     for (size_t i = 0; i < s->small->n_lanes; i++) {
@@ -169,11 +173,19 @@ static KzgRet small_run_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_
 static KzgRet small_run_blob_cells(SmallLane& L, std::vector<SmallReq*>& batch, size_t m);  // (capi_blob_cells.hpp)
 static KzgRet cells_setup_once(const KzgSettings* s);      // (capi_cells.hpp)
 static KzgRet blob_cell_setup_once(const KzgSettings* s);  // (capi_blob_cells.hpp)
+// per kind, indexed by SmallReq::Kind: the launch of one leader, and what it borrows from the shard the lane lives on
+struct SmallKindRun {
+    KzgRet (*run)(SmallLane& L, std::vector<SmallReq*>& batch, size_t m);
+    bool cells_setup, blob_cell_setup;
+};
+static const SmallKindRun small_kind_run[SmallReq::KINDS] = {
+    {small_run_proofs, false, false}, {small_run_blobs, false, false}, {small_run_cells, true, false}, {small_run_blob_cells, true, true}};
 
 // Submit a request and return when it is done (small_queue.hpp small_submit_core); the launch a leader runs on its lane:
 static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
     SmallQueue& Q = *s->small;
     auto run = [&](int li, SmallLane& L, std::vector<SmallReq*>& batch, size_t m, SmallReq::Kind kind, std::string& msg) -> KzgRet {
+        const SmallKindRun& K = small_kind_run[kind];
         const size_t shard = (size_t)li % shard_count(s);  // the lanes of a multi-device handle are dealt to its devices in turn
         KzgRet rc = KZG_OK;
         const KzgSettings* const home = shard_of(s, shard);
@@ -197,14 +209,14 @@ static KzgRet small_submit(const KzgSettings* s, SmallReq& r) {
         }
         // a cell launch borrows the set-up of the shard the lane lives on: the first shard's exists (made before the request was
         // queued); another shard derives its own, once, on its own device, before its first lane leads (one atomic load afterwards)
-        if (rc == KZG_OK && shard != 0 && (kind == SmallReq::CELLS || kind == SmallReq::BLOB_CELLS)) {
-            if ((rc = cells_setup_once(home)) == KZG_OK && kind == SmallReq::BLOB_CELLS) rc = blob_cell_setup_once(home);
+        if (rc == KZG_OK && shard != 0) {
+            if (K.cells_setup) rc = cells_setup_once(home);
+            if (rc == KZG_OK && K.blob_cell_setup) rc = blob_cell_setup_once(home);
             if (rc != KZG_OK) msg = g_err;
         }
         if (rc == KZG_OK) {
             try {
-                rc = kind == SmallReq::PROOFS ? small_run_proofs(L, batch, m) : kind == SmallReq::BLOBS ? small_run_blobs(L, batch, m)
-                   : kind == SmallReq::CELLS ? small_run_cells(L, batch, m) : small_run_blob_cells(L, batch, m);
+                rc = K.run(L, batch, m);
                 if (rc != KZG_OK) msg = g_err;
             } catch (const std::bad_alloc&) {
                 rc = KZG_MALLOC;
@@ -284,20 +296,32 @@ extern "C" KzgRet kzg_debug_small_queue_stats(const KzgSettings* s, uint64_t out
     return KZG_OK;
 }
 
-// measurement + test hook: T host threads (plain std::threads inside the library: no interpreter lock, no ctypes) calling the
-// PUBLIC small entry points on ONE shared handle for `seconds`, each checking every answer it gets.
-//   kind 0: kzg_verify_kzg_proof(c[i], z[i], y[i], p[i])                               expect[i]: 0 false | 1 true | 2 Err(BadArgs)
-//   kind 1: kzg_verify_blob_kzg_proof_batch(blobs / c / p [i per_call, (i + 1) per_call))   expect[i] for call i, i < n_items / per_call
-//   kind 2: kzg_verify_kzg_proofs over tuples [i per_call, (i + 1) per_call) with err_out   expect[j] per tuple
-// thread t takes calls t, t + T, ... (mod the number of distinct calls).  out: [0] calls completed, [1] elapsed seconds,
-// [2] answers that differ from `expect` (or calls that failed with another code), [3] mean latency of a call in ms, [4] the longest one.
-extern "C" KzgRet kzg_debug_concurrent_callers(double out[5], int kind, size_t threads, double seconds, const uint8_t* blobs, const uint8_t* c,
-                                               const uint8_t* z, const uint8_t* y, const uint8_t* p, const uint8_t* expect, size_t n_items, size_t per_call,
-                                               const KzgSettings* s) try {
-    if (!out || !s || !c || !p || !expect || !threads || !n_items || kind < 0 || kind > 2) return fail(KZG_BADARGS, "bad argument");
-    if (kind == 0) per_call = 1;
-    if (!per_call || n_items < per_call || (kind == 1 && !blobs) || (kind != 1 && (!z || !y))) return fail(KZG_BADARGS, "bad argument");
-    const size_t n_calls = n_items / per_call;
+// diagnostic: launches | requests | items | the largest launch in requests, of ONE kind since the last reset
+// (kzg_debug_cell_queue_stats, kzg_debug_blob_cell_queue_stats)
+static KzgRet small_kind_stats(const KzgSettings* s, SmallReq::Kind kind, uint64_t out[4], int reset) {
+    if (!s || !out) return fail(KZG_BADARGS, "null argument");
+    memset(out, 0, 4 * sizeof(uint64_t));
+    if (!s->small) return KZG_OK;
+    std::lock_guard<SmallSpinLock> lk(s->small->mu);
+    SmallKindStats& k = s->small->stats[kind];
+    out[0] = k.launches;
+    out[1] = k.requests;
+    out[2] = k.items;
+    out[3] = k.max_requests;
+    if (reset) k = SmallKindStats();
+    return KZG_OK;
+}
+
+// The harness of the measurement + test hooks below and in capi_cell_groups.hpp / capi_blob_cells.hpp: T host threads (plain
+// std::threads inside the library: no interpreter lock, no ctypes) in a closed loop for `seconds`; thread t makes calls t, t + T, ...
+// (mod n_calls).  call(i, scratch) makes call i and returns how many of its answers are wrong; scratch is the thread's own.
+// out: [0] calls completed, [1] elapsed seconds, [2] wrong answers, [3] mean latency of a call in ms, [4] the longest one.
+struct ConcurrentScratch {
+    std::vector<uint8_t> oks, errs;  // result buffers, sized by the call
+    uint64_t round = 0;              // the calls this thread has made
+};
+template <class Call>
+static KzgRet concurrent_run(double out[5], const char* name, size_t threads, double seconds, size_t n_calls, Call&& call) {
     std::atomic<uint64_t> calls{0}, wrong{0};
     std::atomic<bool> stop{false};
     // the threads wait for the start ASLEEP: 256 threads yielding in a loop while the rest are still being made use up the
@@ -305,6 +329,13 @@ extern "C" KzgRet kzg_debug_concurrent_callers(double out[5], int kind, size_t t
     std::mutex go_mu;
     std::condition_variable go_cv;
     bool go = false;
+    auto start = [&] {
+        {
+            std::lock_guard<std::mutex> lk(go_mu);
+            go = true;
+        }
+        go_cv.notify_all();
+    };
     std::vector<double> lat_sum(threads, 0.0), lat_max(threads, 0.0);
     auto body = [&](size_t t) {
         {
@@ -316,28 +347,10 @@ extern "C" KzgRet kzg_debug_concurrent_callers(double out[5], int kind, size_t t
         // whole run - one launch of ~T in flight, the second lane idle - which is the closed loop's artefact, not the queue's
         // behaviour under arrivals spread over time (measured at T = 256: 86-90 k calls/s in lock-step, 94-107 k spread).
         std::this_thread::sleep_for(std::chrono::microseconds((uint32_t)(t * 2654435761u) % 2500u));
-        std::vector<uint8_t> oks(per_call), errs(per_call);
-        for (size_t i = t % n_calls; !stop.load(std::memory_order_relaxed); i = (i + threads) % n_calls) {
+        ConcurrentScratch scratch;
+        for (size_t i = t % n_calls; !stop.load(std::memory_order_relaxed); i = (i + threads) % n_calls, scratch.round++) {
             const auto t0 = std::chrono::steady_clock::now();
-            uint64_t bad = 0;
-            if (kind == 0) {
-                bool ok = false;
-                const KzgRet rc = kzg_verify_kzg_proof(&ok, c + 48 * i, z + 32 * i, y + 32 * i, p + 48 * i, s);
-                const int got = rc == KZG_BADARGS ? 2 : rc == KZG_OK ? (ok ? 1 : 0) : 3;
-                bad = got != expect[i];
-            } else if (kind == 1) {
-                bool ok = false;
-                const size_t f = i * per_call;
-                const KzgRet rc = kzg_verify_blob_kzg_proof_batch(&ok, blobs + (size_t)BLOB_BYTES * f, c + 48 * f, p + 48 * f, per_call, s);
-                const int got = rc == KZG_BADARGS ? 2 : rc == KZG_OK ? (ok ? 1 : 0) : 3;
-                bad = got != expect[i];
-            } else {
-                const size_t f = i * per_call;
-                const KzgRet rc = kzg_verify_kzg_proofs(reinterpret_cast<bool*>(oks.data()), errs.data(), c + 48 * f, z + 32 * f, y + 32 * f, p + 48 * f, per_call, s);
-                if (rc != KZG_OK) bad = 1;
-                else
-                    for (size_t k = 0; k < per_call; k++) bad += (errs[k] ? 2 : oks[k] ? 1 : 0) != expect[f + k];
-            }
+            const uint64_t bad = call(i, scratch);
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             lat_sum[t] += ms;
             lat_max[t] = std::max(lat_max[t], ms);
@@ -351,21 +364,13 @@ extern "C" KzgRet kzg_debug_concurrent_callers(double out[5], int kind, size_t t
         for (size_t t = 0; t < threads; t++) pool.emplace_back(body, t);
     } catch (...) {  // (no more threads to be had: the ones made leave at once - a joinable thread must not meet its destructor)
         stop.store(true);
-        {
-            std::lock_guard<std::mutex> lk(go_mu);
-            go = true;
-        }
-        go_cv.notify_all();
+        start();
         for (auto& th : pool) th.join();
-        return fail(KZG_ERROR, "kzg_debug_concurrent_callers: could not start the threads");
+        return fail(KZG_ERROR, std::string(name) + ": could not start the threads");
     }
     std::this_thread::sleep_for(std::chrono::milliseconds(20));  // (every thread has reached its wait)
-    {
-        std::lock_guard<std::mutex> lk(go_mu);
-        go = true;
-    }
     const auto t0 = std::chrono::steady_clock::now();
-    go_cv.notify_all();
+    start();
     std::this_thread::sleep_for(std::chrono::duration<double>(seconds));
     const uint64_t counted = calls.load();  // (calls completed inside the interval; the ones in flight at its end are not counted)
     const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -382,6 +387,33 @@ extern "C" KzgRet kzg_debug_concurrent_callers(double out[5], int kind, size_t t
     out[3] = calls.load() ? ls / (double)calls.load() : 0.0;
     out[4] = lm;
     return KZG_OK;
+}
+
+// measurement + test hook: the PUBLIC small entry points from T threads on ONE shared handle, each checking every answer it gets.
+//   kind 0: kzg_verify_kzg_proof(c[i], z[i], y[i], p[i])                               expect[i]: 0 false | 1 true | 2 Err(BadArgs)
+//   kind 1: kzg_verify_blob_kzg_proof_batch(blobs / c / p [i per_call, (i + 1) per_call))   expect[i] for call i, i < n_items / per_call
+//   kind 2: kzg_verify_kzg_proofs over tuples [i per_call, (i + 1) per_call) with err_out   expect[j] per tuple
+// out[2]: answers that differ from `expect` (or calls that failed with another code).
+extern "C" KzgRet kzg_debug_concurrent_callers(double out[5], int kind, size_t threads, double seconds, const uint8_t* blobs, const uint8_t* c,
+                                               const uint8_t* z, const uint8_t* y, const uint8_t* p, const uint8_t* expect, size_t n_items, size_t per_call,
+                                               const KzgSettings* s) try {
+    if (!out || !s || !c || !p || !expect || !threads || !n_items || kind < 0 || kind > 2) return fail(KZG_BADARGS, "bad argument");
+    if (kind == 0) per_call = 1;
+    if (!per_call || n_items < per_call || (kind == 1 && !blobs) || (kind != 1 && (!z || !y))) return fail(KZG_BADARGS, "bad argument");
+    return concurrent_run(out, "kzg_debug_concurrent_callers", threads, seconds, n_items / per_call, [&](size_t i, ConcurrentScratch& sc) -> uint64_t {
+        const size_t f = i * per_call;
+        bool ok = false;
+        if (kind == 2) {
+            sc.oks.resize(per_call), sc.errs.resize(per_call);
+            if (kzg_verify_kzg_proofs(reinterpret_cast<bool*>(sc.oks.data()), sc.errs.data(), c + 48 * f, z + 32 * f, y + 32 * f, p + 48 * f, per_call, s) != KZG_OK) return 1;
+            uint64_t bad = 0;
+            for (size_t k = 0; k < per_call; k++) bad += (sc.errs[k] ? 2 : sc.oks[k] ? 1 : 0) != expect[f + k];
+            return bad;
+        }
+        const KzgRet rc = kind == 0 ? kzg_verify_kzg_proof(&ok, c + 48 * i, z + 32 * i, y + 32 * i, p + 48 * i, s)
+                                    : kzg_verify_blob_kzg_proof_batch(&ok, blobs + (size_t)BLOB_BYTES * f, c + 48 * f, p + 48 * f, per_call, s);
+        return (rc == KZG_BADARGS ? 2 : rc == KZG_OK ? (ok ? 1 : 0) : 3) != expect[i];
+    });
 } catch (const std::exception& e) {
     return fail(KZG_ERROR, std::string("kzg_debug_concurrent_callers: ") + e.what());
 }

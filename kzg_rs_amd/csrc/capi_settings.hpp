@@ -285,15 +285,18 @@ static KzgRet settings_common(KzgSettings** out, const uint8_t tau_g2[96]) {
         s->small->lane_priority = ab_int("small_priority", 1) ? 1 : 0;
         s->small->linger_us = std::max(0L, std::min(2000L, opt_int("small_linger_us", 250)));
         s->small->linger_gap_us = std::max(1L, std::min(1000L, ab_int("small_linger_gap_us", 40)));
-        s->small->cap_proofs = (size_t)std::max(1L, std::min(1024L, ab_int("small_cap_proofs", 1024)));  // (A/B: fewer tuples per launch; a request larger than the cap would never leave)
+        // the kinds' rules (small_queue.hpp SMALL_RULE_DEFAULTS), narrowed by option
+        auto& rule = s->small->rule;
+        auto narrow = [](size_t& v, const char* opt) { v = (size_t)std::max(1L, std::min((long)v, ab_int(opt, (long)v))); };
+        narrow(rule[SmallReq::PROOFS].cap_items, "small_cap_proofs");  // (A/B: fewer tuples per launch; a request larger than the cap would never leave)
         // concurrent kzg_verify_cell_kzg_proof_batch calls (option cell_coalesce=0: every call under the handle's own lock, as
         // before); a launch carries up to 128 calls and 128 x T cells, the largest shape measured (profiles/cell_shared_stage_probes.txt)
-        s->small->cells_on = opt_flag("cell_coalesce", true);
-        s->small->cap_cell_requests = (size_t)std::max(1L, std::min(128L, ab_int("small_cap_cell_requests", 128)));
-        s->small->cap_cells = (size_t)std::max(1L, std::min(128L * (long)CELL_GROUP_MAX_CELLS, ab_int("small_cap_cells", 128L * (long)CELL_GROUP_MAX_CELLS)));
+        rule[SmallReq::CELLS].on = opt_flag("cell_coalesce", true);
+        narrow(rule[SmallReq::CELLS].cap_requests, "small_cap_cell_requests");
+        narrow(rule[SmallReq::CELLS].cap_items, "small_cap_cells");
         // concurrent kzg_verify_blob_cell_kzg_proofs calls of up to KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs (option blob_cell_coalesce=0:
         // every call under the handle's own lock, as before); a launch carries up to 64 blobs, that call's group size
-        s->small->blob_cells_on = opt_flag("blob_cell_coalesce", true);
+        rule[SmallReq::BLOB_CELLS].on = opt_flag("blob_cell_coalesce", true);
     }
     *out = s;
     return KZG_OK;

@@ -2,8 +2,9 @@
 // launch itself left to the caller (capi_coalesce.hpp supplies the GPU launch).  Plain C++17 + Linux futexes, no HIP: part of the
 // translation unit kzg_capi.hip, and compiled on its own with g++ -fsanitize=thread by tests/test_small_queue_host.py
 // (tests/host/small_queue_main.cpp: hundreds of threads, a stand-in launch, every result checked, no lost wake-up, no race), by
-// tests/test_small_queue_cells_host.py (tests/host/small_queue_cells_main.cpp: the same with the third request kind among them) and
-// by tests/test_small_queue_blob_cells_host.py (tests/host/small_queue_blob_cells_main.cpp: the fourth kind).
+// tests/test_small_queue_cells_host.py and tests/test_small_queue_blob_cells_host.py (the same with CELLS and with BLOB_CELLS
+// requests) and by tests/test_small_take_host.py (tests/host/small_take_main.cpp: the taking of a launch's requests, case by case).
+// What differs between the request kinds is data: a row of SmallQueue::rule (what a launch may carry) and of SmallQueue::stats.
 #pragma once
 #include <linux/futex.h>
 #include <stdint.h>
@@ -12,6 +13,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <deque>
@@ -26,13 +28,14 @@
 
 // One request = the small call of one host thread: n (commitment, z, y, proof) tuples, or n host blobs with their commitments
 // and proofs; every item gets its own pairing and the request gets its own results - what the entry point makes of them
-// (one verdict, a conjunction, a verdict per item) is the submitter's business.  The third kind is one call of the cell-proof
+// (one verdict, a conjunction, a verdict per item) is the submitter's business.  CELLS is one call of the cell-proof
 // verifier: n cells with their commitments, cell indices and proofs, ONE verdict - the requests of a launch ride as the slots of a
-// group launch (capi_cell_groups.hpp), each with its own batch challenge.  The fourth kind is one call of
+// group launch (capi_cell_groups.hpp), each with its own batch challenge.  BLOB_CELLS is one call of
 // kzg_verify_blob_cell_kzg_proofs: n <= KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs with their commitments and 128 cell proofs each, a
 // verdict and an error flag PER BLOB - the blobs of a launch's requests are the slots of one blob-cell group (capi_blob_cells.hpp).
 struct SmallReq {
     enum Kind { PROOFS = 0, BLOBS = 1, CELLS = 2, BLOB_CELLS = 3 };
+    enum { KINDS = 4 };
     Kind kind = PROOFS;
     size_t n = 0;
     const uint8_t *c = nullptr, *p = nullptr;  // n x 48 bytes each
@@ -43,16 +46,15 @@ struct SmallReq {
     // verdict and its Err(BadArgs) (the reason in msg), general unused
     const uint64_t* cell_indices = nullptr;
     const uint8_t* cells = nullptr;
-    // ... and the call's batch challenge r, big-endian: whoever moves r_state from 0 to 1 computes it and then stores 2 - the
-    // owner while it waits (wait_work), or the leader of the launch for the requests whose owners have not come to it
-    uint8_t r_be[32] = {0};
-    std::atomic<int> r_state{0};
-    bool (*wait_work)(SmallReq&) = nullptr;  // what the owner can do instead of sleeping; false: nothing (left) to do
     // BLOB_CELLS: blobs n x 131072 bytes, c n x 48, p n x 128 x 48; ok[b] / err[b] per blob, msg the reason of the first blob with
-    // err set.  The challenges, one per blob, in the submitter's buffers: blob_r_state[b] moves 0 -> 1 -> 2 like r_state, so the
-    // owner (wait_work) and the leader share the blobs between them and none is hashed twice
-    uint8_t* blob_r = nullptr;                  // n x 32 big-endian bytes
-    std::atomic<int>* blob_r_state = nullptr;   // n words
+    // err set.
+    // The challenges of a CELLS request (one: the call's batch challenge r) or a BLOB_CELLS request (one per blob), big-endian, in
+    // the submitter's frame: whoever moves chal_state[i] from 0 to 1 computes challenge i and then stores 2 (small_claim) - the
+    // owner while it waits (wait_work), or the leader of the launch for the ones the owner has not come to - so none is hashed twice
+    uint8_t* chal = nullptr;                 // n_chal x 32 bytes
+    std::atomic<int>* chal_state = nullptr;  // n_chal words
+    size_t n_chal = 0;
+    bool (*wait_work)(SmallReq&) = nullptr;  // what the owner can do instead of sleeping; false: nothing (left) to do
     // results.  PROOFS: per item.  BLOBS: [0] only - the conjunction over the request's blobs, any parse failure among them, any z = tau
     bool* ok = nullptr;
     uint8_t *err = nullptr, *general = nullptr;
@@ -61,7 +63,41 @@ struct SmallReq {
     std::atomic<bool> taken{false}, done{false};  // taken: written under the queue's lock; done: the leader's LAST access to the request
     std::atomic<int> lane{-1};                    // the lane whose launch carries the request (its owner then sleeps on that lane's word)
 };
+// Challenge i of request r, by whoever comes first: compute(where its 32 bytes go).  false: somebody else has it, or has had it.
+template <class Compute>
+static bool small_claim(SmallReq& r, size_t i, Compute&& compute) {
+    int idle = 0;
+    if (r.chal_state[i].load(std::memory_order_relaxed) != 0 || !r.chal_state[i].compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return false;
+    compute(r.chal + 32 * i);
+    r.chal_state[i].store(2, std::memory_order_release);
+    return true;
+}
+// ... and the wait for the one who has it (a chain of well under a millisecond)
+static void small_await(const SmallReq& r, size_t i) {
+    while (r.chal_state[i].load(std::memory_order_acquire) != 2) std::this_thread::yield();
+}
 constexpr size_t SMALL_LANES_MAX = 16;
+// What a launch of one kind may carry, and how its requests are chosen (small_take).  in_order = false packs: a request that does
+// not fit is passed over and the scan goes on.  in_order = true overtakes nobody: the oldest request always leaves, whatever its
+// size, and the first later one that does not fit ends the launch.
+struct SmallKindRule {
+    size_t cap_items = 0;            // items per launch
+    size_t cap_requests = SIZE_MAX;  // requests per launch (SIZE_MAX: no limit)
+    bool in_order = false;
+    bool on = true;           // do the kind's entry points queue their calls at all (read when the handle is made)
+    bool cell_lanes = false;  // launches run on the cell set-up: only on the lanes SmallQueue::cell_lane_stride allows
+};
+// (the values of a handle: capi_settings.hpp settings_common narrows them by option)
+constexpr std::array<SmallKindRule, SmallReq::KINDS> SMALL_RULE_DEFAULTS = {{
+    {1024, SIZE_MAX, false, true, false},         // PROOFS: tuples
+    {256, SIZE_MAX, false, true, false},          // BLOBS: the range of the one-pairing-per-blob form
+    {(size_t)128 * 256, 128, true, true, true},   // CELLS: the slots of a group launch, and cells in all (128 x CELL_GROUP_MAX_CELLS)
+    {64, SIZE_MAX, true, true, true},             // BLOB_CELLS: blobs, the group size of kzg_verify_blob_cell_kzg_proofs
+}};
+// launches | requests | items | the largest launch in requests, of one kind since the last reset (capi_coalesce.hpp small_kind_stats)
+struct SmallKindStats {
+    uint64_t launches = 0, requests = 0, items = 0, max_requests = 0;
+};
 struct SmallLane {
     KzgSettings* h = nullptr;  // a private lane (settings_lane) on one device of the handle
     bool busy = false;
@@ -108,29 +144,20 @@ struct SmallQueue {
     uint64_t last_done_us = 0;         // when the last launch finished, and how many calls it carried
     size_t last_done_items = 0;
     uint64_t launches = 0, requests = 0, items = 0, max_items = 0;  // since the last kzg_debug_small_queue_stats(reset)
-    size_t cap_proofs = 1024, cap_blobs = 256;  // items per launch
-    // CELLS: two limits per launch - requests (the slots of a group launch) and cells in all - and counters of their own beside the
-    // queue's totals above (kzg_debug_cell_queue_stats): launches | requests | cells | the largest launch in requests
-    size_t cap_cell_requests = 128, cap_cells = (size_t)128 * 256;
-    bool cells_on = true;  // option cell_coalesce (read when the handle is made)
-    uint64_t cell_launches = 0, cell_requests = 0, cell_items = 0, cell_max_requests = 0;
-    // the lanes that may carry CELLS: lane i with i % cell_lane_stride == 0; 1: every lane, which is what every handle uses - each
-    // shard of a multi-device handle has a cell set-up of its own.  (The stride remains for a queue whose cell set-up is on some
-    // lanes' device only: tests/host/small_queue_cells_main.cpp drives it.)
-    // (BLOB_CELLS run on the cell set-up too: the same rule)
+    // per kind, indexed by SmallReq::Kind: the rule of its launches, and counters of its own beside the queue's totals above
+    std::array<SmallKindRule, SmallReq::KINDS> rule = SMALL_RULE_DEFAULTS;
+    SmallKindStats stats[SmallReq::KINDS];
+    // the lanes that may carry the kinds with rule.cell_lanes: lane i with i % cell_lane_stride == 0; 1: every lane, which is what
+    // every handle uses - each shard of a multi-device handle has a cell set-up of its own.  (The stride remains for a queue whose
+    // cell set-up is on some lanes' device only: tests/host/small_queue_cells_main.cpp drives it.)
     size_t cell_lane_stride = 1;
-    // BLOB_CELLS: one limit per launch - blobs in all, the group size of kzg_verify_blob_cell_kzg_proofs - and counters of their own
-    // (kzg_debug_blob_cell_queue_stats): launches | requests | blobs | the largest launch in requests
-    size_t cap_blob_cell_blobs = 64;
-    bool blob_cells_on = true;  // option blob_cell_coalesce (read when the handle is made)
-    uint64_t blob_cell_launches = 0, blob_cell_requests = 0, blob_cell_items = 0, blob_cell_max_requests = 0;
 };
 static bool small_lane_carries(const SmallQueue& Q, int li, SmallReq::Kind kind) {
-    return (kind != SmallReq::CELLS && kind != SmallReq::BLOB_CELLS) || (size_t)li % Q.cell_lane_stride == 0;
+    return !Q.rule[kind].cell_lanes || (size_t)li % Q.cell_lane_stride == 0;
 }
 // which kzg_verify_blob_cell_kzg_proofs calls become requests: up to KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs (a blob transaction
 // carries at most 6; an engine_getBlobsV2 answer is larger and keeps the handle's lock) on a queue with the kind switched on
-static bool small_blob_cells_queued(const SmallQueue& Q, size_t n) { return Q.blob_cells_on && n >= 1 && n <= (size_t)KZG_BLOB_CELL_COALESCE_MAX_BLOBS; }
+static bool small_blob_cells_queued(const SmallQueue& Q, size_t n) { return Q.rule[SmallReq::BLOB_CELLS].on && n >= 1 && n <= (size_t)KZG_BLOB_CELL_COALESCE_MAX_BLOBS; }
 
 
 // Waiting and waking.  Waiters sleep on 32-bit futex words - the queue's while their request is still in the queue, their
@@ -180,51 +207,35 @@ static int small_take_lane(SmallQueue& Q) {
     return -1;
 }
 
-// The CELLS requests of a launch on lane li, under the queue's lock: oldest first while requests <= cap_cell_requests and cells <=
-// cap_cells (`batch` has room for the whole queue: nothing here allocates).  The first one leaves whatever its size - a request
-// beyond cap_cells on its own (an A/B capacity below the routing threshold) travels alone.  Returns the cells taken.
-static size_t small_take_cells(SmallQueue& Q, int li, std::vector<SmallReq*>& batch) {
+// The requests of a launch of `kind` on lane li, by the kind's rule, under the queue's lock (`batch` has room for the whole queue:
+// nothing here allocates); requests of other kinds keep their place.  Returns the items taken.
+static size_t small_take(SmallQueue& Q, int li, SmallReq::Kind kind, std::vector<SmallReq*>& batch) {
+    const SmallKindRule rule = Q.rule[kind];  // (a copy: the loop runs with hundreds of threads at the lock)
     size_t m = 0;
     for (auto it = Q.q.begin(); it != Q.q.end();) {
         SmallReq* x = *it;
-        if (x->kind != SmallReq::CELLS) {
+        if (x->kind != kind) {
             ++it;
             continue;
         }
-        if (!batch.empty() && (batch.size() >= Q.cap_cell_requests || m + x->n > Q.cap_cells)) break;
+        const bool fits = m + x->n <= rule.cap_items && batch.size() < rule.cap_requests;
+        if (!fits && !(rule.in_order && batch.empty())) {  // (in order, the oldest leaves whatever its size)
+            if (rule.in_order) break;  // it leads the next launch: nobody is overtaken
+            ++it;                      // packed: passed over
+            continue;
+        }
         x->lane.store(li, std::memory_order_release);
         x->taken.store(true, std::memory_order_relaxed);
         m += x->n;
         batch.push_back(x);
         it = Q.q.erase(it);
+        if (!rule.in_order && m == rule.cap_items) break;  // full
     }
-    Q.cell_launches++;
-    Q.cell_items += m;
-    Q.cell_max_requests = std::max<uint64_t>(Q.cell_max_requests, batch.size());
-    return m;
-}
-
-// The BLOB_CELLS requests of a launch on lane li, under the queue's lock: oldest first while the blobs in all stay at or below
-// cap_blob_cell_blobs; the first one that does not fit ends the launch (it leads the next one: nobody is overtaken).  A request
-// holds at most KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs, so the oldest always leaves.  Returns the blobs taken.
-static size_t small_take_blob_cells(SmallQueue& Q, int li, std::vector<SmallReq*>& batch) {
-    size_t m = 0;
-    for (auto it = Q.q.begin(); it != Q.q.end();) {
-        SmallReq* x = *it;
-        if (x->kind != SmallReq::BLOB_CELLS) {
-            ++it;
-            continue;
-        }
-        if (!batch.empty() && m + x->n > Q.cap_blob_cell_blobs) break;
-        x->lane.store(li, std::memory_order_release);
-        x->taken.store(true, std::memory_order_relaxed);
-        m += x->n;
-        batch.push_back(x);
-        it = Q.q.erase(it);
-    }
-    Q.blob_cell_launches++;
-    Q.blob_cell_items += m;
-    Q.blob_cell_max_requests = std::max<uint64_t>(Q.blob_cell_max_requests, batch.size());
+    if (batch.empty()) return 0;  // (a packed kind whose every request is beyond the capacity)
+    SmallKindStats& st = Q.stats[kind];
+    st.launches++;
+    st.items += m;
+    st.max_requests = std::max<uint64_t>(st.max_requests, batch.size());
     return m;
 }
 
@@ -265,8 +276,7 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
             if (!queued) {
                 Q.q.push_back(&r);
                 Q.requests++;
-                if (r.kind == SmallReq::CELLS) Q.cell_requests++;
-                if (r.kind == SmallReq::BLOB_CELLS) Q.blob_cell_requests++;
+                Q.stats[r.kind].requests++;
                 queued = true;
                 Q.arrivals.fetch_add(1, std::memory_order_relaxed);
             }
@@ -343,24 +353,7 @@ static KzgRet small_submit_core(SmallQueue& Q, SmallReq& r, Run&& run) {
                     continue;
                 }
             }
-            if (kind == SmallReq::CELLS) {
-                m = small_take_cells(Q, li, batch);
-            } else if (kind == SmallReq::BLOB_CELLS) {
-                m = small_take_blob_cells(Q, li, batch);
-            } else {
-                const size_t cap = kind == SmallReq::PROOFS ? Q.cap_proofs : Q.cap_blobs;
-                for (auto it = Q.q.begin(); it != Q.q.end();) {
-                    SmallReq* x = *it;
-                    if (x->kind == kind && m + x->n <= cap) {
-                        x->lane.store(li, std::memory_order_release);
-                        x->taken.store(true, std::memory_order_relaxed);
-                        m += x->n;
-                        batch.push_back(x);
-                        it = Q.q.erase(it);
-                        if (m == cap) break;
-                    } else ++it;
-                }
-            }
+            m = small_take(Q, li, kind, batch);
         }
         if (batch.empty()) {  // (everything left while this thread lingered)
             L.busy = false;

@@ -1,4 +1,4 @@
-// small_queue_blob_cells_main.cpp - the small-call queue's fourth request kind (csrc/small_queue.hpp SmallReq::BLOB_CELLS: one call of
+// small_queue_blob_cells_main.cpp - the small-call queue's BLOB_CELLS requests (csrc/small_queue.hpp SmallReq::BLOB_CELLS: one call of
 // kzg_verify_blob_cell_kzg_proofs, 1 to KZG_BLOB_CELL_COALESCE_MAX_BLOBS blobs, coalesced into blob-cell groups of up to 64 blobs) on
 // the CPU with a stand-in launch; built with -fsanitize=thread and once more with address,undefined by
 // tests/test_small_queue_blob_cells_host.py.  Every call has seeded per-blob expected answers (0 false | 1 true | 2 refused); the
@@ -14,27 +14,7 @@
 //   * with one thread, every launch carries one call;
 //   * the kind's counters agree with what the stand-in saw; nothing hangs (a watchdog aborts).
 // usage: threads calls lanes [watchdog_s lane_stride on]
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
-#include <mutex>
-#include <random>
-#include <thread>
-#include <vector>
-
-#define KZG_HOST_FE_PER_BLOB 64  // (host_only.hpp: small "blobs" for the older kinds' hashing pool)
-#include "small_queue.hpp"
-
-static std::atomic<int> failures{0};
-#define CHECK(x)                                                      \
-    do {                                                              \
-        if (!(x)) {                                                   \
-            failures++;                                               \
-            fprintf(stderr, "CHECK failed: %s (line %d)\n", #x, __LINE__); \
-        }                                                             \
-    } while (0)
+#include "small_queue_harness.hpp"
 
 constexpr size_t BLOB = 96, PROOFS = 128;  // a small "blob" and its "cell proofs": the code paths without 137 KB per blob
 // the stand-in for the per-blob challenge: a function of everything blob b of the request points at
@@ -50,15 +30,12 @@ static void blob_r(uint8_t out[32], const SmallReq& r, size_t b) {
 }
 static std::atomic<uint64_t> r_by_owner{0}, r_by_leader{0};
 static bool hash_one(SmallReq& r, size_t b, std::atomic<uint64_t>& who) {
-    int idle = 0;
-    if (!r.blob_r_state[b].compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return false;
-    blob_r(r.blob_r + 32 * b, r, b);
-    r.blob_r_state[b].store(2, std::memory_order_release);
+    if (!small_claim(r, b, [&](uint8_t* out) { blob_r(out, r, b); })) return false;
     who++;
     return true;
 }
 static bool wait_work(SmallReq& r) {
-    for (size_t b = 0; b < r.n; b++)
+    for (size_t b = 0; b < r.n_chal; b++)
         if (hash_one(r, b, r_by_owner)) return true;
     return false;
 }
@@ -72,21 +49,12 @@ int main(int argc, char** argv) {
     SmallQueue Q;
     Q.max_lanes = (size_t)LANES;
     Q.cell_lane_stride = (size_t)STRIDE;
-    Q.blob_cells_on = ON;
-    CHECK(Q.cap_blob_cell_blobs == 64 && KZG_BLOB_CELL_COALESCE_MAX_BLOBS == 16);
-    std::atomic<int> in_launch[SMALL_LANES_MAX];
-    for (auto& x : in_launch) x = 0;
-    std::atomic<uint64_t> launches{0}, carried{0}, carried_blobs{0}, largest{0}, failed_launches{0}, locked_calls{0};
+    Q.rule[SmallReq::BLOB_CELLS].on = ON;
+    CHECK(Q.rule[SmallReq::BLOB_CELLS].cap_items == 64 && KZG_BLOB_CELL_COALESCE_MAX_BLOBS == 16);
+    Harness H(LANES, WATCHDOG_S, 89, 17);
+    std::atomic<uint64_t> carried_blobs{0}, locked_calls{0};
     std::mutex comp_mu;
     std::vector<std::vector<size_t>> compositions;  // the sizes of the requests of every launch, in order
-    std::atomic<bool> finished{false};
-    std::thread watchdog([&] {
-        for (int i = 0; i < 10 * WATCHDOG_S && !finished; i++) std::this_thread::sleep_for(std::chrono::milliseconds(100));
-        if (!finished) {
-            fprintf(stderr, "WATCHDOG: callers still waiting after %d s - a lost wake-up\n", WATCHDOG_S);
-            abort();
-        }
-    });
     // what a blob's bytes say about it: blobs[0] = the expected answer, blobs[1] = which reason a refused blob carries
     auto echo = [&](SmallReq& x, const char** first_why) {
         for (size_t b = 0; b < x.n; b++) {
@@ -96,54 +64,35 @@ int main(int argc, char** argv) {
             if (e == 2 && !*first_why) *first_why = WHY[x.blobs[BLOB * b + 1] % 3];
         }
     };
-    auto run = [&](int li, SmallLane& L, std::vector<SmallReq*>& batch, size_t m, SmallReq::Kind kind, std::string& msg) -> KzgRet {
-        (void)L;
-        CHECK(li >= 0 && li < LANES && li % STRIDE == 0);
-        CHECK(in_launch[li].fetch_add(1) == 0);  // one launch per lane at a time
-        CHECK(kind == SmallReq::BLOB_CELLS && !batch.empty());
-        size_t blobs = 0;
+    auto run = [&](int li, SmallLane&, std::vector<SmallReq*>& batch, size_t m, SmallReq::Kind kind, std::string& msg) -> KzgRet {
+        const bool works = H.enter(li, batch, m, kind, msg);
+        CHECK(li % STRIDE == 0 && kind == SmallReq::BLOB_CELLS && m <= 64);
         std::vector<size_t> comp;
         for (SmallReq* x : batch) {
-            CHECK(x->kind == SmallReq::BLOB_CELLS);
-            CHECK(!x->done.load());                                  // nobody's request twice
             CHECK(x->n >= 1 && x->n <= KZG_BLOB_CELL_COALESCE_MAX_BLOBS);  // nothing above 16 blobs was ever enqueued
-            blobs += x->n;
             comp.push_back(x->n);
         }
-        CHECK(blobs == m && m <= 64);
         if (T == 1) CHECK(batch.size() == 1);
         {
             std::lock_guard<std::mutex> lk(comp_mu);
             compositions.push_back(comp);
         }
-        const uint64_t nth = launches.fetch_add(1);
-        carried += batch.size();
         carried_blobs += m;
-        uint64_t seen = largest.load();
-        while (seen < batch.size() && !largest.compare_exchange_weak(seen, batch.size())) {
-        }
         std::this_thread::sleep_for(std::chrono::microseconds(200 + 4 * m));
-        KzgRet rc = KZG_OK;
-        if (nth % 89 == 17) {  // a launch that fails: every request of it carries the error
-            rc = KZG_ERROR;
-            msg = "injected failure";
-            failed_launches++;
-        } else {
-            for (SmallReq* x : batch) {
-                // the leader collects the challenges: its own work for the blobs nobody has started, a short wait for the others
-                for (size_t b = 0; b < x->n; b++)
-                    if (!hash_one(*x, b, r_by_leader))
-                        while (x->blob_r_state[b].load(std::memory_order_acquire) != 2) std::this_thread::yield();
-                const char* why = nullptr;
-                echo(*x, &why);
-                if (why) snprintf(x->msg, sizeof x->msg, "%s", why);
-            }
+        for (SmallReq* x : batch) {
+            if (!works) break;  // (every request of it carries the error)
+            // the leader collects the challenges: its own work for the blobs nobody has started, a short wait for the others
+            for (size_t b = 0; b < x->n; b++)
+                if (!hash_one(*x, b, r_by_leader)) small_await(*x, b);
+            const char* why = nullptr;
+            echo(*x, &why);
+            if (why) snprintf(x->msg, sizeof x->msg, "%s", why);
         }
-        CHECK(in_launch[li].fetch_sub(1) == 1);
-        return rc;
+        H.leave(li);
+        return works ? KZG_OK : KZG_ERROR;
     };
     std::atomic<uint64_t> done_calls{0}, queued_calls{0}, error_calls{0}, queued_blobs{0}, hashed_ok_blobs{0};
-    auto caller = [&](int t) {
+    H.run_callers(T, [&](int t) {
         std::mt19937_64 rng(9001 + 131 * t);
         for (int k = 0; k < CALLS; k++) {
             size_t n = 1 + rng() % 16;          // 1 to 16 blobs
@@ -166,8 +115,7 @@ int main(int argc, char** argv) {
             r.p = p.data();
             r.ok = reinterpret_cast<bool*>(ok.data());
             r.err = err.data();
-            r.blob_r = r_be.data();
-            r.blob_r_state = state.data();
+            r.chal = r_be.data(), r.chal_state = state.data(), r.n_chal = n;
             r.wait_work = wait_work;
             const char* want_why = nullptr;
             for (size_t b = 0; b < n && !want_why; b++)
@@ -205,17 +153,10 @@ int main(int argc, char** argv) {
             done_calls++;
             if ((rng() & 7) == 0) std::this_thread::sleep_for(std::chrono::microseconds(rng() % 300));  // (not a pure closed loop)
         }
-    };
-    std::vector<std::thread> ths;
-    for (int t = 0; t < T; t++) ths.emplace_back(caller, t);
-    for (auto& th : ths) th.join();
-    finished = true;
-    watchdog.join();
+    });
+    std::atomic<uint64_t> &launches = H.launches, &largest = H.largest;
     CHECK(done_calls.load() == (uint64_t)T * CALLS && queued_calls.load() + locked_calls.load() == done_calls.load());
-    CHECK(Q.q.empty());
-    CHECK(Q.n_lanes <= (size_t)LANES);
-    for (size_t i = 0; i < Q.n_lanes; i++) CHECK(!Q.lanes[i]->busy);
-    CHECK(carried.load() == queued_calls.load());  // every request was carried by exactly one launch
+    H.check_idle(Q, queued_calls.load());
     CHECK(carried_blobs.load() == queued_blobs.load());
     if (!ON) CHECK(launches.load() == 0 && queued_calls.load() == 0);
     if (ON) CHECK(locked_calls.load() > 0 || T * CALLS < 100);  // (calls above the threshold did occur)
@@ -227,17 +168,15 @@ int main(int argc, char** argv) {
         CHECK(m <= 64);
     }
     CHECK(compositions.size() == launches.load());
-    CHECK(Q.launches == launches.load() && Q.requests == queued_calls.load());
-    CHECK(Q.blob_cell_launches == launches.load() && Q.blob_cell_requests == queued_calls.load() && Q.blob_cell_items == queued_blobs.load() &&
-          Q.blob_cell_max_requests == largest.load());
-    CHECK(Q.cell_launches == 0 && Q.cell_requests == 0);
+    const SmallKindStats& st = Q.stats[SmallReq::BLOB_CELLS];
+    CHECK(st.launches == launches.load() && st.requests == queued_calls.load() && st.items == queued_blobs.load() && st.max_requests == largest.load());
+    CHECK(Q.stats[SmallReq::CELLS].launches == 0 && Q.stats[SmallReq::CELLS].requests == 0);
     // no challenge computed twice (a failed launch may leave some uncomputed)
     CHECK(r_by_owner.load() + r_by_leader.load() <= queued_blobs.load() && r_by_owner.load() + r_by_leader.load() >= hashed_ok_blobs.load());
     printf("threads %d calls %llu (%llu locked) launches %llu largest %llu requests, blobs %llu, r by owner %llu by leader %llu | "
            "failed launches %llu -> %llu calls saw the error; failures %d\n",
            T, (unsigned long long)done_calls.load(), (unsigned long long)locked_calls.load(), (unsigned long long)launches.load(),
            (unsigned long long)largest.load(), (unsigned long long)queued_blobs.load(), (unsigned long long)r_by_owner.load(),
-           (unsigned long long)r_by_leader.load(), (unsigned long long)failed_launches.load(), (unsigned long long)error_calls.load(), failures.load());
-    for (size_t i = 0; i < Q.n_lanes; i++) delete Q.lanes[i];
-    return failures ? 1 : 0;
+           (unsigned long long)r_by_leader.load(), (unsigned long long)H.failed_launches.load(), (unsigned long long)error_calls.load(), failures.load());
+    return H.exit_code(Q);
 }

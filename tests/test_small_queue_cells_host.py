@@ -16,7 +16,7 @@ CSRC = os.path.join(ROOT, "kzg_rs_amd", "csrc")
 def _build(tag, flags):
     exe = os.path.join(HOST, "_small_queue_cells_%s" % tag)
     src = os.path.join(HOST, "small_queue_cells_main.cpp")
-    deps = [src, os.path.join(CSRC, "small_queue.hpp"), os.path.join(CSRC, "host_only.hpp")]
+    deps = [src, os.path.join(HOST, "small_queue_harness.hpp"), os.path.join(CSRC, "small_queue.hpp"), os.path.join(CSRC, "host_only.hpp")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-I", CSRC] + flags + ["-o", exe, src])
     return exe
