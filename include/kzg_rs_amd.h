@@ -686,6 +686,44 @@ KzgRet kzg_debug_poly_quotients(uint8_t *q_out, uint8_t *ys_out, const uint8_t *
                                 size_t n_points, size_t n_polys, const KzgSettings *s);
 /* test hook: out = { coefficients per lane, per wavefront, per workgroup tile, scalars per chunk of pairs } (csrc/poly_quotient_plan.hpp) */
 KzgRet kzg_debug_poly_quotient_tiles(size_t out[4]);
+/* EVALUATION-FORM twins of the two calls above (csrc/capi_poly.hpp): the polynomial p_k arrives as its n_evals values on the subgroup
+ * <w_n_evals>, w_n = 7^((r - 1) / n) (kzg_fr_ntt's root), evals = n_polys * n_evals * 32 bytes big-endian, in `order`:
+ * KZG_POLY_ORDER_NATURAL, element i = p_k(w_n^i), or KZG_POLY_ORDER_BRP, element i = p_k(w_n^brp(i)) - the order blobs arrive in.
+ * Per upload the device runs kzg_fr_ntt's inverse transform in place and then the coefficient-form call unchanged (quotient scan or
+ * decode, one fixed-base sum per pair); nothing returns to the host in between, and a z inside the domain needs no special case.
+ * Everything else is the coefficient-form contract: the limits and KZG_POLY_MAX_OPENINGS, the refusals and their order, the chunks,
+ * the verdict read before any sum is queued, the handle check, and the timings slots - slot [4] now holds the transform's launches
+ * with the scan's.  The differences: n_evals must be a power of two, at most the set's count (KZG_BADARGS otherwise; an unknown
+ * order too); an evaluation >= r is refused as "an evaluation is not below r"; n_evals == 0 is the zero polynomial.
+ * Measured (tools/prof/fr_ntt_probe.py, profiles/fr_ntt_probe.json; 10 warm calls, median (min - max), the two commits interleaved): one
+ * polynomial of 2^20 terms committed from evaluations 6.236 (6.122 - 6.422) ms against 6.054 (5.922 - 6.221) ms from coefficients, slot [4]
+ * 0.197 ms beside the sum's 5.146 ms; opened from evaluations 6.453 ms, slot [4] 0.331 ms; 2^16: 1.720 against 1.696 ms; 2^12: 1.091
+ * against 1.054 ms. */
+KzgRet KZG_G1_POINTS_API kzg_poly_commit_evals_prepared(uint8_t *commitments_out, const KzgG1Points *p, const uint8_t *evals,
+        size_t n_evals, int order, size_t n_polys, const KzgSettings *s);
+KzgRet KZG_G1_POINTS_API kzg_poly_compute_kzg_proofs_evals_prepared(uint8_t *proofs_out, uint8_t *ys_out, const KzgG1Points *p,
+        const uint8_t *evals, size_t n_evals, int order, const uint8_t *zs, size_t n_points, size_t n_polys, const KzgSettings *s);
+/* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
+ * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
+ * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out
+ * may equal in.  `order` names the layout of the EVALUATION side - out for the forward direction, in for the inverse -
+ * KZG_POLY_ORDER_NATURAL or KZG_POLY_ORDER_BRP (element i belongs to w_n^brp(i)); the coefficient side is always natural.
+ * On the device (csrc/fr_ntt_plan.hpp, fr_ntt_kernels.hpp): one launch up to 2^10 points, a workgroup per 2^10 elements in LDS;
+ * above, two launches of the four-step form over a scratch vector, the values reduced in between; twiddles from two tables of 1 024
+ * entries derived from 7 and r on the handle's first transform.  Vectors are cut into chunks of at most 2^23 elements (256 MB).
+ * KZG_BADARGS: n not a power of two or above KZG_FR_NTT_MAX, an unknown order, a null pointer, an element >= r (no output is
+ * promised; the handle stays usable).  n == 0 or n_polys == 0: KZG_OK, nothing written; n == 1 copies.  Any handle serves (a
+ * kzg_settings_from_tau_g2 handle needs no setup point).  The handle's lock is taken; a multi-device handle runs the call on its
+ * first device.  The same call twice gives the same bytes.  kzg_last_timings: [4] the launches, [6] the copies.
+ * Measured (tools/prof/fr_ntt_probe.py, profiles/fr_ntt_probe.json; forward, 10 warm calls, medians): one vector of 2^20 elements 1.462 ms,
+ * the two launches 0.191 ms and the copies 1.228 ms; 2^16: 0.214 ms (launches 0.053); 2^12: 0.133 ms (launch 0.044); 16 vectors: 21.775 /
+ * 1.428 / 0.203 ms, launches 2.438 / 0.155 / 0.045 ms. */
+#define KZG_FR_NTT_MAX ((size_t)1 << 20)
+#define KZG_POLY_ORDER_NATURAL 0
+#define KZG_POLY_ORDER_BRP 1
+KzgRet kzg_fr_ntt(uint8_t *out, const uint8_t *in, size_t n, size_t n_polys, int inverse, int order, const KzgSettings *s);
+/* test hook: out = { elements of a workgroup tile, passes at 2^20, n1 at 2^20, vectors per chunk at 2^20 } (csrc/fr_ntt_plan.hpp) */
+KzgRet kzg_debug_fr_ntt_plan(size_t out[4]);
 /* The group DFT over G1 (c-kzg-4844's g1_fft / g1_ifft): out[i] = sum_t w_n^(i t) points[t], n a power of two <= 4096, w_n the
  * n-th root of unity of kzg_settings_root_of_unity's table, natural order on both sides; inverse != 0: w_n^-1 and the factor
  * 1 / n.  points48 / out48: n * 48 bytes compressed, host pointers; the points are decoded and subgroup-tested as in kzg_g1_msm

@@ -167,6 +167,10 @@ def lib():
         L.kzg_poly_compute_kzg_proofs_prepared.argtypes = [u8, u8, vp, u8, sz, u8, sz, sz, vp]
         L.kzg_debug_poly_quotients.argtypes = [u8, u8, u8, sz, u8, sz, sz, vp]
         L.kzg_debug_poly_quotient_tiles.argtypes = [C.POINTER(C.c_size_t)]
+        L.kzg_fr_ntt.argtypes = [u8, u8, sz, sz, C.c_int, C.c_int, vp]
+        L.kzg_poly_commit_evals_prepared.argtypes = [u8, vp, u8, sz, C.c_int, sz, vp]
+        L.kzg_poly_compute_kzg_proofs_evals_prepared.argtypes = [u8, u8, vp, u8, sz, C.c_int, u8, sz, sz, vp]
+        L.kzg_debug_fr_ntt_plan.argtypes = [C.POINTER(C.c_size_t)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -893,6 +897,33 @@ class G1Points:
         cut = lambda buf, w: [[buf.raw[w * (k * n_points + j): w * (k * n_points + j + 1)] for j in range(n_points)] for k in range(len(polys))]
         return cut(proofs, 48), cut(ys, 32)
 
+    def commit_evals(self, evals, order="natural"):
+        """commit(polys) for polynomials given by their values (kzg_poly_commit_evals_prepared): evals = a list of rows of EQUAL length,
+        a power of two not above the set's count, row k the 32-byte big-endian values of p_k on the subgroup <w_n> (fr_ntt's root) in
+        `order`: "natural", element i = p_k(w_n^i), or "brp", element i = p_k(w_n^brp(i)), the order of a blob; what commit accepts as
+        a row is accepted here -> a list of 48-byte commitments"""
+        raw, n_evals = _poly_rows(evals)
+        out = C.create_string_buffer(48 * max(len(evals), 1))
+        _chk(lib().kzg_poly_commit_evals_prepared(out, self._h, raw, n_evals, _poly_order(order), len(evals), self._settings._h))
+        return [out.raw[48 * k: 48 * k + 48] for k in range(len(evals))]
+
+    def open_evals(self, evals, zs, order="natural"):
+        """open(polys, zs) for polynomials given by their values as in commit_evals (kzg_poly_compute_kzg_proofs_evals_prepared) ->
+        (proofs, ys); a z inside the domain is a point like any other; an evaluation or a point that is not below r raises KzgError"""
+        raw, n_evals = _poly_rows(evals)
+        if len(zs) != len(evals) or any(len(row) != len(zs[0]) for row in zs):
+            raise KzgError("InvalidBytesLength", "zs: one row of equally many points per polynomial")
+        n_points = len(zs[0]) if zs else 0
+        zraw = b"".join(bytes(z) for row in zs for z in row)
+        if len(zraw) != 32 * n_points * len(evals):
+            raise KzgError("InvalidBytesLength", "zs: 32 bytes per point")
+        n = n_points * len(evals)
+        proofs, ys = C.create_string_buffer(48 * max(n, 1)), C.create_string_buffer(32 * max(n, 1))
+        _chk(lib().kzg_poly_compute_kzg_proofs_evals_prepared(proofs, ys, self._h, raw, n_evals, _poly_order(order), zraw, n_points, len(evals),
+                                                              self._settings._h))
+        cut = lambda buf, w: [[buf.raw[w * (k * n_points + j): w * (k * n_points + j + 1)] for j in range(n_points)] for k in range(len(evals))]
+        return cut(proofs, 48), cut(ys, 32)
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
@@ -937,6 +968,36 @@ def poly_commit_prepared(point_set, polys):
 
 def poly_compute_kzg_proofs_prepared(point_set, polys, zs):
     return point_set.open(polys, zs)
+
+
+FR_NTT_MAX = 1 << 20
+POLY_ORDERS = {"natural": 0, "brp": 1}
+
+
+def _poly_order(order):
+    if order not in POLY_ORDERS:
+        raise KzgError("BadArgs", "order: \"natural\" or \"brp\"")
+    return POLY_ORDERS[order]
+
+
+def poly_commit_evals_prepared(point_set, evals, order="natural"):
+    return point_set.commit_evals(evals, order)
+
+
+def poly_compute_kzg_proofs_evals_prepared(point_set, evals, zs, order="natural"):
+    return point_set.open_evals(evals, zs, order)
+
+
+def fr_ntt(values, kzg_settings, inverse=False, order="natural"):
+    """The number-theoretic transform over Fr (kzg_fr_ntt): values = a list of vectors of EQUAL length n, a power of two <= FR_NTT_MAX,
+    each a list of 32-byte big-endian elements or one bytes-like object of n x 32 (what G1Points.commit accepts) -> a list of vectors, each
+    a list of n 32-byte canonical elements, out[k][i] = sum_t values[k][t] w_n^(i t) with w_n = 7^((r - 1) / n); inverse: w_n^-1 and the
+    factor 1 / n.  order = the layout of the evaluation side (the output of the forward direction, the input of the inverse one):
+    "natural" or "brp" (element i belongs to w_n^brp(i)); an element that is not below r raises KzgError."""
+    raw, n = _poly_rows(values)
+    out = C.create_string_buffer(max(len(raw), 1))
+    _chk(lib().kzg_fr_ntt(out, raw, n, len(values), 1 if inverse else 0, _poly_order(order), kzg_settings._h))
+    return [[out.raw[32 * (k * n + i): 32 * (k * n + i + 1)] for i in range(n)] for k in range(len(values))]
 
 
 def pairing_check(a, b, kzg_settings):

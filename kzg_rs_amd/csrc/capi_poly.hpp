@@ -11,12 +11,18 @@
 // than the set needs no zero padding.  The commit is the same with k_poly_decode in place of the scan and n_coeffs terms.
 // The verdict on a chunk's coefficients and points is read before any of ITS sums is queued; a call of one chunk - every call whose
 // pairs x n_coeffs stay within 2^23 - has queued nothing when it refuses.
+//
+// The EVALUATION-FORM twins (kzg_poly_commit_evals_prepared, kzg_poly_compute_kzg_proofs_evals_prepared) are the same calls with one
+// more step per upload: the polynomial arrives as its values on <w_n>, and the inverse transform of capi_fr_ntt.hpp runs in place on
+// d_stage, which leaves the coefficients as 32 big-endian canonical bytes exactly where the scan (or k_poly_decode) reads them.  Its
+// launches are queued after the flag word is cleared and before the scan's, inside the interval of timings slot [4].
 
 struct PolyBufs {
     DevBuf<uint8_t> d_zs, d_ys, d_out;  // per pair of a chunk: z as given | y, 32 big-endian bytes | the sums, compressed
     DevBuf<Fr> d_tsum, d_carry;         // [pair][tile]
     DevBuf<uint32_t> d_flag;
     DevBuf<G1Jac> d_sums;               // per pair
+    FrNttBufs ntt;                      // the transform's tables and scratch (capi_fr_ntt.hpp)
     KzgRet reserve(size_t n_coeffs, size_t pairs) {
         HIPCHK(d_zs.grow(32 * pairs));
         HIPCHK(d_ys.grow(32 * pairs));
@@ -32,13 +38,24 @@ static void poly_release(const KzgSettings* s) {
     delete s->poly;
     s->poly = nullptr;
 }
+static KzgRet poly_fr_ntt_bufs(const KzgSettings* s, FrNttBufs** nb_out, uint32_t** flag_out) {
+    if (!s->poly) s->poly = new (std::nothrow) PolyBufs();
+    if (!s->poly) return fail(KZG_MALLOC, "host buffers of the call");
+    HIPCHK(s->poly->d_flag.grow(1));
+    *nb_out = &s->poly->ntt;
+    *flag_out = s->poly->d_flag.p;
+    return KZG_OK;
+}
 
-// what one call asks for; zs == nullptr: the commit (a "pair" is a polynomial, n_points = 1)
+// what one call asks for; zs == nullptr: the commit (a "pair" is a polynomial, n_points = 1).  evals: `coeffs` holds the values on
+// <w_n_coeffs> in `order`, n_coeffs a power of two
 struct PolyCall {
     const uint8_t* coeffs;
     size_t n_coeffs;
     const uint8_t* zs;
     size_t n_points, n_polys;
+    bool evals = false;
+    int order = KZG_POLY_ORDER_NATURAL;
     size_t pairs() const { return n_points * n_polys; }
 };
 static_assert(PQ_MAX_OPENINGS == KZG_POLY_MAX_OPENINGS && PQ_MAX_COEFFS == KZG_G1_POINTS_MAX, "the plan's limits are the header's");
@@ -57,6 +74,10 @@ static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk
     HIPCHK(s->g1_points->d_scalars.grow(pq_quotient_scalars(c.n_coeffs, chunk)));
     *b_out = s->g1_points;
     *pb_out = s->poly;
+    if (c.evals) {
+        const KzgRet rc = fr_ntt_reserve(s, s->poly->ntt, c.n_coeffs, polys);
+        if (rc != KZG_OK) return rc;
+    }
     return s->poly->reserve(c.n_coeffs, chunk);
 }
 
@@ -70,7 +91,8 @@ static KzgRet poly_stage(const KzgSettings* s, G1PointsBufs& b, PolyBufs& pb, co
     const size_t n = c.n_coeffs, k0 = pq_poly_first(lo, c.n_points), k1 = pq_poly_end(lo, m, c.n_points);
     hipStream_t st = s->s1;
     HIPCHK(hipEventRecord(s->ev[0], st));
-    if (staged.first != k0 || staged.end != k1) {
+    const bool fresh = staged.first != k0 || staged.end != k1;
+    if (fresh) {
         HIPCHK(hipMemcpyAsync(b.d_stage.p, c.coeffs + 32 * n * k0, pq_stage_bytes(n, k1 - k0), hipMemcpyHostToDevice, st));
         staged.first = k0, staged.end = k1;
     }
@@ -78,6 +100,10 @@ static KzgRet poly_stage(const KzgSettings* s, G1PointsBufs& b, PolyBufs& pb, co
     HIPCHK(hipMemsetAsync(pb.d_flag.p, 0, 4, st));
     HIPCHK(hipEventRecord(s->ev[1], st));
     HIPCHK(hipEventRecord(s->ev[4], st));
+    if (c.evals && fresh) {  // evaluations -> coefficients, in place (what an earlier chunk left there is coefficients already)
+        const KzgRet rc = fr_ntt_queue(s, pb.ntt, b.d_stage.p, pb.d_flag.p, frntt_log2(n), k1 - k0, true, c.order);
+        if (rc != KZG_OK) return rc;
+    }
     if (c.zs) {
         const PqGrid gt = pq_grid_tiles(n, m), gc = pq_grid_carries(m);
         hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n,
@@ -99,6 +125,7 @@ static KzgRet poly_stage(const KzgSettings* s, G1PointsBufs& b, PolyBufs& pb, co
     ms[0] += t;
     elapsed(&t, s->ev[4], s->ev[5]);
     ms[1] += t;
+    if (flag & FRNTT_BAD_ELEMENT) return fail(KZG_BADARGS, "an evaluation is not below r");
     if (flag & PQ_BAD_COEFF) return fail(KZG_BADARGS, "a coefficient is not below r");
     if (flag & PQ_BAD_Z) return fail(KZG_BADARGS, "an evaluation point is not below r");
     return KZG_OK;
@@ -113,7 +140,9 @@ static void poly_identities(uint8_t* out48, size_t n) {
 static KzgRet poly_run(uint8_t* sums_out, uint8_t* ys_out, const KzgG1Points* p, const PolyCall& c, const KzgSettings* s, const char* who) {
     if (!s || !p) return fail(KZG_BADARGS, "null argument");
     if (p->owner != s) return fail(KZG_BADARGS, std::string(who) + ": the point set was prepared on another handle");
-    if (c.n_coeffs > p->n) return fail(KZG_BADARGS, std::string(who) + ": more coefficients than the set has points");
+    if (c.n_coeffs > p->n) return fail(KZG_BADARGS, std::string(who) + (c.evals ? ": more evaluations than the set has points" : ": more coefficients than the set has points"));
+    if (c.evals && c.n_coeffs && frntt_log2(c.n_coeffs) < 0) return fail(KZG_BADARGS, std::string(who) + ": n_evals must be a power of two");
+    if (c.evals && c.order != KZG_POLY_ORDER_NATURAL && c.order != KZG_POLY_ORDER_BRP) return fail(KZG_BADARGS, std::string(who) + ": unknown order");
     if (c.n_polys == 0 || c.n_points == 0) return KZG_OK;
     if (c.n_polys > KZG_POLY_MAX_OPENINGS || c.n_points > KZG_POLY_MAX_OPENINGS || c.pairs() > KZG_POLY_MAX_OPENINGS)
         return fail(KZG_BADARGS, std::string(who) + ": more than 4096 openings");
@@ -189,6 +218,17 @@ extern "C" KzgRet kzg_poly_compute_kzg_proofs_prepared(uint8_t* proofs_out, uint
                                                        size_t n_points, size_t n_polys, const KzgSettings* s) {
     if (n_points && n_polys && !zs) return fail(KZG_BADARGS, "null argument");
     return poly_run(proofs_out, ys_out, p, PolyCall{coeffs, n_coeffs, zs, n_points, n_polys}, s, "kzg_poly_compute_kzg_proofs_prepared");
+}
+
+extern "C" KzgRet kzg_poly_commit_evals_prepared(uint8_t* commitments_out, const KzgG1Points* p, const uint8_t* evals, size_t n_evals, int order, size_t n_polys,
+                                                 const KzgSettings* s) {
+    return poly_run(commitments_out, nullptr, p, PolyCall{evals, n_evals, nullptr, 1, n_polys, true, order}, s, "kzg_poly_commit_evals_prepared");
+}
+
+extern "C" KzgRet kzg_poly_compute_kzg_proofs_evals_prepared(uint8_t* proofs_out, uint8_t* ys_out, const KzgG1Points* p, const uint8_t* evals, size_t n_evals, int order,
+                                                             const uint8_t* zs, size_t n_points, size_t n_polys, const KzgSettings* s) {
+    if (n_points && n_polys && !zs) return fail(KZG_BADARGS, "null argument");
+    return poly_run(proofs_out, ys_out, p, PolyCall{evals, n_evals, zs, n_points, n_polys, true, order}, s, "kzg_poly_compute_kzg_proofs_evals_prepared");
 }
 
 // test hook (tests/test_gpu_poly_open.py): the device stage alone
