@@ -61,28 +61,6 @@ static void small_free(KzgSettings* s) {
 // the launch of one leader: `batch` = requests of one kind with `m` items in all, on lane L (not shared with anybody meanwhile)
 static KzgRet small_run_proofs(SmallLane& L, std::vector<SmallReq*>& batch, size_t m) {
     const KzgSettings* l = L.h;
-    if (m == 1) {  // nobody else was waiting: the one-proof path as it was (z, y through the pinned mirror, no gather)
-        SmallReq& r = *batch[0];
-        bool general = false, ok = false;
-        if (be_geq_r(r.z) || be_geq_r(r.y)) {  // (:360-371; kzg_verify_kzg_proof has refused these before they are queued, kzg_verify_kzg_proofs has not)
-            r.err[0] = 1;
-            r.ok[0] = false;
-            r.general[0] = 0;
-            return KZG_OK;
-        }
-        const KzgRet rc = proof_single_locked(&ok, &general, r.c, r.z, r.y, r.p, l);
-        if (rc == KZG_BADARGS) {
-            r.err[0] = 1;
-            r.ok[0] = false;
-            r.general[0] = 0;
-            return KZG_OK;
-        }
-        if (rc != KZG_OK) return rc;
-        r.err[0] = 0;
-        r.general[0] = general;
-        r.ok[0] = !general && ok;
-        return KZG_OK;
-    }
     L.c.resize(48 * m);
     L.p.resize(48 * m);
     L.z.resize(32 * m);
@@ -125,22 +103,6 @@ static KzgRet small_run_proofs(SmallLane& L, std::vector<SmallReq*>& batch, size
 
 static KzgRet small_run_blobs(SmallLane& L, std::vector<SmallReq*>& batch, size_t m) {
     const KzgSettings* l = L.h;
-    if (m == 1) {  // the one-blob path as it was: the hash runs while the blob crosses PCIe
-        SmallReq& r = *batch[0];
-        bool general = false, ok = false;
-        const KzgRet rc = blob_single_locked(&ok, &general, r.blobs, r.c, r.p, l, r.hash.get());
-        if (rc == KZG_BADARGS) {
-            r.err[0] = 1;
-            r.ok[0] = false;
-            r.general[0] = 0;
-            return KZG_OK;
-        }
-        if (rc != KZG_OK) return rc;
-        r.err[0] = 0;
-        r.general[0] = general;
-        r.ok[0] = !general && ok;
-        return KZG_OK;
-    }
     std::vector<BlobsPart> parts(batch.size());
     for (size_t k = 0; k < batch.size(); k++) parts[k] = BlobsPart{batch[k]->blobs, batch[k]->c, batch[k]->p, batch[k]->n, batch[k]->hash.get(), false, false, false};
     const KzgRet rc = blobs_parts_locked(parts.data(), parts.size(), m, l);

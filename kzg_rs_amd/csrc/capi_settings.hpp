@@ -110,8 +110,7 @@ struct KzgSettings {
     hipEvent_t ev[12] = {};
     mutable hipStream_t s_copy = nullptr;  // host -> device staging copies of the host-fed stream (made on first use)
     mutable hipStream_t s_aux = nullptr;   // the one-proof path's third stream: the subgroup test beside the pairing (made on first use)
-    mutable DevBuf<Fp> d_proof;            // ... and its device buffers: SCALARS' inputs | VERIFY3's inputs (made on first use)
-    mutable DevBuf<Fp> d_proofs, d_proofs_out;  // the same for MANY independent proofs (kzg_verify_kzg_proofs): [cap_proofs] records each
+    mutable DevBuf<Fp> d_proofs, d_proofs_out;  // ... and its device buffers: SCALARS' | VERIFY3's inputs, VERIFY3's outputs - [cap_proofs] records each (proofs_reserve)
     mutable PinnedBuf<uint8_t> h_proofs;   // ... and their pinned mirror
     mutable size_t cap_proofs = 0;
     mutable hipEvent_t ev_copy[2] = {nullptr, nullptr};
@@ -623,7 +622,6 @@ extern "C" void kzg_settings_free(KzgSettings* s) {
     (void)hipSetDevice(s->device);
     s->ws = Workspace();
     s->d_eval_scratch.release();
-    s->d_proof.release();
     s->d_proofs.release();
     s->d_proofs_out.release();
     s->h_proofs.release();

@@ -307,6 +307,14 @@ static void select_streams(const KzgSettings* s, size_t T) {
     s->s_sha = use_half ? s->s_half[0] : s->s_plain[0];
     s->s2 = use_half ? s->s_half[1] : s->s_plain[1];
 }
+// s2 is another stream until the end of a scope: launch_decode runs on s->s2 (the next select_streams resets the pair anyway)
+struct ScopedS2 {
+    const KzgSettings* const s;
+    const hipStream_t keep;
+    ScopedS2(const KzgSettings* s_, hipStream_t st) : s(s_), keep(s_->s2) { s->s2 = st; }
+    ScopedS2(const ScopedS2&) = delete;
+    ~ScopedS2() { s->s2 = keep; }
+};
 
 // A batch that still lies in HOST memory (the by-value Vec<Blob> of src/kzg_proof.rs:472-477; pageable): phase 1 brings it
 // over itself, into the staging buffers it is given as d_blobs / d_commitments / d_proofs.
@@ -751,8 +759,6 @@ extern "C" KzgRet kzg_verify_blob_kzg_proof_batch_device(bool* ok, const void* d
     return batch_device_locked(ok, d_blobs, d_commitments, d_proofs, n, s);
 }
 
-static KzgRet blob_single_locked(bool* ok, bool* general, const uint8_t* blob, const uint8_t* commitment, const uint8_t* proof, const KzgSettings* s,
-                                 hostpool::Job* job = nullptr);
 // the small-call queue of a shared handle (capi_coalesce.hpp)
 static bool small_enabled(const KzgSettings* s);
 static KzgRet small_proofs(bool* ok, uint8_t* err, uint8_t* general, const uint8_t* c, const uint8_t* z, const uint8_t* y, const uint8_t* p, size_t n,
@@ -773,7 +779,8 @@ extern "C" KzgRet kzg_verify_blob_kzg_proof_batch(bool* ok, const uint8_t* blobs
     static const size_t small_max = (size_t)std::max(0L, std::min(256L, opt_int("small_batch_pairings_max", 256)));
     // The sizes a beacon node calls this with (one blob; the 6-9 blobs of a block; up to small_max): a request in the handle's
     // small-call queue - concurrent callers share launches on pooled lanes, nobody holds the handle's lock (capi_coalesce.hpp)
-    if (small_enabled(s) && !multi_takes(s, n) && ((n == 1 && host_max >= 1) || (n >= 2 && n <= small_max && n <= host_max))) {
+    const bool small = (n == 1 && host_max >= 1) || (n >= 2 && n <= small_max && n <= host_max);
+    if (small && small_enabled(s) && !multi_takes(s, n)) {
         bool each = false;
         uint8_t err = 0, general = 0;
         const KzgRet qrc = small_blobs(&each, &err, &general, blobs, commitments, proofs, n, s);
@@ -791,15 +798,8 @@ extern "C" KzgRet kzg_verify_blob_kzg_proof_batch(bool* ok, const uint8_t* blobs
     if (multi_takes(s, n)) return multi_array_locked(ok, blobs, commitments, proofs, n, true, s);
     KzgRet rc;
     const bool queued = small_enabled(s);  // (the small forms ran above; what is left of them here is the z = tau fallback)
-    if (n == 1 && host_max >= 1 && !msm_path && !queued) {  // verify_blob_kzg_proof (:446-470, :482-489): host hash, one-proof tail
-        bool general = false;
-        if ((rc = blob_single_locked(ok, &general, blobs, commitments, proofs, s)) != KZG_OK) {
-            proof_drain(s);
-            return rc;
-        }
-        if (!general) return KZG_OK;
-    }
-    if (n >= 2 && n <= small_max && n <= host_max && !msm_path && !queued) {  // a few blobs: one pairing each, side by side (blobs_small_locked)
+    // verify_blob_kzg_proof (:446-470, :482-489) and a few blobs: host hash, one pairing each, side by side (blobs_small_locked)
+    if (small && !msm_path && !queued) {
         bool general = false;
         if ((rc = blobs_small_locked(ok, &general, blobs, commitments, proofs, n, s)) != KZG_OK) {
             proof_drain(s);
@@ -950,21 +950,18 @@ extern "C" KzgRet kzg_verify_blob_kzg_proof(bool* ok, const uint8_t* blob, const
     return kzg_verify_blob_kzg_proof_batch(ok, blob, commitment, proof, 1, s);
 }
 
-extern "C" KzgRet kzg_verify_kzg_proof_batch(bool* ok, const uint8_t* commitments, const uint8_t* zs, const uint8_t* ys,
-                                             const uint8_t* proofs, size_t n, const KzgSettings* s);
 // ONE proof, in the reference's own form (src/kzg_proof.rs:384-396): e(C - [y]G, G2) == e(pi, [tau]G2 - [z]G2).  z and y are
 // known before any point is decoded, so three chains run side by side on three streams (proof_kernels.hpp):
 //   A: k_proof_select -> SCALARS ([y]G, the 68 line triples of Q = [tau]G2 - [z]G2) ......... then VERIFY3 (the pairing)
 //   B: k_proof_decompress: the square roots of C and pi on two lanes of one wavefront -> VERIFY3's point inputs
 //   C: the full decode of both points (subgroup test: 2 x 64 doublings) - only its verdict is awaited, beside the pairing
-// Critical path max(A's SCALARS, B) + VERIFY3 instead of decode -> MSM -> pairing.  *general = true: Q is the identity
-// (z = tau: possible only for who knows the setup's secret) - its lines mean nothing, the caller takes the general path.
+// Critical path max(A's SCALARS, B) + VERIFY3 instead of decode -> MSM -> pairing.  Q the identity (z = tau: possible only for
+// who knows the setup's secret): its lines mean nothing, the caller takes the general path.
+// One proof is a launch of m = 1 of the m-proof forms below (ProofsLaunch).
 struct ProofStreams {
     hipStream_t sa, sb, sc;
 };
-// the buffers and streams of the one-proof path, made on first use; the pinned mirror (w.h_buf.p) holds
-//   [0, 64) z | y little-endian (verify_kzg_proof)   [64, 160) C | pi   [160, 168) status of the decompression
-//   [176, 184) status of the full decode   [1024, 1408) VERIFY3's eight outputs
+// the streams of the one-proof path, made on first use
 static KzgRet proof_reserve(ProofStreams& ps, const KzgSettings* s) {
     KzgRet rc = ws_reserve(s, 1, 1, STAGE_BLOBS);
     if (rc != KZG_OK) return rc;
@@ -975,7 +972,6 @@ static KzgRet proof_reserve(ProofStreams& ps, const KzgSettings* s) {
     // batches/s at T = 8 and 414 at T = 16 (10 and 39 ms per call); without it 1 270 and 1 310 - 1 920 and 2 270 with 16 queues.
     select_streams(s, (size_t)-1);
     s->ws.kstamps_valid = false;  // (no launch group on this handle: the decode pass of these paths does not stamp)
-    HIPCHK(s->d_proof.grow(SCALARS_INPUTS + VERIFY3_INPUTS));
     const bool one_stream = !s->s_plain[1];  // option single_stream: everything in sequence (profiling)
     // A lane of the small-call queue runs chain C (the subgroup test) BEHIND chain B on B's stream: the square roots end at
     // ~0.65 ms and the test at ~1.5 ms, still before A's pairing (~1.7 ms), and a lane then holds two streams instead of three -
@@ -991,121 +987,12 @@ static KzgRet proof_reserve(ProofStreams& ps, const KzgSettings* s) {
     ps.sc = one_stream ? ps.sa : two_streams ? ps.sb : s->s_aux;
     return KZG_OK;
 }
-// B and C: the two square roots -> VERIFY3's point inputs (event ev[6]); the full decode for the subgroup verdict
-static KzgRet proof_points_launch(const ProofStreams& ps, const uint8_t* commitment, const uint8_t* proof, const KzgSettings* s) {
-    Workspace& w = s->ws;
-    uint8_t* const h = w.h_buf.p;
-    memcpy(h + 64, commitment, 48);
-    memcpy(h + 112, proof, 48);
-    uint32_t* const h_pre = reinterpret_cast<uint32_t*>(h + 160);
-    uint32_t* const h_full = reinterpret_cast<uint32_t*>(h + 176);
-    h_pre[0] = h_pre[1] = h_full[0] = h_full[1] = G1_INVALID;
-    Fp* const d_v3in = s->d_proof.p + SCALARS_INPUTS;
-    hipLaunchKernelGGL(k_proof_decompress, dim3(1), dim3(64), 64 * PARK_UINT4_PER_THREAD * sizeof(uint4), ps.sb, h + 64, h + 112, 1, d_v3in, h_pre);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->ev[6], ps.sb));
-    struct RestoreS2 {
-        const KzgSettings* s;
-        hipStream_t keep;
-        ~RestoreS2() { s->s2 = keep; }
-    } restore{s, s->s2};
-    s->s2 = ps.sc;
-    KzgRet rc = launch_decode(s, h + 64, h + 112, 1, /*behind_sha=*/false);
-    if (rc != KZG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(h_full, w.d_pflag.p, 8, hipMemcpyDeviceToHost, ps.sc));
-    return KZG_OK;
-}
-// A: the scalars' chain from z and y (8 little-endian limbs each; pinned host or device memory; ordered behind what stream
-// sa already holds), then the pairing once the points are there; waits, and reads the verdicts
-static KzgRet proof_tail_locked(bool* ok, bool* general, const ProofStreams& ps, const uint32_t* z, const uint32_t* y, const KzgSettings* s) {
-    Workspace& w = s->ws;
-    uint8_t* const h = w.h_buf.p;
-    Fp* const d_scal_in = s->d_proof.p;
-    Fp* const d_v3in = s->d_proof.p + SCALARS_INPUTS;
-    Fp* const h_out = reinterpret_cast<Fp*>(h + 1024);
-    hipLaunchKernelGGL(k_proof_select, dim3(1), dim3(128), 0, ps.sa, z, y, 0u, s->t->d_fixed_base.p, s->t->d_tau4.p, d_scal_in);
-    KzgRet rc = run_program2(s->t->scalars, d_scal_in, nullptr, d_v3in + 6, 1, ps.sa);
-    if (rc != KZG_OK) return rc;
-    if (ps.sb != ps.sa) HIPCHK(hipStreamWaitEvent(ps.sa, s->ev[6], 0));
-    HIPCHK(hipEventRecord(s->ev[4], ps.sa));
-    if ((rc = run_program2(s->t->verify3, d_v3in, s->t->d_prep29.p, h_out, 1, ps.sa)) != KZG_OK) return rc;  // the eight outputs go straight into the mirror
-    HIPCHK(hipEventRecord(s->ev[9], ps.sa));
-    HIPCHK(hipStreamSynchronize(ps.sa));
-    if (ps.sc != ps.sa) HIPCHK(hipStreamSynchronize(ps.sc));
-    elapsed(&s->timings[3], s->ev[4], s->ev[9]);
-    elapsed(&s->timings[0], s->ev[0], s->ev[9]);
-    // the reference's order of errors: commitment (:372), then proof (:378); an encoding the decompression accepts can
-    // still fail the subgroup test of the full decode
-    const uint32_t* h_pre = reinterpret_cast<const uint32_t*>(h + 160);
-    const uint32_t* h_full = reinterpret_cast<const uint32_t*>(h + 176);
-    for (int i = 0; i < 2; i++)
-        if (h_pre[i] == G1_INVALID || h_full[i] == G1_INVALID) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
-    const uint32_t* o = reinterpret_cast<const uint32_t*>(h_out);
-    uint32_t any = 0, zq = 0;
-    for (int i = 0; i < 72; i++) any |= o[i];
-    for (int i = 72; i < 96; i++) zq |= o[i];
-    if (!zq) {
-        *general = true;
-        return KZG_OK;
-    }
-    *ok = any == 0;
-    return KZG_OK;
-}
 static void proof_drain(const KzgSettings* s) {  // nothing of the call stays in flight behind an error (the first message is kept)
     const std::string msg = g_err;
     for (hipStream_t st : {s->s_plain[0], s->s_plain[1], s->s_aux})
         if (st) (void)hipStreamSynchronize(st);
     (void)hipGetLastError();
     g_err = msg;
-}
-
-static KzgRet proof_single_locked(bool* ok, bool* general, const uint8_t* commitment, const uint8_t* z_be, const uint8_t* y_be, const uint8_t* proof,
-                                  const KzgSettings* s) {
-    *general = false;
-    ProofStreams ps{};
-    KzgRet rc = proof_reserve(ps, s);
-    if (rc != KZG_OK) return rc;
-    uint8_t* const h = s->ws.h_buf.p;
-    reverse32(h, z_be);
-    reverse32(h + 32, y_be);
-    HIPCHK(hipEventRecord(s->ev[0], ps.sa));
-    if ((rc = proof_points_launch(ps, commitment, proof, s)) != KZG_OK) return rc;
-    return proof_tail_locked(ok, general, ps, reinterpret_cast<const uint32_t*>(h), reinterpret_cast<const uint32_t*>(h + 32), s);
-}
-
-// ONE blob from host memory (KzgProof::verify_blob_kzg_proof, src/kzg_proof.rs:446-470; the n == 1 branch of the batch form,
-// :482-489): the point chains start at once; the host hashes the blob (65 us) while the blob crosses PCIe; z follows as 32
-// bytes; the evaluation (one wavefront) gives y on the device; then the one-proof tail.  *general as in proof_single_locked.
-static KzgRet blob_single_locked(bool* ok, bool* general, const uint8_t* blob, const uint8_t* commitment, const uint8_t* proof, const KzgSettings* s,
-                                 hostpool::Job* job) {
-    *general = false;
-    ProofStreams ps{};
-    KzgRet rc = proof_reserve(ps, s);
-    if (rc != KZG_OK) return rc;
-    Workspace& w = s->ws;
-    uint8_t* const h = w.h_buf.p;
-    HIPCHK(hipEventRecord(s->ev[0], ps.sa));
-    if ((rc = proof_points_launch(ps, commitment, proof, s)) != KZG_OK) return rc;
-    HIPCHK(hipMemsetAsync(w.d_status.p, 0, 4, ps.sa));
-    HIPCHK(hipMemcpyAsync(w.d_stage_blobs.p, blob, BLOB_BYTES, hipMemcpyHostToDevice, ps.sa));  // (pageable: the call returns when the bytes have left)
-    if (job) {  // (a caller that queued behind other calls hashed its blob while it waited: capi_coalesce.hpp)
-        hostpool::finish(*job);
-        memcpy(h + 192, job->z_le, 32);
-    } else host_blob_challenge(h + 192, blob, commitment);
-    HIPCHK(hipMemcpyAsync(w.d_z.p, h + 192, 32, hipMemcpyHostToDevice, ps.sa));
-    if ((rc = launch_evaluate(s, w.d_stage_blobs.p, w.d_z.p, w.d_y.p, w.d_status.p, 1)) != KZG_OK) return rc;  // (on s->s1 = sa)
-    HIPCHK(hipMemcpyAsync(h + 224, w.d_status.p, 4, hipMemcpyDeviceToHost, ps.sa));
-    rc = proof_tail_locked(ok, general, ps, reinterpret_cast<const uint32_t*>(w.d_z.p), reinterpret_cast<const uint32_t*>(w.d_y.p), s);
-    // A runtime failure inside the tail is reported as what it is: the mirrors below are only meaningful once the streams were
-    // synchronised (before that they hold the G1_INVALID they were initialised with, or are still being written), and an
-    // infrastructure failure must never look like the reference's Err(BadArgs) for an invalid input.
-    if (rc != KZG_OK && rc != KZG_BADARGS) return rc;
-    // the reference parses the commitment (:453), the blob (:454: a non-canonical element is BadArgs), then the proof (:455)
-    const uint32_t* h_pre = reinterpret_cast<const uint32_t*>(h + 160);
-    const uint32_t* h_full = reinterpret_cast<const uint32_t*>(h + 176);
-    if (h_pre[0] == G1_INVALID || h_full[0] == G1_INVALID) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
-    if (*reinterpret_cast<const uint32_t*>(h + 224) != 0) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");  // (sic) :38-40
-    return rc;
 }
 
 // MANY INDEPENDENT proofs, each with its own pairing and its own result ("verify_kzg_proof x N, each with its
@@ -1122,6 +1009,7 @@ struct ProofsLaunch {
     uint8_t *h_c, *h_p;
     uint32_t *h_pre, *h_full;
     Fp *h_out, *d_scal_in, *d_v3in;
+    Fp* out;  // where VERIFY3 writes: one proof's eight outputs go straight into the mirror (no copy behind the pairing), more to d_proofs_out
 };
 static KzgRet proofs_reserve(ProofStreams& ps, ProofsLaunch& pl, size_t m, int stage, const KzgSettings* s) {
     KzgRet rc = proof_reserve(ps, s);
@@ -1148,6 +1036,7 @@ static KzgRet proofs_reserve(ProofStreams& ps, ProofsLaunch& pl, size_t m, int s
     pl.h_out = reinterpret_cast<Fp*>(pl.h_full + 2 * m);
     pl.d_scal_in = s->d_proofs.p;
     pl.d_v3in = s->d_proofs.p + (size_t)SCALARS_INPUTS * m;
+    pl.out = m == 1 ? pl.h_out : s->d_proofs_out.p;
     return KZG_OK;
 }
 // streams B and C for m proofs: the square roots (two lanes per proof) -> VERIFY3's point inputs (event ev[6]); the full
@@ -1163,12 +1052,7 @@ static KzgRet proofs_points_launch(const ProofStreams& ps, const ProofsLaunch& p
                        pl.d_v3in, pl.h_pre);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[6], ps.sb));
-    struct RestoreS2 {
-        const KzgSettings* s;
-        hipStream_t keep;
-        ~RestoreS2() { s->s2 = keep; }
-    } restore{s, s->s2};
-    s->s2 = ps.sc;
+    const ScopedS2 on_sc(s, ps.sc);
     const KzgRet rc = launch_decode(s, pl.h_c, pl.h_p, m, /*behind_sha=*/false);
     if (rc != KZG_OK) return rc;
     HIPCHK(hipMemcpyAsync(pl.h_full, s->ws.d_pflag.p, 8 * m, hipMemcpyDeviceToHost, ps.sc));
@@ -1183,8 +1067,8 @@ static KzgRet proofs_tail_locked(const ProofStreams& ps, const ProofsLaunch& pl,
     if (rc != KZG_OK) return rc;
     if (ps.sb != ps.sa) HIPCHK(hipStreamWaitEvent(ps.sa, s->ev[6], 0));
     HIPCHK(hipEventRecord(s->ev[4], ps.sa));
-    if ((rc = run_program2(s->t->verify3, pl.d_v3in, s->t->d_prep29.p, s->d_proofs_out.p, (int)m, ps.sa)) != KZG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(pl.h_out, s->d_proofs_out.p, sizeof(Fp) * VERIFY3_OUTPUTS * m, hipMemcpyDeviceToHost, ps.sa));
+    if ((rc = run_program2(s->t->verify3, pl.d_v3in, s->t->d_prep29.p, pl.out, (int)m, ps.sa)) != KZG_OK) return rc;
+    if (pl.out != pl.h_out) HIPCHK(hipMemcpyAsync(pl.h_out, pl.out, sizeof(Fp) * VERIFY3_OUTPUTS * m, hipMemcpyDeviceToHost, ps.sa));
     HIPCHK(hipEventRecord(s->ev[9], ps.sa));
     HIPCHK(hipStreamSynchronize(ps.sa));
     if (ps.sc != ps.sa) HIPCHK(hipStreamSynchronize(ps.sc));
@@ -1218,14 +1102,23 @@ static KzgRet proofs_independent_locked(bool* ok_out, uint8_t* err, const uint8_
         KzgRet rc = proofs_reserve(ps, pl, m, STAGE_CP, s);
         if (rc != KZG_OK) return rc;
         uint8_t* const h_zy = reinterpret_cast<uint8_t*>(pl.h_zy);
+        size_t refused = 0;
         for (size_t i = 0; i < m; i++) {
             const size_t g = first + i;
             err[g] = be_geq_r(zs + 32 * g) || be_geq_r(ys + 32 * g);  // (:360-371) - the instance still runs, its result is not looked at
+            refused += err[g];
             reverse32(h_zy + 64 * i, zs + 32 * g);
             reverse32(h_zy + 64 * i + 32, ys + 32 * g);
         }
+        if (refused == m) {  // nothing to launch for (the usual case: a lone refused tuple in the small-call queue)
+            std::fill(ok_out + first, ok_out + first + m, false);
+            continue;
+        }
         HIPCHK(hipEventRecord(s->ev[0], ps.sa));
         if ((rc = proofs_points_launch(ps, pl, commitments + 48 * first, proofs + 48 * first, s)) != KZG_OK) return rc;
+        // A failure of the runtime inside the tail goes back as what it is, before any mirror is read (here and in blobs_parts_locked):
+        // a mirror that was never synchronised still holds the G1_INVALID it was initialised with, and an infrastructure failure must
+        // never look like the reference's Err(BadArgs) for an invalid input.
         if ((rc = proofs_tail_locked(ps, pl, pl.h_zy, pl.h_zy + 8, 16u, s)) != KZG_OK) return rc;
         for (size_t i = 0; i < m; i++) {
             const size_t g = first + i;
@@ -1265,12 +1158,14 @@ static KzgRet blobs_parts_locked(BlobsPart* parts, size_t n_parts, size_t m, con
     uint32_t* const h_status = pl.h_zy + 8 * m;
     std::vector<hostpool::JobRef> own(n_parts);
     hostpool::JoinOnExit joined;  // (every HIPCHK / rc return below leaves with the posted jobs finished: they read the callers' blobs)
+    // one blob that nobody has hashed yet: this thread hashes it (65 us) behind the blob's copy - the pool's round trip costs more
+    const bool inline_hash = m == 1 && !parts[0].job;
     size_t off = 0;
     for (size_t k = 0; k < n_parts; k++) {
         BlobsPart& pt = parts[k];
         memcpy(pl.h_c + 48 * off, pt.commitments, 48 * pt.n);
         memcpy(pl.h_p + 48 * off, pt.proofs, 48 * pt.n);
-        if (!pt.job) {  // hashed from here: the pool's workers start at once, this thread joins them after the copies below
+        if (!pt.job && !inline_hash) {  // hashed from here: the pool's workers start at once, this thread joins them after the copies below
             own[k] = hostpool::make(h_z + 32 * off, pt.blobs, pt.commitments, pt.n);
             static const size_t threads = (size_t)std::max(1L, std::min(16L, opt_int("host_threads", 16)));
             joined.add(own[k]);
@@ -1291,7 +1186,8 @@ static KzgRet blobs_parts_locked(BlobsPart* parts, size_t n_parts, size_t m, con
         if (parts[k].job) {
             hostpool::finish(*parts[k].job);
             memcpy(h_z + 32 * off, parts[k].job->z_le, 32 * parts[k].n);
-        } else hostpool::finish(*own[k]);
+        } else if (inline_hash) host_blob_challenge(h_z, parts[k].blobs, parts[k].commitments);
+        else hostpool::finish(*own[k]);
         off += parts[k].n;
     }
     HIPCHK(hipMemcpyAsync(w.d_z.p, h_z, 32 * m, hipMemcpyHostToDevice, ps.sa));
@@ -1368,7 +1264,7 @@ extern "C" KzgRet kzg_verify_kzg_proofs(bool* ok_out, uint8_t* err_out, const ui
 
 extern "C" KzgRet kzg_verify_kzg_proof(bool* ok, const uint8_t commitment[48], const uint8_t z[32], const uint8_t y[32],
                                        const uint8_t proof[48], const KzgSettings* s) try {
-    // src/kzg_proof.rs:353-397.  One proof at a time takes the reference's own equation (proof_single_locked); option
+    // src/kzg_proof.rs:353-397.  One proof at a time takes the reference's own equation (a launch of one proof); option
     // proof_path=msm sends it through the batch form with the single scalar r^0 = 1 instead (round 3's path; A/B, cross-check):
     // e(pi, [tau]G2) == e(C - [y]G + [z]pi, G2)  <=>  e(pi, [tau - z]G2) == e(C - [y]G, G2)
     if (!ok || !s) return fail(KZG_BADARGS, "null argument");
@@ -1376,29 +1272,43 @@ extern "C" KzgRet kzg_verify_kzg_proof(bool* ok, const uint8_t commitment[48], c
     static const bool msm_path = opt_is("proof_path", "msm");
     if (!msm_path) {
         if (be_geq_r(z) || be_geq_r(y)) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");  // (sic) :360-371
-        bool general = false;
+        bool each = false, general = false;
+        uint8_t err = 0;
         if (small_enabled(s)) {  // a request in the shared handle's small-call queue: concurrent callers share launches (capi_coalesce.hpp)
-            bool each = false;
-            uint8_t err = 0, gen = 0;
+            uint8_t gen = 0;
             const KzgRet rc = small_proofs(&each, &err, &gen, commitment, z, y, proof, 1, s);
             if (rc != KZG_OK) return rc;
-            if (err) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
             general = gen != 0;
-            if (!general) *ok = each;
         } else {
             std::lock_guard<std::mutex> lk(s->mu);
             HIPCHK(hipSetDevice(s->device));
-            const KzgRet rc = proof_single_locked(ok, &general, commitment, z, y, proof, s);
+            std::vector<size_t> gen;
+            const KzgRet rc = proofs_independent_locked(&each, &err, commitment, z, y, proof, 1, s, gen);
             if (rc != KZG_OK) {
                 proof_drain(s);
                 return rc;
             }
+            general = !gen.empty();
         }
-        if (!general) return KZG_OK;
+        if (err) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
+        if (!general) {
+            *ok = each;
+            return KZG_OK;
+        }
     }
     return kzg_verify_kzg_proof_batch(ok, commitment, z, y, proof, 1, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (the queue's request list; nothing is thrown across the C ABI)
+}
+
+// n independent verdicts as verify_kzg_proof_batch's ONE answer (the reasoning at blobs_small_locked): Err(BadArgs) if any tuple's
+// is; *decided = false if some z_i = tau (the combined path decides); else *ok = their conjunction
+static KzgRet proofs_conjunction(bool* ok, bool* decided, const bool* each, const uint8_t* err, bool any_general, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (err[i]) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
+    *decided = !any_general;
+    if (*decided) *ok = std::all_of(each, each + n, [](bool b) { return b; });
+    return KZG_OK;
 }
 
 // KzgProof::verify_kzg_proof_batch (src/kzg_proof.rs:399-444) over byte inputs: n (commitment, z, y, proof) tuples checked
@@ -1417,27 +1327,17 @@ extern "C" KzgRet kzg_verify_kzg_proof_batch(bool* ok, const uint8_t* commitment
     // blobs_small_locked) - 1.7 ms against the 2.9 ms of decode -> MSM -> pairing.  option small_batch_pairings_max=0: always combined
     static const size_t small_max = (size_t)std::max(0L, std::min(256L, opt_int("small_batch_pairings_max", 256)));
     static const bool msm_path = opt_is("proof_path", "msm");
-    bool queued = false;
+    KzgRet rc;
+    bool queued = false, decided = false;
     if (n >= 2 && n <= small_max && small_enabled(s)) {  // ... as a request in the shared handle's small-call queue (capi_coalesce.hpp)
         std::vector<uint8_t> res(3 * n);
-        bool* const each = reinterpret_cast<bool*>(res.data());
-        const KzgRet qrc = small_proofs(each, res.data() + n, res.data() + 2 * n, commitments, zs, ys, proofs, n, s);
-        if (qrc != KZG_OK) return qrc;
-        bool all = true, any_general = false;
-        for (size_t i = 0; i < n; i++) {
-            if (res[n + i]) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
-            any_general = any_general || res[2 * n + i];
-            all = all && each[i];
-        }
-        if (!any_general) {
-            *ok = all;
-            return KZG_OK;
-        }
+        if ((rc = small_proofs(reinterpret_cast<bool*>(res.data()), res.data() + n, res.data() + 2 * n, commitments, zs, ys, proofs, n, s)) != KZG_OK) return rc;
+        const bool any_general = std::any_of(res.begin() + 2 * n, res.end(), [](uint8_t g) { return g != 0; });
+        if ((rc = proofs_conjunction(ok, &decided, reinterpret_cast<bool*>(res.data()), res.data() + n, any_general, n)) != KZG_OK || decided) return rc;
         queued = true;  // (some z_i = tau: the combined path below decides)
     }
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
-    KzgRet rc;
     if (n >= 2 && n <= small_max && !msm_path && !queued) {
         std::vector<uint8_t> verdicts(2 * n);
         std::vector<size_t> general;
@@ -1446,15 +1346,7 @@ extern "C" KzgRet kzg_verify_kzg_proof_batch(bool* ok, const uint8_t* commitment
             proof_drain(s);
             return rc;
         }
-        if (general.empty()) {  // (some z_i = tau: the combined path below decides)
-            bool all = true;
-            for (size_t i = 0; i < n; i++) {
-                if (verdicts[n + i]) return fail(KZG_BADARGS, "Failed to parse G1Affine from bytes");
-                all = all && each[i];
-            }
-            *ok = all;
-            return KZG_OK;
-        }
+        if ((rc = proofs_conjunction(ok, &decided, each, verdicts.data() + n, !general.empty(), n)) != KZG_OK || decided) return rc;
     }
     select_streams(s, n);
     if ((rc = ws_reserve(s, n, 1, STAGE_CP)) != KZG_OK) return rc;
@@ -1479,16 +1371,12 @@ extern "C" KzgRet kzg_verify_kzg_proof_batch(bool* ok, const uint8_t* commitment
     // caller's memory is pageable), the MSM waits for it through an event, and the point flags are looked at after the
     // pairing (flagged points have identity table rows: the work on them is wasted, not wrong).
     const bool chained = n <= LATENCY_MAX_BLOBS;
-    struct RestoreS2 {  // the chained form aliases s2 to s1 for this call only
-        const KzgSettings* s;
-        hipStream_t keep;
-        ~RestoreS2() { s->s2 = keep; }
-    } restore_s2{s, s->s2};
+    // nothing runs beside the decode of the chained form: one stream, no event between the kernels - s2 is s1 for this call only
+    const ScopedS2 on_s1(s, chained ? s->s1 : s->s2);
     if (chained) {
         uint8_t* h_cp = w.h_buf.p + 72 * n;
         memcpy(h_cp, commitments, 48 * n);
         memcpy(h_cp + 48 * n, proofs, 48 * n);
-        s->s2 = s->s1;  // nothing runs beside the decode here: one stream, no event between the kernels (select_streams resets the pair)
         if ((rc = launch_decode(s, h_cp, h_cp + 48 * n, n, /*behind_sha=*/false)) != KZG_OK) return rc;
         HIPCHK(hipMemcpyAsync(h_pflag, w.d_pflag.p, 8 * n, hipMemcpyDeviceToHost, s->s1));
     } else {
