@@ -703,6 +703,57 @@ KzgRet KZG_G1_POINTS_API kzg_poly_commit_evals_prepared(uint8_t *commitments_out
         size_t n_evals, int order, size_t n_polys, const KzgSettings *s);
 KzgRet KZG_G1_POINTS_API kzg_poly_compute_kzg_proofs_evals_prepared(uint8_t *proofs_out, uint8_t *ys_out, const KzgG1Points *p,
         const uint8_t *evals, size_t n_evals, int order, const uint8_t *zs, size_t n_points, size_t n_polys, const KzgSettings *s);
+/* BATCHED OPENINGS (csrc/capi_poly_batch.hpp): every polynomial of the call is opened at EVERY point of the call, and each point gets
+ * one proof - what a PLONK-, Marlin- or Sonic-style prover sends per evaluation point.  zs and gammas: n_points * 32 bytes big-endian
+ * each, gamma_j the batching factor of point j (from the caller's transcript).  For point j, with f_j = sum_k gamma_j^k p_k (k = 0 the
+ * first polynomial, gamma^0 = 1 also for gamma = 0):
+ *   ys_out[k * n_points + j] = p_k(z_j)   (32 bytes big-endian canonical; the layout of kzg_poly_compute_kzg_proofs_prepared; may be NULL)
+ *   proofs_out[j] = sum_i q_i * P_i, q = (f_j - f_j(z_j)) / (X - z_j)   (48 bytes)
+ * so that proofs_out[j] opens sum_k gamma_j^k C_k at z_j to sum_k gamma_j^k ys_out[k][j].  On the device (csrc/poly_fold_kernels.hpp):
+ * per upload one streaming fold of the coefficients (k_poly_fold: acc = a_k + gamma acc over the polynomials, last to first), the
+ * n_polys * n_points values from the tile sums of the quotient scan and one finishing launch (k_poly_eval_tiles), then the quotient scan
+ * of kzg_poly_compute_kzg_proofs_prepared on the n_points folded polynomials and ONE fixed-base sum per point instead of one per
+ * (polynomial, point) pair; nothing returns to the host in between.
+ * The contract is that of kzg_poly_compute_kzg_proofs_prepared: coeffs = n_polys * n_coeffs * 32 bytes big-endian, lowest degree first,
+ * host pointers; n_coeffs at most the set's count and `s` the handle the set was prepared on (KZG_BADARGS otherwise); n_polys * n_points
+ * at most KZG_POLY_MAX_OPENINGS; n_polys == 0 or n_points == 0: KZG_OK, nothing written; n_coeffs == 0: the identity 0xC0 00 .. 00 as
+ * every proof and y = 0; n_coeffs == 1: the identity as every proof and y = a_0; KZG_BADARGS, with no output promised and the handle
+ * usable afterwards, for a null pointer, a coefficient or a z that is >= r, in the same order - and for a gamma that is >= r
+ * ("a batching factor is not below r").  The polynomials are staged in chunks of whole polynomials of at most 2^23 scalars (256 MB),
+ * visited from the last to the first; the points in groups of at most 2^23 / n_coeffs (8 at 2^20 coefficients).  The verdict on a
+ * group's elements is read before any of its sums is queued, so a call of one group has queued no sum when it refuses.  The same call
+ * twice gives the same bytes.  The handle's lock is taken; the call runs on the set's device (the first device of a multi-device
+ * handle).  kzg_last_timings afterwards: [2] the sums, [4] fold + evaluations + scan (+ transform), [6] the copies.
+ * kzg_poly_compute_kzg_batch_proofs_evals_prepared: the same call for polynomials given by their values on <w_n_evals> in `order`, as
+ * kzg_poly_compute_kzg_proofs_evals_prepared takes them (n_evals a power of two; "an evaluation is not below r"): the inverse transform
+ * runs in place on each staged upload.
+ * Measured (tools/prof/poly_batch_open_probe.py, profiles/poly_batch_open_probe.json; 10 warm calls each, median (min - max), interleaved
+ * with kzg_poly_compute_kzg_proofs_prepared on the same polynomials at the same point, whole calls from host memory): 16 polynomials of
+ * 2^20 coefficients at one point 16.233 (16.083 - 16.675) ms against 96.458 (95.991 - 97.167) ms - the sums 5.499 against 84.319 ms, slot
+ * [4] 0.912 ms, the copies 9.540 ms in both; 4 polynomials: 8.452 against 24.484 ms; 16 at two points: 22.349 against 182.368 ms; 2^16:
+ * 2.057 against 6.165 ms (m = 4) and 2.487 against 23.009 ms (m = 16); 2^12: 1.259 against 3.635 ms and 1.310 against 12.840 ms. */
+KzgRet KZG_G1_POINTS_API kzg_poly_compute_kzg_batch_proofs_prepared(uint8_t *proofs_out, uint8_t *ys_out, const KzgG1Points *p,
+        const uint8_t *coeffs, size_t n_coeffs, const uint8_t *zs, const uint8_t *gammas, size_t n_points, size_t n_polys,
+        const KzgSettings *s);
+KzgRet KZG_G1_POINTS_API kzg_poly_compute_kzg_batch_proofs_evals_prepared(uint8_t *proofs_out, uint8_t *ys_out, const KzgG1Points *p,
+        const uint8_t *evals, size_t n_evals, int order, const uint8_t *zs, const uint8_t *gammas, size_t n_points, size_t n_polys,
+        const KzgSettings *s);
+/* The verifier of the batched openings: ok_out[j] is what kzg_verify_kzg_proof(sum_k gamma_j^k C_k, z_j, sum_k gamma_j^k y_kj, proofs[j])
+ * answers.  commitments: n_polys * 48 bytes; zs, gammas: n_points * 32; ys: n_polys * n_points * 32, ys[k * n_points + j] = the claimed
+ * p_k(z_j); proofs: n_points * 48; host pointers; n_polys * n_points at most KZG_POLY_MAX_OPENINGS; n_points == 0: KZG_OK, nothing
+ * written.  KZG_BADARGS, for the whole call, for what kzg_verify_kzg_proof refuses on the same bytes - a z or y that is >= r, a
+ * commitment or proof that does not decode or lies outside G1 - and for a gamma that is >= r.  Per point: the powers of gamma_j and the
+ * folded value from one kernel launch, the commitments' sum by kzg_g1_msm, the pairing by kzg_verify_kzg_proof; the host does no field
+ * arithmetic.  Any handle of the right tau serves (kzg_settings_from_tau_g2 included). */
+KzgRet kzg_verify_kzg_batch_proofs(bool *ok_out, const uint8_t *commitments, const uint8_t *zs, const uint8_t *gammas,
+        const uint8_t *ys, const uint8_t *proofs, size_t n_polys, size_t n_points, const KzgSettings *s);
+/* test hook: the device stage of the batched openings alone - q_out[point][i], i < n_coeffs (the last one 0), the quotient of the folded
+ * polynomial; ys_out[poly][point]; fold_ys_out[point] = f_j(z_j); 32 big-endian bytes each; ys_out and fold_ys_out may be NULL; the
+ * limits and refusals of the call; any handle serves, no point set is needed */
+KzgRet kzg_debug_poly_batch_quotients(uint8_t *q_out, uint8_t *ys_out, uint8_t *fold_ys_out, const uint8_t *coeffs, size_t n_coeffs,
+        const uint8_t *zs, const uint8_t *gammas, size_t n_points, size_t n_polys, const KzgSettings *s);
+/* test hook: out = { elements per workgroup of the fold, polynomials per chunk at n_coeffs = 6145, scalars per chunk, 0 } (csrc/poly_fold_plan.hpp) */
+KzgRet kzg_debug_poly_fold_plan(size_t out[4]);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

@@ -171,6 +171,11 @@ def lib():
         L.kzg_poly_commit_evals_prepared.argtypes = [u8, vp, u8, sz, C.c_int, sz, vp]
         L.kzg_poly_compute_kzg_proofs_evals_prepared.argtypes = [u8, u8, vp, u8, sz, C.c_int, u8, sz, sz, vp]
         L.kzg_debug_fr_ntt_plan.argtypes = [C.POINTER(C.c_size_t)]
+        L.kzg_poly_compute_kzg_batch_proofs_prepared.argtypes = [u8, u8, vp, u8, sz, u8, u8, sz, sz, vp]
+        L.kzg_poly_compute_kzg_batch_proofs_evals_prepared.argtypes = [u8, u8, vp, u8, sz, C.c_int, u8, u8, sz, sz, vp]
+        L.kzg_verify_kzg_batch_proofs.argtypes = [C.POINTER(C.c_bool), u8, u8, u8, u8, u8, sz, sz, vp]
+        L.kzg_debug_poly_batch_quotients.argtypes = [u8, u8, u8, u8, sz, u8, u8, sz, sz, vp]
+        L.kzg_debug_poly_fold_plan.argtypes = [C.POINTER(C.c_size_t)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -517,6 +522,19 @@ class KzgProof:
         _chk(lib().kzg_verify_kzg_proof(C.byref(ok), commitment_bytes.data, z_bytes.data, y_bytes.data, proof_bytes.data,
                                         kzg_settings._h))
         return bool(ok.value)
+
+    @staticmethod
+    def verify_kzg_batch_proofs(commitments, zs, gammas, ys, proofs, kzg_settings):
+        """The verifier of G1Points.open_batch (kzg_verify_kzg_batch_proofs): commitments[n_polys] and proofs[n_points] as Bytes48, zs and
+        gammas [n_points] as Bytes32, ys[n_polys][n_points] as Bytes32 -> a list of n_points bool, entry j what
+        verify_kzg_proof(sum_k gammas[j]^k commitments[k], zs[j], sum_k gammas[j]^k ys[k][j], proofs[j]) answers."""
+        n_polys, n_points = len(commitments), len(zs)
+        if len(gammas) != n_points or len(proofs) != n_points or len(ys) != n_polys or any(len(row) != n_points for row in ys):
+            raise KzgError("InvalidBytesLength", "one z, gamma and proof per point, one row of n_points values per commitment")
+        ok = (C.c_bool * max(n_points, 1))()
+        _chk(lib().kzg_verify_kzg_batch_proofs(ok, b"".join(c.data for c in commitments), b"".join(z.data for z in zs), b"".join(g.data for g in gammas),
+                                               b"".join(y.data for row in ys for y in row), b"".join(p.data for p in proofs), n_polys, n_points, kzg_settings._h))
+        return [bool(ok[j]) for j in range(n_points)]
 
     @staticmethod
     def verify_kzg_proof_batch(commitments, zs, ys, proofs, kzg_settings):
@@ -924,6 +942,35 @@ class G1Points:
         cut = lambda buf, w: [[buf.raw[w * (k * n_points + j): w * (k * n_points + j + 1)] for j in range(n_points)] for k in range(len(evals))]
         return cut(proofs, 48), cut(ys, 32)
 
+    def _open_batch(self, rows, zs, gammas, order=None):
+        raw, n = _poly_rows(rows)
+        zraw, graw = b"".join(bytes(z) for z in zs), b"".join(bytes(g) for g in gammas)
+        n_points, n_polys = len(zs), len(rows)
+        if len(gammas) != n_points:
+            raise KzgError("InvalidBytesLength", "gammas: one batching factor per point")
+        if len(zraw) != 32 * n_points or len(graw) != 32 * n_points:
+            raise KzgError("InvalidBytesLength", "zs, gammas: 32 bytes each")
+        proofs, ys = C.create_string_buffer(48 * max(n_points, 1)), C.create_string_buffer(32 * max(n_points * n_polys, 1))
+        if order is None:
+            _chk(lib().kzg_poly_compute_kzg_batch_proofs_prepared(proofs, ys, self._h, raw, n, zraw, graw, n_points, n_polys, self._settings._h))
+        else:
+            _chk(lib().kzg_poly_compute_kzg_batch_proofs_evals_prepared(proofs, ys, self._h, raw, n, _poly_order(order), zraw, graw, n_points, n_polys,
+                                                                        self._settings._h))
+        return ([proofs.raw[48 * j: 48 * j + 48] for j in range(n_points)],
+                [[ys.raw[32 * (k * n_points + j): 32 * (k * n_points + j + 1)] for j in range(n_points)] for k in range(n_polys)])
+
+    def open_batch(self, polys, zs, gammas):
+        """batched openings (kzg_poly_compute_kzg_batch_proofs_prepared): EVERY polynomial of polys (as commit takes them) is opened at every
+        point of zs, one proof per point: with gammas[j] the batching factor of point j (32-byte big-endian values, as many as points) and
+        f_j = sum_k gammas[j]^k polys[k], proofs[j] opens f_j at zs[j] -> (proofs[n_points], ys[n_polys][n_points]), ys[k][j] = p_k(z_j); a
+        coefficient, a point or a batching factor that is not below r raises KzgError"""
+        return self._open_batch(polys, zs, gammas)
+
+    def open_batch_evals(self, evals, zs, gammas, order="natural"):
+        """open_batch for polynomials given by their values as in commit_evals (kzg_poly_compute_kzg_batch_proofs_evals_prepared)"""
+        _poly_order(order)
+        return self._open_batch(evals, zs, gammas, order)
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
@@ -968,6 +1015,14 @@ def poly_commit_prepared(point_set, polys):
 
 def poly_compute_kzg_proofs_prepared(point_set, polys, zs):
     return point_set.open(polys, zs)
+
+
+def poly_compute_kzg_batch_proofs_prepared(point_set, polys, zs, gammas):
+    return point_set.open_batch(polys, zs, gammas)
+
+
+def poly_compute_kzg_batch_proofs_evals_prepared(point_set, evals, zs, gammas, order="natural"):
+    return point_set.open_batch_evals(evals, zs, gammas, order)
 
 
 FR_NTT_MAX = 1 << 20

@@ -23,6 +23,8 @@ struct PolyBufs {
     DevBuf<uint32_t> d_flag;
     DevBuf<G1Jac> d_sums;               // per pair
     FrNttBufs ntt;                      // the transform's tables and scratch (capi_fr_ntt.hpp)
+    DevBuf<uint8_t> d_gammas, d_fold, d_fys, d_bys;  // the batched openings (capi_poly_batch.hpp): per point gamma | f[point][n_coeffs] | f_j(z_j); y[poly][point] of the call
+    DevBuf<uint8_t> d_vin, d_vout;                   // their verifier: gammas | ys as given; the powers of gamma per point | the folded values
     KzgRet reserve(size_t n_coeffs, size_t pairs) {
         HIPCHK(d_zs.grow(32 * pairs));
         HIPCHK(d_ys.grow(32 * pairs));
