@@ -7,9 +7,11 @@
 static KzgRet launch_evaluate(const KzgSettings* s, const void* d_blobs, const Fr* d_z, Fr* d_y, uint32_t* d_status, size_t T, bool alone = false,
                               bool stamp = false) {
     unsigned long long* const kt = stamp && s->ws.d_ktime.p ? s->ws.d_ktime.p + 4 : nullptr;
-    // 576 bytes per blob between the three kernels (fr_kernels.hpp), 1 024 blobs at least; callers hold the handle's lock
-    // (growing waits for the kernels that may still read the old one)
-    HIPCHK(s->d_eval_scratch.grow((size_t)EVAL_SCRATCH_WORDS * std::max<size_t>(T, 1024)));
+    // 504 + 6 144 bytes per blob between the three kernels (fr_kernels.hpp), 1 024 blobs at least; callers hold the handle's lock
+    // (growing waits for the kernels that may still read the old one).  A DevBuf never shrinks: the handle keeps the largest call's
+    // scratch for good - 6.8 MB for 1 024 blobs, 1.74 GB after a 262 144-blob launch group (0.13 GB before the nodes went through it),
+    // against the 34 GB of blobs such a group reads.
+    HIPCHK(s->d_eval_scratch.grow(eval_scratch_words(std::max<size_t>(T, 1024))));
     const unsigned per_lane = (unsigned)((T + 63) / 64);
     hipLaunchKernelGGL(k_eval_powers, dim3(per_lane), dim3(64), 0, s->s1, d_z, s->d_eval_scratch.p, (int)T);
     // A launch that leaves CUs free asks for enough (unused) dynamic LDS that no CU takes a second workgroup: the dispatcher
@@ -31,7 +33,7 @@ static KzgRet launch_evaluate(const KzgSettings* s, const void* d_blobs, const F
     }
     hipLaunchKernelGGL(k_blob_evaluate_t<true>, dim3(eval_blocks), dim3(64 * EVAL_BLOBS_PER_BLOCK), spread_lds, s->s1,
                        (const uint8_t*)d_blobs, EvalTables{s->t->d_eval_a.p, s->t->d_eval_b.p, s->t->d_eval_c.p}, s->d_eval_scratch.p, d_status, (int)T, kt);
-    hipLaunchKernelGGL(k_eval_finish, dim3(per_lane), dim3(64), 0, s->s1, s->d_eval_scratch.p, d_y, (int)T);
+    hipLaunchKernelGGL(k_eval_finish, dim3(per_lane), dim3(64), 0, s->s1, s->d_eval_scratch.p, s->t->d_M29.p, d_y, (int)T);
     return KZG_OK;
 }
 

@@ -11,6 +11,7 @@
 // Lazy reduction.  406 - 381 = 25 spare bits: values may grow to ~6000 p before a product of two of them leaves the
 // range in which the Montgomery output stays below 2p (a b < 2^406 p), so nothing is ever reduced conditionally:
 //   fp29_mul / fp29_sqr : inputs NORMALISED (limbs 0..12 < 2^29) and below 6000 p;  output normalised, below 2p.
+//   fp29_mul2           : a b + c d (or a b + 2 c^2) under one reduction, same output; bounds at its definition.
 //   fp29_add            : limb-wise + carry propagation (normalised output), value = a + b.
 //   fp29_sub<E>(a, b)   : a + 2^E p - b, for b normalised with value(b) <= 2^(E-1) p; the constant is stored with
 //                         every limb below the top one pre-biased by 2^29, so no limb ever borrows.
@@ -135,6 +136,64 @@ FP29_FN Fp29 fp29_mul_impl(const Fp29& a, const Fp29& b) {
 }
 FP29_FN Fp29 fp29_mul(const Fp29& a, const Fp29& b) { return fp29_mul_impl<false>(a, b); }
 FP29_FN Fp29 fp29_sqr(const Fp29& a) { return fp29_mul_impl<true>(a, a); }
+
+// (a b + c d) 2^-406 mod p under ONE Montgomery reduction: 196 + 196 product multiply-adds and 196 for the reduction, where
+// two products take 2 x (196 + 196) - for sums of two products that are only ever used as the sum.  K = 0: a b + c d.
+// K = 2: a b + 2 c^2 (d ignored; the doubling's form, the only square form in use), the square's cross products taken
+// once against a shifted operand as in fp29_sqr: 196 + 105 + 196.  There is no subtraction: a term that enters negatively is negated BEFORE the product (fp29_neg /
+// fp29_sub, which add a multiple of p), so every column is a sum of non-negative terms.
+// Bounds.  Inputs NORMALISED (limbs 0..12 < 2^29; the top limb is below 2^29 as well for every value below 2^27 p).
+//   columns: at most 14 limb products below 2^58 for each of a b, c d and the reduction, 3 * 14 * 2^58 < 2^63.4; with
+//     K = 2 the square's column counts four times the 14 * 2^58 / 2 of its distinct pairs: (1 + 2 + 1) * 14 * 2^58 =
+//     2^63.81; the carry from the column before adds less than 2^35.  Every 64-bit column stays below 2^64.
+//   value: the output is below (a b + c d) / 2^406 + p, so it is normalised and below 2p while
+//     value(a) value(b) + value(c) value(d) [or K value(c)^2] < 2^406 p  (2^406 > 2^25 p: e.g. each product below 2^24 p^2).
+template <int K>
+FP29_FN Fp29 fp29_mul2_impl(const Fp29& a, const Fp29& b, const Fp29& c, const Fp29& d) {
+    static_assert(K == 0 || K == 2, "a b + c d or a b + 2 c^2");
+    uint64_t acc = 0;
+    uint32_t m[14], mod[14], cx[14];
+    Fp29 out;
+#pragma unroll
+    for (int i = 0; i < 14; i++) {
+        mod[i] = fp29_opaque(cp29::FP29_MOD[i]);
+        cx[i] = K ? c.l[i] << K : 0u;  // the cross products' factor 2 K
+    }
+    const uint32_t pinv = fp29_opaque(FP29_INV);
+#pragma unroll
+    for (int k = 0; k < 28; k++) {
+        const int lo = k < 14 ? 0 : k - 13, hi = k < 14 ? k : 13;
+#pragma unroll
+        for (int i = lo; i <= hi; i++) acc += (uint64_t)a.l[i] * b.l[k - i];
+        if (K) {
+#pragma unroll
+            for (int i = lo; i <= hi; i++) {
+                const int j = k - i;
+                if (i < j) acc += (uint64_t)c.l[i] * cx[j];
+                else if (i == j) acc += (uint64_t)c.l[i] * (c.l[i] << (K - 1));
+            }
+        } else {
+#pragma unroll
+            for (int i = lo; i <= hi; i++) acc += (uint64_t)c.l[i] * d.l[k - i];
+        }
+#pragma unroll
+        for (int i = lo; i <= hi; i++)
+            if (k >= 14 || i < k) acc += (uint64_t)m[i] * mod[k - i];
+        if (k < 14) {
+            m[k] = ((uint32_t)acc * pinv) & FP29_MASK;
+            acc += (uint64_t)m[k] * mod[0];  // the low 29 bits are now zero
+        } else {
+            out.l[k - 14] = (uint32_t)acc & FP29_MASK;
+        }
+        acc >>= 29;
+    }
+    out.l[13] |= (uint32_t)acc << 29;  // zero for in-range inputs (output < 2p < 2^382)
+    return out;
+}
+FP29_FN Fp29 fp29_mul2(const Fp29& a, const Fp29& b, const Fp29& c, const Fp29& d) { return fp29_mul2_impl<0>(a, b, c, d); }
+// a b + K c^2, K = 2
+template <int K>
+FP29_FN Fp29 fp29_mul_add_sqr(const Fp29& a, const Fp29& b, const Fp29& c) { return fp29_mul2_impl<K>(a, b, c, c); }
 
 // t = a product output (normalised, below 2p): is t = 0 mod p, i.e. t in {0, p} ?
 FP29_FN bool fp29_is_zero_mod_p(const Fp29& t) {

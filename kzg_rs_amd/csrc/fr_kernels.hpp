@@ -22,12 +22,12 @@
 // same field element, bit for bit.
 //
 // Mapping: ONE WAVEFRONT PER BLOB.  Lane t owns the 64 consecutive elements 64t..64t+63
-// (2 KiB of the blob), folds them depth-first with a 6-entry LDS stack (levels 1..6), then the
-// last 6 levels run across lanes with ds_bpermute shuffles.  No barriers beyond the one that
-// publishes the powers of z.
+// (2 KiB of the blob) and folds them depth-first with an LDS stack; the last 6 levels, which
+// would fill 32, 16, .. 1 lanes of the wavefront, run one lane per blob in k_eval_finish.
 #pragma once
 #include "field.hpp"
 #include "fr29.hpp"
+#include "fr29_eval_fold.hpp"
 #include "sha256.hpp"
 
 namespace kzg {
@@ -457,12 +457,6 @@ __device__ __forceinline__ Fr29 fr29_load(const Fr29Mem* p) {
     r.l[8] = p->l[8];
     return r;
 }
-__device__ __forceinline__ Fr29 fr29_shfl_xor(const Fr29& a, int mask) {
-    Fr29 r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.l[i] = __shfl_xor((int)a.l[i], mask, 64);
-    return r;
-}
 // M29[j] = roots[j] R' , DM29[j] = roots[j] R'^2  (R' = 2^261; values below 2r, limbs below 2^29), from the 8x32 table M
 __global__ void k_roots_tables29(const Fr* __restrict__ M, Fr29Mem* __restrict__ M29, Fr29Mem* __restrict__ DM29) {
     int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -482,8 +476,8 @@ __global__ void k_roots_tables29(const Fr* __restrict__ M, Fr29Mem* __restrict__
 // DM29 the 64 lanes of a load hit 64 different cache lines 3 KiB apart: 1.7 MB of L2->L1 fills per blob for 160 KB
 // of entries.)  Slots:  q (0..31)            leaf pair q of every lane          DM29[2 (32 lane + q)]
 //                       32 + 32 - (32 >> (L-1)) + (q >> L)   in-lane merge at level L = 1..5   M29[((32 lane + q) >> (L-1)) & ~1]
-//                       63 + (L - 6)         cross-lane merge at level L = 6..11  M29[(lane >> (L-6)) & ~1]
-constexpr int EVAL_SLOTS = 69;
+// (levels 6..11 are k_eval_finish's: there an entry is the same for every lane, read straight from M29)
+constexpr int EVAL_SLOTS = 63;
 struct EvalTables {
     const uint4 *a, *b;   // limbs 0..3, 4..7
     const uint32_t* c;    // limb 8
@@ -494,28 +488,18 @@ __global__ void k_eval_tables(const Fr29Mem* __restrict__ M29, const Fr29Mem* __
     const Fr29Mem* e;
     if (slot < 32) {
         e = DM29 + 2 * (32 * lane + slot);
-    } else if (slot < 63) {
+    } else {
         int L = 1, rel = slot - 32;
         while (rel >= (32 >> L)) { rel -= 32 >> L; L++; }
         const int q = (rel << L) | ((1 << L) - 1);
         e = M29 + (((32 * lane + q) >> (L - 1)) & ~1);
-    } else {
-        e = M29 + ((lane >> (slot - 63)) & ~1);
     }
     ta[slot * 64 + lane] = make_uint4(e->l[0], e->l[1], e->l[2], e->l[3]);
     tb[slot * 64 + lane] = make_uint4(e->l[4], e->l[5], e->l[6], e->l[7]);
     tc[slot * 64 + lane] = e->l[8];
 }
-__device__ __forceinline__ Fr29 eval_table_load(const EvalTables& t, int slot, int lane) {
-    const uint4 a = t.a[slot * 64 + lane], b = t.b[slot * 64 + lane];
-    Fr29 r;
-    r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-    r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-    r.l[8] = t.c[slot * 64 + lane];
-    return r;
-}
 
-// The same entry through buffer descriptors (wave-uniform 128-bit resources in SGPRs): the per-lane part of the address is ONE
+// A table entry through buffer descriptors (wave-uniform 128-bit resources in SGPRs): the per-lane part of the address is ONE
 // 32-bit register that never changes (lane * 16, lane * 4), the slot travels in the scalar offset - no 64-bit address
 // pairs in VGPRs and no vector address arithmetic in the loop.
 struct EvalRsrc {
@@ -532,14 +516,24 @@ __device__ __forceinline__ Fr29 eval_table_load(const EvalRsrc& t, int slot, uin
     return r;
 }
 
-// Evaluation = k_eval_powers -> k_blob_evaluate -> k_eval_finish.  The serial parts of a blob's evaluation (13 squarings
-// of z before the tree, 4 products after it) would run on one lane of the blob's wavefront at the price of 64: they are
-// taken out into one-lane-per-blob kernels, with 576 bytes of scratch per blob in between:
-//     [ Z[0..12] = z^(2^L) R' ; Z[13] = z R'^2 (for plain operands) ; tail: N0 , S R' ]   16 x 9 words
+// Evaluation = k_eval_powers -> k_blob_evaluate -> k_eval_finish.  The parts of a blob's evaluation that do not fill the
+// blob's wavefront (13 squarings of z before the tree; after the in-lane tree the six levels that merge 64 nodes into one,
+// the sum of the 64 partial sums and 4 products) would run at the price of 64 lanes for 32, 16, .. 1 useful ones: they
+// are taken out into one-lane-per-blob kernels.  Scratch in between, for T blobs (eval_scratch_words):
+//     per blob     [ Z[0..12] = z^(2^L) R' ; Z[13] = z R'^2 (for plain operands) ]   14 x 9 words
+//     then, per blob, [node | partial sum][lane 0..63] as 48-byte Fr29Mem entries: 6 144 bytes per blob, written once and
+//     read once (the blob itself is 131 072).  The tree kernel's wavefront writes its blob's 3 KiB runs with two b128
+//     and one b32 store per lane and kind; a lane of k_eval_finish walks its blob's entries in order, 128-byte lines
+//     that stay in the L1 for the 2.7 entries each holds.  (Planes [lane][limb][blob] over 64 blobs, coalesced on the
+//     READ side, made the tree kernel 1 152 four-byte stores to as many lines per blob - as many L2 requests as reading
+//     the blob - and cost it more than the six levels it shed: docs/lab_notebook.md 12.)
 // z_in: plain little-endian limbs (any value < 2^256; reduced mod r here, like scalar_from_bytes_unchecked)
 // y_out: plain little-endian canonical limbs.  status[b] |= 1 when a blob element is >= r
 // (src/kzg_proof.rs:36-41 -> KzgError::BadArgs).
-constexpr int EVAL_SCRATCH_WORDS = 16 * 9;
+constexpr int EVAL_SCRATCH_WORDS = 14 * 9;
+constexpr int EVAL_NODE_WORDS = 2 * 64 * 12;  // per blob: 64 nodes, then 64 partial sums (Fr29Mem)
+__host__ __device__ inline size_t eval_nodes_offset(size_t T) { return (T * EVAL_SCRATCH_WORDS + 3) & ~(size_t)3; }  // 16-byte aligned
+__host__ __device__ inline size_t eval_scratch_words(size_t T) { return eval_nodes_offset(T) + T * EVAL_NODE_WORDS; }
 __global__ __launch_bounds__(64) void k_eval_powers(const Fr* __restrict__ z_in, uint32_t* __restrict__ scratch, int T) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= T) return;
@@ -554,16 +548,50 @@ __global__ __launch_bounds__(64) void k_eval_powers(const Fr* __restrict__ z_in,
         Z[l] = z;
     }
 }
-// tail: N0 (the tree's root) and S R' (the sum of the blob's elements), both below 3r with limbs below 2^29
-__global__ __launch_bounds__(64) void k_eval_finish(const uint32_t* __restrict__ scratch, Fr* __restrict__ y_out, int T) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= T) return;
-    const Fr29* Z = reinterpret_cast<const Fr29*>(scratch + (size_t)b * EVAL_SCRATCH_WORDS);
-    const Fr29 n = Z[14], sm = Z[15];
-    // N = z N0 - (z^4096 - 1) S = z N0 + S - z^4096 S
-    const Fr29 x = fr29_mul(sm, Z[12]);
-    const Fr29 nw = fr29_sub_biased(fr29_add(fr29_mul(n, Z[0]), sm), x);
-    const Fr29 y29 = fr29_mul(nw, fr29_const(c29::FR29_INV4096_PLAIN));  // (N R')(1/4096) R'^-1 = N/4096, below 2r
+// One lane per blob: the 64 partial sums, levels 6..11 of the tree over the 64 nodes the tree kernel left (63 two-product
+// merges, fr29_eval_fold.hpp) and the tail.  The node stack and the blob's z^(2^L) live in LDS, one column per lane (the
+// level is a loop variable: in registers the arrays would go to scratch memory); the root-of-unity entry of a merge is
+// the same for all 64 blobs of the wavefront - a scalar load from M29, not a per-lane one.
+__global__ __launch_bounds__(64) void k_eval_finish(const uint32_t* __restrict__ scratch, const Fr29Mem* __restrict__ M29, Fr* __restrict__ y_out, int T) {
+    __shared__ uint32_t zs[6][9][64], stack[6][9][64];  // zs: Z[6..11] of every lane's blob
+    const int lane = threadIdx.x, b = blockIdx.x * 64 + lane;
+    if (b >= T) return;  // no barrier below: a lane only ever touches its own column of the LDS
+    const uint32_t* Z = scratch + (size_t)b * EVAL_SCRATCH_WORDS;
+    const Fr29Mem* nodes = reinterpret_cast<const Fr29Mem*>(scratch + eval_nodes_offset(T)) + (size_t)b * 128;
+    for (int L = 6; L < 12; L++)
+#pragma unroll
+        for (int i = 0; i < 9; i++) zs[L - 6][i][lane] = Z[L * 9 + i];
+    struct Stack {
+        uint32_t (*s)[9][64];
+        int lane;
+        __device__ Fr29 get(int l) const {
+            Fr29 r;
+#pragma unroll
+            for (int i = 0; i < 9; i++) r.l[i] = s[l][i][lane];
+            return r;
+        }
+        __device__ void put(int l, const Fr29& n) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) s[l][i][lane] = n.l[i];
+        }
+    } st{stack, lane};
+    const Fr29 sum = eval_sum_psums([&](int k) { return fr29_load(nodes + 64 + k); });
+    const Fr29 n0 = eval_fold_nodes([&](int k) { return fr29_load(nodes + k); },
+                                    [&](int L) {
+                                        Fr29 r;
+#pragma unroll
+                                        for (int i = 0; i < 9; i++) r.l[i] = zs[L - 6][i][lane];
+                                        return r;
+                                    },
+                                    [&](int j) {  // j is uniform: scalar loads
+                                        Fr29 r;
+#pragma unroll
+                                        for (int i = 0; i < 9; i++) r.l[i] = M29[j].l[i];
+                                        return r;
+                                    },
+                                    st);
+    const Fr29* Zp = reinterpret_cast<const Fr29*>(Z);
+    const Fr29 y29 = eval_tail(n0, sum, Zp[0], Zp[12]);  // below 2r
     Fr y;
     fr29_to_words(y.l, y29);
     y_out[b] = FrF::reduce_once(y);
@@ -683,38 +711,23 @@ __global__ __launch_bounds__(256, 3) void k_blob_evaluate_t(const uint8_t* __res
             stack_c[level - 2][lane] = n.l[8];
         }
     }
-    // n = N0_{6,lane}; fold across lanes
-    for (int L = 6; L < 12; L++) {
-        int sh = L - 6;
-        Fr29 other = fr29_shfl_xor(n, 1 << sh);
-        bool left = ((lane >> sh) & 1) == 0;  // node lane >> sh at level L
-        Fr29 na, nb;
-#pragma unroll
-        for (int i = 0; i < 9; i++) {
-            na.l[i] = left ? n.l[i] : other.l[i];
-            nb.l[i] = left ? other.l[i] : n.l[i];
-        }
-        const Fr29 sum = fr29_add(na, nb), dif = fr29_sub_biased4(na, nb);
-        n = fr29_mul2(sum, Z[L], dif, eval_table_load(tab, 63 + sh, lane));
+    // n = N0_{6,lane} (limbs < 2^29, below 1.2 r) and psum (normalised at the end of the last iteration; a plain integer
+    // below 64 r) go to the blob's entries: levels 6..11 and the sum are k_eval_finish's.  The descriptor spans the
+    // blob's entries only - nothing outside them can be written.
+    {
+        uint32_t* const mine = scratch + eval_nodes_offset((size_t)T) + (size_t)blob_u * EVAL_NODE_WORDS;
+        const __amdgpu_buffer_rsrc_t rs_n = __builtin_amdgcn_make_buffer_rsrc(mine, 0, EVAL_NODE_WORDS * 4, 0x00020000);
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const uint32_t entry = (uint32_t)lane * 48u;
+        auto put = [&](const Fr29& v, int kind_off) {
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{v.l[0], v.l[1], v.l[2], v.l[3]}, rs_n, entry, kind_off, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{v.l[4], v.l[5], v.l[6], v.l[7]}, rs_n, entry + 16, kind_off, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(v.l[8], rs_n, entry + 32, kind_off, 0);
+        };
+        put(n, 0);
+        put(psum, 64 * 48);
     }
-    // S R' per lane (below 2r), then the sum over the 64 lanes (below 128 r), normalised every second step
-    Fr29 sm = fr29_mul(psum, fr29_const(c29::FR29_R2));
-    for (int sh = 1; sh < 64; sh <<= 1) {
-        sm = fr29_add(sm, fr29_shfl_xor(sm, sh));
-        if (sh & 0x2A) sm = fr29_normalize(sm);  // after steps 2, 4, 6
-    }
-    unsigned long long any_bad = __ballot(bad);
-    sm = fr29_mul(sm, fr29_const(c29::FR29_ONE));  // same residue, value back below 3r (every lane holds the same sum)
-    if (lane < 9) {
-        uint32_t vn = n.l[0], vs = sm.l[0];
-#pragma unroll
-        for (int i = 1; i < 9; i++) {
-            vn = lane == i ? n.l[i] : vn;
-            vs = lane == i ? sm.l[i] : vs;
-        }
-        my[14 * 9 + lane] = vn;
-        my[15 * 9 + lane] = vs;
-    }
+    const unsigned long long any_bad = __ballot(bad);
     if (lane == 0 && any_bad) atomicOr(&status[blob_u], 1u);
     kstamp_out(ktime);
 }

@@ -1,8 +1,10 @@
 // g1_29_formulas.hpp - the G1 point formulas over the radix-2^29 field of fp29.hpp: doubling, general and mixed addition
 // with every special case, -phi.  Part of g1_29.hpp, kept apart because it is plain C++ (host + device): the exact code
 // the kernels run is checked on the CPU against an integer model of the curve, with inputs at the documented bounds
-// (tests/test_g1_29_host.py).  Same formulas as g1.hpp (dbl-2009-l, add-2007-bl, madd-2007-bl); every value is
-// normalised (limbs < 2^29) and carries a static bound in multiples of p, noted beside each line.
+// (tests/test_g1_29_host.py, tests/test_fp29_mul2_host.py).  Same formulas as g1.hpp (dbl-2009-l, add-2007-bl, madd-2007-bl),
+// with every Y3 - a difference of two products used nowhere else - taken under ONE Montgomery reduction (fp29_mul2: the
+// subtrahend's factor is negated before the product); every value is normalised (limbs < 2^29) and carries a static bound
+// in multiples of p, noted beside each line.
 #pragma once
 #include "fp29.hpp"
 
@@ -24,35 +26,37 @@ FP29_FN G1Jac29 g1j29_identity() {
     return r;
 }
 
-// dbl-2009-l (a = 0): 2M + 5S.  Inputs below 2^10 p; outputs X < 130p, Y < 34p, Z < 4p.  Z = 0 mod p stays so.
-// The linear steps are taken limb-wise on un-normalised words and carried ONCE per result (8 carry passes instead of
-// 14): every intermediate word stays below 2^32 by the bounds noted, the biases are 16p / 128p with limbs boosted by
-// 2^31 / 2^30 so that no limb borrows (tools/gen_constants.py).
+// dbl-2009-l (a = 0) with its 2M + 5S regrouped as 2M + 3S + one product-plus-square under a shared reduction:
+// D = 2 ((X + B)^2 - A - C) is taken as the product 4 X B, which leaves C = B^2 with one use, 8C in Y3 - and
+// -Y3 = E (X3 - D) + 8 B^2 = E (X3 - D) + 2 (2B)^2 is ONE fp29_mul_add_sqr (497 multiply-adds for the 301 + 301 + 392 of
+// (X + B)^2, C and E (D - X3) less the 392 of X B).  Inputs below 2^10 p; outputs X < 130p, Y <= 4p, Z < 4p.
+// Z = 0 mod p stays so.  The linear steps are taken limb-wise on un-normalised words and carried ONCE per result: every
+// intermediate word stays below 2^32 by the bounds noted, the bias is 128p with limbs boosted by 2^30 so that no limb
+// borrows (tools/gen_constants.py).
 FP29_FN G1Jac29 g1j29_dbl(const G1Jac29& p) {
     G1Jac29 r;
     r.z = fp29_dbl(fp29_mul(p.y, p.z));                                 // < 4p; first, so that p.z and then p.y die early
-    const Fp29 B = fp29_sqr(p.y), C = fp29_sqr(B), A = fp29_sqr(p.x);  // < 2p, limbs < 2^29
-    const Fp29 t = fp29_sqr(fp29_add(p.x, B));                          // < 2p
-    Fp29 D, E, X, C8;
+    const Fp29 B = fp29_sqr(p.y), A = fp29_sqr(p.x);                    // < 2p, limbs < 2^29
+    const Fp29 XB = fp29_mul(p.x, B);                                   // < 2p
+    Fp29 D, E, X;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
-        D.l[i] = ((t.l[i] - A.l[i] - C.l[i]) << 1) + cp29::FP29_BIASX4[i];  // 2t + 16p - 2A - 2C: words < 2^30 + 2^29 + 2^31
-        E.l[i] = (A.l[i] << 1) + A.l[i];                                   // 3A: words < 2^31
-        C8.l[i] = C.l[i] << 3;                                             // 8C: words < 2^32
+        D.l[i] = XB.l[i] << 2;             // 4 X B: words < 2^31
+        E.l[i] = (A.l[i] << 1) + A.l[i];   // 3A: words < 2^31
     }
-    D = fp29_normalize(D);    // < 20p
-    E = fp29_normalize(E);    // < 6p
-    C8 = fp29_normalize(C8);  // < 16p
+    D = fp29_normalize(D);  // < 8p
+    E = fp29_normalize(E);  // < 6p
     const Fp29 F = fp29_sqr(E);  // < 2p
 #pragma unroll
     for (int i = 0; i < 14; i++) X.l[i] = F.l[i] + cp29::FP29_BIASW7[i] - (D.l[i] << 1);  // F + 128p - 2D: words < 2^31
     r.x = fp29_normalize(X);                                            // < 130p
-    r.y = fp29_sub<5>(fp29_mul(E, fp29_sub<9>(D, r.x)), C8);            // E (D + 512p - X3) + 32p - 8C < 34p
+    // E (X3 + 64p - D) + 2 (2B)^2 = -Y3 mod p:  6p * 194p + 2 (4p)^2 < 2^11 p^2, far inside fp29_mul2's range
+    r.y = fp29_neg<2>(fp29_mul_add_sqr<2>(E, fp29_sub<6>(r.x, D), fp29_dbl(B)));  // 4p - (a value below 2p): in (2p, 4p]
     return r;
 }
 
 // general addition with every special case (identity operands, P + P, P - P).  Inputs below 2^10 p;
-// outputs X < 14p, Y < 6p, Z < 2p (or a dbl / operand passed through).
+// outputs X < 14p, Y < 2p, Z < 2p (or a dbl / operand passed through).
 FP29_FN G1Jac29 g1j29_add(const G1Jac29& p, const G1Jac29& q) {
     const Fp29 Z1Z1 = fp29_sqr(p.z), Z2Z2 = fp29_sqr(q.z);
     if (fp29_is_zero_mod_p(Z1Z1)) return q;
@@ -72,14 +76,13 @@ FP29_FN G1Jac29 g1j29_add(const G1Jac29& p, const G1Jac29& q) {
     const Fp29 HHH = fp29_mul(H, HH), V = fp29_mul(U1, HH);
     const Fp29 Rr = fp29_sub<2>(S2, S1);                                              // < 6p
     r.x = fp29_sub<3>(fp29_sub<2>(fp29_sqr(Rr), HHH), fp29_dbl(V));                   // RR + 4p - HHH + 8p - 2V < 14p
-    const Fp29 T = fp29_mul(S1, HHH);
-    r.y = fp29_sub<2>(fp29_mul(Rr, fp29_sub<5>(V, r.x)), T);                          // < 6p
+    r.y = fp29_mul2(Rr, fp29_sub<5>(V, r.x), fp29_neg<2>(S1), HHH);                   // Rr (V + 32p - X3) + (4p - S1) HHH: 6p * 34p + 4p * 2p; < 2p
     return r;
 }
 
 // mixed addition p + q, q affine and not the identity: 8M + 3S instead of 12M + 4S (madd-2007-bl without the
 // doubling tricks).  p below X < 256p, Y < 256p, Z < 2^10 p (every output of dbl / add / this function is); q below 8p.
-// Outputs X < 14p, Y < 6p, Z < 2p (or a dbl / q passed through).
+// Outputs X < 14p, Y < 2p, Z < 2p (or a dbl / q passed through).
 FP29_FN G1Jac29 g1j29_add_affine(const G1Jac29& p, const G1Aff29& q) {
     const Fp29 Z1Z1 = fp29_sqr(p.z);
     if (fp29_is_zero_mod_p(Z1Z1)) {
@@ -103,8 +106,7 @@ FP29_FN G1Jac29 g1j29_add_affine(const G1Jac29& p, const G1Aff29& q) {
     const Fp29 HHH = fp29_mul(H, HH), V = fp29_mul(p.x, HH);
     const Fp29 Rr = fp29_sub<9>(S2, p.y);                                             // < 514p
     r.x = fp29_sub<3>(fp29_sub<2>(fp29_sqr(Rr), HHH), fp29_dbl(V));                   // < 14p
-    const Fp29 T = fp29_mul(p.y, HHH);
-    r.y = fp29_sub<2>(fp29_mul(Rr, fp29_sub<5>(V, r.x)), T);                          // < 6p
+    r.y = fp29_mul2(Rr, fp29_sub<5>(V, r.x), fp29_neg<9>(p.y), HHH);                  // Rr (V + 32p - X3) + (512p - Y1) HHH: 514p * 34p + 512p * 2p < 2^15 p^2; < 2p
     return r;
 }
 
@@ -125,15 +127,14 @@ FP29_FN G1MaddHead g1j29_madd_head(const G1Jac29& p, const G1Aff29& q) {
     return h;
 }
 FP29_FN bool g1j29_madd_special(const G1MaddHead& h) { return fp29_is_zero_mod_p(h.HH); }
-// p + q for g1j29_madd_special(h) == false (p finite, different x): X < 14p, Y < 6p, Z < 2p
+// p + q for g1j29_madd_special(h) == false (p finite, different x): X < 14p, Y < 2p, Z < 2p
 FP29_FN G1Jac29 g1j29_madd_tail(const G1Jac29& p, const G1MaddHead& h) {
     G1Jac29 r;
     r.z = fp29_mul(p.z, h.H);                                                         // < 2p
     const Fp29 HHH = fp29_mul(h.H, h.HH), V = fp29_mul(p.x, h.HH);
     const Fp29 Rr = fp29_sub<9>(h.S2, p.y);                                           // < 514p
     r.x = fp29_sub<3>(fp29_sub<2>(fp29_sqr(Rr), HHH), fp29_dbl(V));                   // < 14p
-    const Fp29 T = fp29_mul(p.y, HHH);
-    r.y = fp29_sub<2>(fp29_mul(Rr, fp29_sub<5>(V, r.x)), T);                          // < 6p
+    r.y = fp29_mul2(Rr, fp29_sub<5>(V, r.x), fp29_neg<9>(p.y), HHH);                  // Rr (V + 32p - X3) + (512p - Y1) HHH: 514p * 34p + 512p * 2p < 2^15 p^2; < 2p
     return r;
 }
 // General addition for the reduction trees, in a form whose later stages need NOTHING of the operands: the head leaves
@@ -161,15 +162,14 @@ FP29_FN G1AddHead g1j29_add_head(const G1Jac29& p, const G1Jac29& q, const Fp29&
     return h;
 }
 FP29_FN bool g1j29_add_same_x(const G1AddHead& h) { return fp29_is_zero_mod_p(h.HH); }
-// different x: X < 14p, Y < 6p, Z < 2p
+// different x: X < 14p, Y < 2p, Z < 2p
 FP29_FN G1Jac29 g1j29_add_tail(const G1AddHead& h) {
     G1Jac29 r;
     r.z = fp29_mul(h.ZZ, h.H);                                                        // < 2p
     const Fp29 HHH = fp29_mul(h.H, h.HH), V = fp29_mul(h.U1, h.HH);
     const Fp29 Rr = fp29_sub<2>(h.S2, h.S1);                                          // < 6p
     r.x = fp29_sub<3>(fp29_sub<2>(fp29_sqr(Rr), HHH), fp29_dbl(V));                   // < 14p
-    const Fp29 T = fp29_mul(h.S1, HHH);
-    r.y = fp29_sub<2>(fp29_mul(Rr, fp29_sub<5>(V, r.x)), T);                          // < 6p
+    r.y = fp29_mul2(Rr, fp29_sub<5>(V, r.x), fp29_neg<2>(h.S1), HHH);                 // Rr (V + 32p - X3) + (4p - S1) HHH: 6p * 34p + 4p * 2p; < 2p
     return r;
 }
 // same x: P + P (the doubling of p = (U1, S1, ZZ)) or P - P (the identity)
