@@ -7,8 +7,9 @@
 // digit 2^15), and the points' flags - 4 KB + 4 B per point.  The rows are built in slices of G1P_SLICE_POINTS points: decode
 // (g1_decode_tables, as kzg_g1_msm), 256 doublings per point into 31 Jacobian temporaries (k_fb_build_rows), one inversion per point for
 // its 31 rows (k_fbp_rows_to_affine) - the temporaries of a slice are 31 x 192 B x 32 768 = 195 MB however large the set is.
-// The sum runs on the kernels of kzg_g1_msm_setup with 8-byte entries (FbEntry64, fb_entry.hpp) and on buffers of its own, sized by the
-// fixed form's needs: 32 B of staged scalars + 32 B of limbs + 128 B of entries per term, the save area (48 KB per workgroup) and the tail.
+// The sum is kzg_g1_msm_setup's (fb_sum_call, capi_prover.hpp) with 8-byte entries (FbEntry64, fb_entry.hpp), on the handle's one set of
+// fixed-base call buffers (FbSumBufs), sized by the sum's plan (fb_sum_plan.hpp): 32 B of staged scalars + 32 B of limbs + 128 B of
+// entries per term, the save area (48 KB per workgroup) and the tail.
 
 constexpr size_t G1P_SLICE_POINTS = 32768;
 
@@ -17,32 +18,8 @@ struct KzgG1Points {
     size_t n = 0;
     DevBuf<G1Aff29Mem> rows;   // [2 FBM_WINDOWS][n]
     DevBuf<uint32_t> pflag;    // [n]: non-zero -> the identity, its terms add nothing
+    FbRows view() const { return FbRows{rows.p, pflag.p, (int)n}; }
 };
-
-// the call buffers of kzg_g1_msm_prepared: grow-only, on the handle, released with it
-struct G1PointsBufs {
-    DevBuf<uint8_t> d_stage;               // the scalars as given (big-endian)
-    DevBuf<Fr> d_scalars;                  // ... reduced, as limbs
-    DevBuf<unsigned long long> d_entries;  // 16 per term
-    DevBuf<uint32_t> d_plan, d_save;
-    DevBuf<uint8_t> d_tail, d_out;
-    DevBuf<G1Jac> d_sum;
-    KzgRet reserve(size_t n, unsigned Z, int gp) {
-        HIPCHK(d_stage.grow(32 * n));
-        HIPCHK(d_scalars.grow(n));
-        HIPCHK(d_entries.grow((size_t)FBM_WINDOWS * n));
-        HIPCHK(d_plan.grow(FBM_PLAN_WORDS));
-        HIPCHK(d_save.grow((size_t)Z * 256 * MSM_SAVE2_WORDS));
-        HIPCHK(d_tail.grow(fb_tail_bytes(gp)));
-        HIPCHK(d_out.grow(48));
-        HIPCHK(d_sum.grow(1));
-        return KZG_OK;
-    }
-};
-static void g1_points_release(const KzgSettings* s) {
-    delete s->g1_points;
-    s->g1_points = nullptr;
-}
 
 extern "C" KzgRet kzg_g1_points_prepare(KzgG1Points** out, const uint8_t* points48, size_t n, const KzgSettings* s) try {
     if (!out || !s || (n && !points48)) return fail(KZG_BADARGS, "null argument");
@@ -142,32 +119,6 @@ extern "C" KzgRet kzg_g1_msm_prepared(uint8_t out[48], const KzgG1Points* p, con
     }
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
-    if (!s->g1_points) s->g1_points = new (std::nothrow) G1PointsBufs();
-    if (!s->g1_points) return fail(KZG_MALLOC, "host buffers of the call");
-    G1PointsBufs& b = *s->g1_points;
-    const int L = FBM_SLICE_ENTRIES, fold_per = 11;
-    const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * n, L);
-    int gp = 0;
-    (void)msm_large_tail_groups(Z, std::max(fold_per, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
-    KzgRet rc = b.reserve(n, Z, gp);
-    if (rc != KZG_OK) return rc;
-    // Nothing of the call stays in flight when an error path leaves: not on the main stream (the host scalars, `out`), and not on the
-    // side stream either - fb_msm_launch runs k_fb_rowsum there, which reads the save area and writes the tail the NEXT call on the
-    // handle reuses on the main stream (declared in this order: the side stream is joined first)
-    StreamDrain drain{s->s1};
-    StreamDrain join_side{s->s2 != s->s1 ? s->s2 : nullptr};
-    HIPCHK(hipMemcpyAsync(b.d_stage.p, scalars, 32 * n, hipMemcpyHostToDevice, s->s1));
-    hipLaunchKernelGGL(k_scalars_reduce_be, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, (const uint8_t*)b.d_stage.p, b.d_scalars.p, (int)n);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->ev[2], s->s1));
-    HIPCHK(fb_msm_launch<FbEntry64>(b.d_scalars.p, p->pflag.p, (int)n, (int)n, p->rows.p, b.d_plan.p, b.d_entries.p, b.d_save.p, b.d_tail.p, b.d_sum.p, L, fold_per, nullptr, s->s1,
-                                    s->s2, s->ev[7], s->ev[8]));
-    HIPCHK(hipEventRecord(s->ev[3], s->s1));
-    hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, (const G1Jac*)b.d_sum.p, b.d_out.p, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, b.d_out.p, 48, hipMemcpyDeviceToHost, s->s1));
-    HIPCHK(hipStreamSynchronize(s->s1));
-    join_side.st = nullptr;  // (the main stream waited for the side stream's event: nothing is left there)
-    elapsed(&s->timings[2], s->ev[2], s->ev[3]);
-    return KZG_OK;
+    return fb_sum_call<FbEntry64>(out, s, scalars, fb_sum_plan(n), p->view());
 }
+

@@ -4,11 +4,11 @@
 // Part of the single translation unit kzg_capi.hip; not a stand-alone header (host code only).
 //
 // The pairs (polynomial, point) of a call are cut into chunks (poly_quotient_plan.hpp).  Per chunk: the coefficients of its polynomials
-// go up once into G1PointsBufs::d_stage, the three launches of poly_quotient_kernels.hpp write every pair's quotient into
-// G1PointsBufs::d_scalars - the limbs k_scalars_reduce_be leaves there for kzg_g1_msm_prepared - the refusal flag is read, and then
-// each pair gets ONE fixed-base sum, fb_msm_launch<FbEntry64>, one after another on the buffers of the prepared path.  A sum takes
-// n_coeffs - 1 TERMS over the set's points (fb_msm_launch keeps the two counts apart: term t uses point t), so a polynomial shorter
-// than the set needs no zero padding.  The commit is the same with k_poly_decode in place of the scan and n_coeffs terms.
+// go up once into FbSumBufs::d_stage, the three launches of poly_quotient_kernels.hpp write every pair's quotient into
+// FbSumBufs::d_scalars - the limbs k_scalars_reduce_be leaves there for kzg_g1_msm_prepared - the refusal flag is read, and then
+// each pair gets ONE fixed-base sum (fb_sum_queue<FbEntry64>, capi_prover.hpp), one after another on the handle's fixed-base call buffers,
+// all by one plan (fb_sum_plan.hpp).  A sum takes n_coeffs - 1 TERMS over the set's points (the plan counts terms, the row view points:
+// term t uses point t), so a polynomial shorter than the set needs no zero padding.  The commit is the same with k_poly_decode in place of the scan and n_coeffs terms.
 // The verdict on a chunk's coefficients and points is read before any of ITS sums is queued; a call of one chunk - every call whose
 // pairs x n_coeffs stay within 2^23 - has queued nothing when it refuses.
 //
@@ -63,19 +63,19 @@ struct PolyCall {
 static_assert(PQ_MAX_OPENINGS == KZG_POLY_MAX_OPENINGS && PQ_MAX_COEFFS == KZG_G1_POINTS_MAX, "the plan's limits are the header's");
 
 // the handle's buffers for a call whose chunks hold at most `chunk` pairs (all growth before anything is queued: grow() keeps no contents)
-static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk, G1PointsBufs** b_out, PolyBufs** pb_out) {
-    if (!s->g1_points) s->g1_points = new (std::nothrow) G1PointsBufs();
+// -> *s->fb_sum, *s->poly
+static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk) {
     if (!s->poly) s->poly = new (std::nothrow) PolyBufs();
-    if (!s->g1_points || !s->poly) return fail(KZG_MALLOC, "host buffers of the call");
+    if (!s->poly) return fail(KZG_MALLOC, "host buffers of the call");
+    const KzgRet rc_b = fb_sum_reserve<FbEntry64>(s, nullptr);
+    if (rc_b != KZG_OK) return rc_b;
     size_t polys = 0;  // the most polynomials a chunk names
     for (size_t k = 0; k < pq_chunks(c.pairs(), chunk); k++) {
         const size_t lo = pq_chunk_lo(k, chunk), m = pq_chunk_size(c.pairs(), k, chunk);
         polys = std::max(polys, pq_poly_end(lo, m, c.n_points) - pq_poly_first(lo, c.n_points));
     }
-    HIPCHK(s->g1_points->d_stage.grow(pq_stage_bytes(c.n_coeffs, polys)));
-    HIPCHK(s->g1_points->d_scalars.grow(pq_quotient_scalars(c.n_coeffs, chunk)));
-    *b_out = s->g1_points;
-    *pb_out = s->poly;
+    HIPCHK(s->fb_sum->d_stage.grow(pq_stage_bytes(c.n_coeffs, polys)));
+    HIPCHK(s->fb_sum->d_scalars.grow(pq_quotient_scalars(c.n_coeffs, chunk)));
     if (c.evals) {
         const KzgRet rc = fr_ntt_reserve(s, s->poly->ntt, c.n_coeffs, polys);
         if (rc != KZG_OK) return rc;
@@ -89,7 +89,7 @@ static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk
 struct PolyStaged {
     size_t first = 1, end = 0;  // the polynomials in d_stage
 };
-static KzgRet poly_stage(const KzgSettings* s, G1PointsBufs& b, PolyBufs& pb, const PolyCall& c, size_t lo, size_t m, PolyStaged& staged, float ms[2]) {
+static KzgRet poly_stage(const KzgSettings* s, FbSumBufs& b, PolyBufs& pb, const PolyCall& c, size_t lo, size_t m, PolyStaged& staged, float ms[2]) {
     const size_t n = c.n_coeffs, k0 = pq_poly_first(lo, c.n_points), k1 = pq_poly_end(lo, m, c.n_points);
     hipStream_t st = s->s1;
     HIPCHK(hipEventRecord(s->ev[0], st));
@@ -161,23 +161,13 @@ static KzgRet poly_run(uint8_t* sums_out, uint8_t* ys_out, const KzgG1Points* p,
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     const size_t terms = c.zs ? n - 1 : n;  // of a pair's sum (the quotient's last coefficient is 0)
     const size_t chunk = std::min(pairs, pq_chunk_pairs(n, c.n_points));
-    G1PointsBufs* bp = nullptr;
-    PolyBufs* pbp = nullptr;
-    KzgRet rc = poly_buffers(s, c, chunk, &bp, &pbp);
+    KzgRet rc = poly_buffers(s, c, chunk);
     if (rc != KZG_OK) return rc;
-    G1PointsBufs& b = *bp;
-    PolyBufs& pb = *pbp;
-    const int L = FBM_SLICE_ENTRIES, fold_per = 11;
-    if (terms) {
-        const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * terms, L);
-        int gp = 0;
-        (void)msm_large_tail_groups(Z, std::max(fold_per, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
-        if ((rc = b.reserve(terms, Z, gp)) != KZG_OK) return rc;
-    }
-    // Nothing of the call stays in flight when an error path leaves, on either stream (kzg_g1_msm_prepared: the side stream runs
-    // k_fb_rowsum on the save area and the tail the next call reuses; declared in this order, it is joined first)
-    StreamDrain drain{s->s1};
-    StreamDrain join_side{s->s2 != s->s1 ? s->s2 : nullptr};
+    FbSumBufs& b = *s->fb_sum;
+    PolyBufs& pb = *s->poly;
+    const FbSumPlan pl = fb_sum_plan(terms);
+    if (terms && (rc = b.reserve(pl, sizeof(FbEntry64::Word))) != KZG_OK) return rc;
+    FbCallGuard guard(s);  // (nothing of the call stays in flight when an error path leaves, on either stream)
     PolyStaged staged;
     float ms[2] = {0.f, 0.f}, ms_sum = 0.f;
     for (size_t k = 0; k < pq_chunks(pairs, chunk); k++) {
@@ -187,9 +177,7 @@ static KzgRet poly_run(uint8_t* sums_out, uint8_t* ys_out, const KzgG1Points* p,
             poly_identities(sums_out + 48 * lo, m);
         } else {
             HIPCHK(hipEventRecord(s->ev[2], s->s1));
-            for (size_t q = 0; q < m; q++)
-                HIPCHK(fb_msm_launch<FbEntry64>(b.d_scalars.p + q * n, p->pflag.p, (int)terms, (int)p->n, p->rows.p, b.d_plan.p, b.d_entries.p, b.d_save.p, b.d_tail.p, pb.d_sums.p + q, L,
-                                                fold_per, nullptr, s->s1, s->s2, s->ev[7], s->ev[8]));
+            for (size_t q = 0; q < m; q++) HIPCHK(fb_sum_queue<FbEntry64>(s, pl, p->view(), b.d_scalars.p + q * n, pb.d_sums.p + q));
             HIPCHK(hipEventRecord(s->ev[3], s->s1));
             hipLaunchKernelGGL(k_jac_compress_n, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const G1Jac*)pb.d_sums.p, pb.d_out.p, (int)m);
             HIPCHK(hipGetLastError());
@@ -207,7 +195,7 @@ static KzgRet poly_run(uint8_t* sums_out, uint8_t* ys_out, const KzgG1Points* p,
         elapsed(&t, s->ev[9], s->ev[10]);
         ms[0] += t;
     }
-    join_side.st = nullptr;
+    guard.done();
     s->timings[2] = ms_sum, s->timings[4] = ms[1], s->timings[6] = ms[0];
     return KZG_OK;
 }
@@ -250,10 +238,10 @@ extern "C" KzgRet kzg_debug_poly_quotients(uint8_t* q_out, uint8_t* ys_out, cons
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);
     const size_t chunk = std::min(pairs, pq_chunk_pairs(n, n_points));
-    G1PointsBufs* b = nullptr;
-    PolyBufs* pb = nullptr;
-    KzgRet rc = poly_buffers(s, c, chunk, &b, &pb);
+    KzgRet rc = poly_buffers(s, c, chunk);
     if (rc != KZG_OK) return rc;
+    FbSumBufs* const b = s->fb_sum;
+    PolyBufs* const pb = s->poly;
     std::vector<uint8_t> limbs(32 * n * chunk);
     StreamDrain drain{s->s1};
     PolyStaged staged;

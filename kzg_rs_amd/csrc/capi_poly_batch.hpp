@@ -7,11 +7,11 @@
 // By linearity q_j = sum_k gamma_j^k q_kj and f_j(z_j) = sum_k gamma_j^k p_k(z_j).  The points of a call are cut into groups and the
 // polynomials into chunks of whole polynomials (poly_fold_plan.hpp; one group and one chunk while n_coeffs x n_points and n_coeffs x
 // n_polys stay within 2^23).  Per group, the chunks are visited from the last to the first.  Per chunk: its coefficients go up once into
-// G1PointsBufs::d_stage (the evaluation-form twin runs the inverse transform in place there), k_poly_fold carries the Horner recurrence
+// FbSumBufs::d_stage (the evaluation-form twin runs the inverse transform in place there), k_poly_fold carries the Horner recurrence
 // in gamma on in PolyBufs::d_fold, and k_poly_tile_sums (unchanged) + k_poly_eval_tiles leave every p_k(z_j) of the chunk.  Behind the
 // last chunk visited the three scan launches of poly_quotient_kernels.hpp run on the fold buffer - the group's points as that many
-// "polynomials" with one point each - and write the quotients into G1PointsBufs::d_scalars; the flag word is read; then one
-// fb_msm_launch<FbEntry64> per POINT and k_jac_compress_n, as poly_run does per pair.  The verdict on a group's elements is read before
+// "polynomials" with one point each - and write the quotients into FbSumBufs::d_scalars; the flag word is read; then one
+// fixed-base sum (fb_sum_queue<FbEntry64>) per POINT and k_jac_compress_n, as poly_run does per pair.  The verdict on a group's elements is read before
 // any of ITS sums is queued; a call of one group has queued nothing when it refuses.
 
 // what one call asks for (evals: `coeffs` holds the values on <w_n_coeffs> in `order`, n_coeffs a power of two)
@@ -28,12 +28,14 @@ struct PolyBatchCall {
 };
 
 // the handle's buffers for the call (all growth before anything is queued: grow() keeps no contents)
-static KzgRet poly_batch_buffers(const KzgSettings* s, const PolyBatchCall& c, G1PointsBufs** b_out, PolyBufs** pb_out) {
-    if (!s->g1_points) s->g1_points = new (std::nothrow) G1PointsBufs();
+// -> *s->fb_sum, *s->poly
+static KzgRet poly_batch_buffers(const KzgSettings* s, const PolyBatchCall& c) {
     if (!s->poly) s->poly = new (std::nothrow) PolyBufs();
-    if (!s->g1_points || !s->poly) return fail(KZG_MALLOC, "host buffers of the call");
+    if (!s->poly) return fail(KZG_MALLOC, "host buffers of the call");
+    const KzgRet rc_b = fb_sum_reserve<FbEntry64>(s, nullptr);
+    if (rc_b != KZG_OK) return rc_b;
     const size_t n = c.n_coeffs, cp = c.chunk_polys(), gp = c.group_points();
-    G1PointsBufs& b = *s->g1_points;
+    FbSumBufs& b = *s->fb_sum;
     PolyBufs& pb = *s->poly;
     HIPCHK(b.d_stage.grow(pf_stage_bytes(n, cp)));
     HIPCHK(b.d_scalars.grow(pf_quotient_scalars(n, gp)));
@@ -47,8 +49,6 @@ static KzgRet poly_batch_buffers(const KzgSettings* s, const PolyBatchCall& c, G
     HIPCHK(pb.d_carry.grow(pq_tile_scalars(n, gp)));
     HIPCHK(pb.d_flag.grow(1));
     HIPCHK(pb.d_sums.grow(gp));
-    *b_out = &b;
-    *pb_out = &pb;
     if (c.evals) return fr_ntt_reserve(s, pb.ntt, n, cp);
     return KZG_OK;
 }
@@ -56,7 +56,7 @@ static KzgRet poly_batch_buffers(const KzgSettings* s, const PolyBatchCall& c, G
 // Points [j0, j0 + g) of the call: every chunk of polynomials (upload, transform, fold, the individual values), the scan of the fold
 // buffer, the verdict.  On KZG_OK the group's quotients are in b.d_scalars, [point][n_coeffs], f_j(z_j) in pb.d_fys, and every p_k(z_j) of
 // the group at its place in pb.d_bys.  zrep: host scratch of 32 x chunk_polys x g bytes.  ms: [0] copies [1] the launches, added to.
-static KzgRet poly_batch_stage(const KzgSettings* s, G1PointsBufs& b, PolyBufs& pb, const PolyBatchCall& c, size_t j0, size_t g, uint8_t* zrep, float ms[2]) {
+static KzgRet poly_batch_stage(const KzgSettings* s, FbSumBufs& b, PolyBufs& pb, const PolyBatchCall& c, size_t j0, size_t g, uint8_t* zrep, float ms[2]) {
     const size_t n = c.n_coeffs, cp = c.chunk_polys(), chunks = pf_chunks(c.n_polys, cp);
     hipStream_t st = s->s1;
     for (size_t k = 0; k < cp; k++) memcpy(zrep + 32 * g * k, c.zs + 32 * j0, 32 * g);  // the group's points, once per polynomial of a chunk
@@ -137,25 +137,15 @@ static KzgRet poly_batch_run(uint8_t* proofs_out, uint8_t* ys_out, const KzgG1Po
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
     const size_t terms = n - 1;  // of a point's sum (the quotient's last coefficient is 0)
-    G1PointsBufs* bp = nullptr;
-    PolyBufs* pbp = nullptr;
-    KzgRet rc = poly_batch_buffers(s, c, &bp, &pbp);
+    KzgRet rc = poly_batch_buffers(s, c);
     if (rc != KZG_OK) return rc;
-    G1PointsBufs& b = *bp;
-    PolyBufs& pb = *pbp;
-    const int L = FBM_SLICE_ENTRIES, fold_per = 11;
-    if (terms) {
-        const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * terms, L);
-        int gp = 0;
-        (void)msm_large_tail_groups(Z, std::max(fold_per, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
-        if ((rc = b.reserve(terms, Z, gp)) != KZG_OK) return rc;
-    }
+    FbSumBufs& b = *s->fb_sum;
+    PolyBufs& pb = *s->poly;
+    const FbSumPlan pl = fb_sum_plan(terms);
+    if (terms && (rc = b.reserve(pl, sizeof(FbEntry64::Word))) != KZG_OK) return rc;
     const size_t gpts = c.group_points();
     std::vector<uint8_t> zrep(32 * c.chunk_polys() * gpts);
-    // Nothing of the call stays in flight when an error path leaves, on either stream (poly_run: declared in this order, the side
-    // stream is joined first; and after zrep, whose bytes the main stream's copies read)
-    StreamDrain drain{s->s1};
-    StreamDrain join_side{s->s2 != s->s1 ? s->s2 : nullptr};
+    FbCallGuard guard(s);  // (nothing of the call stays in flight when an error path leaves, on either stream; declared after zrep, whose bytes the main stream's copies read)
     float ms[2] = {0.f, 0.f}, ms_sum = 0.f;
     for (size_t gi = 0; gi < pf_groups(c.n_points, gpts); gi++) {
         const size_t j0 = pf_group_first(gi, gpts), g = pf_group_size(c.n_points, gi, gpts);
@@ -165,9 +155,7 @@ static KzgRet poly_batch_run(uint8_t* proofs_out, uint8_t* ys_out, const KzgG1Po
             continue;
         }
         HIPCHK(hipEventRecord(s->ev[2], s->s1));
-        for (size_t q = 0; q < g; q++)
-            HIPCHK(fb_msm_launch<FbEntry64>(b.d_scalars.p + q * n, p->pflag.p, (int)terms, (int)p->n, p->rows.p, b.d_plan.p, b.d_entries.p, b.d_save.p, b.d_tail.p, pb.d_sums.p + q, L, fold_per,
-                                            nullptr, s->s1, s->s2, s->ev[7], s->ev[8]));
+        for (size_t q = 0; q < g; q++) HIPCHK(fb_sum_queue<FbEntry64>(s, pl, p->view(), b.d_scalars.p + q * n, pb.d_sums.p + q));
         HIPCHK(hipEventRecord(s->ev[3], s->s1));
         hipLaunchKernelGGL(k_jac_compress_n, dim3((unsigned)((g + 63) / 64)), dim3(64), 0, s->s1, (const G1Jac*)pb.d_sums.p, pb.d_out.p, (int)g);
         HIPCHK(hipGetLastError());
@@ -190,7 +178,7 @@ static KzgRet poly_batch_run(uint8_t* proofs_out, uint8_t* ys_out, const KzgG1Po
         elapsed(&t, s->ev[9], s->ev[10]);
         ms[0] += t;
     }
-    join_side.st = nullptr;
+    guard.done();
     s->timings[2] = ms_sum, s->timings[4] = ms[1], s->timings[6] = ms[0];
     return KZG_OK;
 }
@@ -282,10 +270,10 @@ extern "C" KzgRet kzg_debug_poly_batch_quotients(uint8_t* q_out, uint8_t* ys_out
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);
-    G1PointsBufs* b = nullptr;
-    PolyBufs* pb = nullptr;
-    KzgRet rc = poly_batch_buffers(s, c, &b, &pb);
+    KzgRet rc = poly_batch_buffers(s, c);
     if (rc != KZG_OK) return rc;
+    FbSumBufs* const b = s->fb_sum;
+    PolyBufs* const pb = s->poly;
     const size_t gpts = c.group_points();
     std::vector<uint8_t> zrep(32 * c.chunk_polys() * gpts), limbs(32 * n * gpts);
     StreamDrain drain{s->s1};

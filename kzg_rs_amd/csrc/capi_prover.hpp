@@ -56,7 +56,99 @@ static void prover_release(const KzgSettings* s) {
     delete s->prover;
     s->prover = nullptr;
 }
-static KzgRet fb_rows_ready(const KzgSettings* s);
+
+// ---------------------------------------------------------------- fixed-base sums (msm_fixed.hpp) on the handle
+// ONE set of call buffers for every fixed-base sum of a handle - over its own 4 096 points (setup_msm, kzg_g1_msm_setup: 4-byte
+// entries) and over prepared sets (capi_g1_points.hpp, capi_poly.hpp, capi_poly_batch.hpp: 8-byte entries): grow-only, made by the
+// first such call, released with the handle.  Every call holds the handle's lock and leaves nothing in flight on them.
+struct FbSumBufs {
+    DevBuf<uint8_t> d_stage, d_entries, d_tail, d_out;  // the scalars as given (big-endian) | 16 entries per term, of either width | the plan's tail | the sum, compressed
+    DevBuf<Fr> d_scalars;                               // the scalars reduced, as limbs
+    DevBuf<uint32_t> d_plan, d_save;
+    DevBuf<G1Jac> d_sum;
+    // for one sum of plan `pl` with entries of entry_bytes each
+    KzgRet reserve(const FbSumPlan& pl, size_t entry_bytes) {
+        HIPCHK(d_stage.grow(32 * pl.terms));
+        HIPCHK(d_scalars.grow(pl.terms));
+        HIPCHK(d_entries.grow(entry_bytes * pl.entries));
+        HIPCHK(d_plan.grow(FBM_PLAN_WORDS));
+        HIPCHK(d_save.grow(pl.save_words));
+        HIPCHK(d_tail.grow(pl.tail_bytes));
+        HIPCHK(d_out.grow(48));
+        HIPCHK(d_sum.grow(1));
+        return KZG_OK;
+    }
+};
+// ... made if need be and reserved for one sum of plan `pl` (nullptr: made only) with entries of EF::Word
+template <class EF>
+static KzgRet fb_sum_reserve(const KzgSettings* s, const FbSumPlan* pl) {
+    if (!s->fb_sum) s->fb_sum = new (std::nothrow) FbSumBufs();
+    if (!s->fb_sum) return fail(KZG_MALLOC, "host buffers of the call");
+    return pl ? s->fb_sum->reserve(*pl, sizeof(typename EF::Word)) : KZG_OK;
+}
+static void fb_sum_release(const KzgSettings* s) {
+    delete s->fb_sum;
+    s->fb_sum = nullptr;
+}
+// Nothing of a call stays in flight when an error path leaves: not on the main stream (the host scalars, `out`), and not on the side
+// stream either - fb_msm_launch runs k_fb_rowsum there, which reads the save area and writes the tail the NEXT call on the handle
+// reuses on the main stream.  The side stream is joined first, then the main stream drained; done(): the main stream has waited for
+// the side stream's event and was drained, nothing is left there.  (Declare it after the host vectors the streams' copies read.)
+struct FbCallGuard {
+    StreamDrain drain, join_side;  // (destroyed in reverse order)
+    explicit FbCallGuard(const KzgSettings* s) : drain{s->s1}, join_side{s->s2 != s->s1 ? s->s2 : nullptr} {}
+    void done() { join_side.st = nullptr; }
+};
+// one sum on the handle's buffers (reserved for `pl`), queued: scalars (limbs, device) -> *out.  fork: the row sums on the side stream
+template <class EF>
+static hipError_t fb_sum_queue(const KzgSettings* s, const FbSumPlan& pl, const FbRows& r, const Fr* scalars, G1Jac* out, bool fork = true) {
+    FbSumBufs& b = *s->fb_sum;
+    return fb_msm_launch<EF>(pl, r, scalars, b.d_plan.p, reinterpret_cast<typename EF::Word*>(b.d_entries.p), b.d_save.p, b.d_tail.p, out, s->s1, fork ? s->s2 : nullptr, s->ev[7], s->ev[8]);
+}
+// A whole one-sum call (kzg_g1_msm_setup's fixed form, kzg_g1_msm_prepared): pl.terms big-endian scalars in host memory, any value
+// below 2^256 -> the sum over `r`, compressed, at `out`.  timings[2]: the sum.  Returns with both streams drained.
+template <class EF>
+static KzgRet fb_sum_call(uint8_t out[48], const KzgSettings* s, const uint8_t* scalars, const FbSumPlan& pl, const FbRows& r) {
+    const size_t n = pl.terms;
+    const KzgRet rc = fb_sum_reserve<EF>(s, &pl);
+    if (rc != KZG_OK) return rc;
+    FbSumBufs& b = *s->fb_sum;
+    FbCallGuard guard(s);
+    HIPCHK(hipMemcpyAsync(b.d_stage.p, scalars, 32 * n, hipMemcpyHostToDevice, s->s1));
+    hipLaunchKernelGGL(k_scalars_reduce_be, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->s1, (const uint8_t*)b.d_stage.p, b.d_scalars.p, (int)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev[2], s->s1));
+    HIPCHK(fb_sum_queue<EF>(s, pl, r, b.d_scalars.p, b.d_sum.p));
+    HIPCHK(hipEventRecord(s->ev[3], s->s1));
+    hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, (const G1Jac*)b.d_sum.p, b.d_out.p, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, b.d_out.p, 48, hipMemcpyDeviceToHost, s->s1));
+    HIPCHK(hipStreamSynchronize(s->s1));
+    guard.done();
+    elapsed(&s->timings[2], s->ev[2], s->ev[3]);
+    return KZG_OK;
+}
+// the rows of the handle's own points, 2^(16 v) P_j and the doubled ones (16 MB), made by the first fixed-base sum over them: 256
+// doublings per point into 31 Jacobian temporaries, one inversion per point for its 31 rows - as a prepared set's (capi_g1_points.hpp)
+static KzgRet fb_rows_ready(const KzgSettings* s, FbRows* out) {
+    const int N = s->n_g1;
+    if (!s->t->d_g1_fb_rows.p) {
+        DevBuf<G1Jac29Mem> t_jac;
+        DevBuf<G1Aff29Mem> t_rows;  // (released on an error path)
+        HIPCHK(t_jac.alloc((size_t)(2 * FBM_WINDOWS - 1) * N));
+        HIPCHK(t_rows.alloc((size_t)2 * FBM_WINDOWS * N));
+        const unsigned blocks = (unsigned)((N + 63) / 64);
+        hipLaunchKernelGGL(k_fb_build_rows, dim3(blocks), dim3(64), 0, s->s1, (const G1Aff29Mem*)s->t->d_g1_mult_aff.p, (const uint32_t*)s->t->d_g1_flag.p, t_jac.p, N);
+        hipLaunchKernelGGL(k_fbp_rows_to_affine, dim3(blocks), dim3(64), 0, s->s1, (const G1Aff29Mem*)s->t->d_g1_mult_aff.p, (const uint32_t*)s->t->d_g1_flag.p, (const G1Jac29Mem*)t_jac.p,
+                           t_rows.p, N, N, 0);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s->s1));
+        s->t->d_g1_fb_rows = std::move(t_rows);
+    }
+    *out = FbRows{s->t->d_g1_fb_rows.p, s->t->d_g1_flag.p, N};
+    return KZG_OK;
+}
+
 // m MSMs: out[b] = compress(sum_i sc[b][i] * g1_points[i]); sc = plain canonical scalars (destroyed: GLV split in place)
 static KzgRet setup_msm(const KzgSettings* s, ProverBufs& b, size_t m) {
     const size_t NT = (size_t)FE_PER_BLOB;
@@ -66,18 +158,11 @@ static KzgRet setup_msm(const KzgSettings* s, ProverBufs& b, size_t m) {
     // main stream here: the proof path's second stream is busy with the commitments' decode.
     static const size_t fb_max_blobs = (size_t)std::max(0L, std::min(8L, opt_int("prover_fixed_base_max_blobs", 2)));
     if (m <= fb_max_blobs && msm_affine_enabled() && s->t->d_g1_mult_aff.p && (size_t)s->n_g1 == NT && NT * 2 * FBM_WINDOWS <= 131072) {
-        KzgRet rc = fb_rows_ready(s);
-        if (rc != KZG_OK) return rc;
-        const int L = FBM_SLICE_ENTRIES;
-        const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * NT, L);
-        Workspace& w = s->ws;
-        if ((rc = msm_save_grow(s, (size_t)Z * 256 * MSM_SAVE2_WORDS * 4)) != KZG_OK) return rc;
-        int gp = 0;
-        (void)msm_large_tail_groups(Z, std::max(11, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
-        uint8_t* tmp = nullptr;
-        if ((rc = g1msm_scratch(s, fb_tail_bytes(gp), &tmp)) != KZG_OK) return rc;
-        for (size_t k = 0; k < m; k++)
-            HIPCHK(fb_msm_launch(b.d_sc.p + k * NT, s->t->d_g1_flag.p, (int)NT, s->n_g1, s->t->d_g1_fb_rows.p, s->t->d_fb_plan.p, b.d_sorted.p, w.d_msm_save.p, tmp, b.d_res.p + k, L, 11, nullptr, s->s1));
+        FbRows rows;
+        const FbSumPlan pl = fb_sum_plan(NT);
+        KzgRet rc = fb_rows_ready(s, &rows);
+        if (rc != KZG_OK || (rc = fb_sum_reserve<FbEntry32>(s, &pl)) != KZG_OK) return rc;
+        for (size_t k = 0; k < m; k++) HIPCHK(fb_sum_queue<FbEntry32>(s, pl, rows, b.d_sc.p + k * NT, b.d_res.p + k, /*fork=*/false));
         hipLaunchKernelGGL(k_jac_compress_n, dim3(1), dim3(64), 0, s->s1, b.d_res.p, b.d_out.p, (int)m);
         HIPCHK(hipGetLastError());
         return KZG_OK;
@@ -158,12 +243,7 @@ static KzgRet compute_proofs(uint8_t* proofs48, uint8_t* ys32, const uint8_t* bl
     ProverBufs& b = *bp;
     std::vector<uint8_t> le(32 * PROVER_CHUNK);
     hipStream_t const side = s->s2 && s->s2 != s->s1 ? s->s2 : nullptr;  // the commitments' validity check runs beside the chain
-    struct DrainSide {  // (nothing of the call stays in flight on the side stream, whatever path leaves)
-        hipStream_t st;
-        ~DrainSide() {
-            if (st) (void)hipStreamSynchronize(st);
-        }
-    } drain_side{side};
+    StreamDrain drain_side{side};  // (nothing of the call stays in flight on the side stream, whatever path leaves)
     // a few blobs: their Fiat-Shamir challenges from the host's SHA-NI cores while the blobs cross PCIe - a chain is 2.8 ms on
     // GPU lanes however few blobs there are and 65 us on a host core (the verifier's small host batches do the same)
     const size_t host_hash_max = std::min<size_t>(PROVER_CHUNK, host_challenge_max_blobs());
@@ -245,26 +325,7 @@ extern "C" KzgRet kzg_compute_blob_kzg_proof(uint8_t* proofs48, const uint8_t* b
 //   window  the verification path's window kernel (GLV, 8-bit windows) over the setup's affine table rows: the fallback when the
 //           fixed-base form's bucket sums would pass 2 GiB (above ~2^24.6 terms) or the handle has no affine rows (A/B build, msm_affine=0)
 // option g1_msm_setup_form = window | fixed forces one (tests, A/B).  timings: [2] the MSM, [6] = 0 (no decode, no tables).
-constexpr size_t FBM_MIN_TERMS = 1;
-static KzgRet fb_rows_ready(const KzgSettings* s) {
-    if (s->t->d_g1_fb_rows.p) return KZG_OK;
-    const int N = s->n_g1;
-    DevBuf<G1Jac29Mem> t_jac;
-    DevBuf<G1Aff29Mem> t_rows;  // (released on an error path)
-    HIPCHK(t_jac.alloc((size_t)(2 * FBM_WINDOWS - 1) * N));
-    HIPCHK(t_rows.alloc((size_t)2 * FBM_WINDOWS * N));
-    G1Aff29Mem* const rows = t_rows.p;
-    HIPCHK(s->t->d_fb_plan.grow(FBM_PLAN_WORDS));
-    HIPCHK(hipMemcpyAsync(rows, s->t->d_g1_mult_aff.p, sizeof(G1Aff29Mem) * (size_t)N, hipMemcpyDeviceToDevice, s->s1));  // row 0 = P_j
-    hipLaunchKernelGGL(k_fb_build_rows, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s->s1, (const G1Aff29Mem*)s->t->d_g1_mult_aff.p, (const uint32_t*)s->t->d_g1_flag.p,
-                       t_jac.p, N);
-    const int m = (2 * FBM_WINDOWS - 1) * N;
-    hipLaunchKernelGGL(k_jac29_to_aff29, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s->s1, (const G1Jac29Mem*)t_jac.p, rows + N, m);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s->s1));
-    s->t->d_g1_fb_rows = std::move(t_rows);
-    return KZG_OK;
-}
+// The fixed form runs on the handle's fixed-base buffers (FbSumBufs) alone; only the window form reserves the workspace.
 extern "C" KzgRet kzg_g1_msm_setup(uint8_t out[48], const uint8_t* scalars, size_t n, const KzgSettings* s) try {
     if (!s || !out || (n && !scalars)) return fail(KZG_BADARGS, "null argument");
     if (n > ((size_t)1 << 26)) return fail(KZG_BADARGS, "kzg_g1_msm_setup: more than 2^26 terms");
@@ -273,38 +334,23 @@ extern "C" KzgRet kzg_g1_msm_setup(uint8_t out[48], const uint8_t* scalars, size
     std::lock_guard<std::mutex> lk(s->mu);
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);  // stand-alone pieces run on the plain stream pair
-    if ((rc = ws_reserve(s, (n + 1) / 2 + 1, 1, STAGE_NONE)) != KZG_OK) return rc;
-    Workspace& w = s->ws;
-    StreamDrain drain{s->s1};
     const bool aff = msm_affine_enabled() && s->t->d_g1_mult_aff.p;
     static const int forced = opt_is("g1_msm_setup_form", "window") ? 1 : opt_is("g1_msm_setup_form", "fixed") ? 2 : 0;
     static const int L = (int)std::max(1024L, std::min((long)FBM_SLICE_ENTRIES, ab_int("g1_msm_fb_slice", (long)FBM_SLICE_ENTRIES)));
-    const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * n, L);
-    const size_t save_bytes = (size_t)Z * 256 * MSM_SAVE2_WORDS * 4;
-    const bool fixed = aff && n > 0 && (size_t)s->n_g1 * 2 * FBM_WINDOWS <= 131072 && save_bytes <= ((size_t)2 << 30) && (forced == 2 || (forced == 0 && n >= FBM_MIN_TERMS));
-    if (n && (rc = g1_msm_scalars_in(s, scalars, n, 0)) != KZG_OK) return rc;
+    static const int fold_per_opt = (int)std::max(2L, std::min(64L, ab_int("g1_msm_fold_per", FBM_FOLD_PER)));
+    const FbSumPlan pl = fb_sum_plan(n, L, fold_per_opt);
+    const bool fixed = aff && n > 0 && (size_t)s->n_g1 * 2 * FBM_WINDOWS <= FbEntry32::MAX_ROWS && pl.save_fits() && forced != 1;
     s->timings[6] = 0.0f;
     if (!fixed) {
+        StreamDrain drain{s->s1};
+        if ((rc = ws_reserve(s, (n + 1) / 2 + 1, 1, STAGE_NONE)) != KZG_OK) return rc;
+        if (n && (rc = g1_msm_scalars_in(s, scalars, n, 0)) != KZG_OK) return rc;
         const G1MsmTables tb{aff ? (const void*)s->t->d_g1_mult_aff.p : (const void*)s->t->d_g1_mult.p, s->t->d_g1_flag.p, s->n_g1, aff, true};
         return g1_msm_core(s, n, tb, out);
     }
-    if ((rc = fb_rows_ready(s)) != KZG_OK) return rc;
-    if ((rc = msm_save_grow(s, save_bytes)) != KZG_OK) return rc;  // (this form's layers are 48 KB each)
-    static const int fold_per_opt = (int)std::max(2L, std::min(64L, ab_int("g1_msm_fold_per", 11)));
-    int gp = 0;
-    (void)msm_large_tail_groups(Z, std::max(fold_per_opt, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS)), &gp);
-    uint8_t* tmp = nullptr;
-    if ((rc = g1msm_scratch(s, fb_tail_bytes(gp), &tmp)) != KZG_OK) return rc;
-    HIPCHK(hipEventRecord(s->ev[2], s->s1));
-    HIPCHK(fb_msm_launch(w.d_scalars.p, s->t->d_g1_flag.p, (int)n, s->n_g1, s->t->d_g1_fb_rows.p, s->t->d_fb_plan.p, w.d_sorted.p, w.d_msm_save.p, tmp, w.d_ab.p, L, fold_per_opt,
-                         w.d_ktime.p ? w.d_ktime.p + 8 : nullptr, s->s1, s->s2, s->ev[7], s->ev[8]));
-    HIPCHK(hipEventRecord(s->ev[3], s->s1));
-    hipLaunchKernelGGL(k_jac_compress, dim3(1), dim3(64), 0, s->s1, w.d_ab.p, w.d_bytes.p, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, w.d_bytes.p, 48, hipMemcpyDeviceToHost, s->s1));
-    HIPCHK(hipStreamSynchronize(s->s1));
-    elapsed(&s->timings[2], s->ev[2], s->ev[3]);
-    return KZG_OK;
+    FbRows rows;
+    if ((rc = fb_rows_ready(s, &rows)) != KZG_OK) return rc;
+    return fb_sum_call<FbEntry32>(out, s, scalars, pl, rows);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
 }

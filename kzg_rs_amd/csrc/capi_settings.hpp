@@ -47,10 +47,11 @@ struct GroupBufs {
     DevBuf<uint8_t> d_bytes, d_records;
     DevBuf<uint32_t> d_sha_mid;  // SHA-256 midstates between the segments of a sliced challenge chain, 32 B per blob
     PinnedBuf<uint8_t> h_buf;    // pinned host mirrors
-    // Two scratch areas that grow on demand (msm_save_grow, g1msm_scratch) and are RELEASED with the group: up to 512 MiB of save
-    // area does not stay allocated while a larger set is made; the next MSM allocates its area again
-    DevBuf<uint32_t> d_msm_save;  // the window kernel's bucket sums between its row and column trees (msm.hpp MsmDesc::save)
-    DevBuf<uint8_t> d_g1msm;  // kzg_g1_msm / kzg_g1_msm_setup: window sums, fold trees, the large-sum tail (a per-call hipFree stalls every lane of the device)
+    // Two scratch areas of the WINDOW form (the fixed-base sums have buffers of their own: FbSumBufs) that grow on demand (msm_save_grow,
+    // g1msm_scratch) and are RELEASED with the group: up to 512 MiB of save area does not stay allocated while a larger set is made; the
+    // next MSM allocates its area again
+    DevBuf<uint32_t> d_msm_save;  // the window kernel's bucket sums between its row and column trees (msm.hpp MsmDesc::save): run_msm, g1_msm_core, setup_msm's window branch
+    DevBuf<uint8_t> d_g1msm;  // g1_msm_core (kzg_g1_msm, kzg_g1_msm_setup's window form): window sums, fold trees, the large-sum tail (a per-call hipFree stalls every lane of the device)
     void reset() { *this = GroupBufs(); }  // everything above released, capacities and state back to their defaults
 };
 // ... and the grow-only staging buffers with lifetimes of their own, which ws_reserve never touches
@@ -79,8 +80,7 @@ struct SettingsTables {
     DevBuf<uint32_t> d_g1_flag;    // 0 finite / 1 identity (unchecked decode, build.rs:68)
     DevBuf<G1Jac29Mem> d_g1_mult;  // their MSM multiples (msm.hpp), valid iff g1_in_subgroup
     DevBuf<G1Aff29Mem> d_g1_mult_aff;  // the same as AFFINE rows (the throughput layout of the verification path's MSM): kzg_g1_msm_setup's 8-bit form
-    mutable DevBuf<G1Aff29Mem> d_g1_fb_rows;  // fixed-base rows 2^(16 v) P_j (msm_fixed.hpp), made by the first large kzg_g1_msm_setup call
-    mutable DevBuf<uint32_t> d_fb_plan;       // ... and that form's device-side plan words
+    mutable DevBuf<G1Aff29Mem> d_g1_fb_rows;  // fixed-base rows 2^(16 v) P_j (msm_fixed.hpp), made by the first fixed-base sum over the handle's points (fb_rows_ready)
     DevBuf<Fp> d_g2;               // g2_points (monomial), n_g2 x 4 Fp
     DevProgram prep, verify;
     DevProgram2 verify2;            // VERIFY scheduled for one check at a time (kzg_rs_amd/slp/schedule2.py)
@@ -92,7 +92,7 @@ struct SettingsTables {
 struct KzgSettings {
     int device = 0;
     SettingsTables own;               // empty on a lane
-    const SettingsTables* t = &own;   // a lane: its parent's - but not the full-setup members (d_g1*, d_fb_plan, d_g2): a lane's n_g1 / n_g2 stay 0
+    const SettingsTables* t = &own;   // a lane: its parent's - but not the full-setup members (d_g1*, d_g2): a lane's n_g1 / n_g2 stay 0
     int n_g1 = 0;                     // number of G1 Lagrange points (4096)
     bool g1_in_subgroup = false;      // every G1 point lies in the r-torsion (what the GLV multiples need)
     size_t n_g2 = 0;
@@ -131,7 +131,7 @@ struct KzgSettings {
     mutable const Fr29Mem* blob_cell_W = nullptr;
     mutable struct CellProverState* cell_prover = nullptr;  // the cell prover's tables and buffers, made by its first call (capi_cell_prover.hpp)
     mutable struct CellRecoverState* cell_recover = nullptr;  // cell recovery's own buffers, made by its first call (capi_cell_recover.hpp)
-    mutable struct G1PointsBufs* g1_points = nullptr;  // kzg_g1_msm_prepared's call buffers, made by its first call (capi_g1_points.hpp)
+    mutable struct FbSumBufs* fb_sum = nullptr;  // the call buffers of every fixed-base sum (msm_fixed.hpp), made by the first such call (capi_prover.hpp)
     mutable struct PolyBufs* poly = nullptr;  // the quotient stage's buffers of the coefficient-form openings, made by their first call (capi_poly.hpp)
     // the EIP-7594 cell work this shard has run since the last reset (kzg_debug_cell_shard_stats, capi_cell_multi.hpp): launches
     // (locked ranges and coalesced launches) | cells verified | blobs verified against cell proofs | blobs proved or recovered.
@@ -609,7 +609,7 @@ static void prover_release(const KzgSettings* s);  // (capi_prover.hpp)
 static void cells_release(const KzgSettings* s);   // (capi_cells.hpp)
 static void cell_prover_release(const KzgSettings* s);  // (capi_cell_prover.hpp)
 static void cell_recover_release(const KzgSettings* s);  // (capi_cell_recover.hpp)
-static void g1_points_release(const KzgSettings* s);  // (capi_g1_points.hpp)
+static void fb_sum_release(const KzgSettings* s);  // (capi_prover.hpp)
 static void poly_release(const KzgSettings* s);  // (capi_poly.hpp)
 extern "C" void kzg_settings_free(KzgSettings* s) {
     if (!s) return;
@@ -629,7 +629,7 @@ extern "C" void kzg_settings_free(KzgSettings* s) {
     cells_release(s);
     cell_prover_release(s);
     cell_recover_release(s);
-    g1_points_release(s);
+    fb_sum_release(s);
     poly_release(s);
     s->own = SettingsTables();  // (a lane's is empty: it reads its parent's, which is freed after its lanes)
     for (auto& e : s->ev)

@@ -16,18 +16,16 @@
 //   sum_b b B_b  with  b = 256 p + l :   sum_l l C_l + 256 sum_p p R_p,   C_l = sum over all workgroups of bucket l,  R_p = sum of
 //   everything partition p's workgroups accumulated - two 256-bucket reductions, run by the large-sum tail of msm.hpp
 //   (k_msm_bucket_fold, k_msm_bucket_sum_quads, k_msm_reduce_quads) as TWO "windows" 8 bits apart, joined by k_msm_combine_quad.
+// The same kernels sum over a PREPARED set of any points (capi_g1_points.hpp) with 8-byte entries (fb_entry.hpp).  The host side is one
+// launch path for every caller, fb_msm_launch, driven by the sum's plan (fb_sum_plan.hpp: grids, fold, buffer sizes, the tail's layout)
+// on the handle's one set of fixed-base call buffers (FbSumBufs, capi_prover.hpp).
 // Part of the single translation unit kzg_capi.hip (after msm.hpp).
 #pragma once
-#include "fb_entry.hpp"  // FBM_WINDOWS, fb_digits, the entry formats FbEntry32 / FbEntry64
+#include "fb_sum_plan.hpp"  // the FBM_ constants, FbSumPlan; fb_entry.hpp: FBM_WINDOWS, fb_digits, the entry formats FbEntry32 / FbEntry64
 
 namespace kzg {
 
-constexpr int FBM_PARTS = 128;            // |digit| >> 8 for |digit| <= 2^15 - 1 (a digit of exactly 2^15 travels as two entries of 2^14, below)
-constexpr int FBM_SLICE_ENTRIES = 12288;  // entries a workgroup sorts in LDS (48 KB: three workgroups per CU, like k_msm_window)
-constexpr uint32_t FBM_ENTRY_ROW_MASK = FbEntry32::ROW_MASK, FBM_ENTRY_NEG = FbEntry32::NEG;  // the setup form's entry = low byte of |digit| << 24 | negative << 17 | row (v N + j; doubled rows from 16 N on)
-// device-side plan of one call: entries per partition | their exclusive scan (+ total) | first workgroup of
-// each partition (+ total workgroups) | then the scatter's cursors
-constexpr int FBM_PLAN_COUNT = 0, FBM_PLAN_OFF = FBM_PARTS, FBM_PLAN_BLK = 2 * FBM_PARTS + 1, FBM_PLAN_CUR = 3 * FBM_PARTS + 2, FBM_PLAN_WORDS = 4 * FBM_PARTS + 2;
+static_assert(FBM_FOLD_MAX_GROUPS == MSM_FOLD_MAX_GROUPS && FBM_SAVE_WORDS == MSM_SAVE2_WORDS && FBM_JAC_BYTES == sizeof(G1Jac), "the plan's constants are the kernels'");
 
 // big-endian scalars of any value < 2^256 -> canonical little-endian limbs (Scalar::from_raw semantics: reduced mod r; 2^256 < 3 r)
 __global__ __launch_bounds__(256) void k_scalars_reduce_be(const uint8_t* __restrict__ be, Fr* __restrict__ out, int n) {
@@ -40,7 +38,6 @@ __global__ __launch_bounds__(256) void k_scalars_reduce_be(const uint8_t* __rest
     out[i] = v;
 }
 
-constexpr int FBM_TERMS_PER_BLOCK = 1024;
 // pass 1a: entries per partition.  pflag[j] != 0: point j is the identity (unchecked decode, build.rs:66-70) - its terms add nothing
 __global__ __launch_bounds__(256) void k_fb_count(const Fr* __restrict__ scalars, const uint32_t* __restrict__ pflag, int n, int npoints,
                                                   uint32_t* __restrict__ plan) {
@@ -113,7 +110,7 @@ __global__ __launch_bounds__(256) void k_fbp_scatter(const Fr* __restrict__ scal
 }
 
 // table build, once per handle: jac[(v - 1) N + j] = 2^(16 v) P_j for v = 1 .. 15, jac[(15 + v) N + j] = 2^(16 v + 1) P_j for v = 0 .. 15
-// (k_jac29_to_aff29 turns them into rows 1 .. 31; row 0 = P_j is the setup's affine table row)
+// (k_fbp_rows_to_affine turns them into rows 1 .. 31; row 0 = P_j is the decode's affine table row)
 __global__ __launch_bounds__(64) void k_fb_build_rows(const G1Aff29Mem* __restrict__ row0, const uint32_t* __restrict__ pflag, G1Jac29Mem* __restrict__ jac, int npoints) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= npoints) return;
@@ -138,7 +135,7 @@ __global__ __launch_bounds__(64) void k_fb_build_rows(const G1Aff29Mem* __restri
     }
 }
 
-// table build of a PREPARED set (kzg_g1_points_prepare), one slice of m points [j0, j0 + m) of the set's npoints at a time: row0 = the
+// table build of a prepared set (kzg_g1_points_prepare) and of the handle's own points (fb_rows_ready: one slice, m = npoints), one slice of m points [j0, j0 + m) of the set's npoints at a time: row0 = the
 // slice's decoded affine points, jac = what k_fb_build_rows made of them ([31][m]: jac row r becomes table row r + 1) -> the set's
 // affine rows[(r + 1) npoints + j0 + j] and rows[j0 + j] = P.  Lane j converts the 31 multiples of ITS point with one inversion
 // (Montgomery's trick, as k_mult_to_affine29: the prefix products are parked in the x slot of the output row until the backward sweep
@@ -339,41 +336,40 @@ __global__ __launch_bounds__(256) void k_fb_rowsum(const uint32_t* __restrict__ 
     if (tid < SUMQ_POINT_WORDS / 4) reinterpret_cast<uint4*>(out + (size_t)p * SUMQ_POINT_WORDS)[tid] = reinterpret_cast<const uint4*>(pts)[tid];
 }
 
-// device memory the tail wants beside the save area: flags [gp] | partial sums [256][gp] | buckets [2][256] | window sums [2] (G1Jac)
-constexpr size_t fb_tail_bytes(int gp) { return 4 * ((size_t)MSM_FOLD_MAX_GROUPS + (size_t)256 * gp * MSM_SAVE2_WORDS + 2 * 256 * MSM_SAVE2_WORDS) + 2 * sizeof(G1Jac) + 256; }
-// workgroups of pass 2 for n_entries entries at most (every partition may end in a part-filled slice)
-inline unsigned fb_max_blocks(size_t n_entries, int L) { return (unsigned)(FBM_PARTS + (n_entries + (size_t)L - 1) / (size_t)L); }
+// the table a sum runs over: rows[2 FBM_WINDOWS][npoints] and the points' flags - a prepared set's, or the handle's own 4 096 points'
+struct FbRows {
+    const G1Aff29Mem* rows;
+    const uint32_t* pflag;
+    int npoints;
+};
 
-// Host side: scalars (canonical limbs, n of them) -> out_ab[0] = the sum (Jacobian, 12x32 form).  `entries`: 16 n words; `save`:
-// fb_max_blocks x 48 KB; `tmp`: fb_tail_bytes(gp); plan: FBM_PLAN_WORDS words.  Everything on `st`.  EF: the entry format (fb_entry.hpp) -
-// FbEntry32 over the setup's 4 096 points, FbEntry64 over a prepared set (`entries`: 16 n words of EF::Word either way).
-template <class EF = FbEntry32>
-inline hipError_t fb_msm_launch(const Fr* scalars, const uint32_t* pflag, int n, int npoints, const G1Aff29Mem* rows, uint32_t* plan, typename EF::Word* entries,
-                                uint32_t* save, uint8_t* tmp, G1Jac* out_ab, int L, int fold_per_min, unsigned long long* ktime, hipStream_t st,
-                                hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr) {
-    const unsigned nb = (unsigned)((n + FBM_TERMS_PER_BLOCK - 1) / FBM_TERMS_PER_BLOCK);
+// Host side: scalars (canonical limbs, pl.terms of them; term t uses point t mod npoints) -> *out = the sum (Jacobian, 12x32 form).
+// Everything else is the plan's (fb_sum_plan.hpp): `entries` pl.entries words of EF::Word, `save` pl.save_words words, `tail`
+// pl.tail_bytes bytes, `plan` FBM_PLAN_WORDS words.  EF: the entry format (fb_entry.hpp) - FbEntry32 over the handle's 4 096 points,
+// FbEntry64 over a prepared set.  Everything on `st`, but the row sums on `side` when the caller has a second stream and the events.
+template <class EF>
+inline hipError_t fb_msm_launch(const FbSumPlan& pl, const FbRows& r, const Fr* scalars, uint32_t* plan, typename EF::Word* entries, uint32_t* save, uint8_t* tail, G1Jac* out,
+                                hipStream_t st, hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr) {
+    const int n = (int)pl.terms, Z = (int)pl.Z;
+    const size_t lds = 4 * (size_t)pl.L + 16;
+    unsigned long long* const ktime = nullptr;  // (no caller reads the window kernel's stamps)
     hipError_t e = hipMemsetAsync(plan, 0, 4 * FBM_PLAN_WORDS, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fb_count, dim3(nb), dim3(256), 0, st, scalars, pflag, n, npoints, plan);
-    hipLaunchKernelGGL(k_fb_plan, dim3(1), dim3(64), 0, st, plan, L);
-    const unsigned Z = fb_max_blocks((size_t)FBM_WINDOWS * n, L);
+    hipLaunchKernelGGL(k_fb_count, dim3(pl.nb), dim3(256), 0, st, scalars, r.pflag, n, r.npoints, plan);
+    hipLaunchKernelGGL(k_fb_plan, dim3(1), dim3(64), 0, st, plan, pl.L);
     if constexpr (EF::WIDE) {
-        hipLaunchKernelGGL(k_fbp_scatter, dim3(nb), dim3(256), 0, st, scalars, pflag, n, npoints, plan, entries);
-        if ((e = DYN_LDS(k_fbp_window, 4 * (size_t)L + 16)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_fbp_window, dim3(Z), dim3(256), 4 * (size_t)L + 16, st, (const unsigned long long*)entries, (const uint32_t*)plan, rows, save, L, ktime);
+        hipLaunchKernelGGL(k_fbp_scatter, dim3(pl.nb), dim3(256), 0, st, scalars, r.pflag, n, r.npoints, plan, entries);
+        if ((e = DYN_LDS(k_fbp_window, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_fbp_window, dim3(pl.Z), dim3(256), lds, st, (const unsigned long long*)entries, (const uint32_t*)plan, r.rows, save, pl.L, ktime);
     } else {
-        hipLaunchKernelGGL(k_fb_scatter, dim3(nb), dim3(256), 0, st, scalars, pflag, n, npoints, plan, entries);
-        if ((e = DYN_LDS(k_fb_window, 4 * (size_t)L + 16)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_fb_window, dim3(Z), dim3(256), 4 * (size_t)L + 16, st, (const uint32_t*)entries, (const uint32_t*)plan, rows, save, L, ktime);
+        hipLaunchKernelGGL(k_fb_scatter, dim3(pl.nb), dim3(256), 0, st, scalars, r.pflag, n, r.npoints, plan, entries);
+        if ((e = DYN_LDS(k_fb_window, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_fb_window, dim3(pl.Z), dim3(256), lds, st, (const uint32_t*)entries, (const uint32_t*)plan, r.rows, save, pl.L, ktime);
     }
-    // C_l: every workgroup's bucket l, folded layer by layer (groups of `per` layers per thread, then a tree with four lanes per addition)
-    const int per = std::max(fold_per_min, (int)((Z + MSM_FOLD_MAX_GROUPS - 1) / MSM_FOLD_MAX_GROUPS));
-    int gp;
-    const int groups = msm_large_tail_groups(Z, per, &gp);
-    uint32_t* const flags = reinterpret_cast<uint32_t*>(tmp);
-    uint32_t* const part = flags + MSM_FOLD_MAX_GROUPS;
-    uint32_t* const buckets = part + (size_t)256 * gp * MSM_SAVE2_WORDS;  // [2][256] records: C | R
-    G1Jac* const wsums = reinterpret_cast<G1Jac*>(reinterpret_cast<uint8_t*>(buckets + (size_t)2 * 256 * MSM_SAVE2_WORDS) + 64);
+    uint32_t* const flags = reinterpret_cast<uint32_t*>(tail + pl.off_flags);
+    uint32_t* const part = reinterpret_cast<uint32_t*>(tail + pl.off_part);
+    uint32_t* const buckets = reinterpret_cast<uint32_t*>(tail + pl.off_buckets);  // [2][256] records: C | R
+    G1Jac* const wsums = reinterpret_cast<G1Jac*>(tail + pl.off_wsums);
     // R_p (k_fb_rowsum: a chain of ~19 additions per lane, 128 workgroups) beside the fold of C on a second stream when the caller has one
     const bool forked = side && side != st && ev_fork && ev_join;
     if (forked) {
@@ -382,16 +378,18 @@ inline hipError_t fb_msm_launch(const Fr* scalars, const uint32_t* pflag, int n,
     }
     hipLaunchKernelGGL(k_fb_rowsum, dim3(256), dim3(256), 0, forked ? side : st, (const uint32_t*)save, (const uint32_t*)plan, buckets + (size_t)256 * MSM_SAVE2_WORDS);
     if (forked && (e = hipEventRecord(ev_join, side)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(flags, 0, 4 * (size_t)gp, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_msm_bucket_fold<false>, dim3(gp), dim3(256), 0, st, (const uint32_t*)save, part, flags, 1, (int)Z, per, groups, gp);
-    hipLaunchKernelGGL(k_msm_bucket_fold<true>, dim3(gp), dim3(256), 0, st, (const uint32_t*)save, part, flags, 1, (int)Z, per, groups, gp);
+    // C_l: every workgroup's bucket l, folded layer by layer (groups of `per` layers per thread, then a tree with four lanes per addition)
+    if ((e = hipMemsetAsync(flags, 0, 4 * (size_t)pl.gp, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_msm_bucket_fold<false>, dim3(pl.gp), dim3(256), 0, st, (const uint32_t*)save, part, flags, 1, Z, pl.per, pl.groups, pl.gp);
+    hipLaunchKernelGGL(k_msm_bucket_fold<true>, dim3(pl.gp), dim3(256), 0, st, (const uint32_t*)save, part, flags, 1, Z, pl.per, pl.groups, pl.gp);
     if ((e = DYN_LDS(k_msm_bucket_sum_quads, msm_bucket_sum_lds_bytes(MSM_FOLD_MAX_GROUPS))) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_msm_bucket_sum_quads, dim3(256), dim3(64), msm_bucket_sum_lds_bytes(gp), st, (const uint32_t*)part, buckets, gp);
+    hipLaunchKernelGGL(k_msm_bucket_sum_quads, dim3(256), dim3(64), msm_bucket_sum_lds_bytes(pl.gp), st, (const uint32_t*)part, buckets, pl.gp);
     if (forked && (e = hipStreamWaitEvent(st, ev_join, 0)) != hipSuccess) return e;
     if ((e = DYN_LDS(k_msm_reduce_quads, MSM_REDQ_LDS_BYTES)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_msm_reduce_quads, dim3(2), dim3(256), MSM_REDQ_LDS_BYTES, st, (const uint32_t*)buckets, wsums);
-    hipLaunchKernelGGL(k_msm_combine_quad, dim3(1), dim3(64), 0, st, (const G1Jac*)wsums, out_ab, 2);  // sum_l l C_l + 2^8 sum_p p R_p
+    hipLaunchKernelGGL(k_msm_combine_quad, dim3(1), dim3(64), 0, st, (const G1Jac*)wsums, out, 2);  // sum_l l C_l + 2^8 sum_p p R_p
     return hipGetLastError();
 }
 
 }  // namespace kzg
+
