@@ -10,8 +10,18 @@
 // Reference semantics implemented here (sp1_bls12_381 is un-vendored; call sites in
 // /root/reference/src/kzg_proof.rs): Scalar::from_bytes (:36), Scalar::from_raw (:90),
 // Scalar::to_bytes (:321), + - * (:105-131, :172-198).
+//
+// The header also compiles as plain C++ (tests/host/field32_host.cpp, against Python integers): off the device the
+// qualifiers are empty and the carry builtins and v_mad_u64_u32 chains are replaced by their uint64_t / unsigned __int128 twins.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define KZG_DEV __device__ __forceinline__
+#define KZG_FN __device__ inline
+#else
+#define KZG_DEV inline
+#define KZG_FN inline
+#endif
 #include <stdint.h>
 
 namespace kzg {
@@ -19,14 +29,14 @@ namespace kzg {
 // such a launch also times the wait for free CUs): kt[0] = max over the waves of ~start, kt[1] = max of end, in ticks of the
 // 100 MHz s_memrealtime counter; the first lane of every wavefront stamps, the host zeroes kt before the launch and reads
 // end - start = kt[1] - ~kt[0].  kt == nullptr: no stamp.
-__device__ __forceinline__ void kstamp_in(unsigned long long* kt) {
+KZG_DEV void kstamp_in(unsigned long long* kt) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (kt && (threadIdx.x & 63) == 0) atomicMax(&kt[0], ~__builtin_amdgcn_s_memrealtime());
 #else
     (void)kt;
 #endif
 }
-__device__ __forceinline__ void kstamp_out(unsigned long long* kt) {
+KZG_DEV void kstamp_out(unsigned long long* kt) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (kt && (threadIdx.x & 63) == 0) atomicMax(&kt[1], __builtin_amdgcn_s_memrealtime());
 #else
@@ -38,8 +48,6 @@ namespace consts {
 #include "constants.inc"
 #undef KZG_CONST
 }  // namespace consts
-
-#define KZG_DEV __device__ __forceinline__
 
 template <int N>
 struct alignas(16) Limbs {
@@ -66,16 +74,28 @@ struct FpParams {
 // gfx950: one VALU instruction per limb.  (The portable `(uint64_t)a + b + carry` idiom is compiled by
 // hipcc into 64-bit adds plus register-pair shuffling, ~7 instructions per limb.)
 KZG_DEV uint32_t addc(uint32_t a, uint32_t b, uint32_t& carry) {
+#if defined(__HIP_DEVICE_COMPILE__)
     unsigned c = carry;
     uint32_t r = __builtin_addc(a, b, c, &c);
     carry = c;
     return r;
+#else
+    const uint64_t s = (uint64_t)a + b + carry;
+    carry = (uint32_t)(s >> 32);
+    return (uint32_t)s;
+#endif
 }
 KZG_DEV uint32_t subb(uint32_t a, uint32_t b, uint32_t& borrow) {
+#if defined(__HIP_DEVICE_COMPILE__)
     unsigned c = borrow;
     uint32_t r = __builtin_subc(a, b, c, &c);
     borrow = c;
     return r;
+#else
+    const uint64_t d = (uint64_t)a - b - borrow;
+    borrow = (uint32_t)(d >> 63);
+    return (uint32_t)d;
+#endif
 }
 
 #include "mac_chains.inc"
@@ -198,10 +218,16 @@ struct Field {
     // v_mad_u64_u32 that accumulates in place (no register-pair shuffling) plus one 32-bit
     // v_addc for the carry-out.  4N^2 + O(N) VALU instructions instead of ~10N^2.
     KZG_DEV static void mac(uint64_t& acc, uint32_t& hi, uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
         asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc"
             : "+v"(acc), "+v"(hi)
             : "v"(a), "v"(b)
             : "vcc");
+#else
+        const unsigned __int128 t = (((unsigned __int128)hi << 64) | acc) + (uint64_t)a * b;
+        acc = (uint64_t)t;
+        hi = (uint32_t)(t >> 64);
+#endif
     }
     KZG_DEV static E mul_ps(const E& a, const E& b) {
         uint64_t acc = 0;
@@ -329,7 +355,7 @@ using Fp = FpF::E;
 // generic exponentiation, exponent as NE 32-bit limbs (plain integer), MSB-first square-multiply.
 // `mulfn` is a callable so heavy fields can pass a non-inlined multiply.
 template <class E, int NE, class Mul>
-__device__ inline E pow_limbs(const E& a, const uint32_t (&e)[NE], const E& one, Mul mulfn) {
+KZG_FN E pow_limbs(const E& a, const uint32_t (&e)[NE], const E& one, Mul mulfn) {
     E acc = one;
     bool started = false;
     for (int i = 32 * NE - 1; i >= 0; i--) {

@@ -15,6 +15,10 @@ namespace kzg {
 
 // Out-of-line Fp product.  Operands travel as 12-lane ext-vectors: AMDGPU passes vector arguments in VGPRs,
 // whereas a 48-byte struct argument goes through scratch memory (a store + load round trip per call).
+// (A plain compiler - the host tests - has neither the vector type nor the reason for it: fp_mul is FpF::mul there.)
+#if !defined(__HIPCC__)
+KZG_FN Fp fp_mul(const Fp& a, const Fp& b) { return FpF::mul(a, b); }
+#else
 typedef uint32_t v12u __attribute__((ext_vector_type(12)));
 __device__ __noinline__ v12u fp_mul_raw(v12u a, v12u b) {
     Fp x, y;
@@ -29,7 +33,7 @@ __device__ __noinline__ v12u fp_mul_raw(v12u a, v12u b) {
     for (int i = 0; i < 12; i++) o[i] = r.l[i];
     return o;
 }
-__device__ __forceinline__ Fp fp_mul(const Fp& a, const Fp& b) {
+KZG_DEV Fp fp_mul(const Fp& a, const Fp& b) {
     v12u x, y;
 #pragma unroll
     for (int i = 0; i < 12; i++) {
@@ -42,14 +46,15 @@ __device__ __forceinline__ Fp fp_mul(const Fp& a, const Fp& b) {
     for (int i = 0; i < 12; i++) r.l[i] = o[i];
     return r;
 }
-__device__ __forceinline__ Fp fp_sqr(const Fp& a) { return fp_mul(a, a); }
-__device__ __forceinline__ Fp fp_add(const Fp& a, const Fp& b) { return FpF::add(a, b); }
-__device__ __forceinline__ Fp fp_sub(const Fp& a, const Fp& b) { return FpF::sub(a, b); }
-__device__ __forceinline__ Fp fp_neg(const Fp& a) { return FpF::neg(a); }
-__device__ __forceinline__ Fp fp_dbl(const Fp& a) { return FpF::add(a, a); }
+#endif
+KZG_DEV Fp fp_sqr(const Fp& a) { return fp_mul(a, a); }
+KZG_DEV Fp fp_add(const Fp& a, const Fp& b) { return FpF::add(a, b); }
+KZG_DEV Fp fp_sub(const Fp& a, const Fp& b) { return FpF::sub(a, b); }
+KZG_DEV Fp fp_neg(const Fp& a) { return FpF::neg(a); }
+KZG_DEV Fp fp_dbl(const Fp& a) { return FpF::add(a, a); }
 
 template <int NE>
-__device__ inline Fp fp_pow(const Fp& a, const uint32_t (&e)[NE]) {
+KZG_FN Fp fp_pow(const Fp& a, const uint32_t (&e)[NE]) {
     Fp acc = FpF::one();
     bool started = false;
     for (int i = 32 * NE - 1; i >= 0; i--) {
@@ -62,7 +67,7 @@ __device__ inline Fp fp_pow(const Fp& a, const uint32_t (&e)[NE]) {
     return acc;
 }
 
-__device__ inline Fp fp_const(const uint32_t (&c)[12]) {
+KZG_FN Fp fp_const(const uint32_t (&c)[12]) {
     Fp r;
 #pragma unroll
     for (int i = 0; i < 12; i++) r.l[i] = c[i];
@@ -70,14 +75,20 @@ __device__ inline Fp fp_const(const uint32_t (&c)[12]) {
 }
 
 // a^-1 by Fermat (a != 0).  Used only in set-up / per-call tails, never per blob element.
-__device__ inline Fp fp_inv(const Fp& a) { return fp_pow(a, consts::FP_P_MINUS_2); }
+KZG_FN Fp fp_inv(const Fp& a) { return fp_pow(a, consts::FP_P_MINUS_2); }
 
 // a^-1 for a LONE LANE (a != 0): the binary extended Euclidean algorithm on the plain integers - ~760 halvings and ~380 subtractions of
 // 12-limb numbers (~55 k instructions) against the 381 squarings + 190 products of the Fermat chain (~260 k): 0.1 ms instead of 1.0 ms
 // when one lane converts one point (k_jac_compress: the tail of every kzg_g1_msm / kzg_g1_msm_setup call).  Variable time and full of
 // data-dependent branches: right for a single lane, wasteful for a wavefront of independent inversions (those keep fp_inv).
 // Input and output in Montgomery form: the algorithm inverts x = a R as an integer, t = a^-1 R^-1; two products by R^2 give a^-1 R.
-__device__ inline Fp fp_inv_lone_lane(const Fp& a) {
+// No input spins: the loop also leaves when u reaches 0, and the result is then 0.  Between two rounds u and v are non-zero, so each
+// run of halvings ends; v stays odd and positive (it only loses a smaller u), and after the first round each subtraction of two odd
+// numbers leaves an even one, so every round takes at least one bit off bits(u) + bits(v) <= 384 + 381: at most 766 rounds, 765
+// halvings.  u = 0 is reached only from an input that is 0 mod p (0, or a non-canonical multiple of p: the gcd is then p, not 1);
+// for 0 < a < p the gcd is 1 and the loop leaves through u == 1 or v == 1 first, as before.  No caller passes 0 (g1_to_affine asks
+// g1_is_identity first, FK20 inverts a product of non-zero Z).  Host-tested with 0 and p in tests/test_field32_host.py.
+KZG_FN Fp fp_inv_lone_lane(const Fp& a) {
     auto is_one = [](const Fp& x) {
         uint32_t o = x.l[0] ^ 1u;
 #pragma unroll
@@ -110,7 +121,7 @@ __device__ inline Fp fp_inv_lone_lane(const Fp& a) {
     Fp u = a, v = fp_const(consts::FP_MOD), x1 = FpF::zero(), x2 = FpF::zero();
     x1.l[0] = 1u;
 #pragma unroll 1
-    while (!is_one(u) && !is_one(v)) {
+    while (!is_one(u) && !is_one(v) && !FpF::is_zero(u)) {
 #pragma unroll 1
         while ((u.l[0] & 1u) == 0) {
             shr1(u, 0u);
@@ -135,6 +146,7 @@ __device__ inline Fp fp_inv_lone_lane(const Fp& a) {
             sub_mod(x2, x1);
         }
     }
+    if (FpF::is_zero(u)) return FpF::zero();  // a = 0 mod p: no inverse
     const Fp t = is_one(u) ? x1 : x2;  // (a R)^-1 as a plain integer
     const Fp r2 = fp_const(consts::FP_R2);
     return fp_mul(fp_mul(t, r2), r2);
@@ -144,7 +156,7 @@ __device__ inline Fp fp_inv_lone_lane(const Fp& a) {
 // wave-uniform and the table of odd powers a, a^3, a^5, a^7 lives in registers, picked by selects).  For the
 // square-root exponent: 379 squarings + 107 multiplications + 4 for the table, against 379 + 229 bit by bit.
 template <int NE>
-__device__ inline Fp fp_pow_window3(const Fp& a, const uint32_t (&e)[NE]) {
+KZG_FN Fp fp_pow_window3(const Fp& a, const uint32_t (&e)[NE]) {
     const Fp a2 = fp_sqr(a);
     Fp t[4];
     t[0] = a;
@@ -177,14 +189,14 @@ __device__ inline Fp fp_pow_window3(const Fp& a, const uint32_t (&e)[NE]) {
 }
 
 // sqrt for p = 3 mod 4: candidate a^((p+1)/4); returns false if a is not a square
-__device__ inline bool fp_sqrt(Fp& r, const Fp& a) {
+KZG_FN bool fp_sqrt(Fp& r, const Fp& a) {
     Fp c = fp_pow_window3(a, consts::FP_SQRT_EXP);
     r = c;
     return FpF::eq(fp_sqr(c), a);
 }
 
 // plain-integer test  v > (p-1)/2  of a Montgomery-form element ("lexicographically largest")
-__device__ inline bool fp_is_lex_largest(const Fp& a_mont) {
+KZG_FN bool fp_is_lex_largest(const Fp& a_mont) {
     Fp a = FpF::from_mont(a_mont);
     uint32_t borrow = 0;
 #pragma unroll
@@ -200,16 +212,16 @@ struct G1Jac {
     Fp x, y, z;  // Jacobian, z == 0 <=> infinity
 };
 
-__device__ inline G1Jac g1_identity() {
+KZG_FN G1Jac g1_identity() {
     G1Jac r;
     r.x = FpF::zero();
     r.y = FpF::one();
     r.z = FpF::zero();
     return r;
 }
-__device__ inline bool g1_is_identity(const G1Jac& p) { return FpF::is_zero(p.z); }
+KZG_FN bool g1_is_identity(const G1Jac& p) { return FpF::is_zero(p.z); }
 
-__device__ inline G1Jac g1_from_affine(const G1Aff& a) {
+KZG_FN G1Jac g1_from_affine(const G1Aff& a) {
     G1Jac r;
     r.x = a.x;
     r.y = a.y;
@@ -218,7 +230,7 @@ __device__ inline G1Jac g1_from_affine(const G1Aff& a) {
 }
 
 // dbl-2009-l (a = 0): 2M + 5S
-__device__ __forceinline__ G1Jac g1_dbl(const G1Jac& p) {
+KZG_DEV G1Jac g1_dbl(const G1Jac& p) {
     Fp A = fp_sqr(p.x), B = fp_sqr(p.y), C = fp_sqr(B);
     Fp t = fp_sqr(fp_add(p.x, B));
     Fp D = fp_dbl(fp_sub(fp_sub(t, A), C));
@@ -233,7 +245,7 @@ __device__ __forceinline__ G1Jac g1_dbl(const G1Jac& p) {
 }
 
 // general Jacobian addition with every special case handled (identity operands, P+P, P-P)
-__device__ __forceinline__ G1Jac g1_add(const G1Jac& p, const G1Jac& q) {
+KZG_DEV G1Jac g1_add(const G1Jac& p, const G1Jac& q) {
     if (g1_is_identity(p)) return q;
     if (g1_is_identity(q)) return p;
     Fp Z1Z1 = fp_sqr(p.z), Z2Z2 = fp_sqr(q.z);
@@ -253,7 +265,7 @@ __device__ __forceinline__ G1Jac g1_add(const G1Jac& p, const G1Jac& q) {
 }
 
 // mixed addition p + (affine q, q != identity)
-__device__ __forceinline__ G1Jac g1_add_affine(const G1Jac& p, const G1Aff& q) {
+KZG_DEV G1Jac g1_add_affine(const G1Jac& p, const G1Aff& q) {
     if (g1_is_identity(p)) return g1_from_affine(q);
     Fp Z1Z1 = fp_sqr(p.z);
     Fp U2 = fp_mul(q.x, Z1Z1), S2 = fp_mul(fp_mul(q.y, p.z), Z1Z1);
@@ -271,7 +283,7 @@ __device__ __forceinline__ G1Jac g1_add_affine(const G1Jac& p, const G1Aff& q) {
 }
 
 // [|x|]P for the BLS parameter |x| = 0xd201000000010000 (63 doublings + 5 additions)
-__device__ inline G1Jac g1_mul_xabs(const G1Jac& p) {
+KZG_FN G1Jac g1_mul_xabs(const G1Jac& p) {
     G1Jac acc = p;
 #pragma unroll 1
     for (int i = 62; i >= 0; i--) {
@@ -285,7 +297,7 @@ __device__ inline G1Jac g1_mul_xabs(const G1Jac& p) {
 // (Scott, "A note on group membership tests for G1, G2 and GT", eprint 2021/1130 - the same
 // criterion zkcrypto/bls12_381 uses).  Accepts exactly the points with [r]P = O, which is what the
 // CPU checker tests by definition; tests/test_gpu_parity.py::test_g1_decompress compares the two on and off the subgroup.
-__device__ inline bool g1_in_subgroup(const G1Aff& p) {
+KZG_FN bool g1_in_subgroup(const G1Aff& p) {
     G1Jac q = g1_from_affine(p);
 #pragma unroll 1
     for (int rep = 0; rep < 2; rep++) q = g1_mul_xabs(q);  // [x^2]P (the two signs cancel); one copy of the loop body
@@ -296,10 +308,19 @@ __device__ inline bool g1_in_subgroup(const G1Aff& p) {
     return FpF::eq(q.x, fp_mul(bx, zz)) && FpF::eq(q.y, fp_neg(fp_mul(p.y, zzz)));
 }
 
+// the second table half of the GLV split (msm.hpp): -phi(P) = (beta X, -Y, Z) = [x^2]P on G1
+KZG_DEV G1Jac g1_neg_phi(const G1Jac& p) {
+    G1Jac r;
+    r.x = fp_mul(p.x, fp_const(consts::FP_BETA_MONT));
+    r.y = fp_neg(p.y);
+    r.z = p.z;
+    return r;
+}
+
 enum : uint32_t { G1_OK = 0, G1_INFINITY = 1, G1_INVALID = 2 };
 
 // 48 compressed bytes -> affine (Montgomery).  Returns G1_OK / G1_INFINITY / G1_INVALID.
-__device__ inline uint32_t g1_decompress(G1Aff& out, const uint8_t* b, bool check_subgroup) {
+KZG_FN uint32_t g1_decompress(G1Aff& out, const uint8_t* b, bool check_subgroup) {
     uint32_t w[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) {
@@ -332,7 +353,7 @@ __device__ inline uint32_t g1_decompress(G1Aff& out, const uint8_t* b, bool chec
 }
 
 // affine (Montgomery) -> 48 compressed bytes; `inf` selects the identity encoding
-__device__ inline void g1_compress(uint8_t* b, const G1Aff& a, bool inf) {
+KZG_FN void g1_compress(uint8_t* b, const G1Aff& a, bool inf) {
     if (inf) {
         for (int i = 0; i < 48; i++) b[i] = 0;
         b[0] = 0xc0;
@@ -346,7 +367,7 @@ __device__ inline void g1_compress(uint8_t* b, const G1Aff& a, bool inf) {
 
 // Jacobian -> affine (one Fermat inversion); returns false for the identity
 template <bool LONE_LANE = false>
-__device__ inline bool g1_to_affine(G1Aff& out, const G1Jac& p) {
+KZG_FN bool g1_to_affine(G1Aff& out, const G1Jac& p) {
     if (g1_is_identity(p)) {
         out.x = FpF::zero();
         out.y = FpF::zero();
@@ -362,7 +383,7 @@ __device__ inline bool g1_to_affine(G1Aff& out, const G1Jac& p) {
 struct Fp2 {
     Fp c0, c1;
 };
-__device__ inline Fp2 fp2_mul(const Fp2& a, const Fp2& b) {
+KZG_FN Fp2 fp2_mul(const Fp2& a, const Fp2& b) {
     Fp t0 = fp_mul(a.c0, b.c0), t1 = fp_mul(a.c1, b.c1);
     Fp m = fp_mul(fp_add(a.c0, a.c1), fp_add(b.c0, b.c1));
     Fp2 r;
@@ -370,11 +391,11 @@ __device__ inline Fp2 fp2_mul(const Fp2& a, const Fp2& b) {
     r.c1 = fp_sub(fp_sub(m, t0), t1);
     return r;
 }
-__device__ inline Fp2 fp2_sqr(const Fp2& a) { return fp2_mul(a, a); }
-__device__ inline bool fp2_eq(const Fp2& a, const Fp2& b) { return FpF::eq(a.c0, b.c0) && FpF::eq(a.c1, b.c1); }
+KZG_FN Fp2 fp2_sqr(const Fp2& a) { return fp2_mul(a, a); }
+KZG_FN bool fp2_eq(const Fp2& a, const Fp2& b) { return FpF::eq(a.c0, b.c0) && FpF::eq(a.c1, b.c1); }
 
 // sqrt in Fp2 = Fp[u]/(u^2+1):  a = (x + y u)^2  =>  x^2 = (a0 +- sqrt(a0^2 + a1^2))/2,  y = a1/(2x)
-__device__ inline bool fp2_sqrt(Fp2& r, const Fp2& a) {
+KZG_FN bool fp2_sqrt(Fp2& r, const Fp2& a) {
     if (FpF::is_zero(a.c0) && FpF::is_zero(a.c1)) {
         r = a;
         return true;
@@ -401,7 +422,7 @@ struct G2Aff {
 
 // 96 compressed bytes (x.c1 || x.c0, flags in byte 0) -> affine; subgroup NOT checked
 // (trusted-setup data, like build.rs:73).  Returns G1_OK / G1_INFINITY / G1_INVALID.
-__device__ inline uint32_t g2_decompress(G2Aff& out, const uint8_t* b) {
+KZG_FN uint32_t g2_decompress(G2Aff& out, const uint8_t* b) {
     bool c_flag = (b[0] >> 7) & 1, i_flag = (b[0] >> 6) & 1, s_flag = (b[0] >> 5) & 1;
     uint8_t xb[96];
     for (int i = 0; i < 96; i++) xb[i] = b[i];

@@ -23,6 +23,7 @@
 #include "dyn_lds.hpp"
 #include "g1.hpp"
 #include "g1_29.hpp"
+#include "glv_split.hpp"
 
 namespace kzg {
 
@@ -104,13 +105,6 @@ constexpr int MSM_CHUNKS = 4;
 constexpr int MSM_CHUNKS_LATENCY = 32;
 constexpr int MSM_ENTRY_CHUNK_SHIFT = 27;  // a sorted-list entry: chunk << 27 | point index
 constexpr uint32_t MSM_ENTRY_POINT_MASK = (1u << MSM_ENTRY_CHUNK_SHIFT) - 1;
-__device__ __forceinline__ G1Jac g1_neg_phi(const G1Jac& p) {
-    G1Jac r;
-    r.x = fp_mul(p.x, fp_const(consts::FP_BETA_MONT));
-    r.y = fp_neg(p.y);
-    r.z = p.z;
-    return r;
-}
 // table j of `chunks` tables: j < chunks/2 -> 2^(step j) P, j >= chunks/2 -> -phi of table j - chunks/2; step = 256 / chunks
 __global__ __launch_bounds__(64, 4) void k_g1_multiples(const G1Aff* __restrict__ points, const uint32_t* __restrict__ pflag,
                                                      G1Jac* __restrict__ mult, int n, int stride, int chunks) {
@@ -250,8 +244,7 @@ __global__ void k_jac_to_jac29(const G1Jac* __restrict__ in, G1Jac29Mem* __restr
     g1j29_store(out[i], g1j29_from_std(in[i]));
 }
 
-// in place: canonical k (< r) -> k1 (limbs 0..3) | k2 (limbs 4..7) with k = k1 + k2 * x^2.
-// Barrett with M = floor(2^383 / x^2): the quotient estimate is low by at most 1 for k < 2^255.
+// in place: canonical k (< r) -> k1 (limbs 0..3) | k2 (limbs 4..7) with k = k1 + k2 * x^2 (glv_split.hpp).
 // (Round 5 tried a DIGIT-major copy of the split scalars - digits_t[b * count + i] = byte b of scalar i - so that the window
 // kernel's sort reads consecutive bytes for consecutive terms instead of one byte per 32-byte scalar: the window kernel's HBM
 // bytes went from 1.182 to 1.169 GB per launch group and its time and SQ_WAIT_ANY share did not move - those byte reads were L2
@@ -261,53 +254,7 @@ __global__ __launch_bounds__(256) void k_glv_split(Fr* __restrict__ scalars, int
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     Fr k = scalars[i];
-    uint32_t prod[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) prod[j] = 0;
-#pragma unroll
-    for (int a = 0; a < 8; a++) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            uint64_t t = (uint64_t)k.l[a] * consts::GLV_M[b] + prod[a + b] + c;
-            prod[a + b] = (uint32_t)t;
-            c = t >> 32;
-        }
-        prod[a + 8] = (uint32_t)c;
-    }
-    uint32_t q[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) q[j] = (prod[11 + j] >> 31) | (prod[12 + j] << 1);
-    // rem = k - q * L  (fits in 160 bits: rem < 2 L)
-    uint32_t ql[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) ql[j] = 0;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            uint64_t t = (uint64_t)q[a] * consts::GLV_L[b] + ql[a + b] + c;
-            ql[a + b] = (uint32_t)t;
-            c = t >> 32;
-        }
-        ql[a + 4] = (uint32_t)c;
-    }
-    uint32_t rem[5], borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 5; j++) rem[j] = subb(k.l[j], ql[j], borrow);
-    // if rem >= L: rem -= L, q += 1
-    uint32_t d[5], bo = 0;
-#pragma unroll
-    for (int j = 0; j < 5; j++) d[j] = subb(rem[j], j < 4 ? consts::GLV_L[j] : 0u, bo);
-    const bool ge = bo == 0;
-    uint32_t carry = ge ? 1u : 0u;
-    Fr out;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        out.l[j] = ge ? d[j] : rem[j];
-        out.l[4 + j] = addc(q[j], 0u, carry);
-    }
+#include "glv_split_body.inc"  // the statements of glv_split, not a call to it: see glv_split.hpp
     scalars[i] = out;
 }
 
