@@ -754,6 +754,69 @@ KzgRet kzg_debug_poly_batch_quotients(uint8_t *q_out, uint8_t *ys_out, uint8_t *
         const uint8_t *zs, const uint8_t *gammas, size_t n_points, size_t n_polys, const KzgSettings *s);
 /* test hook: out = { elements per workgroup of the fold, polynomials per chunk at n_coeffs = 6145, scalars per chunk, 0 } (csrc/poly_fold_plan.hpp) */
 KzgRet kzg_debug_poly_fold_plan(size_t out[4]);
+/* RESIDENT POLYNOMIAL SETS (csrc/capi_polys.hpp): hand the polynomials over once, then commit, evaluate and open from points and
+ * factors alone - what kzg_g1_points_prepare is for the points.  A Fiat-Shamir prover commits, hashes the commitments into z,
+ * evaluates every polynomial at z, hashes the values into gamma and opens with gamma: five steps, one upload.
+ * kzg_polys_upload: coeffs = n_polys * n_coeffs * 32 bytes big-endian, lowest degree first, host pointer, as kzg_poly_commit_prepared
+ * takes them.  kzg_polys_upload_evals: the values on <w_n_evals> in `order`, as kzg_poly_commit_evals_prepared takes them; the inverse
+ * transform runs once, at upload, and the set holds coefficients.  Limits: n_coeffs <= KZG_POLYS_MAX_COEFFS, n_polys <=
+ * KZG_POLYS_MAX_POLYS, n_coeffs * n_polys <= KZG_POLYS_MAX_SCALARS (2 GB on the device, 32 B per scalar, for as long as the set lives);
+ * n_evals a power of two and a known order; KZG_BADARGS otherwise.  An element >= r is refused ("a coefficient is not below r" / "an
+ * evaluation is not below r": *out untouched, nothing kept).  n_polys == 0 or n_coeffs == 0 gives a valid set; an allocation the
+ * device refuses is KZG_MALLOC.  The set belongs to the handle's device (the first device of a multi-device handle) and to the handle
+ * `s`: it must be freed BEFORE the handle, is immutable, and any number of threads may use it (each call takes the handle's lock, the
+ * upload too).  kzg_polys_shape: the set's n_coeffs and n_polys.  kzg_polys_coeffs: polynomials [first, first + count) in coefficient
+ * form, count * n_coeffs * 32 bytes big-endian canonical.  kzg_polys_free(NULL) does nothing.
+ * The four calls work on the polynomials [first, first + count) of the set - a prover orders its polynomials so that each opening
+ * subset is a range - and are, argument for argument and byte for byte, the host-pointer call on those polynomials:
+ *   kzg_polys_commit                   = kzg_poly_commit_prepared
+ *   kzg_polys_compute_kzg_proofs       = kzg_poly_compute_kzg_proofs_prepared (zs: n_points points PER polynomial, count * n_points * 32)
+ *   kzg_polys_compute_kzg_batch_proofs = kzg_poly_compute_kzg_batch_proofs_prepared (zs, gammas: n_points shared points, one factor each)
+ *   kzg_polys_evaluate: zs = n_points shared points, ys_out[k * n_points + j] = p_(first + k)(z_j), 32 bytes big-endian canonical - the
+ *                       values of the batched opening without its factors, its fold and its sums; needs no point set.
+ * Theirs are the contract - n_coeffs == 0 and 1, count == 0 or n_points == 0 (KZG_OK, nothing written), KZG_POLY_MAX_OPENINGS on count *
+ * n_points (count of a commit), n_coeffs above the point set's count, a z or gamma >= r, the same call twice the same bytes, the handle's
+ * lock - the chunks, the point groups and the rule that a refusal is read before any sum is queued.  In addition KZG_BADARGS when `f`,
+ * `p` and `s` do not belong to one handle and when first + count runs past the set.
+ * On the device the calls run the kernels of the host-pointer calls on views of the set; kzg_polys_evaluate and the individual values
+ * of kzg_polys_compute_kzg_batch_proofs take their tile sums from k_poly_tile_sums_points (csrc/poly_eval_kernels.hpp), which loads and
+ * range-checks a lane's coefficients once for a block of up to 8 points where k_poly_tile_sums does so per (polynomial, point) pair.
+ * kzg_last_timings: [2] the sums, [4] the device stage, [6] the copies - points, factors and outputs; no coefficient crosses the bus
+ * (kzg_debug_polys_stats' fourth counter).  Measured (tools/prof/polys_resident_probe.py, profiles/polys_resident_probe.json; 10 warm flows
+ * each, median (min - max), interleaved): upload + commit + evaluate at 2 points + batch proofs at 2 points for 16 polynomials of 2^20
+ * coefficients 103.497 (102.707 - 104.051) ms against 112.840 (111.866 - 113.741) ms for kzg_poly_commit_prepared +
+ * kzg_poly_compute_kzg_batch_proofs_prepared from host memory; 4 polynomials 34.281 against 36.594 ms; at 2^12 coefficients 14.904 against
+ * 14.691 ms - the sums are the call there and the extra step costs more than the copies it saves. */
+typedef struct KzgPolys KzgPolys;
+#define KZG_POLYS_MAX_COEFFS ((size_t)1 << 20)
+#define KZG_POLYS_MAX_POLYS 4096
+#define KZG_POLYS_MAX_SCALARS ((size_t)1 << 26)
+/* KZG_POLYS_API expands to nothing, as KZG_G1_POINTS_API does: it marks the entry points that take a KzgPolys and no point set, which
+ * the Rust shim does not bind either. */
+#define KZG_POLYS_API
+KzgRet KZG_POLYS_API kzg_polys_upload(KzgPolys **out, const uint8_t *coeffs, size_t n_coeffs, size_t n_polys, const KzgSettings *s);
+KzgRet KZG_POLYS_API kzg_polys_upload_evals(KzgPolys **out, const uint8_t *evals, size_t n_evals, int order, size_t n_polys,
+        const KzgSettings *s);
+KzgRet KZG_POLYS_API kzg_polys_shape(const KzgPolys *f, size_t *n_coeffs, size_t *n_polys);
+KzgRet KZG_POLYS_API kzg_polys_coeffs(const KzgPolys *f, size_t first, size_t count, uint8_t *out);
+void KZG_POLYS_API kzg_polys_free(KzgPolys *f);
+KzgRet KZG_G1_POINTS_API kzg_polys_commit(uint8_t *commitments_out, const KzgG1Points *p, const KzgPolys *f, size_t first, size_t count,
+        const KzgSettings *s);
+KzgRet KZG_POLYS_API kzg_polys_evaluate(uint8_t *ys_out, const KzgPolys *f, size_t first, size_t count, const uint8_t *zs,
+        size_t n_points, const KzgSettings *s);
+KzgRet KZG_G1_POINTS_API kzg_polys_compute_kzg_proofs(uint8_t *proofs_out, uint8_t *ys_out, const KzgG1Points *p, const KzgPolys *f,
+        size_t first, size_t count, const uint8_t *zs, size_t n_points, const KzgSettings *s);
+KzgRet KZG_G1_POINTS_API kzg_polys_compute_kzg_batch_proofs(uint8_t *proofs_out, uint8_t *ys_out, const KzgG1Points *p, const KzgPolys *f,
+        size_t first, size_t count, const uint8_t *zs, const uint8_t *gammas, size_t n_points, const KzgSettings *s);
+/* diagnostic: out = { uploads of resident sets on this handle | coefficient bytes they copied host -> device | calls served from a
+ * resident set (kzg_debug_polys_batch_quotients included) | coefficient bytes THOSE calls copied host -> device: 0 } since the last
+ * reset; reset != 0 zeroes them */
+KzgRet kzg_debug_polys_stats(const KzgSettings *s, uint64_t out[4], int reset);
+/* test hook: kzg_debug_poly_batch_quotients over polynomials [first, first + count) of a resident set */
+KzgRet KZG_POLYS_API kzg_debug_polys_batch_quotients(uint8_t *q_out, uint8_t *ys_out, uint8_t *fold_ys_out, const KzgPolys *f, size_t first,
+        size_t count, const uint8_t *zs, const uint8_t *gammas, size_t n_points, const KzgSettings *s);
+/* test hook: out = { points per block of k_poly_tile_sums_points, lanes of its workgroup, coefficients per workgroup tile, 0 } (csrc/poly_eval_plan.hpp) */
+KzgRet kzg_debug_poly_eval_plan(size_t out[4]);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

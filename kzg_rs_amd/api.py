@@ -176,6 +176,19 @@ def lib():
         L.kzg_verify_kzg_batch_proofs.argtypes = [C.POINTER(C.c_bool), u8, u8, u8, u8, u8, sz, sz, vp]
         L.kzg_debug_poly_batch_quotients.argtypes = [u8, u8, u8, u8, sz, u8, u8, sz, sz, vp]
         L.kzg_debug_poly_fold_plan.argtypes = [C.POINTER(C.c_size_t)]
+        L.kzg_polys_upload.argtypes = [C.POINTER(vp), u8, sz, sz, vp]
+        L.kzg_polys_upload_evals.argtypes = [C.POINTER(vp), u8, sz, C.c_int, sz, vp]
+        L.kzg_polys_shape.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.kzg_polys_coeffs.argtypes = [vp, sz, sz, u8]
+        L.kzg_polys_free.argtypes = [vp]
+        L.kzg_polys_free.restype = None
+        L.kzg_polys_commit.argtypes = [u8, vp, vp, sz, sz, vp]
+        L.kzg_polys_evaluate.argtypes = [u8, vp, sz, sz, u8, sz, vp]
+        L.kzg_polys_compute_kzg_proofs.argtypes = [u8, u8, vp, vp, sz, sz, u8, sz, vp]
+        L.kzg_polys_compute_kzg_batch_proofs.argtypes = [u8, u8, vp, vp, sz, sz, u8, u8, sz, vp]
+        L.kzg_debug_polys_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.kzg_debug_polys_batch_quotients.argtypes = [u8, u8, u8, vp, sz, sz, u8, u8, sz, vp]
+        L.kzg_debug_poly_eval_plan.argtypes = [C.POINTER(C.c_size_t)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -358,6 +371,13 @@ class KzgSettings:
         this handle since the last reset, summed over its shards."""
         out = (C.c_uint64 * 4)()
         _chk(lib().kzg_debug_data_column_stats(self._h, out, 1 if reset else 0))
+        return tuple(int(x) for x in out)
+
+    def polys_stats(self, reset=False):
+        """kzg_debug_polys_stats: (uploads of resident polynomial sets, coefficient bytes they copied host -> device, calls served from a
+        resident set, coefficient bytes those calls copied host -> device - 0) on this handle since the last reset."""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().kzg_debug_polys_stats(self._h, out, 1 if reset else 0))
         return tuple(int(x) for x in out)
 
     def data_column_recover_stats(self, reset=False):
@@ -1041,6 +1061,148 @@ def poly_commit_evals_prepared(point_set, evals, order="natural"):
 
 def poly_compute_kzg_proofs_evals_prepared(point_set, evals, zs, order="natural"):
     return point_set.open_evals(evals, zs, order)
+
+
+def _points32(values, what):
+    """a list of 32-byte values -> (their bytes, how many); anything else raises before a device call"""
+    if isinstance(values, (bytes, bytearray, memoryview, str)):
+        raise TypeError(what + ": a list of 32-byte values")
+    rows = [bytes(v) for v in values]
+    if any(len(r) != 32 for r in rows):
+        raise KzgError("InvalidBytesLength", what + ": 32 bytes each")
+    return b"".join(rows), len(rows)
+
+
+class Polys:
+    """A resident set of polynomials (kzg_polys_upload): polys = a list of polynomials of EQUAL length, as G1Points.commit takes them, go
+    up to the handle's device once; commit, evaluate, open and open_batch then work on a contiguous range [first, first + count) of
+    them (count=None: to the end of the set) from points and factors alone, with the bytes of the G1Points call on the same polynomials.
+    Polys.from_evals uploads values on <w_n> in `order` as G1Points.commit_evals takes them; the set holds coefficients either way.
+    An element that is not below r raises KzgError.  The set keeps its handle alive and must be closed (or dropped) before the handle
+    is freed."""
+
+    def __init__(self, polys, kzg_settings, _order=None):
+        raw, n = _poly_rows(polys)
+        if not isinstance(kzg_settings, KzgSettings):
+            raise TypeError("kzg_settings: a KzgSettings")
+        self._settings = kzg_settings
+        h = C.c_void_p()
+        if _order is None:
+            _chk(lib().kzg_polys_upload(C.byref(h), raw, n, len(polys), kzg_settings._h))
+        else:
+            _chk(lib().kzg_polys_upload_evals(C.byref(h), raw, n, _order, len(polys), kzg_settings._h))
+        self._h = h
+
+    @classmethod
+    def from_evals(cls, evals, kzg_settings, order="natural"):
+        return cls(evals, kzg_settings, _order=_poly_order(order))
+
+    def _shape(self):
+        n, m = C.c_size_t(0), C.c_size_t(0)
+        _chk(lib().kzg_polys_shape(self._h, C.byref(n), C.byref(m)))
+        return n.value, m.value
+
+    def __len__(self):
+        return self._shape()[1]
+
+    def n_coeffs(self):
+        return self._shape()[0]
+
+    def _range(self, first, count):
+        if not isinstance(first, int) or not (count is None or isinstance(count, int)):
+            raise TypeError("first, count: integers")
+        if first < 0 or (count is not None and count < 0):
+            raise KzgError("BadArgs", "first, count: not negative")
+        return first, (max(len(self) - first, 0) if count is None else count)
+
+    def coeffs(self, first=0, count=None):
+        """polynomials [first, first + count) in coefficient form: a list of lists of 32-byte big-endian canonical values"""
+        first, count = self._range(first, count)
+        n = self.n_coeffs()
+        out = C.create_string_buffer(max(32 * n * count, 1))
+        _chk(lib().kzg_polys_coeffs(self._h, first, count, out))
+        return [[out.raw[32 * (k * n + i): 32 * (k * n + i + 1)] for i in range(n)] for k in range(count)]
+
+    def commit(self, point_set, first=0, count=None):
+        """G1Points.commit of the range (kzg_polys_commit) -> a list of 48-byte commitments"""
+        if not isinstance(point_set, G1Points):
+            raise TypeError("point_set: a G1Points")
+        first, count = self._range(first, count)
+        out = C.create_string_buffer(48 * max(count, 1))
+        _chk(lib().kzg_polys_commit(out, point_set._h, self._h, first, count, self._settings._h))
+        return [out.raw[48 * k: 48 * k + 48] for k in range(count)]
+
+    def evaluate(self, zs, first=0, count=None):
+        """every polynomial of the range at every point of zs (kzg_polys_evaluate) -> ys[k][j] = p_(first + k)(zs[j]); needs no point set"""
+        zraw, n_points = _points32(zs, "zs")
+        first, count = self._range(first, count)
+        ys = C.create_string_buffer(32 * max(n_points * count, 1))
+        _chk(lib().kzg_polys_evaluate(ys, self._h, first, count, zraw, n_points, self._settings._h))
+        return [[ys.raw[32 * (k * n_points + j): 32 * (k * n_points + j + 1)] for j in range(n_points)] for k in range(count)]
+
+    def open(self, point_set, zs, first=0, count=None):
+        """G1Points.open of the range (kzg_polys_compute_kzg_proofs): zs[k] = the points of polynomial first + k -> (proofs, ys)"""
+        if not isinstance(point_set, G1Points):
+            raise TypeError("point_set: a G1Points")
+        first, count = self._range(first, count)
+        if isinstance(zs, (bytes, bytearray, memoryview, str)):
+            raise TypeError("zs: one row of points per polynomial")
+        if len(zs) != count or any(len(row) != len(zs[0]) for row in zs):
+            raise KzgError("InvalidBytesLength", "zs: one row of equally many points per polynomial")
+        n_points = len(zs[0]) if zs else 0
+        zraw = b"".join(_points32(row, "zs")[0] for row in zs)
+        n = n_points * count
+        proofs, ys = C.create_string_buffer(48 * max(n, 1)), C.create_string_buffer(32 * max(n, 1))
+        _chk(lib().kzg_polys_compute_kzg_proofs(proofs, ys, point_set._h, self._h, first, count, zraw, n_points, self._settings._h))
+        cut = lambda buf, w: [[buf.raw[w * (k * n_points + j): w * (k * n_points + j + 1)] for j in range(n_points)] for k in range(count)]
+        return cut(proofs, 48), cut(ys, 32)
+
+    def open_batch(self, point_set, zs, gammas, first=0, count=None):
+        """G1Points.open_batch of the range (kzg_polys_compute_kzg_batch_proofs) -> (proofs[n_points], ys[count][n_points])"""
+        if not isinstance(point_set, G1Points):
+            raise TypeError("point_set: a G1Points")
+        zraw, n_points = _points32(zs, "zs")
+        graw, n_gammas = _points32(gammas, "gammas")
+        if n_gammas != n_points:
+            raise KzgError("InvalidBytesLength", "gammas: one batching factor per point")
+        first, count = self._range(first, count)
+        proofs, ys = C.create_string_buffer(48 * max(n_points, 1)), C.create_string_buffer(32 * max(n_points * count, 1))
+        _chk(lib().kzg_polys_compute_kzg_batch_proofs(proofs, ys, point_set._h, self._h, first, count, zraw, graw, n_points, self._settings._h))
+        return ([proofs.raw[48 * j: 48 * j + 48] for j in range(n_points)],
+                [[ys.raw[32 * (k * n_points + j): 32 * (k * n_points + j + 1)] for j in range(n_points)] for k in range(count)])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
+                lib().kzg_polys_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def polys_upload(polys, kzg_settings):
+    return Polys(polys, kzg_settings)
+
+
+def polys_upload_evals(evals, kzg_settings, order="natural"):
+    return Polys.from_evals(evals, kzg_settings, order)
+
+
+def poly_eval_plan():
+    """kzg_debug_poly_eval_plan: (points per block of k_poly_tile_sums_points, lanes of its workgroup, coefficients per tile, 0); host code"""
+    out = (C.c_size_t * 4)()
+    _chk(lib().kzg_debug_poly_eval_plan(out))
+    return tuple(int(x) for x in out)
 
 
 def fr_ntt(values, kzg_settings, inverse=False, order="natural"):

@@ -49,8 +49,31 @@ static KzgRet poly_fr_ntt_bufs(const KzgSettings* s, FrNttBufs** nb_out, uint32_
     return KZG_OK;
 }
 
+// Every host -> device copy of coefficients (or evaluations) of the polynomial family is queued here.  A call on a resident set
+// (capi_polys.hpp) queues none: the fourth counter of kzg_debug_polys_stats says whether one did.
+static hipError_t poly_coeffs_h2d(const KzgSettings* s, uint8_t* dst, const uint8_t* src, size_t bytes, hipStream_t st) {
+    if (s->polys_resident_call) s->polys_stats[3].fetch_add(bytes, std::memory_order_relaxed);
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+}
+
+// A call on a resident set, from taking the handle's lock to leaving it: counted as served, and poly_coeffs_h2d counts what it copies meanwhile.
+struct PolyResidentCall {
+    const KzgSettings* s;
+    PolyResidentCall(const KzgSettings* s_, bool resident) : s(resident ? s_ : nullptr) {
+        if (!s) return;
+        s->polys_resident_call = true;
+        s->polys_stats[2].fetch_add(1, std::memory_order_relaxed);
+    }
+    ~PolyResidentCall() {
+        if (s) s->polys_resident_call = false;
+    }
+    PolyResidentCall(const PolyResidentCall&) = delete;
+    PolyResidentCall& operator=(const PolyResidentCall&) = delete;
+};
+
 // what one call asks for; zs == nullptr: the commit (a "pair" is a polynomial, n_points = 1).  evals: `coeffs` holds the values on
-// <w_n_coeffs> in `order`, n_coeffs a power of two
+// <w_n_coeffs> in `order`, n_coeffs a power of two.  resident: the call's polynomials lie on the device already (a range of a KzgPolys,
+// capi_polys.hpp: coefficient form, as d_stage holds them) - a chunk is then a view of them and `coeffs` is not read
 struct PolyCall {
     const uint8_t* coeffs;
     size_t n_coeffs;
@@ -58,6 +81,7 @@ struct PolyCall {
     size_t n_points, n_polys;
     bool evals = false;
     int order = KZG_POLY_ORDER_NATURAL;
+    const uint8_t* resident = nullptr;
     size_t pairs() const { return n_points * n_polys; }
 };
 static_assert(PQ_MAX_OPENINGS == KZG_POLY_MAX_OPENINGS && PQ_MAX_COEFFS == KZG_G1_POINTS_MAX, "the plan's limits are the header's");
@@ -74,7 +98,7 @@ static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk
         const size_t lo = pq_chunk_lo(k, chunk), m = pq_chunk_size(c.pairs(), k, chunk);
         polys = std::max(polys, pq_poly_end(lo, m, c.n_points) - pq_poly_first(lo, c.n_points));
     }
-    HIPCHK(s->fb_sum->d_stage.grow(pq_stage_bytes(c.n_coeffs, polys)));
+    if (!c.resident) HIPCHK(s->fb_sum->d_stage.grow(pq_stage_bytes(c.n_coeffs, polys)));
     HIPCHK(s->fb_sum->d_scalars.grow(pq_quotient_scalars(c.n_coeffs, chunk)));
     if (c.evals) {
         const KzgRet rc = fr_ntt_reserve(s, s->poly->ntt, c.n_coeffs, polys);
@@ -83,8 +107,8 @@ static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk
     return s->poly->reserve(c.n_coeffs, chunk);
 }
 
-// Pairs [lo, lo + m) of the call: upload (the coefficients only if the chunk before did not leave the same polynomials there), the
-// stage's launches, the verdict.  On KZG_OK the chunk's quotients (the commit: its coefficients) are in b.d_scalars, [pair][n_coeffs],
+// Pairs [lo, lo + m) of the call: upload (the coefficients only if the chunk before did not leave the same polynomials there; none of
+// a resident call, whose chunk is a view of the set), the stage's launches, the verdict.  On KZG_OK the chunk's quotients (the commit: its coefficients) are in b.d_scalars, [pair][n_coeffs],
 // and its y in pb.d_ys.  ms: [0] copies [1] the launches, added to.
 struct PolyStaged {
     size_t first = 1, end = 0;  // the polynomials in d_stage
@@ -93,9 +117,10 @@ static KzgRet poly_stage(const KzgSettings* s, FbSumBufs& b, PolyBufs& pb, const
     const size_t n = c.n_coeffs, k0 = pq_poly_first(lo, c.n_points), k1 = pq_poly_end(lo, m, c.n_points);
     hipStream_t st = s->s1;
     HIPCHK(hipEventRecord(s->ev[0], st));
-    const bool fresh = staged.first != k0 || staged.end != k1;
+    const bool fresh = !c.resident && (staged.first != k0 || staged.end != k1);
+    const uint8_t* const src = c.resident ? c.resident + 32 * n * k0 : b.d_stage.p;  // the chunk's polynomials [k0, k1)
     if (fresh) {
-        HIPCHK(hipMemcpyAsync(b.d_stage.p, c.coeffs + 32 * n * k0, pq_stage_bytes(n, k1 - k0), hipMemcpyHostToDevice, st));
+        HIPCHK(poly_coeffs_h2d(s, b.d_stage.p, c.coeffs + 32 * n * k0, pq_stage_bytes(n, k1 - k0), st));
         staged.first = k0, staged.end = k1;
     }
     if (c.zs) HIPCHK(hipMemcpyAsync(pb.d_zs.p, c.zs + 32 * lo, 32 * m, hipMemcpyHostToDevice, st));
@@ -108,14 +133,14 @@ static KzgRet poly_stage(const KzgSettings* s, FbSumBufs& b, PolyBufs& pb, const
     }
     if (c.zs) {
         const PqGrid gt = pq_grid_tiles(n, m), gc = pq_grid_carries(m);
-        hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n,
+        hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, src, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n,
                            (int)c.n_points, (int)lo, (int)k0);
         hipLaunchKernelGGL(k_poly_tile_carries, dim3(gc.x, gc.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_tsum.p, pb.d_carry.p, (int)gt.x);
-        hipLaunchKernelGGL(k_poly_apply, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_carry.p, b.d_scalars.p,
+        hipLaunchKernelGGL(k_poly_apply, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, src, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_carry.p, b.d_scalars.p,
                            pb.d_ys.p, (int)n, (int)c.n_points, (int)lo, (int)k0);
     } else {
         const PqGrid gd = pq_grid_decode(n, m);
-        hipLaunchKernelGGL(k_poly_decode, dim3(gd.x, gd.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, b.d_scalars.p, pb.d_flag.p, (int)n);
+        hipLaunchKernelGGL(k_poly_decode, dim3(gd.x, gd.y), dim3(PQ_THREADS), 0, st, src, b.d_scalars.p, pb.d_flag.p, (int)n);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev[5], st));
@@ -149,8 +174,9 @@ static KzgRet poly_run(uint8_t* sums_out, uint8_t* ys_out, const KzgG1Points* p,
     if (c.n_polys > KZG_POLY_MAX_OPENINGS || c.n_points > KZG_POLY_MAX_OPENINGS || c.pairs() > KZG_POLY_MAX_OPENINGS)
         return fail(KZG_BADARGS, std::string(who) + ": more than 4096 openings");
     const size_t pairs = c.pairs(), n = c.n_coeffs;
-    if (!sums_out || (n && !c.coeffs)) return fail(KZG_BADARGS, "null argument");
+    if (!sums_out || (n && !c.coeffs && !c.resident)) return fail(KZG_BADARGS, "null argument");
     std::lock_guard<std::mutex> lk(s->mu);
+    PolyResidentCall resident_call(s, c.resident != nullptr);
     s->timings[2] = s->timings[4] = s->timings[6] = 0.0f;
     if (n == 0) {  // the zero polynomial
         poly_identities(sums_out, pairs);

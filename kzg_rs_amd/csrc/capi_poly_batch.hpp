@@ -14,7 +14,8 @@
 // fixed-base sum (fb_sum_queue<FbEntry64>) per POINT and k_jac_compress_n, as poly_run does per pair.  The verdict on a group's elements is read before
 // any of ITS sums is queued; a call of one group has queued nothing when it refuses.
 
-// what one call asks for (evals: `coeffs` holds the values on <w_n_coeffs> in `order`, n_coeffs a power of two)
+// what one call asks for (evals: `coeffs` holds the values on <w_n_coeffs> in `order`, n_coeffs a power of two; resident: the call's
+// polynomials lie on the device already, as in PolyCall)
 struct PolyBatchCall {
     const uint8_t* coeffs;
     size_t n_coeffs;
@@ -22,6 +23,7 @@ struct PolyBatchCall {
     size_t n_points, n_polys;
     bool evals = false;
     int order = KZG_POLY_ORDER_NATURAL;
+    const uint8_t* resident = nullptr;
     size_t pairs() const { return n_points * n_polys; }
     size_t chunk_polys() const { return std::min(n_polys, pf_chunk_polys(n_coeffs)); }
     size_t group_points() const { return std::min(n_points, pf_group_points(n_coeffs)); }
@@ -37,7 +39,7 @@ static KzgRet poly_batch_buffers(const KzgSettings* s, const PolyBatchCall& c) {
     const size_t n = c.n_coeffs, cp = c.chunk_polys(), gp = c.group_points();
     FbSumBufs& b = *s->fb_sum;
     PolyBufs& pb = *s->poly;
-    HIPCHK(b.d_stage.grow(pf_stage_bytes(n, cp)));
+    if (!c.resident) HIPCHK(b.d_stage.grow(pf_stage_bytes(n, cp)));
     HIPCHK(b.d_scalars.grow(pf_quotient_scalars(n, gp)));
     HIPCHK(pb.d_fold.grow(pf_fold_bytes(n, gp)));
     HIPCHK(pb.d_zs.grow(32 * pf_pairs(cp, gp)));
@@ -53,6 +55,22 @@ static KzgRet poly_batch_buffers(const KzgSettings* s, const PolyBatchCall& c) {
     return KZG_OK;
 }
 
+// Every p_k(z_j) of `m` polynomials at `src` ([poly][n], polynomial k0 of the call first) and the g points at the head of pb.d_zs (the
+// group's points, repeated once per polynomial: k_poly_eval_tiles reads pair q's z at zs[q]) -> their places in pb.d_bys, rows of
+// ys_stride values.  by_blocks: the tile sums by k_poly_tile_sums_points (poly_eval_kernels.hpp: a block of points per pass over the
+// coefficients), else by k_poly_tile_sums (a pair per workgroup); the sums are the same.  Queued on st, nothing is waited for.
+static void poly_values_queue(hipStream_t st, PolyBufs& pb, const uint8_t* src, size_t n, size_t m, size_t g, size_t k0, size_t ys_stride, size_t j0, bool by_blocks) {
+    const PqGrid gt = pq_grid_tiles(n, pf_pairs(m, g));
+    if (by_blocks) {
+        const PqGrid ge = pe_grid(n, m, g);
+        hipLaunchKernelGGL(k_poly_tile_sums_points, dim3(ge.x, ge.y), dim3(PE_THREADS), 0, st, src, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n, (int)g);
+    } else {
+        hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, src, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n, (int)g, 0, 0);
+    }
+    hipLaunchKernelGGL(k_poly_eval_tiles, dim3(gt.y), dim3(PF_EVAL_THREADS), 0, st, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_tsum.p, pb.d_bys.p, (int)pq_tiles(n), (int)g, (int)k0,
+                       (int)ys_stride, (int)j0);
+}
+
 // Points [j0, j0 + g) of the call: every chunk of polynomials (upload, transform, fold, the individual values), the scan of the fold
 // buffer, the verdict.  On KZG_OK the group's quotients are in b.d_scalars, [point][n_coeffs], f_j(z_j) in pb.d_fys, and every p_k(z_j) of
 // the group at its place in pb.d_bys.  zrep: host scratch of 32 x chunk_polys x g bytes.  ms: [0] copies [1] the launches, added to.
@@ -65,24 +83,21 @@ static KzgRet poly_batch_stage(const KzgSettings* s, FbSumBufs& b, PolyBufs& pb,
     HIPCHK(hipMemcpyAsync(pb.d_gammas.p, c.gammas + 32 * j0, 32 * g, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(pb.d_flag.p, 0, 4, st));
     const PqGrid gf = pf_grid_fold(n, g);
-    const int tiles = (int)pq_tiles(n);
     float t = 0.f;
     for (size_t v = 0; v < chunks; v++) {
         const size_t ch = pf_visit(chunks, v), k0 = pf_chunk_first(ch, cp), k1 = pf_chunk_end(c.n_polys, ch, cp), m = k1 - k0;
         if (v) HIPCHK(hipEventRecord(s->ev[0], st));
-        HIPCHK(hipMemcpyAsync(b.d_stage.p, c.coeffs + 32 * n * k0, pf_stage_bytes(n, m), hipMemcpyHostToDevice, st));
+        const uint8_t* const src = c.resident ? c.resident + 32 * n * k0 : b.d_stage.p;  // the chunk: a view of the set, or the upload
+        if (!c.resident) HIPCHK(poly_coeffs_h2d(s, b.d_stage.p, c.coeffs + 32 * n * k0, pf_stage_bytes(n, m), st));
         HIPCHK(hipEventRecord(s->ev[1], st));
         HIPCHK(hipEventRecord(s->ev[4], st));
         if (c.evals) {  // evaluations -> coefficients, in place
             const KzgRet rc = fr_ntt_queue(s, pb.ntt, b.d_stage.p, pb.d_flag.p, frntt_log2(n), m, true, c.order);
             if (rc != KZG_OK) return rc;
         }
-        hipLaunchKernelGGL(k_poly_fold, dim3(gf.x, gf.y), dim3(PF_THREADS), 0, st, (const uint8_t*)b.d_stage.p, (const uint8_t*)pb.d_gammas.p, pb.d_fold.p, pb.d_flag.p, (int)n, (int)m,
+        hipLaunchKernelGGL(k_poly_fold, dim3(gf.x, gf.y), dim3(PF_THREADS), 0, st, src, (const uint8_t*)pb.d_gammas.p, pb.d_fold.p, pb.d_flag.p, (int)n, (int)m,
                            (int)(v == 0));
-        const PqGrid gt = pq_grid_tiles(n, pf_pairs(m, g));
-        hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)b.d_stage.p, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n, (int)g, 0, 0);
-        hipLaunchKernelGGL(k_poly_eval_tiles, dim3(gt.y), dim3(PF_EVAL_THREADS), 0, st, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_tsum.p, pb.d_bys.p, tiles, (int)g, (int)k0,
-                           (int)c.n_points, (int)j0);
+        poly_values_queue(st, pb, src, n, m, g, k0, c.n_points, j0, c.resident != nullptr);
         HIPCHK(hipGetLastError());
         if (v + 1 < chunks) {  // (the next upload waits behind these launches anyway: the wait only reads the clocks)
             HIPCHK(hipEventRecord(s->ev[5], st));
@@ -126,8 +141,9 @@ static KzgRet poly_batch_run(uint8_t* proofs_out, uint8_t* ys_out, const KzgG1Po
     if (c.n_polys > KZG_POLY_MAX_OPENINGS || c.n_points > KZG_POLY_MAX_OPENINGS || c.pairs() > KZG_POLY_MAX_OPENINGS)
         return fail(KZG_BADARGS, std::string(who) + ": more than 4096 openings");
     const size_t pairs = c.pairs(), n = c.n_coeffs;
-    if (!proofs_out || (n && !c.coeffs)) return fail(KZG_BADARGS, "null argument");
+    if (!proofs_out || (n && !c.coeffs && !c.resident)) return fail(KZG_BADARGS, "null argument");
     std::lock_guard<std::mutex> lk(s->mu);
+    PolyResidentCall resident_call(s, c.resident != nullptr);
     s->timings[2] = s->timings[4] = s->timings[6] = 0.0f;
     if (n == 0) {  // zero polynomials
         poly_identities(proofs_out, c.n_points);
@@ -254,20 +270,21 @@ extern "C" KzgRet kzg_verify_kzg_batch_proofs(bool* ok_out, const uint8_t* commi
 
 // test hook (tests/test_gpu_poly_batch_open.py): the device stage alone - q_out[point][i] the folded quotients, ys_out[poly][point],
 // fold_ys_out[point] = f_j(z_j) (either may be NULL)
-extern "C" KzgRet kzg_debug_poly_batch_quotients(uint8_t* q_out, uint8_t* ys_out, uint8_t* fold_ys_out, const uint8_t* coeffs, size_t n_coeffs, const uint8_t* zs,
-                                                 const uint8_t* gammas, size_t n_points, size_t n_polys, const KzgSettings* s) try {
-    const PolyBatchCall c{coeffs, n_coeffs, zs, gammas, n_points, n_polys};
+// (kzg_debug_polys_batch_quotients, capi_polys.hpp, is the same hook over a range of a resident set)
+static KzgRet poly_batch_quotients_run(uint8_t* q_out, uint8_t* ys_out, uint8_t* fold_ys_out, const PolyBatchCall& c, const KzgSettings* s) {
+    const size_t n_coeffs = c.n_coeffs, n_points = c.n_points, n_polys = c.n_polys;
     if (!s) return fail(KZG_BADARGS, "null argument");
     if (n_polys == 0 || n_points == 0) return KZG_OK;
     if (n_coeffs > PQ_MAX_COEFFS || n_polys > PQ_MAX_OPENINGS || n_points > PQ_MAX_OPENINGS || c.pairs() > PQ_MAX_OPENINGS) return fail(KZG_BADARGS, "bad argument");
     const size_t n = n_coeffs;
-    if (!zs || !gammas || (n && (!coeffs || !q_out))) return fail(KZG_BADARGS, "null argument");
+    if (!c.zs || !c.gammas || (n && ((!c.coeffs && !c.resident) || !q_out))) return fail(KZG_BADARGS, "null argument");
     if (n == 0) {
         if (ys_out) memset(ys_out, 0, 32 * c.pairs());
         if (fold_ys_out) memset(fold_ys_out, 0, 32 * n_points);
         return KZG_OK;
     }
     std::lock_guard<std::mutex> lk(s->mu);
+    PolyResidentCall resident_call(s, c.resident != nullptr);
     HIPCHK(hipSetDevice(s->device));
     select_streams(s, (size_t)-1);
     KzgRet rc = poly_batch_buffers(s, c);
@@ -293,6 +310,11 @@ extern "C" KzgRet kzg_debug_poly_batch_quotients(uint8_t* q_out, uint8_t* ys_out
     }
     s->timings[4] = ms[1], s->timings[6] = ms[0];
     return KZG_OK;
+}
+
+extern "C" KzgRet kzg_debug_poly_batch_quotients(uint8_t* q_out, uint8_t* ys_out, uint8_t* fold_ys_out, const uint8_t* coeffs, size_t n_coeffs, const uint8_t* zs,
+                                                 const uint8_t* gammas, size_t n_points, size_t n_polys, const KzgSettings* s) try {
+    return poly_batch_quotients_run(q_out, ys_out, fold_ys_out, PolyBatchCall{coeffs, n_coeffs, zs, gammas, n_points, n_polys}, s);
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
 }

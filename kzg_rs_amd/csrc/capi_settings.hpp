@@ -141,6 +141,10 @@ struct KzgSettings {
     mutable std::atomic<uint64_t> data_column_stats[4] = {};
     // kzg_debug_data_column_recover_stats (capi_data_column_recover.hpp): ranges run on this shard | blobs | columns written | index-list set-ups
     mutable std::atomic<uint64_t> data_column_recover_stats[4] = {};
+    // kzg_debug_polys_stats (capi_polys.hpp): uploads of resident polynomial sets | coefficient bytes they copied host -> device | calls
+    // served from a resident set | coefficient bytes THOSE calls copied host -> device (poly_coeffs_h2d, capi_poly.hpp: stays 0)
+    mutable std::atomic<uint64_t> polys_stats[4] = {};
+    mutable bool polys_resident_call = false;  // the call that holds the lock reads a resident set (PolyResidentCall)
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the
     // last launch group, and summed over the groups finished since the last reset (kzg_kernel_stamp_totals)

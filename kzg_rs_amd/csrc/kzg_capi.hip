@@ -34,6 +34,7 @@
 #include "blob_cell_kernels.hpp"
 #include "poly_quotient_kernels.hpp"
 #include "poly_fold_kernels.hpp"
+#include "poly_eval_kernels.hpp"
 #include "fr_ntt_kernels.hpp"
 
 using namespace kzg;
@@ -75,6 +76,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_fr_ntt.hpp"
 #include "capi_poly.hpp"
 #include "capi_poly_batch.hpp"
+#include "capi_polys.hpp"
 #include "capi_cells.hpp"
 #include "capi_cell_groups.hpp"
 #include "capi_cell_prover.hpp"
