@@ -817,6 +817,68 @@ KzgRet KZG_POLYS_API kzg_debug_polys_batch_quotients(uint8_t *q_out, uint8_t *ys
         size_t count, const uint8_t *zs, const uint8_t *gammas, size_t n_points, const KzgSettings *s);
 /* test hook: out = { points per block of k_poly_tile_sums_points, lanes of its workgroup, coefficients per workgroup tile, 0 } (csrc/poly_eval_plan.hpp) */
 KzgRet kzg_debug_poly_eval_plan(size_t out[4]);
+/* MULTI-POINT OPENING AT PER-GROUP POINT SETS (csrc/capi_polys_multiopen.hpp): the opening of Boneh, Drake, Fisch and Gabizon (BDFG20
+ * section 4, "SHPLONK") over polynomials [first, first + count) of a resident set.  The range is cut into n_groups consecutive groups;
+ * group g holds group_sizes[g] >= 1 polynomials, all opened at the group's own set_sizes[g] >= 1 pairwise distinct points - a PLONK
+ * permutation polynomial at {z, z w}, a halo2 column at {z}, {z, z w} or {z, z w, z / w}.  The proof is TWO G1 elements and the prover
+ * takes TWO fixed-base sums whatever the number of points, where kzg_polys_compute_kzg_batch_proofs takes one of each per distinct
+ * point; the verifier reads [tau]G2 alone, so any handle of the right tau serves it (kzg_settings_from_tau_g2).
+ * All arithmetic mod r; p_i = polynomial i of the call, g(i) its group, S_g the group's points, T the union of the S_g as field values,
+ * Z_A = prod_(s in A) (X - s), r_i the interpolant of p_i on S_g(i).  gamma and z come from the caller's transcript: gamma after the
+ * values, z after W.
+ *   kzg_polys_multiopen_begin:  h = sum_g (sum_(i in g) gamma^i (p_i - r_i)) / Z_(S_g), w_out = W = [h(tau)], ys_out = the values.
+ *   kzg_polys_multiopen_finish: c_i = gamma^i Z_(T \ S_g(i))(z), M = sum_i c_i p_i - Z_T(z) h, w2_out = W' = [((M - M(z)) / (X - z))(tau)],
+ *                               y_out = M(z) (for cross-checking; may be NULL).
+ *   kzg_verify_kzg_multiopen:   y = sum_i c_i r_i(z) from the claimed values, F = sum_i c_i C_i - Z_T(z) W (one sum of kzg_g1_msm's kind over
+ *                               count + 1 points), *ok = what kzg_verify_kzg_proof(F, z, y, W') answers.
+ * points: sum_g set_sizes[g] * 32 bytes big-endian, group after group.  ys / ys_out: group after group and, per polynomial of the group
+ * in order, its set_sizes[g] values in the order of the group's points - sum_g group_sizes[g] * set_sizes[g] * 32 bytes, canonical; ys_out
+ * may be NULL.  commitments: count * 48 bytes.  Host pointers; the handle's lock per call; the set's device; the same call twice gives the
+ * same bytes.  n_coeffs == 0 gives the identity 0xC0 00 .. 00 as W and W' and zero values; polynomials shorter than a group's point
+ * count add nothing to h.
+ * KZG_BADARGS - nothing kept, *out and the outputs untouched, the handle usable afterwards - for a null pointer; `f`, `p`, `s` (and the
+ * state) not of one handle; a range past the set; n_coeffs above the point set's count; n_groups == 0 or above KZG_MULTIOPEN_MAX_GROUPS; a
+ * group size or set size of 0; a set size above KZG_MULTIOPEN_MAX_SET_POINTS; group sizes that do not add up to count; more than
+ * KZG_POLY_MAX_OPENINGS values (sum_g group_sizes[g] * set_sizes[g]); a point, gamma or z that is >= r; two equal points inside one group;
+ * z among the points.  The same point may appear in several groups.  Equality of points is decided on the host by comparing the canonical
+ * bytes; the host does no field arithmetic.  The verifier refuses the same and, in kzg_verify_kzg_proof's words, what that call refuses
+ * of the commitments, W and W'; a claimed value >= r is "a claimed value is not below r".
+ * The KzgMultiOpen state keeps h (32 B per coefficient) and the call's small arguments on the device.  It belongs to `f`, `p` and `s`
+ * and must be freed BEFORE them; it is immutable, so kzg_polys_multiopen_finish may be called any number of times and from several
+ * threads.  kzg_multiopen_free(NULL) does nothing.
+ * On the device (csrc/poly_multiopen_kernels.hpp): by partial fractions h is a weighted sum of single-point quotients of the folded
+ * polynomials F_g = sum_(i in g) gamma^i p_i, so a group takes one launch of k_poly_lincomb (the fold), the three scan launches of the
+ * single-point opening on its (F_g, s) pairs and one more k_poly_lincomb that adds the weighted quotients to h; the values come from the
+ * launches of kzg_polys_evaluate.  finish is one k_poly_lincomb over the range and h, one scan and one sum.  Powers, weights, vanishing
+ * and Lagrange values come from one small kernel per side.  kzg_last_timings: [2] the sum, [4] the device stage, [6] the copies - points,
+ * factors and outputs; no coefficient crosses the bus (kzg_debug_polys_stats counts both steps as calls served; its fourth counter stays 0).
+ * Measured (tools/prof/polys_multiopen_probe.py, profiles/polys_multiopen_probe.json; 10 warm runs each, median (min - max), interleaved):
+ * groups {z}, {z, z w}, {z, z w, z / w} over m/2, m/4 and m/4 polynomials, begin + finish against one kzg_polys_compute_kzg_batch_proofs
+ * per distinct point over the range that holds it, on the same resident set.  16 polynomials of 2^20 coefficients 12.921 (12.726 - 13.083)
+ * ms against 17.379 (17.027 - 17.594) ms, ratio 1.345: the sums 9.64 against 14.53 ms, the device stage 2.54 against 1.72 ms; 4 polynomials
+ * 12.221 against 16.578 ms; at 2^16 coefficients 4.231 against 5.310 ms; at 2^12 3.144 against 3.714 ms - there the stage, 0.98 ms, costs
+ * more than the 0.73 ms sum it saves, and the call is ahead only by the 0.48 ms today's route spends on its own stages. */
+typedef struct KzgMultiOpen KzgMultiOpen;
+#define KZG_MULTIOPEN_MAX_GROUPS 16
+#define KZG_MULTIOPEN_MAX_SET_POINTS 8
+KzgRet KZG_G1_POINTS_API kzg_polys_multiopen_begin(KzgMultiOpen **out, uint8_t w_out[48], uint8_t *ys_out,
+        const KzgG1Points *p, const KzgPolys *f, size_t first, size_t count,
+        const size_t *group_sizes, const size_t *set_sizes, size_t n_groups,
+        const uint8_t *points, const uint8_t gamma[32], const KzgSettings *s);
+KzgRet KZG_G1_POINTS_API kzg_polys_multiopen_finish(uint8_t w2_out[48], uint8_t y_out[32], const KzgMultiOpen *m,
+        const uint8_t z[32], const KzgSettings *s);
+void   KZG_G1_POINTS_API kzg_multiopen_free(KzgMultiOpen *m);
+KzgRet kzg_verify_kzg_multiopen(bool *ok, const uint8_t *commitments, const size_t *group_sizes, const size_t *set_sizes,
+        size_t n_groups, const uint8_t *points, const uint8_t *ys, const uint8_t gamma[32], const uint8_t z[32],
+        const uint8_t w[48], const uint8_t w2[48], const KzgSettings *s);
+/* test hook: the device stages of the two steps alone, no point set needed.  h_out: n_coeffs * 32 and ys_out as above (either may be
+ * NULL); with z (may be NULL): q_out = the n_coeffs coefficients of (M - M(z)) / (X - z) and y_out = M(z) (either may be NULL).
+ * Big-endian canonical scalars; the limits and refusals of the two calls. */
+KzgRet KZG_POLYS_API kzg_debug_polys_multiopen_quotients(uint8_t *h_out, uint8_t *ys_out, uint8_t *q_out, uint8_t *y_out,
+        const KzgPolys *f, size_t first, size_t count, const size_t *group_sizes, const size_t *set_sizes, size_t n_groups,
+        const uint8_t *points, const uint8_t gamma[32], const uint8_t *z, const KzgSettings *s);
+/* test hook: out = { KZG_MULTIOPEN_MAX_GROUPS, KZG_MULTIOPEN_MAX_SET_POINTS, elements per workgroup of k_poly_lincomb, lanes of a scalar kernel } (csrc/poly_multiopen_plan.hpp) */
+KzgRet kzg_debug_poly_multiopen_plan(size_t out[4]);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

@@ -189,6 +189,14 @@ def lib():
         L.kzg_debug_polys_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.kzg_debug_polys_batch_quotients.argtypes = [u8, u8, u8, vp, sz, sz, u8, u8, sz, vp]
         L.kzg_debug_poly_eval_plan.argtypes = [C.POINTER(C.c_size_t)]
+        szp = C.POINTER(C.c_size_t)
+        L.kzg_polys_multiopen_begin.argtypes = [C.POINTER(vp), u8, u8, vp, vp, sz, sz, szp, szp, sz, u8, u8, vp]
+        L.kzg_polys_multiopen_finish.argtypes = [u8, u8, vp, u8, vp]
+        L.kzg_multiopen_free.argtypes = [vp]
+        L.kzg_multiopen_free.restype = None
+        L.kzg_verify_kzg_multiopen.argtypes = [C.POINTER(C.c_bool), u8, szp, szp, sz, u8, u8, u8, u8, u8, u8, vp]
+        L.kzg_debug_polys_multiopen_quotients.argtypes = [u8, u8, u8, u8, vp, sz, sz, szp, szp, sz, u8, u8, u8, vp]
+        L.kzg_debug_poly_multiopen_plan.argtypes = [szp]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -555,6 +563,21 @@ class KzgProof:
         _chk(lib().kzg_verify_kzg_batch_proofs(ok, b"".join(c.data for c in commitments), b"".join(z.data for z in zs), b"".join(g.data for g in gammas),
                                                b"".join(y.data for row in ys for y in row), b"".join(p.data for p in proofs), n_polys, n_points, kzg_settings._h))
         return [bool(ok[j]) for j in range(n_points)]
+
+    @staticmethod
+    def verify_kzg_multiopen(commitments, groups, ys, gamma, z, w, w2, kzg_settings):
+        """The verifier of Polys.multiopen (kzg_verify_kzg_multiopen): commitments[count], w and w2 as Bytes48; groups = [(n_polys, [points
+        as Bytes32 ...]), ...]; ys[count] = per polynomial its claimed values at its group's points, as Bytes32; gamma, z as Bytes32 -> bool."""
+        sizes, sets, praw = _multiopen_groups(groups, lambda p: p.data)
+        per_poly = [t for m, t in zip(sizes, sets) for _ in range(m)]
+        if len(commitments) != len(per_poly) or len(ys) != len(per_poly) or any(len(row) != t for row, t in zip(ys, per_poly)):
+            raise KzgError("InvalidBytesLength", "one commitment and one row of values per polynomial of the groups, one value per point of its group")
+        n_groups = len(sizes)
+        arr = lambda v: (C.c_size_t * max(n_groups, 1))(*v)
+        ok = C.c_bool(False)
+        _chk(lib().kzg_verify_kzg_multiopen(C.byref(ok), b"".join(c.data for c in commitments), arr(sizes), arr(sets), n_groups, praw,
+                                            b"".join(y.data for row in ys for y in row), gamma.data, z.data, w.data, w2.data, kzg_settings._h))
+        return bool(ok.value)
 
     @staticmethod
     def verify_kzg_proof_batch(commitments, zs, ys, proofs, kzg_settings):
@@ -1171,10 +1194,80 @@ class Polys:
         return ([proofs.raw[48 * j: 48 * j + 48] for j in range(n_points)],
                 [[ys.raw[32 * (k * n_points + j): 32 * (k * n_points + j + 1)] for j in range(n_points)] for k in range(count)])
 
+    def multiopen(self, point_set, groups, gamma, first=0):
+        """The first step of the multi-point opening at per-group point sets (kzg_polys_multiopen_begin): groups = [(n_polys, [points ...]),
+        ...] cuts the polynomials from `first` on into consecutive groups, each opened at its own 32-byte points; gamma = the 32-byte
+        batching factor -> a MultiOpen holding .w (48 bytes) and .ys (per polynomial its values at its group's points), whose
+        finish(z) gives the second proof element."""
+        if not isinstance(point_set, G1Points):
+            raise TypeError("point_set: a G1Points")
+        sizes, sets, praw = _multiopen_groups(groups, lambda p: p)
+        graw = bytes(gamma)
+        if len(graw) != 32:
+            raise KzgError("InvalidBytesLength", "gamma: 32 bytes")
+        first, count = self._range(first, sum(sizes))
+        n_groups = len(sizes)
+        arr = lambda v: (C.c_size_t * max(n_groups, 1))(*v)
+        n_values = sum(m * t for m, t in zip(sizes, sets))
+        h, w, ys = C.c_void_p(), C.create_string_buffer(48), C.create_string_buffer(32 * max(n_values, 1))
+        _chk(lib().kzg_polys_multiopen_begin(C.byref(h), w, ys, point_set._h, self._h, first, count, arr(sizes), arr(sets), n_groups, praw, graw, self._settings._h))
+        rows, at = [], 0
+        for m, t in zip(sizes, sets):
+            for _ in range(m):
+                rows.append([ys.raw[32 * (at + a): 32 * (at + a + 1)] for a in range(t)])
+                at += t
+        return MultiOpen(h, w.raw, rows, self, point_set)
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
                 lib().kzg_polys_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _multiopen_groups(groups, raw):
+    """[(n_polys, [points ...]), ...] -> (group sizes, set sizes, the points' bytes); raw: a point -> its 32 bytes"""
+    sizes, sets, chunks = [], [], []
+    for m, pts in groups:
+        if not isinstance(m, int) or m < 0:
+            raise KzgError("BadArgs", "groups: (n_polys, [points ...]) with n_polys not negative")
+        praw, t = _points32([raw(p) for p in pts] if not isinstance(pts, (bytes, bytearray, memoryview, str)) else pts, "groups: the points of a group")
+        sizes.append(m), sets.append(t), chunks.append(praw)
+    return sizes, sets, b"".join(chunks)
+
+
+class MultiOpen:
+    """The state of a multi-point opening between its two steps (Polys.multiopen): .w = W, .ys = per polynomial of the call its values at
+    its group's points.  finish(z) -> (w2, y) for the verifier's 32-byte z, any number of times and from several threads.  It keeps its
+    polynomial set, point set and handle alive and must be closed (or dropped) before them."""
+
+    def __init__(self, h, w, ys, polys, point_set):
+        self._h, self.w, self.ys, self._polys, self._point_set, self._settings = h, w, ys, polys, point_set, polys._settings
+
+    def finish(self, z):
+        zraw = bytes(z)
+        if len(zraw) != 32:
+            raise KzgError("InvalidBytesLength", "z: 32 bytes")
+        w2, y = C.create_string_buffer(48), C.create_string_buffer(32)
+        _chk(lib().kzg_polys_multiopen_finish(w2, y, self._h, zraw, self._settings._h))
+        return w2.raw, y.raw
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._settings, "_h", None):  # (the free takes the handle's lock)
+                lib().kzg_multiopen_free(self._h)
             self._h = None
 
     def __enter__(self):

@@ -35,6 +35,7 @@
 #include "poly_quotient_kernels.hpp"
 #include "poly_fold_kernels.hpp"
 #include "poly_eval_kernels.hpp"
+#include "poly_multiopen_kernels.hpp"
 #include "fr_ntt_kernels.hpp"
 
 using namespace kzg;
@@ -77,6 +78,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_poly.hpp"
 #include "capi_poly_batch.hpp"
 #include "capi_polys.hpp"
+#include "capi_polys_multiopen.hpp"
 #include "capi_cells.hpp"
 #include "capi_cell_groups.hpp"
 #include "capi_cell_prover.hpp"
