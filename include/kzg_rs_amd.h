@@ -686,6 +686,14 @@ KzgRet kzg_debug_poly_quotients(uint8_t *q_out, uint8_t *ys_out, const uint8_t *
                                 size_t n_points, size_t n_polys, const KzgSettings *s);
 /* test hook: out = { coefficients per lane, per wavefront, per workgroup tile, scalars per chunk of pairs } (csrc/poly_quotient_plan.hpp) */
 KzgRet kzg_debug_poly_quotient_tiles(size_t out[4]);
+/* test hook: the two launches of the stages that read TILE SUMS alone, on tile sums as given, so that the tile count is an argument
+ * and not n_coeffs / 2048.  tile_sums[pair][tiles] and zs[pair], 32 big-endian bytes each, every one below r.  With Z = z^2048:
+ *   carries_out[pair][t] = sum_(u > t) tile_sums[pair][u] Z^(u - t - 1)   (k_poly_tile_carries; the last one 0)
+ *   ys_out[pair]         = sum_u tile_sums[pair][u] Z^u                    (k_poly_eval_tiles)
+ * Either output may be NULL: its launch is not queued.  tiles == 0 or pairs == 0: KZG_OK, nothing written.  KZG_BADARGS for tiles above
+ * 512 (those of 2^20 coefficients), pairs above KZG_POLY_MAX_OPENINGS, a null s, tile_sums or zs, an element >= r; any handle serves */
+KzgRet kzg_debug_poly_tile_chain(uint8_t *carries_out, uint8_t *ys_out, const uint8_t *tile_sums, size_t tiles, const uint8_t *zs,
+                                 size_t pairs, const KzgSettings *s);
 /* EVALUATION-FORM twins of the two calls above (csrc/capi_poly.hpp): the polynomial p_k arrives as its n_evals values on the subgroup
  * <w_n_evals>, w_n = 7^((r - 1) / n) (kzg_fr_ntt's root), evals = n_polys * n_evals * 32 bytes big-endian, in `order`:
  * KZG_POLY_ORDER_NATURAL, element i = p_k(w_n^i), or KZG_POLY_ORDER_BRP, element i = p_k(w_n^brp(i)) - the order blobs arrive in.

@@ -167,6 +167,7 @@ def lib():
         L.kzg_poly_compute_kzg_proofs_prepared.argtypes = [u8, u8, vp, u8, sz, u8, sz, sz, vp]
         L.kzg_debug_poly_quotients.argtypes = [u8, u8, u8, sz, u8, sz, sz, vp]
         L.kzg_debug_poly_quotient_tiles.argtypes = [C.POINTER(C.c_size_t)]
+        L.kzg_debug_poly_tile_chain.argtypes = [u8, u8, u8, sz, u8, sz, vp]
         L.kzg_fr_ntt.argtypes = [u8, u8, sz, sz, C.c_int, C.c_int, vp]
         L.kzg_poly_commit_evals_prepared.argtypes = [u8, vp, u8, sz, C.c_int, sz, vp]
         L.kzg_poly_compute_kzg_proofs_evals_prepared.argtypes = [u8, u8, vp, u8, sz, C.c_int, u8, sz, sz, vp]

@@ -107,6 +107,14 @@ static KzgRet poly_buffers(const KzgSettings* s, const PolyCall& c, size_t chunk
     return s->poly->reserve(c.n_coeffs, chunk);
 }
 
+// The carry launch of the scan, queued on st: carry[q][t] for `pairs` pairs of `tiles` tile sums each, pair q's point at zs[q].  Every
+// caller - poly_stage, poly_batch_stage, the multi-point opening (capi_polys_multiopen.hpp) and the test hook of the tile-level launches
+// (capi_poly_batch.hpp, beside poly_eval_tiles_queue, the other launch that reads tile sums alone) - launches it through this.
+static void poly_tile_carries_queue(hipStream_t st, const uint8_t* zs, const Fr* tsum, Fr* carry, size_t tiles, size_t pairs) {
+    const PqGrid gc = pq_grid_carries(pairs);
+    hipLaunchKernelGGL(k_poly_tile_carries, dim3(gc.x, gc.y), dim3(PQ_THREADS), 0, st, zs, tsum, carry, (int)tiles);
+}
+
 // Pairs [lo, lo + m) of the call: upload (the coefficients only if the chunk before did not leave the same polynomials there; none of
 // a resident call, whose chunk is a view of the set), the stage's launches, the verdict.  On KZG_OK the chunk's quotients (the commit: its coefficients) are in b.d_scalars, [pair][n_coeffs],
 // and its y in pb.d_ys.  ms: [0] copies [1] the launches, added to.
@@ -132,10 +140,10 @@ static KzgRet poly_stage(const KzgSettings* s, FbSumBufs& b, PolyBufs& pb, const
         if (rc != KZG_OK) return rc;
     }
     if (c.zs) {
-        const PqGrid gt = pq_grid_tiles(n, m), gc = pq_grid_carries(m);
+        const PqGrid gt = pq_grid_tiles(n, m);
         hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, src, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n,
                            (int)c.n_points, (int)lo, (int)k0);
-        hipLaunchKernelGGL(k_poly_tile_carries, dim3(gc.x, gc.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_tsum.p, pb.d_carry.p, (int)gt.x);
+        poly_tile_carries_queue(st, pb.d_zs.p, pb.d_tsum.p, pb.d_carry.p, gt.x, m);
         hipLaunchKernelGGL(k_poly_apply, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, src, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_carry.p, b.d_scalars.p,
                            pb.d_ys.p, (int)n, (int)c.n_points, (int)lo, (int)k0);
     } else {

@@ -55,6 +55,14 @@ static KzgRet poly_batch_buffers(const KzgSettings* s, const PolyBatchCall& c) {
     return KZG_OK;
 }
 
+// the finishing launch of the individual values, queued on st: y of pair q = (polynomial q / points, point q % points), its point at zs[q] and
+// its `tiles` tile sums at tsum[q] -> ys[(poly_first + q / points) * ys_stride + point_first + q % points].  Every caller - poly_values_queue,
+// the multi-point opening (capi_polys_multiopen.hpp) and the test hook below - launches it through this.
+static void poly_eval_tiles_queue(hipStream_t st, const uint8_t* zs, const Fr* tsum, uint8_t* ys, size_t tiles, size_t pairs, size_t points, size_t poly_first, size_t ys_stride,
+                                  size_t point_first) {
+    hipLaunchKernelGGL(k_poly_eval_tiles, dim3((unsigned)pairs), dim3(PF_EVAL_THREADS), 0, st, zs, tsum, ys, (int)tiles, (int)points, (int)poly_first, (int)ys_stride, (int)point_first);
+}
+
 // Every p_k(z_j) of `m` polynomials at `src` ([poly][n], polynomial k0 of the call first) and the g points at the head of pb.d_zs (the
 // group's points, repeated once per polynomial: k_poly_eval_tiles reads pair q's z at zs[q]) -> their places in pb.d_bys, rows of
 // ys_stride values.  by_blocks: the tile sums by k_poly_tile_sums_points (poly_eval_kernels.hpp: a block of points per pass over the
@@ -67,8 +75,7 @@ static void poly_values_queue(hipStream_t st, PolyBufs& pb, const uint8_t* src, 
     } else {
         hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, src, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n, (int)g, 0, 0);
     }
-    hipLaunchKernelGGL(k_poly_eval_tiles, dim3(gt.y), dim3(PF_EVAL_THREADS), 0, st, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_tsum.p, pb.d_bys.p, (int)pq_tiles(n), (int)g, (int)k0,
-                       (int)ys_stride, (int)j0);
+    poly_eval_tiles_queue(st, pb.d_zs.p, pb.d_tsum.p, pb.d_bys.p, pq_tiles(n), gt.y, g, k0, ys_stride, j0);
 }
 
 // Points [j0, j0 + g) of the call: every chunk of polynomials (upload, transform, fold, the individual values), the scan of the fold
@@ -109,9 +116,9 @@ static KzgRet poly_batch_stage(const KzgSettings* s, FbSumBufs& b, PolyBufs& pb,
         }
     }
     // the fold buffer as g polynomials with one point each: the first g entries of d_zs are the group's points
-    const PqGrid gt = pq_grid_tiles(n, g), gc = pq_grid_carries(g);
+    const PqGrid gt = pq_grid_tiles(n, g);
     hipLaunchKernelGGL(k_poly_tile_sums, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)pb.d_fold.p, (const uint8_t*)pb.d_zs.p, pb.d_tsum.p, pb.d_flag.p, (int)n, 1, 0, 0);
-    hipLaunchKernelGGL(k_poly_tile_carries, dim3(gc.x, gc.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_tsum.p, pb.d_carry.p, (int)gt.x);
+    poly_tile_carries_queue(st, pb.d_zs.p, pb.d_tsum.p, pb.d_carry.p, gt.x, g);
     hipLaunchKernelGGL(k_poly_apply, dim3(gt.x, gt.y), dim3(PQ_THREADS), 0, st, (const uint8_t*)pb.d_fold.p, (const uint8_t*)pb.d_zs.p, (const Fr*)pb.d_carry.p, b.d_scalars.p, pb.d_fys.p,
                        (int)n, 1, 0, 0);
     HIPCHK(hipGetLastError());
@@ -315,6 +322,54 @@ static KzgRet poly_batch_quotients_run(uint8_t* q_out, uint8_t* ys_out, uint8_t*
 extern "C" KzgRet kzg_debug_poly_batch_quotients(uint8_t* q_out, uint8_t* ys_out, uint8_t* fold_ys_out, const uint8_t* coeffs, size_t n_coeffs, const uint8_t* zs,
                                                  const uint8_t* gammas, size_t n_points, size_t n_polys, const KzgSettings* s) try {
     return poly_batch_quotients_run(q_out, ys_out, fold_ys_out, PolyBatchCall{coeffs, n_coeffs, zs, gammas, n_points, n_polys}, s);
+} catch (const std::bad_alloc&) {
+    return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
+}
+
+// test hook (tests/test_gpu_poly_tile_chain.py): the two launches that read tile sums alone, on tile sums as given - tile_sums[pair][tiles]
+// and zs[pair] big-endian; carries_out[pair][tiles] is what the carry launch (k_poly_tile_carries, poly_tile_carries_queue) writes, ys_out[pair] what
+// poly_eval_tiles_queue's launch writes.  The tile count is an argument here, where every other call derives it from n_coeffs at 64 KB of
+// coefficients a tile.
+extern "C" KzgRet kzg_debug_poly_tile_chain(uint8_t* carries_out, uint8_t* ys_out, const uint8_t* tile_sums, size_t tiles, const uint8_t* zs, size_t pairs,
+                                            const KzgSettings* s) try {
+    if (!s) return fail(KZG_BADARGS, "null argument");
+    if (tiles > pq_tiles(PQ_MAX_COEFFS) || pairs > PQ_MAX_OPENINGS) return fail(KZG_BADARGS, "bad argument");
+    if (tiles == 0 || pairs == 0) return KZG_OK;
+    if (!tile_sums || !zs) return fail(KZG_BADARGS, "null argument");
+    const size_t count = pq_tile_index(tiles, pairs, 0);
+    for (size_t q = 0; q < pairs; q++)
+        if (!mo_below_r(zs + 32 * q)) return fail(KZG_BADARGS, "an evaluation point is not below r");
+    std::vector<uint8_t> limbs(32 * count);
+    for (size_t i = 0; i < count; i++) {  // big-endian bytes -> little-endian limbs
+        if (!mo_below_r(tile_sums + 32 * i)) return fail(KZG_BADARGS, "a tile sum is not below r");
+        for (int j = 0; j < 32; j++) limbs[32 * i + j] = tile_sums[32 * i + 31 - j];
+    }
+    std::lock_guard<std::mutex> lk(s->mu);
+    HIPCHK(hipSetDevice(s->device));
+    select_streams(s, (size_t)-1);
+    if (!s->poly) s->poly = new (std::nothrow) PolyBufs();
+    if (!s->poly) return fail(KZG_MALLOC, "host buffers of the call");
+    PolyBufs& pb = *s->poly;
+    HIPCHK(pb.d_zs.grow(32 * pairs));
+    HIPCHK(pb.d_ys.grow(32 * pairs));
+    HIPCHK(pb.d_tsum.grow(count));
+    HIPCHK(pb.d_carry.grow(count));
+    StreamDrain drain{s->s1};  // (declared after limbs, whose bytes the stream's copies read and write)
+    hipStream_t st = s->s1;
+    HIPCHK(hipMemcpyAsync(pb.d_zs.p, zs, 32 * pairs, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pb.d_tsum.p, limbs.data(), 32 * count, hipMemcpyHostToDevice, st));
+    if (carries_out) poly_tile_carries_queue(st, pb.d_zs.p, pb.d_tsum.p, pb.d_carry.p, tiles, pairs);
+    if (ys_out) poly_eval_tiles_queue(st, pb.d_zs.p, pb.d_tsum.p, pb.d_ys.p, tiles, pairs, pairs, 0, pairs, 0);  // one "polynomial", pair q its point q: ys[q]
+    HIPCHK(hipGetLastError());
+    if (ys_out) HIPCHK(hipMemcpyAsync(ys_out, pb.d_ys.p, 32 * pairs, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // (the tile sums are up: limbs may take the carries)
+    if (carries_out) {
+        HIPCHK(hipMemcpyAsync(limbs.data(), pb.d_carry.p, 32 * count, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < count; i++)  // little-endian limbs -> big-endian bytes
+            for (int j = 0; j < 32; j++) carries_out[32 * i + j] = limbs[32 * i + 31 - j];
+    }
+    return KZG_OK;
 } catch (const std::bad_alloc&) {
     return fail(KZG_MALLOC, "host buffers of the call");  // (nothing is thrown across the C ABI)
 }

@@ -52,6 +52,7 @@ extern "C" {
     pub fn kzg_g1_msm_setup(out: *mut u8, scalars: *const u8, n: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_debug_poly_quotients(q_out: *mut u8, ys_out: *mut u8, coeffs: *const u8, n_coeffs: usize, zs: *const u8, n_points: usize, n_polys: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_debug_poly_quotient_tiles(out: *mut usize) -> c_int;
+    pub fn kzg_debug_poly_tile_chain(carries_out: *mut u8, ys_out: *mut u8, tile_sums: *const u8, tiles: usize, zs: *const u8, pairs: usize, s: *const RawSettings) -> c_int;
     pub fn kzg_last_error() -> *const c_char;
 }
 

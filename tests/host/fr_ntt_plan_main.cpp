@@ -9,6 +9,8 @@
 //   ntt k polys inverse order in -> the transform of the polys x 2^k values of file `in` (64 hex digits a line, big-endian), composed
 //                                   as the kernels compose it: "top limb" (the largest top limb and the largest lower limb any stage
 //                                   output had), then the results, one a line
+//   nttbin k polys inverse order in out -> the same with the values as 32 big-endian bytes each in file `in`, the results likewise in
+//                                   file `out`; "top limb" alone is printed (the sizes whose values as text would be 100 MB)
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -135,15 +137,24 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
-    if (!strcmp(argv[1], "ntt") && argc == 7) {
+    const bool bin = !strcmp(argv[1], "nttbin") && argc == 8;
+    if ((!strcmp(argv[1], "ntt") && argc == 7) || bin) {
         const int k = atoi(argv[2]);
+        if (k < 0 || k > FRNTT_MAX_LOG2) return 2;
         const size_t polys = strtoull(argv[3], nullptr, 10), total = polys << k;
         const bool inverse = atoi(argv[4]) != 0, brp = atoi(argv[5]) != 0;
         std::vector<Words> io(total), tmp(frntt_scratch_scalars((size_t)1 << k, polys));
-        FILE* f = fopen(argv[6], "r");
+        FILE* f = fopen(argv[6], bin ? "rb" : "r");
         if (!f) return 4;
         char line[128];
         for (size_t i = 0; i < total; i++) {
+            if (bin) {
+                uint8_t be[32];
+                if (fread(be, 1, 32, f) != 32) return 5;
+                for (int wd = 0; wd < 8; wd++)
+                    io[i][7 - wd] = (uint32_t)be[4 * wd] << 24 | (uint32_t)be[4 * wd + 1] << 16 | (uint32_t)be[4 * wd + 2] << 8 | (uint32_t)be[4 * wd + 3];
+                continue;
+            }
             if (!fgets(line, sizeof line, f) || strlen(line) < 64) return 5;
             for (int wd = 0; wd < 8; wd++) {
                 char h[9];
@@ -165,6 +176,17 @@ int main(int argc, char** argv) {
             run_pass(FRNTT_ROWS, tmp, io, W, k, total, false, perm_out, inverse, scale);
         }
         printf("%u %u\n", g_top, g_limb);
+        if (bin) {
+            FILE* o = fopen(argv[7], "wb");
+            if (!o) return 4;
+            for (size_t i = 0; i < total; i++) {
+                uint8_t be[32];
+                for (int wd = 0; wd < 8; wd++)
+                    for (int b = 0; b < 4; b++) be[4 * wd + b] = (uint8_t)(io[i][7 - wd] >> (24 - 8 * b));
+                if (fwrite(be, 1, 32, o) != 32) return 6;
+            }
+            return fclose(o) ? 6 : 0;
+        }
         for (size_t i = 0; i < total; i++) {
             for (int wd = 7; wd >= 0; wd--) printf("%08x", io[i][wd]);
             printf("\n");

@@ -51,24 +51,44 @@ def transform_model(vec, inverse, order):
     return [v * inv_n % R for v in ntt_model(ev, pow(root(n), R - 2, R))]
 
 
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
+def _build_plan(tmp_path_factory, flags):
     d = tmp_path_factory.mktemp("frntt")
     exe = str(d / "fr_ntt_plan_main")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I",
-                           os.path.join(ROOT, "kzg_rs_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "host", "fr_ntt_plan_main.cpp")])
+    subprocess.check_call(["g++", "-std=c++17"] + flags + ["-I", os.path.join(ROOT, "kzg_rs_amd", "csrc"), "-o", exe,
+                                                           os.path.join(ROOT, "tests", "host", "fr_ntt_plan_main.cpp")])
 
-    def run(*args, values=None):
+    def run(*args, values=None, raw=None):
+        """values: integers, handed over as text; raw: 32 big-endian bytes each, handed over and returned as files (-> rows, bytes)"""
         args = [str(a) for a in args]
         if values is not None:
             path = str(d / "in.txt")
             with open(path, "w") as f:
                 f.write("".join("%064x\n" % v for v in values))
             args.append(path)
+        if raw is not None:
+            with open(str(d / "in.bin"), "wb") as f:
+                f.write(raw)
+            args += [str(d / "in.bin"), str(d / "out.bin")]
         out = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300)
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-        return [ln.split() for ln in out.stdout.splitlines()]
+        rows = [ln.split() for ln in out.stdout.splitlines()]
+        if raw is None:
+            return rows
+        with open(str(d / "out.bin"), "rb") as f:
+            return rows, f.read()
     return run
+
+
+@pytest.fixture(scope="module")
+def plan(tmp_path_factory):
+    return _build_plan(tmp_path_factory, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+@pytest.fixture(scope="module")
+def plan_optimised(tmp_path_factory):
+    """the same program without the sanitizers: a transform of 2^20 points takes the sanitized build over a minute; the index maps of
+    every size are under the sanitizers in test_each_pass_is_a_bijection_for_every_size, the arithmetic at k = 10 and 11"""
+    return _build_plan(tmp_path_factory, ["-O2"])
 
 
 def ints(rows):
@@ -168,6 +188,50 @@ def test_small_sizes_on_the_host(plan):
                 rows = plan("ntt", k, 3, inverse, order, values=sum(vecs, []))
                 got = [int(r[0], 16) for r in rows[1:]]
                 assert got == sum((transform_model(v, inverse, order) for v in vecs), []), (k, inverse, order)
+
+
+def test_the_closed_forms_are_the_models_and_notice_a_wrong_output():
+    """tests/fr_ntt_closed_forms.py against the recursive model at sizes where both are cheap: what it expects is what the model gives,
+    and it refuses an output whose elements are swapped, one that is scaled by a power of w, and one moved by a constant"""
+    import fr_ntt_closed_forms as F
+    for k in (1, 3, 6):
+        n = 1 << k
+        c = F.Case(k)
+        vecs = [F.ints(c.inputs[name]) for name in F.VECTORS]
+        for inverse in (0, 1):
+            for order in (0, 1):
+                outs = [transform_model(v, inverse, order) for v in vecs]
+                good = b"".join(x.to_bytes(32, "big") for o in outs for x in o)
+                c.check(good, inverse, order)
+                if n < 4:
+                    continue
+                for what in ("swap", "scale", "shift"):
+                    for vec in (1, 3):                       # e_1 | random
+                        bad = [list(o) for o in outs]
+                        if what == "swap":
+                            bad[vec][1], bad[vec][2] = bad[vec][2], bad[vec][1]
+                        elif what == "scale":
+                            bad[vec][n - 1] = bad[vec][n - 1] * root(n) % R
+                        else:
+                            bad[vec][0] = (bad[vec][0] + 1) % R
+                        with pytest.raises(AssertionError):
+                            c.check(b"".join(x.to_bytes(32, "big") for o in bad for x in o), inverse, order)
+
+
+# (2^19 and 2^20 in bit-reversed order only: it is the natural order's index map with one more permutation in the first load of the
+# inverse and the last store of the forward transform, and each of these cases takes the host ten seconds and more)
+@pytest.mark.parametrize("k,inverse,order", [(k, inverse, order) for k in range(12, 21) for inverse in (0, 1) for order in (0, 1) if order or k < 19])
+def test_the_host_composition_of_every_two_pass_split(plan, plan_optimised, k, inverse, order):
+    """2^12 .. 2^20 - the splits 6x6 to 10x10 - composed on the host pass by pass as the kernels compose them: the index maps of both
+    passes and the twiddle exponent between them against the closed forms and the evaluation identity of tests/fr_ntt_closed_forms.py
+    (r - 1 everywhere among the inputs: the largest values), and the header's bound on every stage output.  Under the sanitizers up to
+    2^15; above, the same program built without them"""
+    import fr_ntt_closed_forms as F
+    c = F.case(k)
+    rows, out = (plan if k <= 15 else plan_optimised)("nttbin", k, len(F.VECTORS), inverse, order, raw=c.input_bytes())
+    top, limb = int(rows[0][0]), int(rows[0][1])
+    assert top <= (83 * R) >> 232 and limb < 1 << 29
+    c.check(out, inverse, order)
 
 
 def test_the_root_is_the_projects_own():

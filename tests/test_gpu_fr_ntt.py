@@ -198,6 +198,18 @@ def test_the_largest_size(s):
     assert np.array_equal(np.frombuffer(back, dtype=np.uint8), np.frombuffer(raw, dtype=np.uint8))
 
 
+# 2^14 .. 2^20: the splits 7x7, 8x7, 8x8, 9x8, 9x9, 10x9 and 10x10, each with its own index maps and inter-pass twiddle exponent.  A second
+# transform in Python would take minutes here; tests/fr_ntt_closed_forms.py has what the WHOLE output must be for three inputs, and an
+# identity over every output of a random one.  One call per case, four vectors; what a size needs is computed once and kept while it is used.
+@pytest.mark.parametrize("k,inverse,order", [(k, inverse, order) for k in range(14, 21) for inverse in (False, True) for order in ("natural", "brp")])
+def test_the_two_pass_sizes_against_closed_forms_and_the_evaluation_identity(s, k, inverse, order):
+    import fr_ntt_closed_forms as F
+    c = F.case(k)
+    rc, out = call(s, c.input_bytes(), 1 << k, len(F.VECTORS), inverse, order)
+    assert rc == OK, api.lib().kzg_last_error()
+    c.check(out, inverse, ORDERS[order])
+
+
 def test_refusals(s):
     L = api.lib()
     rng = random.Random(5)

@@ -105,12 +105,15 @@ def test_entry_points_are_declared_and_exported():
     assert sig.get("kzg_debug_poly_quotients") == ("uint8_t *q_out, uint8_t *ys_out, const uint8_t *coeffs, size_t n_coeffs, const uint8_t *zs, size_t n_points, "
                                                    "size_t n_polys, const KzgSettings *s")
     assert sig.get("kzg_debug_poly_quotient_tiles") == "size_t out[4]"
+    assert sig.get("kzg_debug_poly_tile_chain") == ("uint8_t *carries_out, uint8_t *ys_out, const uint8_t *tile_sums, size_t tiles, const uint8_t *zs, size_t pairs, "
+                                                    "const KzgSettings *s")
     assert re.search(r"KzgRet KZG_G1_POINTS_API kzg_poly_commit_prepared\(", h) and re.search(r"KzgRet KZG_G1_POINTS_API kzg_poly_compute_kzg_proofs_prepared\(", h)
     from kzg_rs_amd import api, build
     build.build()
     for path in (api.LIB_PATH, api.LIB_AB_PATH):
         L = ctypes.CDLL(path)
-        for name in ("kzg_poly_commit_prepared", "kzg_poly_compute_kzg_proofs_prepared", "kzg_debug_poly_quotients", "kzg_debug_poly_quotient_tiles"):
+        for name in ("kzg_poly_commit_prepared", "kzg_poly_compute_kzg_proofs_prepared", "kzg_debug_poly_quotients", "kzg_debug_poly_quotient_tiles",
+                     "kzg_debug_poly_tile_chain"):
             assert hasattr(L, name), (path, name)
     assert callable(api.G1Points.commit) and callable(api.G1Points.open)
     assert callable(api.poly_commit_prepared) and callable(api.poly_compute_kzg_proofs_prepared) and api.POLY_MAX_OPENINGS == OPENINGS
@@ -126,6 +129,20 @@ def test_the_tile_hook_needs_no_device_and_reports_the_plan(plan, geometry):
     assert L.kzg_debug_poly_quotient_tiles(out) == 0
     assert tuple(out) == (geometry[0], geometry[1], geometry[2], CAP)
     assert L.kzg_debug_poly_quotient_tiles(None) == 1
+
+
+def test_the_tile_chain_hook_refuses_a_null_handle_before_any_device_call(plan):
+    """kzg_debug_poly_tile_chain (tests/test_gpu_poly_tile_chain.py) checks its handle first; its tile limit is the plan's for 2^20 coefficients"""
+    from kzg_rs_amd import api, build
+    build.build()
+    L = ctypes.CDLL(api.LIB_PATH)
+    sz, u8 = ctypes.c_size_t, ctypes.c_char_p
+    L.kzg_debug_poly_tile_chain.argtypes = [u8, u8, u8, sz, u8, sz, ctypes.c_void_p]
+    out = ctypes.create_string_buffer(64)
+    for tiles, pairs in ((0, 0), (1, 1), (513, 1), (1, 4097)):
+        assert L.kzg_debug_poly_tile_chain(out, out, bytes(32), tiles, bytes(32), pairs, None) == 1, (tiles, pairs)
+    assert out.raw == bytes(64)
+    assert plan("cover", 1 << 20, 1 << 20)[0][1] == 512
 
 
 def test_the_python_wrapper_refuses_ragged_rows_before_any_device_call():
