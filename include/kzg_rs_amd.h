@@ -887,6 +887,59 @@ KzgRet KZG_POLYS_API kzg_debug_polys_multiopen_quotients(uint8_t *h_out, uint8_t
         const uint8_t *points, const uint8_t gamma[32], const uint8_t *z, const KzgSettings *s);
 /* test hook: out = { KZG_MULTIOPEN_MAX_GROUPS, KZG_MULTIOPEN_MAX_SET_POINTS, elements per workgroup of k_poly_lincomb, lanes of a scalar kernel } (csrc/poly_multiopen_plan.hpp) */
 KzgRet kzg_debug_poly_multiopen_plan(size_t out[4]);
+/* RESIDENT POLYNOMIAL ARITHMETIC (csrc/capi_polys_arith.hpp): sums of products and linear combinations of resident polynomials whose
+ * result is a NEW resident set, so that the polynomials a prover commits to in its middle rounds - the quotient t = (gate and permutation
+ * constraints) / Z_H cut into pieces of n coefficients, the linearisation polynomial r = sum_k c_k p_k - never leave the device: commit ->
+ * z -> evaluate -> gamma -> open runs, quotient included, on ONE upload.  All arithmetic mod r.
+ *   kzg_polys_sum_of_products: P = sum_t c_t prod_j p_(t,j).  sets[n_sets]: the sets the factors come from (they may differ in n_coeffs);
+ *     term_coeffs: n_terms * 32 bytes big-endian; term_sizes[t]: the factors of term t, 0 .. KZG_POLYS_SOP_MAX_FACTORS (0: the constant
+ *     c_t); factors: per factor, in order, two uint32_t - the index into `sets`, the polynomial's index in that set.  A polynomial may
+ *     appear any number of times, also within one term.  The formal length of term t is 1 + sum_j (n_coeffs(set_j) - 1), L0 the largest
+ *     (1 when no term has a factor), N the smallest power of two >= L0.  vanishing_n = v > 0: the result is P / (X^v - 1), of formal
+ *     length L = L0 - v, and a remainder is refused ("the sum is not divisible by X^v - 1"); v == 0: L = L0.  piece_coeffs == 0: one
+ *     polynomial of L coefficients; otherwise ceil(L / piece_coeffs) polynomials of piece_coeffs coefficients, result = sum_j X^(j *
+ *     piece_coeffs) piece_j, the last piece zero-padded - t_lo, t_mid, t_hi, each committable over piece_coeffs points.  Every shape follows
+ *     from the arguments' shapes, never from the actual degree.  n_terms == 0 gives the zero polynomial of length 1.
+ *   kzg_polys_linear_combinations: out_j = sum_k factors[j * count + k] p_(first + k), j < n_out; factors: n_out * count * 32 bytes
+ *     big-endian; the new set has f's n_coeffs and n_out polynomials; count == 0 gives zero polynomials.
+ * The returned set is an ordinary KzgPolys: immutable, owned by `s`, freed with kzg_polys_free before the handle, accepted by every call
+ * that takes one - a further product included; its coefficients are canonical.  The handle's lock is taken; the call runs on the sets'
+ * device; the same call twice gives the same bytes.
+ * KZG_BADARGS - *out untouched, nothing kept, the handle usable afterwards - for: a null pointer; n_sets above KZG_POLYS_SOP_MAX_SETS;
+ * n_terms above KZG_POLYS_SOP_MAX_TERMS; a term size above KZG_POLYS_SOP_MAX_FACTORS; a factor while n_sets == 0; a set uploaded on
+ * another handle; a set or polynomial index out of range; a referenced set of n_coeffs == 0; N above KZG_FR_NTT_MAX; v >= L0; ceil(L0 / v)
+ * above KZG_POLYS_SOP_MAX_CHAIN; piece_coeffs above KZG_POLYS_MAX_COEFFS; more than KZG_POLYS_MAX_POLYS pieces; U * N above
+ * KZG_POLYS_MAX_SCALARS for the U distinct polynomials named; a term coefficient >= r ("a term coefficient is not below r"); a
+ * remainder.  kzg_polys_linear_combinations: a range past the set, n_out above KZG_POLYS_MAX_POLYS, n_out * n_coeffs above
+ * KZG_POLYS_MAX_SCALARS, a factor >= r ("a factor is not below r").  An allocation the device refuses is KZG_MALLOC.
+ * On the device (csrc/poly_arith_plan.hpp, poly_arith_kernels.hpp) the product is taken at full size: the U polynomials are padded into
+ * a workspace of (U + 1) * N scalars - up to 2 GB, the call's own, released on return - transformed forward in place (the transform of
+ * kzg_fr_ntt, in its chunks), multiplied and summed pointwise by k_poly_sop, the sum is transformed back and k_poly_div_vanishing walks
+ * every residue class mod v from the top down, q_(i - v) = P_i + q_i: at most KZG_POLYS_SOP_MAX_CHAIN additions per lane, and what is
+ * left below v is the remainder.  A linear combination is one launch of k_poly_lincomb per output polynomial.
+ * kzg_last_timings: [4] the device stage, [6] the copies - the term table and the factors; no coefficient crosses the bus
+ * (kzg_debug_polys_stats counts each call as served from a resident set; its other counters do not move).
+ * Measured (tools/prof/polys_arith_probe.py, profiles/polys_arith_probe.json; 10 warm calls each, median (min - max)): the PLONK-shaped call - 13
+ * distinct polynomials of n coefficients, 9 terms of up to 4 factors (21 factor references), v = n, pieces of n; N = 4 n.  n = 2^17 (N = 2^19):
+ * 1.555 (1.533 - 1.600) ms, slot [4] 1.235 ms = pad 0.053 + forward transforms 0.934 + k_poly_sop 0.130 + inverse 0.103 + division 0.014 ms, copies
+ * 0.008 ms; k_poly_sop moves its 369 MB at 2.97 TB/s where k_poly_lincomb moves the same bytes in 0.141 ms (2.74 TB/s).  n = 2^16: 0.944 (0.910 -
+ * 1.016) ms, stage 0.629 ms (transforms 0.448, k_poly_sop 0.072); n = 2^12: 0.455 (0.451 - 0.508) ms, stage 0.167 ms.  N = 2^20: not yet measured. */
+#define KZG_POLYS_SOP_MAX_SETS    8
+#define KZG_POLYS_SOP_MAX_TERMS   256
+#define KZG_POLYS_SOP_MAX_FACTORS 8    /* per term */
+#define KZG_POLYS_SOP_MAX_CHAIN   16   /* ceil(L0 / vanishing_n) */
+KzgRet KZG_POLYS_API kzg_polys_sum_of_products(KzgPolys **out, const KzgPolys *const *sets, size_t n_sets,
+        const uint8_t *term_coeffs, const size_t *term_sizes, const uint32_t *factors, size_t n_terms,
+        size_t vanishing_n, size_t piece_coeffs, const KzgSettings *s);
+KzgRet KZG_POLYS_API kzg_polys_linear_combinations(KzgPolys **out, const KzgPolys *f, size_t first, size_t count,
+        const uint8_t *factors, size_t n_out, const KzgSettings *s);
+/* test hook: the host plan alone, no handle and no GPU - out = { L0, N, L, pieces, U, workspace scalars, chain length, refusal code (0:
+ * none; otherwise the rest is 0) }; the sets are given by their n_coeffs, so polynomial indices are not checked (csrc/poly_arith_plan.hpp) */
+KzgRet KZG_POLYS_API kzg_debug_poly_arith_plan(size_t out[8], const size_t *set_coeffs, size_t n_sets, const size_t *term_sizes,
+        const uint32_t *factors, size_t n_terms, size_t vanishing_n, size_t piece_coeffs);
+/* diagnostic: slot [4] of the handle's last kzg_polys_sum_of_products split by events, ms - out = { coefficients + pad, forward
+ * transforms, k_poly_sop, inverse transform, division or copy } */
+KzgRet kzg_debug_polys_arith_split(const KzgSettings *s, float out[5]);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

@@ -198,6 +198,11 @@ def lib():
         L.kzg_verify_kzg_multiopen.argtypes = [C.POINTER(C.c_bool), u8, szp, szp, sz, u8, u8, u8, u8, u8, u8, vp]
         L.kzg_debug_polys_multiopen_quotients.argtypes = [u8, u8, u8, u8, vp, sz, sz, szp, szp, sz, u8, u8, u8, vp]
         L.kzg_debug_poly_multiopen_plan.argtypes = [szp]
+        u32p = C.POINTER(C.c_uint32)
+        L.kzg_polys_sum_of_products.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, u8, szp, u32p, sz, sz, sz, vp]
+        L.kzg_polys_linear_combinations.argtypes = [C.POINTER(vp), vp, sz, sz, u8, sz, vp]
+        L.kzg_debug_poly_arith_plan.argtypes = [szp, szp, sz, szp, u32p, sz, sz, sz]
+        L.kzg_debug_polys_arith_split.argtypes = [vp, C.POINTER(C.c_float)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -1121,6 +1126,13 @@ class Polys:
     def from_evals(cls, evals, kzg_settings, order="natural"):
         return cls(evals, kzg_settings, _order=_poly_order(order))
 
+    @classmethod
+    def _from_handle(cls, h, kzg_settings):
+        """a set the library derived on the device (polys_sum_of_products, lincomb): it closes and frees like an uploaded one"""
+        self = cls.__new__(cls)
+        self._settings, self._h = kzg_settings, h
+        return self
+
     def _shape(self):
         n, m = C.c_size_t(0), C.c_size_t(0)
         _chk(lib().kzg_polys_shape(self._h, C.byref(n), C.byref(m)))
@@ -1219,6 +1231,19 @@ class Polys:
                 at += t
         return MultiOpen(h, w.raw, rows, self, point_set)
 
+    def lincomb(self, rows, first=0, count=None):
+        """kzg_polys_linear_combinations: rows[j] = the `count` 32-byte factors of output polynomial j over polynomials [first, first + count)
+        -> a new resident set of len(rows) polynomials, out_j = sum_k rows[j][k] p_(first + k); nothing crosses the bus but the factors"""
+        first, count = self._range(first, count)
+        if isinstance(rows, (bytes, bytearray, memoryview, str)):
+            raise TypeError("rows: one row of factors per output polynomial")
+        raws = [_points32(row, "rows") for row in rows]
+        if any(k != count for _, k in raws):
+            raise KzgError("InvalidBytesLength", "rows: one factor per polynomial of the range")
+        h = C.c_void_p()
+        _chk(lib().kzg_polys_linear_combinations(C.byref(h), self._h, first, count, b"".join(r for r, _ in raws), len(raws), self._settings._h))
+        return Polys._from_handle(h, self._settings)
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
@@ -1290,6 +1315,56 @@ def polys_upload(polys, kzg_settings):
 
 def polys_upload_evals(evals, kzg_settings, order="natural"):
     return Polys.from_evals(evals, kzg_settings, order)
+
+
+POLYS_SOP_MAX_SETS, POLYS_SOP_MAX_TERMS, POLYS_SOP_MAX_FACTORS, POLYS_SOP_MAX_CHAIN = 8, 256, 8, 16
+
+
+def _sop_terms(terms):
+    """[(coeff, [(set_index, poly_index), ...]), ...] -> (coefficient bytes, term sizes, the factors' index pairs, flat)"""
+    craw, sizes, flat = [], [], []
+    for coeff, facs in terms:
+        c = bytes(coeff)
+        if len(c) != 32:
+            raise KzgError("InvalidBytesLength", "terms: 32 bytes per coefficient")
+        craw.append(c)
+        facs = list(facs)
+        sizes.append(len(facs))
+        for si, pi in facs:
+            if not isinstance(si, int) or not isinstance(pi, int) or not 0 <= si < 1 << 32 or not 0 <= pi < 1 << 32:
+                raise KzgError("BadArgs", "terms: a factor is (set_index, poly_index), not negative")
+            flat += [si, pi]
+    return b"".join(craw), sizes, flat
+
+
+def polys_sum_of_products(sets, terms, kzg_settings, vanishing=0, piece_coeffs=0):
+    """kzg_polys_sum_of_products: sets = a list of Polys of the handle, terms = [(coeff, [(set_index, poly_index), ...]), ...] with 32-byte
+    big-endian coefficients -> a new resident Polys holding sum_t coeff_t prod_j sets[set_index][poly_index], divided by X^vanishing - 1
+    when vanishing > 0 (a remainder raises KzgError) and cut into pieces of piece_coeffs coefficients when piece_coeffs > 0."""
+    if not isinstance(kzg_settings, KzgSettings):
+        raise TypeError("kzg_settings: a KzgSettings")
+    sets = list(sets)
+    if any(not isinstance(f, Polys) for f in sets):
+        raise TypeError("sets: a list of Polys")
+    if not isinstance(vanishing, int) or not isinstance(piece_coeffs, int) or vanishing < 0 or piece_coeffs < 0:
+        raise KzgError("BadArgs", "vanishing, piece_coeffs: integers, not negative")
+    craw, sizes, flat = _sop_terms(terms)
+    hs = (C.c_void_p * max(len(sets), 1))(*[f._h for f in sets])
+    h = C.c_void_p()
+    _chk(lib().kzg_polys_sum_of_products(C.byref(h), hs, len(sets), craw, (C.c_size_t * max(len(sizes), 1))(*sizes), (C.c_uint32 * max(len(flat), 1))(*flat),
+                                         len(sizes), vanishing, piece_coeffs, kzg_settings._h))
+    return Polys._from_handle(h, kzg_settings)
+
+
+def poly_arith_plan(set_coeffs, terms, vanishing=0, piece_coeffs=0):
+    """kzg_debug_poly_arith_plan: set_coeffs = n_coeffs of every set, terms = per term its [(set_index, poly_index), ...] -> (L0, N, L,
+    pieces, distinct polynomials, workspace scalars, chain length, refusal code); host code"""
+    set_coeffs = list(set_coeffs)
+    _, sizes, flat = _sop_terms([(bytes(32), facs) for facs in terms])
+    out = (C.c_size_t * 8)()
+    _chk(lib().kzg_debug_poly_arith_plan(out, (C.c_size_t * max(len(set_coeffs), 1))(*set_coeffs), len(set_coeffs), (C.c_size_t * max(len(sizes), 1))(*sizes),
+                                         (C.c_uint32 * max(len(flat), 1))(*flat), len(sizes), vanishing, piece_coeffs))
+    return tuple(int(x) for x in out)
 
 
 def poly_eval_plan():

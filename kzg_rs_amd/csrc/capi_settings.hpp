@@ -145,6 +145,7 @@ struct KzgSettings {
     // served from a resident set | coefficient bytes THOSE calls copied host -> device (poly_coeffs_h2d, capi_poly.hpp: stays 0)
     mutable std::atomic<uint64_t> polys_stats[4] = {};
     mutable bool polys_resident_call = false;  // the call that holds the lock reads a resident set (PolyResidentCall)
+    mutable float polys_arith_split[5] = {};   // kzg_debug_polys_arith_split (capi_polys_arith.hpp): slot [4] of the last product call, by stage
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the
     // last launch group, and summed over the groups finished since the last reset (kzg_kernel_stamp_totals)

@@ -36,6 +36,7 @@
 #include "poly_fold_kernels.hpp"
 #include "poly_eval_kernels.hpp"
 #include "poly_multiopen_kernels.hpp"
+#include "poly_arith_kernels.hpp"
 #include "fr_ntt_kernels.hpp"
 
 using namespace kzg;
@@ -79,6 +80,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_poly_batch.hpp"
 #include "capi_polys.hpp"
 #include "capi_polys_multiopen.hpp"
+#include "capi_polys_arith.hpp"
 #include "capi_cells.hpp"
 #include "capi_cell_groups.hpp"
 #include "capi_cell_prover.hpp"
