@@ -940,6 +940,59 @@ KzgRet KZG_POLYS_API kzg_debug_poly_arith_plan(size_t out[8], const size_t *set_
 /* diagnostic: slot [4] of the handle's last kzg_polys_sum_of_products split by events, ms - out = { coefficients + pad, forward
  * transforms, k_poly_sop, inverse transform, division or copy } */
 KzgRet kzg_debug_polys_arith_split(const KzgSettings *s, float out[5]);
+/* RESIDENT GRAND PRODUCTS (csrc/capi_polys_grand_product.hpp): the running product of a permutation, lookup or multiset-equality
+ * argument - round 2 of a PLONK prover, plookup, halo2's permutation and lookup arguments - over resident polynomials, returned as a NEW
+ * resident set.  Its challenges are drawn after the witness commitments, so it cannot be prepared in advance; with this call the prover's
+ * five rounds run on ONE upload.  All arithmetic mod r; w = w_n is the root kzg_fr_ntt uses for n = domain_n.
+ *   Product g has num_sizes[g] numerator polynomials A_(g,j) and den_sizes[g] denominator polynomials B_(g,j), 0 ..
+ *   KZG_POLYS_GP_MAX_FACTORS each (0: the constant 1).  factors names them in order - product after product, numerators first - as
+ *   kzg_polys_sum_of_products does: per factor two uint32_t, the index into `sets` and the polynomial's index in that set.  A polynomial
+ *   may be named any number of times.  The sets may differ in n_coeffs, each at most domain_n (shorter ones are zero-padded).
+ *   With a_i = prod_j A_(g,j)(w^i) and b_i = prod_j B_(g,j)(w^i), z_g is the polynomial of degree < n with z_g(w^i) = prod_(k<i) a_k / b_k,
+ *   i = 0 .. n - 1, so z_g(1) = 1.  The new set holds n_products polynomials of domain_n coefficients; with_shift != 0: 2 n_products,
+ *   polynomial 2g = z_g and polynomial 2g + 1 = z_g(wX), whose evaluations are those of z_g rotated by one place (entry n - 1 is z_0 = 1).
+ *   totals_out may be NULL; otherwise totals_out[32 g ..] = prod_(k<n) a_k / b_k, big-endian: 1 exactly when the two multisets agree.
+ *   The call does NOT refuse another value: judging it is the caller's business.
+ * The returned set is an ordinary KzgPolys: immutable, owned by `s`, freed with kzg_polys_free before the handle, accepted by every call
+ * that takes one - a further grand product, kzg_polys_sum_of_products and the openings included; its coefficients are canonical.  The
+ * handle's lock is taken; the call runs on the sets' device; the same call twice gives the same bytes.
+ * KZG_BADARGS - *out and totals_out untouched, nothing kept, the handle usable afterwards - for: a null pointer; n_products == 0 or above
+ * KZG_POLYS_GP_MAX_PRODUCTS; a side above KZG_POLYS_GP_MAX_FACTORS; n_sets above KZG_POLYS_SOP_MAX_SETS; a factor while n_sets == 0; a set
+ * uploaded on another handle; a set or polynomial index out of range; a referenced set of n_coeffs == 0; domain_n zero, no power of two
+ * or above KZG_FR_NTT_MAX; a referenced set longer than domain_n; U * domain_n above KZG_POLYS_MAX_SCALARS for the U distinct polynomials
+ * named; more than KZG_POLYS_MAX_POLYS output polynomials (out of reach under the limits above: 32 at most); a denominator that is zero
+ * somewhere on the domain ("a denominator vanishes on the domain").  An allocation the device refuses is KZG_MALLOC.
+ * On the device (csrc/poly_grand_product_plan.hpp, poly_grand_product_kernels.hpp): the U polynomials are padded into a workspace of U *
+ * domain_n scalars - the call's own, released on return - and transformed forward in place (the transform of kzg_fr_ntt, in its chunks).
+ * z_i = (prod_(k<i) a_k) (prod_(k>=i) b_k) / prod_k b_k: an exclusive prefix product, an inclusive suffix product and ONE inversion per
+ * product, in three launches over tiles of 1 024 indices (256 lanes x 4 consecutive indices) - k_gp_tile_products, k_gp_tile_carries (one
+ * workgroup per product; a zero total is the vanishing denominator, F_r having no zero divisors), k_gp_apply, which writes z and z(wX)
+ * as evaluations into the new set's buffer - and the inverse transform runs in place there.
+ * kzg_last_timings: [4] the device stage, [6] the copies - the factor table; no coefficient crosses the bus (kzg_debug_polys_stats
+ * counts the call as served from a resident set; its byte counters do not move).
+ * NOT in this call: blinding terms (b2 X^2 + b1 X + b0) Z_H, which lengthen z beyond n coefficients; logUp-style running SUMS of
+ * fractions, which can reuse the products-and-one-inverse scheme.
+ * Measured (tools/prof/polys_grand_product_probe.py, profiles/polys_grand_product_probe.json; 10 warm calls each, median (min - max); 3 + 3
+ * factors, one product, with shift): n = 2^20: 2.154 (2.105 - 2.248) ms, slot [4] 1.873 ms = pad 0.063 + forward transforms 0.881 + tile
+ * products and carries 0.440 + apply 0.150 + inverse transforms 0.327 ms, copies 0.009 ms; n = 2^18: 1.042 (0.997 - 1.143) ms, stage 0.757 ms;
+ * n = 2^16: 0.866 (0.813 - 0.955) ms, stage 0.576 ms; n = 2^12: 0.624 (0.567 - 0.655) ms, stage 0.537 ms.  The one serial piece, the single-lane
+ * inversion in k_gp_tile_carries, is at most 0.377 ms of every call (the two scan launches on a domain of one point): 20 % of the stage at
+ * 2^20, 70 % at 2^12.  In the same run kzg_polys_sum_of_products over the same six polynomials at N = n has a stage of 1.240 ms at 2^20 and
+ * one k_poly_lincomb row over them takes 0.079 ms (2.99 TB/s). */
+#define KZG_POLYS_GP_MAX_PRODUCTS 16
+#define KZG_POLYS_GP_MAX_FACTORS  8     /* per side of one product */
+KzgRet KZG_POLYS_API kzg_polys_grand_product(KzgPolys **out, uint8_t *totals_out,
+        const KzgPolys *const *sets, size_t n_sets,
+        const size_t *num_sizes, const size_t *den_sizes, const uint32_t *factors, size_t n_products,
+        size_t domain_n, int with_shift, const KzgSettings *s);
+/* test hook: the host plan alone, no handle and no GPU - out = { U, workspace scalars, elements per tile, tiles, lanes per workgroup,
+ * tiles per lane of the carry kernel, output polynomials, refusal code (0: none; otherwise the rest is 0) }; the sets are given by their
+ * n_coeffs, so polynomial indices are not checked (csrc/poly_grand_product_plan.hpp) */
+KzgRet KZG_POLYS_API kzg_debug_poly_grand_product_plan(size_t out[8], const size_t *set_coeffs, size_t n_sets, const size_t *num_sizes,
+        const size_t *den_sizes, const uint32_t *factors, size_t n_products, size_t domain_n, int with_shift);
+/* diagnostic: slot [4] of the handle's last kzg_polys_grand_product split by events, ms - out = { pad, forward transforms, tile products +
+ * carries, apply, inverse transform } */
+KzgRet kzg_debug_polys_grand_product_split(const KzgSettings *s, float out[5]);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

@@ -203,6 +203,9 @@ def lib():
         L.kzg_polys_linear_combinations.argtypes = [C.POINTER(vp), vp, sz, sz, u8, sz, vp]
         L.kzg_debug_poly_arith_plan.argtypes = [szp, szp, sz, szp, u32p, sz, sz, sz]
         L.kzg_debug_polys_arith_split.argtypes = [vp, C.POINTER(C.c_float)]
+        L.kzg_polys_grand_product.argtypes = [C.POINTER(vp), u8, C.POINTER(vp), sz, szp, szp, u32p, sz, sz, C.c_int, vp]
+        L.kzg_debug_poly_grand_product_plan.argtypes = [szp, szp, sz, szp, szp, u32p, sz, sz, C.c_int]
+        L.kzg_debug_polys_grand_product_split.argtypes = [vp, C.POINTER(C.c_float)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -1364,6 +1367,61 @@ def poly_arith_plan(set_coeffs, terms, vanishing=0, piece_coeffs=0):
     out = (C.c_size_t * 8)()
     _chk(lib().kzg_debug_poly_arith_plan(out, (C.c_size_t * max(len(set_coeffs), 1))(*set_coeffs), len(set_coeffs), (C.c_size_t * max(len(sizes), 1))(*sizes),
                                          (C.c_uint32 * max(len(flat), 1))(*flat), len(sizes), vanishing, piece_coeffs))
+    return tuple(int(x) for x in out)
+
+
+POLYS_GP_MAX_PRODUCTS, POLYS_GP_MAX_FACTORS = 16, 8
+
+
+def _gp_products(products):
+    """[(num_factors, den_factors), ...], the factors (set_index, poly_index) pairs -> (numerator sizes, denominator sizes, the index pairs, flat)"""
+    nums, dens, flat = [], [], []
+    for num, den in products:
+        num, den = list(num), list(den)
+        nums.append(len(num)), dens.append(len(den))
+        for si, pi in num + den:
+            if not isinstance(si, int) or not isinstance(pi, int) or not 0 <= si < 1 << 32 or not 0 <= pi < 1 << 32:
+                raise KzgError("BadArgs", "products: a factor is (set_index, poly_index), not negative")
+            flat += [si, pi]
+    return nums, dens, flat
+
+
+def polys_grand_product(sets, products, kzg_settings, domain=None, shift=False):
+    """kzg_polys_grand_product: sets = a list of Polys of the handle, products = [(num_factors, den_factors), ...] with (set_index,
+    poly_index) factors -> (a new resident Polys, totals).  Polynomial g of the new set (2g with shift=True, 2g + 1 then being z_g(wX)) is
+    z_g with z_g(w^i) = prod_(k<i) prod_j num_j(w^k) / prod_j den_j(w^k) on the domain of `domain` points (None: the largest n_coeffs of the
+    sets, rounded up to a power of two); totals[g] = the product over the whole domain as Bytes32, 1 exactly when the multisets agree.  A
+    denominator that is zero somewhere on the domain raises KzgError."""
+    if not isinstance(kzg_settings, KzgSettings):
+        raise TypeError("kzg_settings: a KzgSettings")
+    sets = list(sets)
+    if any(not isinstance(f, Polys) for f in sets):
+        raise TypeError("sets: a list of Polys")
+    nums, dens, flat = _gp_products(products)
+    if domain is None:
+        domain = 1
+        while domain < max([f.n_coeffs() for f in sets] + [1]):
+            domain *= 2
+    if not isinstance(domain, int) or domain < 0:
+        raise KzgError("BadArgs", "domain: an integer, not negative")
+    hs = (C.c_void_p * max(len(sets), 1))(*[f._h for f in sets])
+    h, totals = C.c_void_p(), C.create_string_buffer(32 * max(len(nums), 1))
+    arr = lambda xs: (C.c_size_t * max(len(xs), 1))(*xs)
+    _chk(lib().kzg_polys_grand_product(C.byref(h), totals, hs, len(sets), arr(nums), arr(dens), (C.c_uint32 * max(len(flat), 1))(*flat), len(nums), domain,
+                                       1 if shift else 0, kzg_settings._h))
+    return Polys._from_handle(h, kzg_settings), [Bytes32(totals.raw[32 * g: 32 * g + 32]) for g in range(len(nums))]
+
+
+def poly_grand_product_plan(set_coeffs, products, domain, shift=False):
+    """kzg_debug_poly_grand_product_plan: set_coeffs = n_coeffs of every set, products as polys_grand_product takes them -> (distinct
+    polynomials, workspace scalars, elements per tile, tiles, lanes per workgroup, tiles per lane of the carry kernel, output polynomials,
+    refusal code); host code"""
+    set_coeffs = list(set_coeffs)
+    nums, dens, flat = _gp_products(products)
+    out = (C.c_size_t * 8)()
+    arr = lambda xs: (C.c_size_t * max(len(xs), 1))(*xs)
+    _chk(lib().kzg_debug_poly_grand_product_plan(out, arr(set_coeffs), len(set_coeffs), arr(nums), arr(dens), (C.c_uint32 * max(len(flat), 1))(*flat), len(nums), domain,
+                                                 1 if shift else 0))
     return tuple(int(x) for x in out)
 
 
