@@ -86,6 +86,28 @@ def lincomb(polys, rows):
     return [[sum(f * p[i] for f, p in zip(row, polys)) % R for i in range(n)] for row in rows]
 
 
+# Closed form: terms c_t k_(t,1) ... k_(t,j) p with 1-coefficient polynomials k and ONE long polynomial p each sum to (sum_t c_t prod_j
+# k_(t,j)) p, so that a size schoolbook products cannot reach is still compared with THIS model (tests/test_poly_closed_forms_cpu.py
+# holds it to result() at 64 and 256 coefficients).
+def scalar_sums(sets, terms, long_polys):
+    """per polynomial of long_polys (each a (set, poly) pair) the sum over the terms that name it - each term names exactly one of them,
+    once - of the coefficient times the term's other factors, which are 1-coefficient polynomials"""
+    sums = [0] * len(long_polys)
+    for c, facs in terms:
+        named = [f for f in facs if f in long_polys]
+        assert len(named) == 1 and all(len(sets[si][pi]) == 1 for si, pi in facs if (si, pi) not in long_polys)
+        for si, pi in facs:
+            if (si, pi) != named[0]:
+                c = c * sets[si][pi][0] % R
+        sums[long_polys.index(named[0])] = (sums[long_polys.index(named[0])] + c) % R
+    return sums
+
+
+def scaled_sum(scalars, polys):
+    """sum_k scalars[k] polys[k], the polynomials of equal length"""
+    return [sum(s * p[i] for s, p in zip(scalars, polys)) % R for i in range(len(polys[0]))]
+
+
 def evaluate(p, z):
     acc = 0
     for c in reversed(p):

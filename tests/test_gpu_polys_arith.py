@@ -1,7 +1,8 @@
 """Arithmetic on resident polynomial sets (kzg_polys_sum_of_products, kzg_polys_linear_combinations; csrc/capi_polys_arith.hpp, kernels
 csrc/poly_arith_kernels.hpp).  Every result is exact: expected coefficients come from the Python-integer model (tests/poly_arith_model.py)
 byte for byte - the transform-size edges, the term forms, the division by X^v - 1 and its refusal, the pieces, the linear combinations -
-one shape at N = 2^20 by an identity at random points, one prover round under a known tau, and the contract."""
+one shape at N = 2^20 by an identity at random points, two shapes at N = 2^17 whose forward transforms take two chunks by a closed form
+of the model, one prover round under a known tau, and the contract."""
 import ctypes as C
 import hashlib
 import random
@@ -243,6 +244,87 @@ def test_a_product_of_two_to_the_twenty_by_identity(known):
             for j, z in enumerate(zs):
                 assert (ys[0][j] * ys[1][j] - ys[2][j]) % R == ts[0][j] * (pow(z, v, R) - 1) % R, j
             assert all(ts[0]), "a quotient that vanished would prove nothing"
+
+
+# ---------------------------------------------------------------- 6b. past one transform chunk
+# N = 2^17, where one launch transforms 64 rows.  Ten terms of a coefficient, seven 1-coefficient polynomials - 70 distinct ones - and one
+# long polynomial sum to (sum_t c_t prod_j k_(t,j)) times the long one (poly_arith_model.py: scalar_sums, scaled_sum, held to result by
+# tests/test_poly_closed_forms_cpu.py): a row the forward loop leaves untransformed is read as evaluations all the same.
+TWO_CHUNK_N = 1 << 17
+
+
+def chunk_cap(n):
+    """frntt_chunk_polys(n) - the rows of n points one transform launch takes - from the transform's own plan hook"""
+    out = (C.c_size_t * 4)()
+    assert api.lib().kzg_debug_fr_ntt_plan(out) == OK
+    return max(1, out[3] * api.FR_NTT_MAX // n)
+
+
+def rand_raw(rng, n):
+    """n random elements -> (their bytes, the integers)"""
+    raw = bytearray(rng.randbytes(32 * n))
+    raw[0::32] = bytes(x & 0x3F for x in raw[0::32])       # below r
+    return bytes(raw), [int.from_bytes(raw[32 * i: 32 * i + 32], "big") for i in range(n)]
+
+
+def raw_result(polys):
+    """the one polynomial of a derived set as bytes (kzg_polys_coeffs into one buffer, read once)"""
+    assert len(polys) == 1
+    out = C.create_string_buffer(32 * polys.n_coeffs())
+    assert api.lib().kzg_polys_coeffs(polys._h, 0, 1, out) == OK
+    return out.raw
+
+
+def seventy_constants(rng, last):
+    """-> (70 distinct non-zero constants, ten terms over them: (0, 0) the first factor of term 0 and the last of terms 1 .. 8, `last`
+    the last factor of term 9; the constants are set 1)"""
+    consts = [rng.randrange(1, R) for _ in range(70)]
+    assert len(set(consts)) == 70
+    terms = [(rng.randrange(1, R), [(0, 0)] + [(1, k) for k in range(7)])]
+    terms += [(rng.randrange(1, R), [(1, 7 * t + k) for k in range(7)] + [(0, 0)]) for t in range(1, 9)]
+    terms += [(R - 1, [(1, 63 + k) for k in range(7)] + [last])]
+    return consts, terms
+
+
+def test_forward_transforms_in_two_chunks(known):
+    """a the first distinct polynomial, b the last - row 71 of 72, in the second chunk: the result is S_a a + S_b b byte for byte"""
+    s = known[0]
+    N = TWO_CHUNK_N
+    cp = chunk_cap(N)
+    rng = random.Random(9710)
+    (raw_a, a), (raw_b, b) = rand_raw(rng, N), rand_raw(rng, N)
+    consts, terms = seventy_constants(rng, (0, 1))
+    order = list(dict.fromkeys(f for _, facs in terms for f in facs))
+    assert (order[0], order[-1], len(order)) == ((0, 0), (0, 1), 72)
+    plan = api.poly_arith_plan([N, 1], [facs for _, facs in terms])
+    assert plan[:5] == (N, N, N, 1, 72) and (-(-plan[4] // cp), plan[4] % cp) == (2, 8), "two forward chunks: %r at %d rows a launch" % (plan, cp)
+    S = M.scalar_sums([[a, b], [[c] for c in consts]], terms, [(0, 0), (0, 1)])
+    assert all(S)
+    with api.Polys([raw_a, raw_b], s) as f0, api.Polys([be32(c) for c in consts], s) as f1:
+        with api.polys_sum_of_products([f0, f1], [(be32(c), facs) for c, facs in terms], s) as out:
+            assert (out.n_coeffs(), len(out)) == (N, 1)
+            got = raw_result(out)
+    assert got == raw_poly(M.scaled_sum(S, [a, b]))
+
+
+def test_division_of_a_sum_from_two_chunks(known):
+    """the same shape with a = q (X^v - 1), v = 2^16, in every term and no b: 71 rows, and the quotient is S_a q"""
+    s = known[0]
+    N, v = TWO_CHUNK_N, TWO_CHUNK_N // 2
+    cp = chunk_cap(N)
+    rng = random.Random(9720)
+    raw_q, q = rand_raw(rng, N - v)
+    consts, terms = seventy_constants(rng, (0, 0))
+    plan = api.poly_arith_plan([N, 1], [facs for _, facs in terms], vanishing=v)
+    assert plan[:5] == (N, N, N - v, 1, 71) and plan[6] == 2 and (-(-plan[4] // cp), plan[4] % cp) == (2, 7), "two forward chunks: %r at %d rows a launch" % (plan, cp)
+    P = M.times_vanishing(q, v)
+    (S_a,) = M.scalar_sums([[P], [[c] for c in consts]], terms, [(0, 0)])
+    assert S_a
+    with api.Polys([raw_poly(P)], s) as f0, api.Polys([be32(c) for c in consts], s) as f1:
+        with api.polys_sum_of_products([f0, f1], [(be32(c), facs) for c, facs in terms], s, vanishing=v) as out:
+            assert (out.n_coeffs(), len(out)) == (N - v, 1)
+            got = raw_result(out)
+    assert got == raw_poly(M.scaled_sum([S_a], [q]))
 
 
 # ---------------------------------------------------------------- 7. a prover round under a known tau

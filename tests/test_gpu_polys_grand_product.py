@@ -1,7 +1,9 @@
 """The grand product over resident polynomial sets (kzg_polys_grand_product; csrc/capi_polys_grand_product.hpp, kernels
 csrc/poly_grand_product_kernels.hpp).  Every result is exact: expected coefficients and totals come from the Python-integer model
 (tests/poly_grand_product_model.py) byte for byte - the size edges around the tile, the forms of a product - the sizes 2^15 .. 2^20 by a
-product that telescopes to a closed form, a permutation argument end to end under a known tau, and the contract."""
+product that telescopes to a closed form, by the model's closed forms the shapes past one transform chunk (forward at 2^17, inverse at
+2^20) and several products where the carry kernel's lanes share tiles (2^19), zeros at the seams of lanes, wavefronts and tiles, a
+permutation argument end to end under a known tau, and the contract."""
 import ctypes as C
 import random
 import threading
@@ -196,6 +198,267 @@ def test_large_sizes_by_a_telescoping_product(known, log_n):
             got = rows_of(out)
     assert got[0] == raw_poly(c * inv % R for c in F), "z = F / F(1)"
     assert got[1] == raw_poly(c * inv % R for c in Fw), "z(wX) = F(wX) / F(1)"
+
+
+# ---------------------------------------------------------------- 3b. past one transform chunk, several products on shared lanes
+# Expected rows are the model's closed forms (poly_grand_product_model.py: ratio_constants, monomial_at, telescoping_rows, held to
+# grand_product by tests/test_poly_closed_forms_cpu.py), compared as bytes.  Every test asserts the plan fields it is there for, so a
+# change of the tile, the lanes or the chunk fails here and does not empty the test.
+def chunk_cap(n):
+    """frntt_chunk_polys(n) - the rows of n points one transform launch takes - from the transform's own plan hook"""
+    out = (C.c_size_t * 4)()
+    assert api.lib().kzg_debug_fr_ntt_plan(out) == OK
+    return max(1, out[3] * api.FR_NTT_MAX // n)
+
+
+def rand_raw(rng, n):
+    """n random elements -> (their bytes, the integers)"""
+    raw = bytearray(rng.randbytes(32 * n))
+    raw[0::32] = bytes(x & 0x3F for x in raw[0::32])       # below r
+    return bytes(raw), [int.from_bytes(raw[32 * i: 32 * i + 32], "big") for i in range(n)]
+
+
+def raw_monomial(n, m, shifted=False):
+    """the row of z = X^m - or of z(wX) = w^m X^m - as bytes"""
+    at, wm = M.monomial_at(n, m)
+    return bytes(32 * at) + be32(wm if shifted else 1) + bytes(32 * (n - at - 1))
+
+
+def call_raw(s, fs, products, n, shift):
+    """one call on uploaded sets -> (the rows as bytes, the totals as integers)"""
+    out, totals = api.polys_grand_product(fs, products, s, domain=n, shift=shift)
+    with out:
+        assert (out.n_coeffs(), len(out)) == (n, (2 if shift else 1) * len(products))
+        return rows_of(out), [int.from_bytes(bytes(t.data), "big") for t in totals]
+
+
+def constant_products(rng, n, ms, first=0):
+    """one product of 8 + 8 constants of ratio w^m per m of ms, the constants distinct polynomials of set 0 from `first` on ->
+    (the constants, the products)"""
+    consts, products = [], []
+    for m in ms:
+        num, den = M.ratio_constants(rng, n, m, 8, 8)
+        at = first + len(consts)
+        products.append(([(0, at + k) for k in range(8)], [(0, at + 8 + k) for k in range(8)]))
+        consts += num + den
+    return consts, products
+
+
+@pytest.mark.parametrize("part", ["64 + 2 rows", "64 + 64 rows"])
+def test_forward_transforms_in_two_chunks(known, part):
+    """n = 2^17, where one launch transforms 64 rows.  Part A: 64 distinct constants in four products, then F(wX) and F in a fifth - the
+    last two rows of the workspace, alone in the second chunk - with the shift.  Part B: 128 rows, two full chunks, F(wX) and F the
+    first two, nine products, without the shift.  A row the forward loop leaves untransformed is read as evaluations all the same."""
+    s = known[0]
+    n = 1 << 17
+    cp, w = chunk_cap(n), M.root(n)
+    rng = random.Random(6000 + len(part))
+    raw_F, F = rand_raw(rng, n)
+    Fw = M.shifted(F, n)
+    if part == "64 + 2 rows":
+        shift, ms = True, [n - 1, 1, n // 2, 77777, 12345]
+        consts, products = constant_products(rng, n, ms[:4])
+        # product 4 takes 7 + 7 constants of product 0 again: c_0 .. c_6 over c_8 .. c_14 of ratio w^(m_4), and c_7 / c_15 = w^(m_0 - m_4)
+        consts[0:7], consts[8:15] = M.ratio_constants(rng, n, ms[4], 7, 7)
+        consts[7] = consts[15] * pow(w, ms[0] - ms[4], R) % R
+        products.append(([(0, k) for k in range(7)] + [(1, 1)], [(0, 8 + k) for k in range(7)] + [(1, 0)]))
+        long_at, want_U = 4, (66, 2, 2)
+        assert M.dedup(products)[-2:] == [(1, 1), (1, 0)], "F(wX) and F are the last two rows"
+    else:
+        shift, ms = False, [31, 0, 1, n // 2, n - 1, 4097, 99999, 2 * T + 1, 5]
+        c0 = M.ratio_constants(rng, n, ms[0], 6, 6)
+        more, products = constant_products(rng, n, ms[1:8], first=12)
+        last = M.ratio_constants(rng, n, ms[8], 1, 1)
+        consts = c0[0] + c0[1] + more + last[0] + last[1]
+        # product 0: F(wX) F over F F and 6 + 6 constants - F once more on either side changes nothing
+        products.insert(0, ([(1, 1), (1, 0)] + [(0, k) for k in range(6)], [(1, 0), (1, 0)] + [(0, 6 + k) for k in range(6)]))
+        products.append(([(0, 124)], [(0, 125)]))
+        long_at, want_U = 0, (128, 2, 0)
+        assert M.dedup(products)[:2] == [(1, 1), (1, 0)], "F(wX) and F are the first two rows"
+    assert len(set(consts)) == len(consts) and all(consts)
+    plan = api.poly_grand_product_plan([1, n], products, n, shift=shift)
+    assert (plan[0], -(-plan[0] // cp), plan[0] % cp) == want_U and plan[3] == n // T > 4 and len(products) >= 5, "two forward chunks: %r at %d rows a launch" % (plan, cp)
+    per = 2 if shift else 1
+    want = []
+    for g, m in enumerate(ms):
+        want += [raw_poly(row) for row in M.telescoping_rows(F, n, m, shift)] if g == long_at else [raw_monomial(n, m, k == 1) for k in range(per)]
+    with api.Polys([be32(c) for c in consts], s) as f0, api.Polys([raw_F, raw_poly(Fw)], s) as f1:
+        got, totals = call_raw(s, [f0, f1], products, n, shift)
+    assert totals == [1] * len(products)
+    for g in range(len(products)):
+        assert got[per * g: per * g + per] == want[per * g: per * g + per], "product %d of ratio w^%d" % (g, ms[g])
+
+
+def test_inverse_transforms_in_two_chunks(known):
+    """n = 2^20, where one launch transforms 8 rows: five products of constants with the shift are ten output rows, 8 + 2.  Row 2g is
+    X^(m_g), row 2g + 1 is w^(m_g) X^(m_g); eight workspace rows, so the forward loop has one chunk."""
+    s = known[0]
+    n = api.FR_NTT_MAX
+    cp = chunk_cap(n)
+    rng = random.Random(6020)
+    ms = [0, 1, n // 2, n - 1, 3 * T + 1]
+    consts, products = [], []
+    for m, (n_num, n_den) in zip(ms, ((1, 1), (1, 1), (1, 1), (0, 1), (0, 1))):
+        num, den = M.ratio_constants(rng, n, m, n_num, n_den)
+        at = len(consts)
+        products.append(([(0, at + k) for k in range(n_num)], [(0, at + n_num + k) for k in range(n_den)]))
+        consts += num + den
+    plan = api.poly_grand_product_plan([1], products, n, shift=True)
+    assert plan[0] <= cp and (plan[6], -(-plan[6] // cp), plan[6] % cp) == (10, 2, 2) and plan[5] == n // T // LANES, "one forward chunk, two inverse: %r" % (plan,)
+    with api.Polys([be32(c) for c in consts], s) as f:
+        out, totals = api.polys_grand_product([f], products, s, domain=n, shift=True)
+        with out:
+            assert (out.n_coeffs(), len(out)) == (n, 10) and [t.data for t in totals] == [be32(1)] * 5
+            for g, m in enumerate(ms):
+                for k in range(2):           # a row at a time: 32 MiB each
+                    assert rows_of(out, 2 * g + k, 1)[0] == raw_monomial(n, m, k == 1), "row %d: m = %d" % (2 * g + k, m)
+
+
+@pytest.fixture(scope="module")
+def shared_lanes(known):
+    """Three products on the domain of 2 T LANES points, where every lane of the carry kernel owns two tiles: product 0 telescopes with
+    its own F_0; product 1 has 8 + 8 factors - F_1(wX), F_1 (of n / 8 coefficients) and 7 + 7 constants of ratio w^(m_1); product 2 has
+    no numerator and the one denominator w^(-m_2), so z_i = w^(m_2 i).  (19 workspace rows: at 16 rows a launch the forward transforms
+    take two chunks here as well.)  -> the uploaded sets, the products, the six rows with the shift."""
+    s = known[0]
+    n = 2 * T * LANES
+    rng = random.Random(6030)
+    m1, m2 = n - T - 3, T * LANES + 1
+    raw_F0, F0 = rand_raw(rng, n)
+    raw_F1, F1 = rand_raw(rng, n // 8)
+    num, den = M.ratio_constants(rng, n, m1, 7, 7)
+    (d,) = M.ratio_constants(rng, n, m2, 0, 1)[1]
+    assert d == pow(M.root(n), -m2, R)
+    products = [([(0, 1)], [(0, 0)]), ([(2, k) for k in range(7)] + [(1, 1)], [(1, 0)] + [(2, 7 + k) for k in range(7)]), ([], [(2, 14)])]
+    plan = api.poly_grand_product_plan([n, n // 8, 1], products, n)
+    assert (plan[0], plan[3], plan[5]) == (19, 2 * LANES, 2), "three products, g > 0, at two tiles a lane: %r" % (plan,)
+    want = [raw_poly(row) for row in M.telescoping_rows(F0, n, 0, True) + M.telescoping_rows(F1, n, m1, True)] + [raw_monomial(n, m2), raw_monomial(n, m2, True)]
+    fs = [api.Polys([raw_F0, raw_poly(M.shifted(F0, n))], s), api.Polys([raw_F1, raw_poly(M.shifted(F1, n))], s), api.Polys([be32(c) for c in num + den + [d]], s)]
+    yield fs, products, n, want
+    for f in fs:
+        f.close()
+
+
+def test_several_products_where_lanes_share_tiles(known, shared_lanes):
+    """... without the shift (row g, not 2g), then with it: the even rows are the rows of the run without"""
+    s = known[0]
+    fs, products, n, want = shared_lanes
+    plain, totals = call_raw(s, fs, products, n, False)
+    assert totals == [1, 1, 1]
+    for g in range(3):
+        assert plain[g] == want[2 * g], "z_%d without the shift" % g
+    both, totals = call_raw(s, fs, products, n, True)
+    assert totals == [1, 1, 1] and both[0::2] == plain
+    for k in range(6):
+        assert both[k] == want[k], "row %d with the shift" % k
+
+
+def test_the_argument_buffer_after_a_smaller_call(known, shared_lanes):
+    """tile products, carries and totals lie in the handle's grow-only argument buffer at offsets of the plan: the large call, 16
+    products on 8 points, the large call again - the same bytes, and the small one is the model's"""
+    s = known[0]
+    fs, products, n, want = shared_lanes
+    first = call_raw(s, fs, products, n, True)
+    rng = random.Random(6040)
+    sets = [[rand_poly(rng, 8) for _ in range(3)], [rand_poly(rng, 3) for _ in range(3)]]
+    pick = lambda k: [(rng.randrange(2), rng.randrange(3)) for _ in range(k)]
+    small = [(pick(g % 9), pick((3 * g + 2) % 9)) for g in range(16)]
+    assert api.poly_grand_product_plan([8, 3], small, 8, shift=True)[6] == 32
+    model = M.grand_product(sets, small, 8, shift=True)
+    assert model is not None and run(s, sets, small, 8, shift=True) == model
+    third = call_raw(s, fs, products, n, True)
+    assert first == third and third == (want, [1, 1, 1])
+
+
+# ---------------------------------------------------------------- 3c. zeros at the seams, extreme values
+SEAM_N = 4 * T
+SEAMS = [0, 3, 4, 255, 256, T - 1, T, SEAM_N - 1]      # either side of a lane's four indices, of a wavefront's 256, of a tile; the ends
+
+
+@pytest.fixture(scope="module")
+def seam_polys():
+    rng = random.Random(6050)
+    return [rand_poly(rng, SEAM_N) for _ in range(3)]
+
+
+def linear_zero(n, k):
+    """X - w^k"""
+    return [(-pow(M.root(n), k, R)) % R, 1] + [0] * (n - 2)
+
+
+@pytest.mark.parametrize("k", SEAMS)
+def test_a_numerator_zero_at_a_seam(known, seam_polys, k):
+    """A = X - w^k: z is non-zero up to and including index k and zero behind it, the total is 0; for k = n - 1 no z_i is zero"""
+    s = known[0]
+    n = SEAM_N
+    sets = [[linear_zero(n, k)] + seam_polys[:2]]
+    products = [([(0, 0), (0, 1)], [(0, 2)])]
+    assert api.poly_grand_product_plan([n], products, n, shift=True)[3] == 4
+    polys, totals = run(s, sets, products, n, shift=True)
+    assert (polys, totals) == M.grand_product(sets, products, n, shift=True) and totals == [0]
+    z = M.evals(polys[0], n)
+    assert all(z[: k + 1]) and not any(z[k + 1:]) and (k < n - 1 or all(z))
+
+
+def test_numerator_zeros_in_two_tiles_and_in_the_second_product(known, seam_polys):
+    s = known[0]
+    n = SEAM_N
+    k0, k3 = 5, 3 * T + 9
+    sets = [[linear_zero(n, k0), linear_zero(n, k3)] + seam_polys]
+    # zeros in tiles 0 and 3 of one product
+    products = [([(0, 0), (0, 1), (0, 2)], [(0, 3)])]
+    polys, totals = run(s, sets, products, n, shift=True)
+    assert (polys, totals) == M.grand_product(sets, products, n, shift=True) and totals == [0]
+    z = M.evals(polys[0], n)
+    assert all(z[: k0 + 1]) and not any(z[k0 + 1:])
+    # product 0 clean, the zero (in tile 3) in product 1
+    products = [([(0, 2)], [(0, 3)]), ([(0, 1), (0, 4)], [(0, 3)])]
+    polys, totals = run(s, sets, products, n)
+    assert (polys, totals) == M.grand_product(sets, products, n) and totals[0] != 0 and totals[1] == 0
+    z0, z1 = M.evals(polys[0], n), M.evals(polys[1], n)
+    assert all(z0) and all(z1[: k3 + 1]) and not any(z1[k3 + 1:])
+
+
+def test_a_denominator_zero_in_the_last_tile_of_the_second_product(known):
+    """n = 2 T LANES (two tiles a lane), B = X - w^k as the denominator of product 1 of 2: refused, *out and totals_out untouched, and
+    the next call - B as a numerator - succeeds, its totals (a^n - 1) / (c^n - 1) and 0"""
+    s = known[0]
+    L = api.lib()
+    n = 2 * T * LANES
+    rng = random.Random(6060)
+    assert api.poly_grand_product_plan([2], [([(0, 0)], [(0, 2)]), ([(0, 0)], [(0, 1)])], n)[3:6] == (2 * LANES, LANES, 2)
+    a, c = rng.randrange(2, R), rng.randrange(2, R)
+    MARK = b"\xa5" * 32
+
+    def call(flat, shift):
+        o, tot = C.c_void_p(), C.create_string_buffer(MARK * 2, 64)
+        rc = L.kzg_polys_grand_product(C.byref(o), tot, (C.c_void_p * 1)(f._h), 1, (C.c_size_t * 2)(1, 1), (C.c_size_t * 2)(1, 1), (C.c_uint32 * 8)(*flat), 2, n, shift, s._h)
+        if rc == OK:
+            L.kzg_polys_free(o)
+        return rc, o.value, tot.raw
+
+    for k in (n - 1, n - T, n - T + 257):
+        with api.Polys([raw_poly([(-a) % R, 1]), raw_poly(linear_zero(n, k)[:2]), raw_poly([(-c) % R, 1])], s) as f:
+            for shift in (0, 1):
+                rc, o, tot = call([0, 0, 0, 2, 0, 0, 0, 1], shift)
+                assert rc == BADARGS and VANISHES in last_error() and not o and tot == MARK * 2, (k, shift, rc, last_error())
+            rc, o, tot = call([0, 0, 0, 2, 0, 1, 0, 2], 0)
+            total = (pow(a, n, R) - 1) * pow(pow(c, n, R) - 1, -1, R) % R
+            assert rc == OK and tot == be32(total) + be32(0), (k, rc, last_error())
+
+
+def test_extreme_values(known):
+    """the constants 1 and r - 1 alone on two tiles: 8 + 8 factors of r - 1 give z = 1; 7 + 8, and r - 1 among fifteen ones, the ratio
+    -1 = w^(n/2), z = X^(n/2).  The 7 + 8 product is also what sees the starting power of an 8-factor chain: a factor common to every
+    a_i and b_i of a product cancels in prefix x suffix / total, so an 8 + 8 product is blind to it."""
+    s = known[0]
+    n = 2 * T
+    sets = [[[1], [R - 1]]]
+    products = [([(0, 1)] * 8, [(0, 1)] * 8), ([(0, 1)] * 7, [(0, 1)] * 8), ([(0, 1)] + [(0, 0)] * 7, [(0, 0)] * 8)]
+    want = ([row for m in (0, n // 2, n // 2) for row in M.monomial_rows(n, m, True)], [1, 1, 1])
+    assert api.poly_grand_product_plan([1], products, n, shift=True)[3] == 2
+    assert M.monomial_at(n, n // 2) == (n // 2, R - 1)
+    assert run(s, sets, products, n, shift=True) == want == M.grand_product(sets, products, n, shift=True)
 
 
 # ---------------------------------------------------------------- 4. a permutation argument end to end
