@@ -970,8 +970,8 @@ KzgRet kzg_debug_polys_arith_split(const KzgSettings *s, float out[5]);
  * as evaluations into the new set's buffer - and the inverse transform runs in place there.
  * kzg_last_timings: [4] the device stage, [6] the copies - the factor table; no coefficient crosses the bus (kzg_debug_polys_stats
  * counts the call as served from a resident set; its byte counters do not move).
- * NOT in this call: blinding terms (b2 X^2 + b1 X + b0) Z_H, which lengthen z beyond n coefficients; logUp-style running SUMS of
- * fractions, which can reuse the products-and-one-inverse scheme.
+ * NOT in this call: blinding terms (b2 X^2 + b1 X + b0) Z_H, which lengthen z beyond n coefficients.  logUp-style running SUMS of
+ * fractions are kzg_polys_fraction_sum's, below, which reuses the products-and-one-inverse scheme.
  * Measured (tools/prof/polys_grand_product_probe.py, profiles/polys_grand_product_probe.json; 10 warm calls each, median (min - max); 3 + 3
  * factors, one product, with shift): n = 2^20: 2.154 (2.105 - 2.248) ms, slot [4] 1.873 ms = pad 0.063 + forward transforms 0.881 + tile
  * products and carries 0.440 + apply 0.150 + inverse transforms 0.327 ms, copies 0.009 ms; n = 2^18: 1.042 (0.997 - 1.143) ms, stage 0.757 ms;
@@ -993,6 +993,74 @@ KzgRet KZG_POLYS_API kzg_debug_poly_grand_product_plan(size_t out[8], const size
 /* diagnostic: slot [4] of the handle's last kzg_polys_grand_product split by events, ms - out = { pad, forward transforms, tile products +
  * carries, apply, inverse transform } */
 KzgRet kzg_debug_polys_grand_product_split(const KzgSettings *s, float out[5]);
+/* RESIDENT FRACTION SUMS (csrc/capi_polys_fraction_sum.hpp): the running sum of a log-derivative lookup argument - logUp as in halo2's
+ * logUp forks, multi-column lookups, bus arguments - over resident polynomials, returned as a NEW resident set.  Its challenges are drawn
+ * after the witness commitments, and the grand product cannot express a sum of fractions; with this call a lookup's round stays on the
+ * device like the rounds around it.  All arithmetic mod r; w = w_n is the root kzg_fr_ntt uses for n = domain_n.
+ *   The call holds n_sums sums; sum g has frac_counts[g] fractions, 0 .. KZG_POLYS_FS_MAX_FRACTIONS (0: the zero polynomial, total 0).
+ *   The fractions are listed sum after sum: fraction k has the coefficient c_k = frac_coeffs[32 k ..] (big-endian, below r), num_sizes[k]
+ *   numerator polynomials N_(k,j) and den_sizes[k] denominator polynomials D_(k,j), 0 .. KZG_POLYS_FS_MAX_FACTORS each (0: the constant
+ *   1).  factors names them fraction after fraction, numerators first, exactly as kzg_polys_grand_product names its factors: per factor
+ *   two uint32_t, the index into `sets` and the polynomial's index in that set.  A polynomial may be named any number of times.  The
+ *   sets may differ in n_coeffs, each at most domain_n (shorter ones are zero-padded).
+ *   With s_i = sum_k c_k prod_j N_(k,j)(w^i) / prod_j D_(k,j)(w^i), phi_g is the polynomial of degree < n with phi_g(w^i) = sum_(m<i) s_m,
+ *   i = 0 .. n - 1, so phi_g(1) = 0.  totals_out may be NULL; otherwise totals_out[32 g ..] = sum_(m<n) s_m, big-endian: 0 exactly when
+ *   the lookup closes.  The call does NOT refuse another value: judging it is the caller's business.
+ *   flags selects further rows per sum, in this order: KZG_POLYS_FS_WITH_SHIFT adds phi_g(wX), whose evaluations are those of phi_g
+ *   rotated by one place (entry n - 1 is phi_0 = 0); KZG_POLYS_FS_WITH_STEPS adds s_g, the polynomial with s_g(w^i) = s_i - for a lone
+ *   fraction 1 / (beta + f) the batch inverse as a polynomial.  Sum g occupies polynomials g R .. g R + R - 1 of the new set, R = 1 +
+ *   shift + steps, in the order phi, phi(wX), s; every polynomial has domain_n coefficients.
+ *   phi(wX) - phi = s holds on the WHOLE domain exactly when the total is 0: at index n - 1 the difference is s_(n-1) - total (the rotation
+ *   wraps to phi_0 = 0, not to the total); at every other index it is s_i whatever the total.
+ * The returned set is an ordinary KzgPolys: immutable, owned by `s`, freed with kzg_polys_free before the handle, accepted by every call
+ * that takes one - a further fraction sum, kzg_polys_grand_product, kzg_polys_sum_of_products and the openings included; its coefficients
+ * are canonical.  The handle's lock is taken; the call runs on the sets' device; the same call twice gives the same bytes.
+ * KZG_BADARGS - *out and totals_out untouched, nothing kept, the handle usable afterwards - each with its own words in kzg_last_error(),
+ * the first of this order (csrc/poly_fraction_sum_plan.hpp, FsRefusal): a null pointer; n_sums == 0 or above KZG_POLYS_FS_MAX_SUMS; a
+ * fraction count above KZG_POLYS_FS_MAX_FRACTIONS; a side above KZG_POLYS_FS_MAX_FACTORS; n_sets above KZG_POLYS_SOP_MAX_SETS; a factor
+ * while n_sets == 0; a set uploaded on another handle; a set index out of range; a polynomial index out of range; a referenced set of
+ * n_coeffs == 0; domain_n zero, no power of two or above KZG_FR_NTT_MAX; a referenced set longer than domain_n; U * domain_n above
+ * KZG_POLYS_MAX_SCALARS for the U distinct polynomials named; a bit of flags beside the two above ("unknown flag bits"); a c_k that is
+ * not below r ("a fraction coefficient is not below r"); a denominator that is zero somewhere on the domain ("a denominator vanishes on
+ * the domain").  An allocation the device refuses is KZG_MALLOC.
+ * On the device (csrc/poly_fraction_sum_plan.hpp, poly_fraction_sum_kernels.hpp): the U polynomials are padded into a workspace of U *
+ * domain_n scalars - the call's own, released on return - and transformed forward in place (the transform of kzg_fr_ntt, in its chunks).
+ * Per index the fractions are streamed into ONE fraction P_i / Q_i (P <- P d_k + c_k n_k Q, Q <- Q d_k), and 1 / Q_i = (prod_(m<i) Q_m)
+ * (prod_(m>i) Q_m) / prod_m Q_m: an exclusive prefix product, an exclusive suffix product and ONE inversion per sum, then an additive scan
+ * of the s_i - five launches over tiles of 1 024 indices (256 lanes x 4 consecutive indices): k_fs_tile_products, k_fs_product_carries
+ * (one workgroup per sum; a zero total product is the vanishing denominator, F_r having no zero divisors), k_fs_steps, k_fs_sum_carries,
+ * k_fs_apply, which writes phi and phi(wX) as evaluations into the new set's buffer - and the inverse transform runs in place there.
+ * The host does no field arithmetic: the c_k go up as bytes and the device range-checks them.
+ * kzg_last_timings: [4] the device stage, [6] the copies - the fraction table; no coefficient crosses the bus (kzg_debug_polys_stats
+ * counts the call as served from a resident set; its byte counters do not move).
+ * NOT in this call: blinding terms; a judgement of the total.
+ * Measured (tools/prof/polys_fraction_sum_probe.py, profiles/polys_fraction_sum_probe.json; 10 warm calls each, median (min - max); one
+ * sum of 4 fractions of 1 + 1 factors, with shift and steps): n = 2^20: 2.741 (2.598 - 3.063) ms, slot [4] 2.448 ms = pad 0.084 + forward
+ * transforms 1.076 + tile products, carries and the inverse 0.454 + steps and tile sums 0.315 + apply 0.037 + inverse transforms 0.462 ms,
+ * copies 0.009 ms, the grand product 2.447 ms (stage 2.157 ms); n = 2^18: 1.417 (1.296 - 1.539) ms, stage 0.922 ms, the grand product
+ * 1.325 ms (stage 0.837 ms); n = 2^16: 0.921 (0.891 - 0.991) ms, stage 0.629 ms, the grand product 0.886 ms (stage 0.588 ms); n = 2^12:
+ * 0.664 (0.658 - 0.670) ms, stage 0.560 ms, the grand product 0.662 ms (stage 0.568 ms).  The one serial piece, the single-lane inversion
+ * in k_fs_product_carries, holds the 'tile products, carries and the inverse' stage at 0.36 ms from 2^12 to 2^18 (64 % of the stage at
+ * 2^12, 19 % at 2^20); the five launches together cost 0.34 ms more at 2^20 than at 2^12, the third inverse transform
+ * and the third row explain the rest of the distance to the grand product. */
+#define KZG_POLYS_FS_MAX_SUMS      16
+#define KZG_POLYS_FS_MAX_FRACTIONS 8     /* per sum */
+#define KZG_POLYS_FS_MAX_FACTORS   4     /* per side of one fraction */
+#define KZG_POLYS_FS_WITH_SHIFT    1u
+#define KZG_POLYS_FS_WITH_STEPS    2u
+KzgRet KZG_POLYS_API kzg_polys_fraction_sum(KzgPolys **out, uint8_t *totals_out,
+        const KzgPolys *const *sets, size_t n_sets,
+        const size_t *frac_counts, size_t n_sums, const uint8_t *frac_coeffs,
+        const size_t *num_sizes, const size_t *den_sizes, const uint32_t *factors,
+        size_t domain_n, unsigned flags, const KzgSettings *s);
+/* test hook: the host plan alone, no handle and no GPU - out = { U, workspace scalars, elements per tile, tiles, lanes per workgroup,
+ * tiles per lane of the carry kernels, output polynomials, refusal code (0: none; otherwise the rest is 0) }; the sets are given by their
+ * n_coeffs, so polynomial indices are not checked, and no coefficient is read (csrc/poly_fraction_sum_plan.hpp) */
+KzgRet KZG_POLYS_API kzg_debug_poly_fraction_sum_plan(size_t out[8], const size_t *set_coeffs, size_t n_sets, const size_t *frac_counts,
+        size_t n_sums, const size_t *num_sizes, const size_t *den_sizes, const uint32_t *factors, size_t domain_n, unsigned flags);
+/* diagnostic: slot [4] of the handle's last kzg_polys_fraction_sum split by events, ms - out = { pad, forward transforms, tile products +
+ * carries with the inverse, steps + tile sums + their carries, apply, inverse transforms } */
+KzgRet kzg_debug_polys_fraction_sum_split(const KzgSettings *s, float out[6]);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

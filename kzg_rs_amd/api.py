@@ -206,6 +206,9 @@ def lib():
         L.kzg_polys_grand_product.argtypes = [C.POINTER(vp), u8, C.POINTER(vp), sz, szp, szp, u32p, sz, sz, C.c_int, vp]
         L.kzg_debug_poly_grand_product_plan.argtypes = [szp, szp, sz, szp, szp, u32p, sz, sz, C.c_int]
         L.kzg_debug_polys_grand_product_split.argtypes = [vp, C.POINTER(C.c_float)]
+        L.kzg_polys_fraction_sum.argtypes = [C.POINTER(vp), u8, C.POINTER(vp), sz, szp, sz, u8, szp, szp, u32p, sz, C.c_uint, vp]
+        L.kzg_debug_poly_fraction_sum_plan.argtypes = [szp, szp, sz, szp, sz, szp, szp, u32p, sz, C.c_uint]
+        L.kzg_debug_polys_fraction_sum_split.argtypes = [vp, C.POINTER(C.c_float)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -1422,6 +1425,74 @@ def poly_grand_product_plan(set_coeffs, products, domain, shift=False):
     arr = lambda xs: (C.c_size_t * max(len(xs), 1))(*xs)
     _chk(lib().kzg_debug_poly_grand_product_plan(out, arr(set_coeffs), len(set_coeffs), arr(nums), arr(dens), (C.c_uint32 * max(len(flat), 1))(*flat), len(nums), domain,
                                                  1 if shift else 0))
+    return tuple(int(x) for x in out)
+
+
+POLYS_FS_MAX_SUMS, POLYS_FS_MAX_FRACTIONS, POLYS_FS_MAX_FACTORS = 16, 8, 4
+POLYS_FS_WITH_SHIFT, POLYS_FS_WITH_STEPS = 1, 2
+
+
+def _fs_sums(sums, with_coeffs=True):
+    """[[(coeff32, num_factors, den_factors), ...], ...], the factors (set_index, poly_index) pairs -> (fractions per sum, the coefficients
+    as bytes, numerator sizes, denominator sizes, the index pairs, flat)"""
+    counts, coeffs, nums, dens, flat = [], [], [], [], []
+    for fractions in sums:
+        fractions = list(fractions)
+        counts.append(len(fractions))
+        for coeff, num, den in fractions:
+            num, den = list(num), list(den)
+            if with_coeffs:
+                coeff = bytes(getattr(coeff, "data", coeff))
+                if len(coeff) != 32:
+                    raise KzgError("BadArgs", "sums: a fraction's coefficient is 32 bytes")
+                coeffs.append(coeff)
+            nums.append(len(num)), dens.append(len(den))
+            for si, pi in num + den:
+                if not isinstance(si, int) or not isinstance(pi, int) or not 0 <= si < 1 << 32 or not 0 <= pi < 1 << 32:
+                    raise KzgError("BadArgs", "sums: a factor is (set_index, poly_index), not negative")
+                flat += [si, pi]
+    return counts, b"".join(coeffs), nums, dens, flat
+
+
+def polys_fraction_sum(sets, sums, kzg_settings, domain=None, shift=False, steps=False):
+    """kzg_polys_fraction_sum: sets = a list of Polys of the handle, sums = [[(coeff32, num_factors, den_factors), ...], ...] with
+    (set_index, poly_index) factors -> (a new resident Polys, totals).  Sum g occupies the polynomials g R .. g R + R - 1 of the new set,
+    R = 1 + shift + steps, in the order phi_g, phi_g(wX), s_g: phi_g(w^i) = sum_(m<i) s_m and s_g(w^i) = s_i = sum_k coeff_k prod_j num_j(w^i)
+    / prod_j den_j(w^i) on the domain of `domain` points (None: the largest n_coeffs of the sets, rounded up to a power of two); totals[g]
+    = the sum over the whole domain as Bytes32, 0 exactly when the lookup closes.  A denominator that is zero somewhere on the domain
+    raises KzgError."""
+    if not isinstance(kzg_settings, KzgSettings):
+        raise TypeError("kzg_settings: a KzgSettings")
+    sets = list(sets)
+    if any(not isinstance(f, Polys) for f in sets):
+        raise TypeError("sets: a list of Polys")
+    counts, coeffs, nums, dens, flat = _fs_sums(sums)
+    if domain is None:
+        domain = 1
+        while domain < max([f.n_coeffs() for f in sets] + [1]):
+            domain *= 2
+    if not isinstance(domain, int) or domain < 0:
+        raise KzgError("BadArgs", "domain: an integer, not negative")
+    hs = (C.c_void_p * max(len(sets), 1))(*[f._h for f in sets])
+    h, totals = C.c_void_p(), C.create_string_buffer(32 * max(len(counts), 1))
+    arr = lambda xs: (C.c_size_t * max(len(xs), 1))(*xs)
+    flags = (POLYS_FS_WITH_SHIFT if shift else 0) | (POLYS_FS_WITH_STEPS if steps else 0)
+    _chk(lib().kzg_polys_fraction_sum(C.byref(h), totals, hs, len(sets), arr(counts), len(counts), C.create_string_buffer(coeffs, max(len(coeffs), 1)), arr(nums), arr(dens),
+                                      (C.c_uint32 * max(len(flat), 1))(*flat), domain, flags, kzg_settings._h))
+    return Polys._from_handle(h, kzg_settings), [Bytes32(totals.raw[32 * g: 32 * g + 32]) for g in range(len(counts))]
+
+
+def poly_fraction_sum_plan(set_coeffs, sums, domain, shift=False, steps=False):
+    """kzg_debug_poly_fraction_sum_plan: set_coeffs = n_coeffs of every set, sums as polys_fraction_sum takes them (the coefficients are
+    not read: None will do) -> (distinct polynomials, workspace scalars, elements per tile, tiles, lanes per workgroup, tiles per lane of
+    the carry kernels, output polynomials, refusal code); host code"""
+    set_coeffs = list(set_coeffs)
+    counts, _, nums, dens, flat = _fs_sums(sums, with_coeffs=False)
+    out = (C.c_size_t * 8)()
+    arr = lambda xs: (C.c_size_t * max(len(xs), 1))(*xs)
+    flags = (POLYS_FS_WITH_SHIFT if shift else 0) | (POLYS_FS_WITH_STEPS if steps else 0)
+    _chk(lib().kzg_debug_poly_fraction_sum_plan(out, arr(set_coeffs), len(set_coeffs), arr(counts), len(counts), arr(nums), arr(dens), (C.c_uint32 * max(len(flat), 1))(*flat),
+                                                domain, flags))
     return tuple(int(x) for x in out)
 
 
