@@ -1022,7 +1022,8 @@ KzgRet kzg_debug_polys_grand_product_split(const KzgSettings *s, float out[5]);
  * n_coeffs == 0; domain_n zero, no power of two or above KZG_FR_NTT_MAX; a referenced set longer than domain_n; U * domain_n above
  * KZG_POLYS_MAX_SCALARS for the U distinct polynomials named; a bit of flags beside the two above ("unknown flag bits"); a c_k that is
  * not below r ("a fraction coefficient is not below r"); a denominator that is zero somewhere on the domain ("a denominator vanishes on
- * the domain").  An allocation the device refuses is KZG_MALLOC.
+ * the domain").  The common denominator Q takes every d_k whatever c_k is, so a fraction with c_k = 0 whose denominator vanishes on the
+ * domain is refused like any other.  An allocation the device refuses is KZG_MALLOC.
  * On the device (csrc/poly_fraction_sum_plan.hpp, poly_fraction_sum_kernels.hpp): the U polynomials are padded into a workspace of U *
  * domain_n scalars - the call's own, released on return - and transformed forward in place (the transform of kzg_fr_ntt, in its chunks).
  * Per index the fractions are streamed into ONE fraction P_i / Q_i (P <- P d_k + c_k n_k Q, Q <- Q d_k), and 1 / Q_i = (prod_(m<i) Q_m)

@@ -3,7 +3,10 @@ csrc/poly_fraction_sum_kernels.hpp).  Every result is exact: expected coefficien
 (tests/poly_fraction_sum_model.py) byte for byte - the size edges around the tile, the forms of a sum, sixteen sums in one call, zeros at
 the seams of lanes, wavefronts and tiles - the sizes a Python transform cannot reach by the model's closed forms (a telescoping fraction,
 fractions of constants: 2^15, two tiles a lane of the carry kernels, past one transform chunk forward at 2^17 and back at 2^20), a lookup
-argument end to end under a known tau, and the contract.  Every test asserts the plan fields it is there for, so a change of the tile,
+argument end to end under a known tau, and the contract; then, with a different value at every index, the model's monomial closed form
+in whole rows at 2 T LANES (the full shape of 8 fractions of 4 + 4 factors, sixteen sums, the argument buffer, one flag alone), the four
+flag values over five sums on two tiles, extreme evaluations and coefficients at the seams, and the two refusals of the device in the
+last fraction of the last sum, together in one call and in the second tile of a carry lane.  Every test asserts the plan fields it is there for, so a change of the tile,
 the lanes or the chunk fails here and does not empty the test."""
 import ctypes as C
 import random
@@ -620,3 +623,279 @@ def test_two_threads_share_one_handle(known):
         t.join()
     f.close()
     assert not errors and got == want, errors
+
+
+# ---------------------------------------------------------------- 8. monomials: a different value at every index, whole rows
+BIG_N = 2 * T * LANES         # the smallest n at which a lane of the carry kernels owns two tiles
+
+
+def mono_bytes(a, length):
+    return bytes(32 * a) + be32(1) + bytes(32 * (length - a - 1))
+
+
+def monomial_fractions(rng, n, exps, count, sides=None):
+    """`count` fractions over the two sets of mono_big - eight short monomials, the full-length one - every net exponent non-zero, sides
+    of `sides` factors (None: 1 .. 4 each), c_k among 1, r - 1 and random values"""
+    fractions = []
+    while len(fractions) < count:
+        a, b = sides or (rng.randrange(1, 5), rng.randrange(1, 5))
+        pick = lambda k: [(1, 0) if rng.randrange(6) == 0 else (0, rng.randrange(8)) for _ in range(k)]
+        num, den = pick(a), pick(b)
+        if (sum(exps[si][pi] for si, pi in num) - sum(exps[si][pi] for si, pi in den)) % n:
+            fractions.append((rng.choice([1, R - 1, rng.randrange(R), rng.randrange(R)]), num, den))
+    return fractions
+
+
+@pytest.fixture(scope="module")
+def mono_big(known):
+    """n = 2 T LANES: eight monomials of exponents below 64 in one set of 64 coefficients (k_poly_pad pads them) and X^(n-3) in a set of
+    its own -> the uploaded sets, the exponents, n"""
+    s = known[0]
+    n = BIG_N
+    assert 64 < n <= 1 << 20
+    rng = random.Random(9000)
+    exps = [[rng.randrange(1, 64) for _ in range(8)], [n - 3]]
+    fs = [api.Polys([mono_bytes(a, 64) for a in exps[0]], s), api.Polys([mono_bytes(n - 3, n)], s)]
+    yield fs, exps, n
+    for f in fs:
+        f.close()
+
+
+def check_monomials(s, fs, exps, sums, n, shift, steps):
+    """one call; every row (read one at a time) and every total against the sparse closed form, byte for byte"""
+    per = M.row_count(shift, steps)
+    out, totals = api.polys_fraction_sum(fs, to_api(sums), s, domain=n, shift=shift, steps=steps)
+    with out:
+        assert (out.n_coeffs(), len(out)) == (n, per * len(sums))
+        assert [t.data for t in totals] == [be32(0)] * len(sums), "every net exponent is non-zero: each sum closes"
+        for g, fractions in enumerate(sums):
+            (phi, phis, st), _ = M.monomials(n, fractions, exps)
+            want = [phi] + ([phis] if shift else []) + ([st] if steps else [])
+            for k, row in enumerate(want):
+                assert rows_of(out, per * g + k, 1)[0] == M.sparse_bytes(row, n), "sum %d, row %d of %d" % (g, k, per)
+
+
+def test_monomials_full_shape_two_tiles_a_lane(known, mono_big):
+    """one sum of 8 fractions of 4 + 4 factors with shift and steps where a lane of the carry kernels owns two tiles: three whole rows"""
+    fs, exps, n = mono_big
+    sums = [monomial_fractions(random.Random(9010), n, exps, 8, (4, 4))]
+    assert any((1, 0) in num + den for _, num, den in sums[0])
+    assert plan_of([64, n], sums, n, True, True)[3:7] == (2 * LANES, LANES, 2, 3)
+    check_monomials(known[0], fs, exps, sums, n, True, True)
+
+
+def sixteen_monomial_sums(n, exps):
+    """sum g of g mod 8 + 1 fractions, each sum with its own c_k and exponents; the eight-fraction sums (g = 7, 15) of 4 + 4 factors"""
+    rng = random.Random(9020)
+    sums = [monomial_fractions(rng, n, exps, g % 8 + 1, (4, 4) if g % 8 == 7 else None) for g in range(16)]
+    assert [len(f) for f in sums] == [g % 8 + 1 for g in range(16)] and len(sums[7]) == len(sums[15]) == 8
+    return sums
+
+
+def test_monomials_sixteen_sums_two_tiles_a_lane(known, mono_big):
+    """16 rows and 16 totals in one call, gp_tile_index(tiles, g, t) for g up to 15 with tiles > LANES, the plan's offsets at 16 x 2 LANES
+    entries; the 16 output rows are one inverse chunk, exactly full"""
+    fs, exps, n = mono_big
+    sums = sixteen_monomial_sums(n, exps)
+    plan = plan_of([64, n], sums, n)
+    assert plan[3:7] == (2 * LANES, LANES, 2, 16) and plan[0] <= chunk_cap(n) == 16, "one forward chunk, one inverse chunk of 16 rows: %r" % (plan,)
+    check_monomials(known[0], fs, exps, sums, n, False, False)
+
+
+def test_the_argument_buffer_sixteen_sums_after_a_smaller_call(known, mono_big):
+    """16 sums on 8 points (the model's), then the sixteen sums at 2 T LANES: the same bytes as the closed form's, whatever the smaller
+    call left in the handle's argument buffer"""
+    s = known[0]
+    fs, exps, n = mono_big
+    rng = random.Random(9030)
+    sets = [[rand_poly(rng, 8) for _ in range(3)], [rand_poly(rng, 3) for _ in range(3)]]
+    pick = lambda k: [(rng.randrange(2), rng.randrange(3)) for _ in range(k)]
+    small = [[(rng.randrange(R), pick((g + k) % 5), pick((g + 2 * k + 2) % 5)) for k in range((5 * g + 3) % 9)] for g in range(16)]
+    assert plan_of([8, 3], small, 8, True, True)[6] == 48
+    model = M.fraction_sum(sets, small, 8, shift=True, steps=True)
+    assert model is not None and run(s, sets, small, 8, shift=True, steps=True) == model
+    check_monomials(s, fs, exps, sixteen_monomial_sums(n, exps), n, False, False)
+
+
+# ---------------------------------------------------------------- 9. the flag forms with several sums on several tiles
+def test_flag_forms_five_sums_two_tiles(known):
+    """five sums of 0, 1, 3, 8 and 2 fractions at n = 2 T: each flag value against the model, and the rows of flags 0, SHIFT and STEPS
+    equal to the matching rows of the call with both (fs_row_park / fs_row_phi with g > 0 and 1, 2 and 3 rows a sum)"""
+    s = known[0]
+    rng = random.Random(9100)
+    n = 2 * T
+    sets = [[rand_poly(rng, n) for _ in range(3)], [rand_poly(rng, 40) for _ in range(2)]]
+    every = [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1)]
+    pick = lambda k: [rng.choice(every) for _ in range(k)]
+    sums = [[(rng.randrange(R), pick(4 if count == 8 else rng.randrange(5)), pick(4 if count == 8 else rng.randrange(5))) for _ in range(count)] for count in (0, 1, 3, 8, 2)]
+    for shift, steps, rows in ((False, False, 5), (True, False, 10), (False, True, 10), (True, True, 15)):
+        assert plan_of([n, 40], sums, n, shift, steps)[3:7] == (2, LANES, 1, rows)
+    want_rows, want_totals = M.fraction_sum(sets, sums, n, shift=True, steps=True)
+    assert want_totals[0] == 0 and all(want_totals[1:])
+    want = [raw_poly(row) for row in want_rows]
+    fs = upload(s, sets)
+    try:
+        full, totals = call_raw(s, fs, sums, n, True, True)
+        assert full == want and totals == want_totals
+        for shift, steps in ((False, False), (True, False), (False, True)):
+            keep = [3 * g + k for g in range(5) for k in range(3) if k == 0 or (k == 1 and shift) or (k == 2 and steps)]
+            rows, totals = call_raw(s, fs, sums, n, shift, steps)
+            assert totals == want_totals, (shift, steps)
+            assert rows == [want[k] for k in keep] and rows == [full[k] for k in keep], (shift, steps)
+    finally:
+        for f in fs:
+            f.close()
+
+
+@pytest.mark.parametrize("shift,steps", [(True, False), (False, True)])
+def test_monomials_one_flag_three_sums_two_tiles_a_lane(known, mono_big, shift, steps):
+    """SHIFT alone and STEPS alone at 2 T LANES, three sums of 2, 8 and 3 fractions: two rows a sum, the s_i parked in the row of phi
+    (SHIFT alone) or read out of the steps row that stays (STEPS alone) over 2 LANES tiles"""
+    fs, exps, n = mono_big
+    rng = random.Random(9110)
+    sums = [monomial_fractions(rng, n, exps, 2), monomial_fractions(rng, n, exps, 8, (4, 4)), monomial_fractions(rng, n, exps, 3)]
+    assert plan_of([64, n], sums, n, shift, steps)[3:7] == (2 * LANES, LANES, 2, 6)
+    check_monomials(known[0], fs, exps, sums, n, shift, steps)
+
+
+# ---------------------------------------------------------------- 10. extreme operands
+EXTREME = [0, 1, 2, R - 2, R - 1]
+
+
+@pytest.fixture(scope="module")
+def extreme(known):
+    """n = 4 T, five columns given as EVALUATIONS (Polys.from_evals): two numerator columns drawn from 0, 1, 2, r - 2, r - 1, two
+    denominator columns from the same without 0, one that is r - 1 everywhere; chosen values on either side of every seam"""
+    s = known[0]
+    n = SEAM_N
+    rng = random.Random(9200)
+    cols = [[rng.choice(EXTREME) for _ in range(n)] for _ in range(2)] + [[rng.choice(EXTREME[1:]) for _ in range(n)] for _ in range(2)] + [[R - 1] * n]
+    for j, k in enumerate(SEAMS):
+        for col, (here, behind) in zip(cols[:4], ((0, R - 1), (R - 1, 0), (R - 1, 1), (R - 2, R - 1))):
+            col[k], col[(k + 1) % n] = (here, behind) if j % 2 == 0 else (behind, here)
+    assert all(all(col) for col in cols[2:]) and not all(cols[0]) and not all(cols[1])
+    f = api.Polys.from_evals([raw_poly(col) for col in cols], s)
+    yield f, cols, n
+    f.close()
+
+
+def extreme_chain(c):
+    """8 fractions of 4 + 4 factors, all with the coefficient c: P <- P d + c n Q adds eight full-size terms"""
+    return [(c, [(0, (k + j) % 5) for j in range(4)], [(0, 2 + (k + 2 * j) % 3) for j in range(4)]) for k in range(8)]
+
+
+def test_extreme_operands(known, extreme):
+    """chains of 4 + 4 over 8 fractions with c_k = r - 1 and with c_k = 1 on evaluations 0, 1, 2, r - 2, r - 1; seven fractions N / D with
+    c = r - 1 and one with c = 7 (eight fractions a sum at most): steps, phi and the total are 0; a sum whose c_k are all 0: zero rows"""
+    s = known[0]
+    f, cols, n = extreme
+    N, D = [(0, 0), (0, 1), (0, 4), (0, 1)], [(0, 2), (0, 3), (0, 4), (0, 3)]
+    sums = [extreme_chain(R - 1), extreme_chain(1), [(R - 1, N, D)] * 7 + [(7, N, D)], [(0, N, D), (0, [], [(0, 2)]), (0, [(0, 0)], [])]]
+    assert plan_of([n], sums, n, True, True)[3:7] == (4, LANES, 1, 12)
+    want = M.fraction_sum([cols], sums, n, shift=True, steps=True, evaluations=True)
+    assert want is not None and want[1][0] != 0 and want[1][1] == (-want[1][0]) % R and want[1][2:] == [0, 0]
+    assert want[0][6:] == [[0] * n] * 6 and any(M.evals(want[0][2], n)[k] for k in SEAMS)
+    rows, totals = call_raw(s, [f], sums, n, True, True)
+    assert totals == want[1]
+    for k, row in enumerate(want[0]):
+        assert rows[k] == raw_poly(row), "sum %d, row %d" % divmod(k, 3)
+
+
+def test_a_zero_coefficient_does_not_excuse_a_vanishing_denominator(known, extreme):
+    """Q takes every d_k, whatever c_k: a fraction with c_k = 0 whose denominator is zero at one index is refused like any other"""
+    s = known[0]
+    f, cols, n = extreme
+    zero_once = [1 if i != T + 3 else 0 for i in range(n)]
+    with api.Polys.from_evals([raw_poly(zero_once)], s) as z:
+        sums = [[(1, [(0, 0)], [(0, 2)]), (0, [(0, 1)], [(1, 0)])]]
+        assert M.fraction_sum([cols, [zero_once]], sums, n, evaluations=True) is None
+        with pytest.raises(api.KzgError):
+            api.polys_fraction_sum([f, z], to_api(sums), s, domain=n, shift=True, steps=True)
+        assert VANISHES in last_error()
+        sums = [[(1, [(0, 0)], [(0, 2)]), (0, [(1, 0)], [(0, 3)])]]        # as a numerator: no refusal, and the fraction adds nothing
+        assert call_raw(s, [f, z], sums, n) == call_raw(s, [f], [sums[0][:1]], n)
+
+
+# ---------------------------------------------------------------- 11. the device refusals, everywhere
+MARK = b"\xa5" * 32
+NOT_BELOW_R = "a fraction coefficient is not below r"
+
+
+def c_call(s, fs, sums, n, flags=3):
+    """the C call itself; sums with their coefficients as bytes -> (rc, *out, totals_out); both untouched by a refusal"""
+    L = api.lib()
+    counts, coeffs, nums, dens, flat = api._fs_sums(sums)
+    arr = lambda xs: (C.c_size_t * max(len(xs), 1))(*xs)
+    o, tot = C.c_void_p(), C.create_string_buffer(MARK * len(counts), 32 * len(counts))
+    rc = L.kzg_polys_fraction_sum(C.byref(o), tot, (C.c_void_p * len(fs))(*[f._h for f in fs]), len(fs), arr(counts), len(counts), coeffs, arr(nums), arr(dens),
+                                  (C.c_uint32 * max(len(flat), 1))(*flat), n, flags, s._h)
+    if rc == OK:
+        L.kzg_polys_free(o)
+    return rc, o.value, tot.raw
+
+
+@pytest.mark.parametrize("n", [1, SEAM_N])
+def test_a_coefficient_not_below_r_in_the_last_fraction_of_the_sixteenth_sum(known, n):
+    """the range check runs in tile 0, lane k < count[g]: lane 7 of sum 15, on one point and on four tiles"""
+    s = known[0]
+    rng = random.Random(9300 + n)
+    sets = [[rand_poly(rng, min(n, 5)) for _ in range(2)]]
+    sums = [[(g + 1, [(0, 0)], [(0, 1)])] for g in range(15)] + [[(k + 2, [(0, k % 2)], [(0, (k + 1) % 2)]) for k in range(8)]]
+    assert plan_of([min(n, 5)], sums, n, True, True)[3:7] == (max(1, n // T), LANES, 1, 48) and len(sums[15]) == 8
+    (f,) = upload(s, sets)
+    with f:
+        for bad in (be32(R), b"\xff" * 32, bytes([be32(R)[0] + 1]) + be32(R)[1:]):
+            assert int.from_bytes(bad, "big") >= R
+            call = to_api(sums)
+            call[15][7] = (bad,) + call[15][7][1:]
+            for flags in (3, 0):
+                rc, o, tot = c_call(s, [f], call, n, flags)
+                assert rc == BADARGS and NOT_BELOW_R in last_error() and not o and tot == MARK * 16, (bad.hex(), flags, rc, last_error())
+        sums[15][7] = (R - 1,) + sums[15][7][1:]
+        rc, o, tot = c_call(s, [f], to_api(sums), n)
+        assert rc == OK and MARK not in [tot[32 * g: 32 * g + 32] for g in range(16)], (rc, last_error())
+        if n == 1:
+            assert [int.from_bytes(tot[32 * g: 32 * g + 32], "big") for g in range(16)] == M.fraction_sum(sets, sums, 1)[1]
+
+
+def test_a_bad_coefficient_comes_before_a_vanishing_denominator(known):
+    """both device refusals raised in one call, in different sums, either way round: the words are the coefficient's"""
+    s = known[0]
+    n = 2 * T
+    rng = random.Random(9310)
+    (f,) = upload(s, [[rand_poly(rng, 5), linear_zero(n, T + 7)[:5], rand_poly(rng, 5)]])
+    good, vanishing = (be32(3), [(0, 0)], [(0, 2)]), (be32(5), [(0, 2)], [(0, 0), (0, 1)])
+    bad = (be32(R), [(0, 2)], [(0, 0)])
+    assert plan_of([5], [[good], [good]], n)[3] == 2
+    with f:
+        for sums in ([[good, bad], [good, vanishing]], [[vanishing, good], [good, good, bad]], [[good, (be32(R), [(0, 0)], [(0, 1)])], [good]]):
+            rc, o, tot = c_call(s, [f], sums, n)
+            assert rc == BADARGS and NOT_BELOW_R in last_error() and VANISHES not in last_error() and not o and tot == MARK * 2, (rc, last_error())
+        rc, o, tot = c_call(s, [f], [[good], [good, vanishing]], n)
+        assert rc == BADARGS and VANISHES in last_error() and NOT_BELOW_R not in last_error() and not o and tot == MARK * 2, (rc, last_error())
+        assert c_call(s, [f], [[good], [good, good]], n)[0] == OK
+
+
+def test_a_denominator_zero_in_the_second_tile_of_a_lane_is_refused(known):
+    """n = 2 T LANES, the last sum of three; X - w^k with k = T (2 j + 1) + 5 is zero in the second tile of the run of carry lane j;
+    the next call on the handle, the polynomial as a numerator, gives 7 (X - w^k) / X = 7 - 7 w^k X^(n-1) and the total 7 n"""
+    s = known[0]
+    n = BIG_N
+    j = LANES - 3
+    k = T * (2 * j + 1) + 5
+    wk = pow(M.root(n), k, R)
+    exps = [[None, 1]]
+    with api.Polys([raw_poly([(-wk) % R, 1]), raw_poly([0, 1])], s) as f:
+        sums = [[(3, [(0, 1)], [])], [(5, [], [(0, 1)])], [(7, [(0, 1)], [(0, 1), (0, 0)])]]
+        assert plan_of([2], sums, n, True, True)[3:6] == (2 * LANES, LANES, 2) and k // T == 2 * j + 1 < 2 * LANES
+        for flags in (3, 0):
+            rc, o, tot = c_call(s, [f], to_api(sums), n, flags)
+            assert rc == BADARGS and VANISHES in last_error() and not o and tot == MARK * 3, (flags, rc, last_error())
+        sums[2] = [(7, [(0, 0)], [(0, 1)])]
+        out, totals = api.polys_fraction_sum([f], to_api(sums), s, domain=n, steps=True)
+        with out:
+            assert [int.from_bytes(t.data, "big") for t in totals] == [0, 0, 7 * n % R]
+            for g in (0, 1):
+                (phi, _, st), _ = M.monomials(n, sums[g], exps)
+                assert rows_of(out, 2 * g, 2) == [M.sparse_bytes(phi, n), M.sparse_bytes(st, n)], g
+            assert rows_of(out, 5, 1)[0] == M.sparse_bytes({0: 7, n - 1: -7 * wk}, n)

@@ -1,6 +1,6 @@
 """The Python-integer model of kzg_polys_fraction_sum (tests/poly_fraction_sum_model.py) held to the definition: a brute-force evaluation
 that shares no transform with it - Horner at every w^i, O(n^2) - at n <= 32, and the model's closed forms (telescoping, fractions of
-constants) held to the model at 8 and 64 points.  The GPU tests compare the library with this model, and with the closed forms at the
+constants) held to the model at 8 and 64 points, the monomials at 8, 64 and 256, and sets given as evaluations.  The GPU tests compare the library with this model, and with the closed forms at the
 sizes a Python transform cannot reach."""
 import random
 
@@ -102,3 +102,56 @@ def test_the_closed_forms_against_the_model(n):
     w = M.root(n)
     assert [M.evaluate(rows[0], pow(w, i, R)) for i in range(n)] == [i * S % R for i in range(n)]
     assert [M.evaluate(rows[1], pow(w, i, R)) for i in range(n)] == [(i + 1) * S % R for i in range(n - 1)] + [0]
+
+
+def mono(a, length):
+    return [0] * a + [1] + [0] * (length - a - 1)
+
+
+@pytest.mark.parametrize("n", [8, 64, 256])
+def test_the_monomial_closed_form_against_the_model(n):
+    """8 fractions of 4 + 4 factors over 8 short monomials and the full-length X^(n-3), c_k among 1, r - 1, 0 and random values: the
+    sparse rows of monomials() are fraction_sum's, under every flag value"""
+    rng = random.Random(7400 + n)
+    short = min(n, 64)
+    exps = [[rng.randrange(short) for _ in range(8)], [n - 3]]
+    sets = [[mono(a, short) for a in exps[0]], [mono(n - 3, n)]]
+    pick = lambda: [(1, 0) if rng.randrange(6) == 0 else (0, rng.randrange(8)) for _ in range(4)]
+    net = lambda num, den: (sum(exps[si][pi] for si, pi in num) - sum(exps[si][pi] for si, pi in den)) % n
+    fractions = []
+    while len(fractions) < 8:
+        num, den = pick(), pick()
+        if net(num, den):
+            fractions.append(([1, R - 1, 0, rng.randrange(R)][len(fractions) % 4], num, den))
+    assert any((1, 0) in num + den for _, num, den in fractions), "the full-length monomial takes part"
+    (phi, phis, s), total = M.monomials(n, fractions, exps)
+    want = [M.dense(row, n) for row in (phi, phis, s)]
+    assert total == 0 and M.fraction_sum(sets, [fractions], n, shift=True, steps=True) == (want, [0])
+    assert M.fraction_sum(sets, [fractions], n) == (want[:1], [0])
+    assert M.fraction_sum(sets, [fractions], n, shift=True) == (want[:2], [0])
+    assert M.fraction_sum(sets, [fractions], n, steps=True) == ([want[0], want[2]], [0])
+    assert [M.sparse_bytes(row, n) for row in (phi, phis, s)] == [b"".join(v.to_bytes(32, "big") for v in row) for row in want]
+    # two fractions of one net exponent add up in one coefficient; a lone fraction X^a / 1 is the step X^a itself
+    twice = [(3, [(0, 0)], [(0, 1)]), (5, [(0, 0), (0, 2)], [(0, 2), (0, 1)])]
+    if net(*twice[0][1:]):
+        rows, _ = M.monomials(n, twice, exps)
+        assert M.fraction_sum(sets, [twice], n, shift=True, steps=True) == ([M.dense(row, n) for row in rows], [0])
+        assert rows[2] == {net(*twice[0][1:]): 8}
+
+
+def test_sets_given_as_evaluations_and_a_zero_coefficient_on_a_vanishing_denominator():
+    """fraction_sum(evaluations=True) is fraction_sum on the interpolated coefficients; extreme values pass through it; a fraction with
+    c_k = 0 whose denominator vanishes at one index is refused all the same (the call's common denominator takes every d_k)"""
+    n = 64
+    rng = random.Random(7500)
+    ext = [0, 1, 2, R - 2, R - 1]
+    cols = [[rng.choice(ext) for _ in range(n)] for _ in range(2)] + [[rng.choice(ext[1:]) for _ in range(n)] for _ in range(2)] + [[R - 1] * n]
+    sums = [[(R - 1, [(0, k % 5), (0, 0), (0, 1), (0, 4)], [(0, 2), (0, 3), (0, 4), (0, 2 + k % 3)]) for k in range(8)],
+            [(0, [(0, 0)], [(0, 2)]), (0, [], [(0, 4)])]]
+    want = M.fraction_sum([cols], sums, n, shift=True, steps=True, evaluations=True)
+    assert want is not None and want[1][0] != 0 and want[1][1] == 0 and want[0][3:] == [[0] * n] * 3
+    assert M.fraction_sum([[M.coeffs(e) for e in cols]], sums, n, shift=True, steps=True) == want
+    zero_at = cols[0].index(0)
+    assert M.fraction_sum([cols], [[(1, [(0, 1)], [(0, 2)]), (0, [(0, 1)], [(0, 0)])]], n, evaluations=True) is None, zero_at
+    assert M.step_values([cols], [(0, [], [(0, 0)])], n, evaluations=True) is None
+    assert M.step_values([cols], [(0, [(0, 0)], [(0, 3)])], n, evaluations=True) == [0] * n
