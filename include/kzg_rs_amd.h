@@ -1062,6 +1062,61 @@ KzgRet KZG_POLYS_API kzg_debug_poly_fraction_sum_plan(size_t out[8], const size_
 /* diagnostic: slot [4] of the handle's last kzg_polys_fraction_sum split by events, ms - out = { pad, forward transforms, tile products +
  * carries with the inverse, steps + tile sums + their carries, apply, inverse transforms } */
 KzgRet kzg_debug_polys_fraction_sum_split(const KzgSettings *s, float out[6]);
+/* THE QUOTIENT BY X^n - 1 ON COSETS (csrc/capi_polys_quotient.hpp): the quotient round of a PLONK-style prover for circuits of up to
+ * KZG_FR_NTT_MAX rows.  kzg_polys_sum_of_products takes its product at full size, one transform of N >= L0 points, and a gate of four
+ * factors has L0 = 4 n - 3: its largest circuit has n = 2^18 rows.  This call uses transforms of n points only, so the quotient no longer
+ * leaves the device at n = 2^19 and 2^20, and its workspace is (U + D) n scalars where the full-size form needs (U + 1) D n.
+ *   P = sum_t c_t prod_j p_(t,j): sets, term_coeffs, term_sizes, factors, n_terms and the formal length L0 are EXACTLY those of
+ *   kzg_polys_sum_of_products.  n = domain_n, a power of two, 1 <= n <= KZG_FR_NTT_MAX.  The result is P / (X^n - 1), of formal length
+ *   L = L0 - n, as ceil(L / n) polynomials of n coefficients, the last one zero-padded; a remainder is refused.  Where
+ *   kzg_polys_sum_of_products accepts the same arguments, the result is byte for byte that of kzg_polys_sum_of_products(...,
+ *   vanishing_n = n, piece_coeffs = n).  The factor sets may have any n_coeffs up to KZG_POLYS_MAX_COEFFS, longer than n included - a
+ *   blinded witness a + (b1 X + b0)(X^n - 1) has n + 2 coefficients.  D, the number of cosets, is the smallest power of two with
+ *   D n >= L0, at most KZG_POLYS_QUOTIENT_MAX_COSETS.
+ * The returned set is an ordinary KzgPolys: immutable, owned by `s`, freed with kzg_polys_free before the handle, accepted by every call
+ * that takes one; its coefficients are canonical.  The handle's lock is taken; the call runs on the sets' device; the same call twice
+ * gives the same bytes.
+ * KZG_BADARGS - *out untouched, nothing kept, the handle usable afterwards - each with its own words in kzg_last_error(), the first of
+ * this order (csrc/poly_coset_quotient_plan.hpp, CqRefusal): a null pointer; n_sets above KZG_POLYS_SOP_MAX_SETS; n_terms above
+ * KZG_POLYS_SOP_MAX_TERMS; a term size above KZG_POLYS_SOP_MAX_FACTORS; a factor while n_sets == 0; a set uploaded on another handle; a
+ * set index out of range; a polynomial index out of range; a referenced set of n_coeffs == 0; domain_n zero, no power of two or above
+ * KZG_FR_NTT_MAX; n >= L0, which has nothing to divide ("domain_n is not below the length of the sum"); D above
+ * KZG_POLYS_QUOTIENT_MAX_COSETS ("the sum is more than 16 times as long as domain_n"); U n, D n or pieces n above KZG_POLYS_MAX_SCALARS;
+ * a term coefficient >= r ("a term coefficient is not below r"); a remainder ("the sum is not divisible by X^n - 1").  An allocation the
+ * device refuses is KZG_MALLOC.
+ * On the device (csrc/poly_coset_quotient_plan.hpp, which holds the derivation and the bounds, poly_coset_quotient_kernels.hpp): with g a
+ * root of unity of order 2 D n and zeta = g^2, coset j is sigma_j <w_n>, sigma_j = g zeta^j, where X^n = c_j = sigma_j^n is an odd power
+ * of a primitive 2 D-th root and never 1.  Per coset k_cq_load folds each of the U polynomials mod X^n - c_j and twists it by sigma_j^i,
+ * the transform of kzg_fr_ntt runs forward over the U rows in its chunks, and k_poly_sop sums the products over the n indices; the D
+ * sums are transformed back and k_cq_pieces runs, per index and in registers, the radix-D step that is left of a coset inverse transform,
+ * with the constants 1 / (D (c_j - 1)) from ONE inversion (k_cq_constants).  The pieces beyond the result are rem / (g^(n D) - 1) copied
+ * D - pieces times, so the remainder check is exact; g is invisible in the result.  The host does no field arithmetic.
+ * kzg_last_timings: [4] the device stage, [6] the copies - the term table and the coefficients; no coefficient of a polynomial crosses
+ * the bus (kzg_debug_polys_stats counts the call as served from a resident set; its byte counters do not move).
+ * NOT in this call: a vanishing polynomial other than X^n - 1, pieces of another length, blinding of the pieces.
+ * Measured (tools/prof/polys_quotient_probe.py, profiles/polys_quotient_probe.json): 13 polynomials, 9 terms of up to 4 factors, D = 4, 3
+ * pieces; 10 warm calls each, median (min - max), interleaved with kzg_polys_sum_of_products on the same arguments in the same run.  n =
+ * 2^20: 11.734 (11.324 - 11.882) ms, slot [4] 11.225 ms = load 1.053 + forward transforms 7.787 + k_poly_sop 1.000 + inverse transforms
+ * 0.609 + coefficients and constants 0.430 + pieces 0.331 ms, copies 0.008 ms; n = 2^19: 6.316 (6.107 - 6.549) ms, stage 5.802 ms - both
+ * refused by sum-of-products.  n = 2^18: 3.686 (3.586 - 3.929) ms against 2.903 (2.837 - 3.056) ms for sum-of-products, stage 3.192
+ * against 2.404 ms; n = 2^17: 2.650 against 1.692 ms; n = 2^16: 2.159 against 1.140 ms; n = 2^12: 1.267 against 0.419 ms.  The new call is
+ * SLOWER than sum-of-products wherever both apply, outside its min - max spread: by 0.78 ms at 2^18 and 0.85 ms at 2^12.  0.43 ms of the
+ * gap at every size is the constants launch (the single-lane inversion and the powers in front of it, serial before the first coset), 0.34
+ * - 0.49 ms the load (a pass sum-of-products' pad does in 0.05 ms: the twist is a product per element and per coset), and k_poly_sop runs
+ * D times over n indices (0.18 - 0.29 ms against 0.13); the D U transforms of n points (1.694 ms at 2^18) cost about what the U transforms
+ * of D n points do. */
+#define KZG_POLYS_QUOTIENT_MAX_COSETS 16
+KzgRet KZG_POLYS_API kzg_polys_quotient(KzgPolys **out, const KzgPolys *const *sets, size_t n_sets,
+        const uint8_t *term_coeffs, const size_t *term_sizes, const uint32_t *factors, size_t n_terms,
+        size_t domain_n, const KzgSettings *s);
+/* test hook: the host plan alone, no handle and no GPU - out = { L0, D, L, pieces, U, workspace scalars, indices per lane, refusal code
+ * (0: none; otherwise the rest is 0) }; the sets are given by their n_coeffs, so polynomial indices are not checked
+ * (csrc/poly_coset_quotient_plan.hpp) */
+KzgRet KZG_POLYS_API kzg_debug_poly_coset_quotient_plan(size_t out[8], const size_t *set_coeffs, size_t n_sets, const size_t *term_sizes,
+        const uint32_t *factors, size_t n_terms, size_t domain_n);
+/* diagnostic: slot [4] of the handle's last kzg_polys_quotient split by events and summed over the cosets, ms - out = { load, forward
+ * transforms, k_poly_sop, inverse transforms, coefficients + constants, pieces } */
+KzgRet kzg_debug_polys_quotient_split(const KzgSettings *s, float out[6]);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

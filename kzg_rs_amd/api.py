@@ -209,6 +209,9 @@ def lib():
         L.kzg_polys_fraction_sum.argtypes = [C.POINTER(vp), u8, C.POINTER(vp), sz, szp, sz, u8, szp, szp, u32p, sz, C.c_uint, vp]
         L.kzg_debug_poly_fraction_sum_plan.argtypes = [szp, szp, sz, szp, sz, szp, szp, u32p, sz, C.c_uint]
         L.kzg_debug_polys_fraction_sum_split.argtypes = [vp, C.POINTER(C.c_float)]
+        L.kzg_polys_quotient.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, u8, szp, u32p, sz, sz, vp]
+        L.kzg_debug_poly_coset_quotient_plan.argtypes = [szp, szp, sz, szp, u32p, sz, sz]
+        L.kzg_debug_polys_quotient_split.argtypes = [vp, C.POINTER(C.c_float)]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -1370,6 +1373,44 @@ def poly_arith_plan(set_coeffs, terms, vanishing=0, piece_coeffs=0):
     out = (C.c_size_t * 8)()
     _chk(lib().kzg_debug_poly_arith_plan(out, (C.c_size_t * max(len(set_coeffs), 1))(*set_coeffs), len(set_coeffs), (C.c_size_t * max(len(sizes), 1))(*sizes),
                                          (C.c_uint32 * max(len(flat), 1))(*flat), len(sizes), vanishing, piece_coeffs))
+    return tuple(int(x) for x in out)
+
+
+POLYS_QUOTIENT_MAX_COSETS = 16
+
+
+def polys_quotient(sets, terms, kzg_settings, domain=None):
+    """kzg_polys_quotient: sets and terms exactly as polys_sum_of_products takes them -> a new resident Polys holding sum_t coeff_t prod_j
+    sets[set_index][poly_index] divided by X^domain - 1, as pieces of `domain` coefficients (None: the largest n_coeffs of the sets, rounded
+    up to a power of two).  Taken on 2 .. 16 cosets of the domain with transforms of `domain` points, so it reaches domains of 2^20 points;
+    where polys_sum_of_products(..., vanishing=domain, piece_coeffs=domain) is accepted the bytes are the same.  A remainder raises KzgError."""
+    if not isinstance(kzg_settings, KzgSettings):
+        raise TypeError("kzg_settings: a KzgSettings")
+    sets = list(sets)
+    if any(not isinstance(f, Polys) for f in sets):
+        raise TypeError("sets: a list of Polys")
+    if domain is None:
+        domain = 1
+        while domain < max([f.n_coeffs() for f in sets] + [1]):
+            domain *= 2
+    if not isinstance(domain, int) or domain < 0:
+        raise KzgError("BadArgs", "domain: an integer, not negative")
+    craw, sizes, flat = _sop_terms(terms)
+    hs = (C.c_void_p * max(len(sets), 1))(*[f._h for f in sets])
+    h = C.c_void_p()
+    _chk(lib().kzg_polys_quotient(C.byref(h), hs, len(sets), craw, (C.c_size_t * max(len(sizes), 1))(*sizes), (C.c_uint32 * max(len(flat), 1))(*flat), len(sizes), domain,
+                                  kzg_settings._h))
+    return Polys._from_handle(h, kzg_settings)
+
+
+def poly_coset_quotient_plan(set_coeffs, terms, domain):
+    """kzg_debug_poly_coset_quotient_plan: set_coeffs = n_coeffs of every set, terms = per term its [(set_index, poly_index), ...] -> (L0,
+    cosets, L, pieces, distinct polynomials, workspace scalars, indices per lane, refusal code); host code"""
+    set_coeffs = list(set_coeffs)
+    _, sizes, flat = _sop_terms([(bytes(32), facs) for facs in terms])
+    out = (C.c_size_t * 8)()
+    _chk(lib().kzg_debug_poly_coset_quotient_plan(out, (C.c_size_t * max(len(set_coeffs), 1))(*set_coeffs), len(set_coeffs), (C.c_size_t * max(len(sizes), 1))(*sizes),
+                                                  (C.c_uint32 * max(len(flat), 1))(*flat), len(sizes), domain))
     return tuple(int(x) for x in out)
 
 

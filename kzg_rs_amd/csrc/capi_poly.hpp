@@ -17,6 +17,27 @@
 // d_stage, which leaves the coefficients as 32 big-endian canonical bytes exactly where the scan (or k_poly_decode) reads them.  Its
 // launches are queued after the flag word is cleared and before the scan's, inside the interval of timings slot [4].
 
+// events a call records between its stages when it has more stages than the handle has events (capi_polys_quotient.hpp: three per
+// coset); made on first use, kept, destroyed with the poly state
+struct PolyMarks {
+    std::vector<hipEvent_t> ev;
+    hipError_t reserve(size_t count) {
+        while (ev.size() < count) {
+            hipEvent_t e = nullptr;
+            const hipError_t rc = hipEventCreate(&e);
+            if (rc != hipSuccess) return rc;
+            ev.push_back(e);
+        }
+        return hipSuccess;
+    }
+    PolyMarks() = default;
+    PolyMarks(const PolyMarks&) = delete;
+    PolyMarks& operator=(const PolyMarks&) = delete;
+    ~PolyMarks() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
+
 struct PolyBufs {
     DevBuf<uint8_t> d_zs, d_ys, d_out;  // per pair of a chunk: z as given | y, 32 big-endian bytes | the sums, compressed
     DevBuf<Fr> d_tsum, d_carry;         // [pair][tile]
@@ -25,6 +46,7 @@ struct PolyBufs {
     FrNttBufs ntt;                      // the transform's tables and scratch (capi_fr_ntt.hpp)
     DevBuf<uint8_t> d_gammas, d_fold, d_fys, d_bys;  // the batched openings (capi_poly_batch.hpp): per point gamma | f[point][n_coeffs] | f_j(z_j); y[poly][point] of the call
     DevBuf<uint8_t> d_vin, d_vout;                   // their verifier: gammas | ys as given; the powers of gamma per point | the folded values
+    PolyMarks marks;                                 // kzg_polys_quotient's per-coset stage marks
     KzgRet reserve(size_t n_coeffs, size_t pairs) {
         HIPCHK(d_zs.grow(32 * pairs));
         HIPCHK(d_ys.grow(32 * pairs));

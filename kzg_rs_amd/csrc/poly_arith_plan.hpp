@@ -108,11 +108,13 @@ constexpr size_t pa_pow2_at_least(size_t x) {
     return n;
 }
 
-// The shapes of a kzg_polys_sum_of_products call -> the plan, or the first refusal in the order of the list above.  set_coeffs[n_sets]:
-// n_coeffs of every set; set_polys[n_sets]: its n_polys, or nullptr (kzg_debug_poly_arith_plan: polynomial indices are not checked).
-// factors: two words per factor - the set index, the polynomial index - term after term.
-constexpr PaRefusal pa_plan(PaPlan& pl, const size_t* set_coeffs, const size_t* set_polys, size_t n_sets, const size_t* term_sizes, const uint32_t* factors, size_t n_terms,
-                            size_t vanishing_n, size_t piece_coeffs) {
+// The terms of a call -> L0, U, the deduplicated list of its polynomials and the term table, or the first refusal in the order of the
+// list above (PA_NULL .. PA_EMPTY_SET, and PA_TRANSFORM for a set longer than PA_MAX_COEFFS).  set_coeffs[n_sets]: n_coeffs of every set;
+// set_polys[n_sets]: its n_polys, or nullptr (kzg_debug_poly_arith_plan: polynomial indices are not checked).  factors: two words per
+// factor - the set index, the polynomial index - term after term.  Shared with kzg_polys_quotient (poly_coset_quotient_plan.hpp).
+// pa_plan below is pa_parse and then the checks that were behind it, in the order they had: the refusal order of
+// kzg_polys_sum_of_products is unchanged (PA_TRANSFORM for an over-long set still comes before the check of L0).
+constexpr PaRefusal pa_parse(PaPlan& pl, const size_t* set_coeffs, const size_t* set_polys, size_t n_sets, const size_t* term_sizes, const uint32_t* factors, size_t n_terms) {
     if ((n_sets && !set_coeffs) || (n_terms && !term_sizes)) return PA_NULL;
     if (n_sets > PA_MAX_SETS) return PA_SETS;
     if (n_terms > PA_MAX_TERMS) return PA_TERMS;
@@ -131,7 +133,7 @@ constexpr PaRefusal pa_plan(PaPlan& pl, const size_t* set_coeffs, const size_t* 
         if (set_coeffs[factors[2 * f]] == 0) return PA_EMPTY_SET;
     for (size_t f = 0; f < refs; f++)
         if (set_coeffs[factors[2 * f]] > PA_MAX_COEFFS) return PA_TRANSFORM;  // (no set is longer; below, no sum can wrap)
-    pl.L0 = 1, pl.U = 0, pl.v = vanishing_n;
+    pl.L0 = 1, pl.U = 0;
     pl.table.n_terms = (uint32_t)n_terms;
     for (size_t t = 0, f = 0; t < n_terms; t++) {
         size_t len = 1;
@@ -147,6 +149,15 @@ constexpr PaRefusal pa_plan(PaPlan& pl, const size_t* set_coeffs, const size_t* 
         }
         if (len > pl.L0) pl.L0 = len;
     }
+    return PA_OK;
+}
+
+// The shapes of a kzg_polys_sum_of_products call -> the plan, or the first refusal in the order of the list above.
+constexpr PaRefusal pa_plan(PaPlan& pl, const size_t* set_coeffs, const size_t* set_polys, size_t n_sets, const size_t* term_sizes, const uint32_t* factors, size_t n_terms,
+                            size_t vanishing_n, size_t piece_coeffs) {
+    const PaRefusal bad = pa_parse(pl, set_coeffs, set_polys, n_sets, term_sizes, factors, n_terms);
+    if (bad != PA_OK) return bad;
+    pl.v = vanishing_n;
     if (pl.L0 > FRNTT_MAX) return PA_TRANSFORM;
     pl.N = pa_pow2_at_least(pl.L0);
     pl.logN = frntt_log2(pl.N);
