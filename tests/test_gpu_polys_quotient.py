@@ -1,7 +1,9 @@
 """The quotient by X^n - 1 on cosets (kzg_polys_quotient; csrc/capi_polys_quotient.hpp, kernels csrc/poly_coset_quotient_kernels.hpp).
 Every comparison is byte-exact: against kzg_polys_sum_of_products(..., vanishing_n = n, piece_coeffs = n) wherever that call accepts
 the arguments, against the Python-integer model (tests/poly_coset_quotient_model.py), and at n = 2^20 - which sum-of-products refuses -
-against closed forms built from shifts of the input."""
+against closed forms built from shifts of the input.  Sections 8 to 11: every piece count 1 .. 15 at n = 2^11, accepted (also held to
+the quotient identity at hashed points, in Python integers) and refused for a remainder at one index; the domains 1, 2, 4 and 8
+against schoolbook long division; input forms and extreme values; the two shapes with M = 2 D n = 2^25, the order of the root."""
 import ctypes as C
 import hashlib
 import random
@@ -354,3 +356,323 @@ def test_two_threads_same_bytes_and_counters(settings):
         after = stats()
     assert first == ref and results[0] == first and results[1] == first
     assert after[1] == before[1] and after[3] == before[3] and after[2] > before[2], "served from the resident set: no coefficient bytes copied"
+
+
+# ---------------------------------------------------------------- 8. every (D, pieces) at n = 2^11: two tiles, all four lane steps
+def row_ints(row):
+    return [int.from_bytes(row[32 * i: 32 * i + 32], "big") for i in range(len(row) // 32)]
+
+
+def cosets_of(L0, n):
+    D = 2
+    while D * n < L0:
+        D *= 2
+    return D
+
+
+def identity_holds(got, n, sum_at):
+    """P(z) = (z^n - 1) sum_m z^(n m) T_m(z) with Python integers, by Horner, at two points hashed from the output bytes;
+    sum_at(z) = P(z) from the inputs"""
+    pieces = [row_ints(row) for row in got]
+    seed = hashlib.sha256(b"".join(got)).digest()
+    for t in range(2):
+        z = int.from_bytes(hashlib.sha256(seed + bytes([t])).digest(), "big") % R
+        zn = pow(z, n, R)
+        if (zn - 1) * sum(pow(zn, m, R) * A.evaluate(p, z) for m, p in enumerate(pieces)) % R != sum_at(z) % R:
+            return False
+    return True
+
+
+SWEEP_N = 1 << 11
+SWEEP_LENGTHS = {"one": lambda p, n: (p - 1) * n + 1, "odd": lambda p, n: p * n - (n // 2 + 3), "full": lambda p, n: p * n}
+_sweep_cases = {}
+
+
+def sweep_case(p, kind):
+    """a, b of la ~ 2 lb coefficients with la + lb - 1 = L0 = L + n, and red = a b mod X^n - 1 through the folded factors on the domain
+    -> (L0, L, a, b, red); made once per (p, kind) and never changed.  The fold depths of a and b differ, and neither length is a
+    multiple of n: the top fold exists for a part of the indices only."""
+    if (p, kind) not in _sweep_cases:
+        n = SWEEP_N
+        L = SWEEP_LENGTHS[kind](p, n)
+        L0 = L + n
+        lb = (L0 + 1) // 3
+        la = L0 + 1 - lb
+        rng = random.Random(8000 + 16 * p + sorted(SWEEP_LENGTHS).index(kind))
+        a, b = rand_poly(rng, la), rand_poly(rng, lb)
+        w = M.root(n)
+        fa, fb = [sum(a[i::n]) % R for i in range(n)], [sum(b[i::n]) % R for i in range(n)]
+        red = M.intt([x * y % R for x, y in zip(M.ntt(fa, w), M.ntt(fb, w))], w)
+        _sweep_cases[(p, kind)] = (L0, L, tuple(a), tuple(b), tuple(red))
+    return _sweep_cases[(p, kind)]
+
+
+SWEEP_TERMS = [(1, [(0, 0), (1, 0)]), (R - 1, [(2, 0)])]
+
+
+@pytest.mark.parametrize("kind", ["one", "odd", "full"])
+@pytest.mark.parametrize("p", [1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 13, 14, 15])
+def test_every_piece_count_against_sum_of_products_and_the_identity(settings, p, kind):
+    """a b - (a b mod X^n - 1) with L = (p - 1) n + 1 (the last piece holds one coefficient), p n - (n / 2 + 3), and p n (the last
+    piece is full; L0 = D n at p = D - 1): p pieces on D = the power of two >= p + 1 cosets.  The bytes are sum-of-products' (one
+    transform of 2^15 points at most and the chain division) and, independently of both, satisfy the quotient identity at two points."""
+    n = SWEEP_N
+    L0, L, a, b, red = sweep_case(p, kind)
+    assert api.poly_coset_quotient_plan([len(a), len(b), n], [facs for _, facs in SWEEP_TERMS], n)[:4] + (0,) == (L0, cosets_of(L0, n), L, p, 0)
+    with api.Polys([raw_poly(a)], settings) as fa, api.Polys([raw_poly(b)], settings) as fb, api.Polys([raw_poly(red)], settings) as fr:
+        got, ref = both(settings, [fa, fb, fr], SWEEP_TERMS, n)
+    assert len(got) == p and got == ref
+    assert identity_holds(got, n, lambda z: A.evaluate(a, z) * A.evaluate(b, z) - A.evaluate(red, z))
+
+
+SWEEP_REFUSALS = {1: "full", 2: "odd", 3: "one", 5: "full", 7: "odd", 8: "one", 12: "odd", 14: "full", 15: "full"}
+
+
+@pytest.mark.parametrize("p", sorted(SWEEP_REFUSALS))
+def test_every_piece_count_refuses_a_single_coefficient(settings, p):
+    """the same sums plus c X^k, k on the lane edges, the step edges and the tile edge: a remainder at ONE index, which one lane sees in
+    the pieces from p on alone - at p = D - 1 in one register (D = 16, p = 15: piece 15, pass 1, v[brp(7)]).  Every LOGD, both passes
+    of D = 16, one spare piece and many.  The handle serves on with the accepted bytes."""
+    n = SWEEP_N
+    L0, L, a, b, red = sweep_case(p, SWEEP_REFUSALS[p])
+    rng = random.Random(8500 + p)
+    with api.Polys([raw_poly(a)], settings) as fa, api.Polys([raw_poly(b)], settings) as fb, api.Polys([raw_poly(red)], settings) as fr:
+        for k in (0, 255, 256, 1023, 1024, 1279, n - 1):
+            with api.Polys([raw_poly([0] * k + [1])], settings) as mono:
+                terms = SWEEP_TERMS + [(rng.randrange(1, R), [(3, 0)])]
+                assert api.poly_coset_quotient_plan([len(a), len(b), n, k + 1], [facs for _, facs in terms], n)[:4] == (L0, cosets_of(L0, n), L, p)
+                rc, h, words = refused(settings, [fa, fb, fr, mono], terms, n)
+                assert (rc, h) == (1, 0x1234) and words.endswith(NOT_DIVISIBLE), (k, rc, h, words)
+        got, ref = both(settings, [fa, fb, fr], SWEEP_TERMS, n)
+    assert len(got) == p and got == ref
+    assert identity_holds(got, n, lambda z: A.evaluate(a, z) * A.evaluate(b, z) - A.evaluate(red, z))
+
+
+# ---------------------------------------------------------------- 9. domains below 16 against schoolbook division
+def small_case(n, D, q, seed):
+    """factors whose product has L0 = D n coefficients (q = D - 1 pieces, the last one full) or q n + 1 (q = D / 2 pieces, one
+    coefficient in the last): as many factors of max(n, 2) coefficients as it takes, or of 2 n, 4 n .. where eight of them fall short,
+    and a shorter last one -> (the sets as lists of polynomials, the last of them [red]; the terms)"""
+    L0 = D * n if q == D - 1 else q * n + 1
+    ell = max(n, 2)
+    while 8 * (ell - 1) < L0 - 1:
+        ell *= 2
+    F = -(-(L0 - 1) // (ell - 1))
+    last = L0 - (F - 1) * (ell - 1)
+    rng = random.Random(seed)
+    sets = ([[rand_poly(rng, ell) for _ in range(F - 1)]] if F > 1 else []) + [[rand_poly(rng, last)]]
+    facs = [(0, k) for k in range(F - 1)] + [(len(sets) - 1, 0)]
+    P = A.sum_of_products(sets, [(1, facs)])
+    assert len(P) == L0
+    sets.append([[sum(P[i::n]) % R for i in range(n)]])
+    return sets, [(1, facs), (R - 1, [(len(sets) - 1, 0)])]
+
+
+@pytest.mark.parametrize("D,q", [(2, 1), (4, 2), (4, 3), (8, 4), (8, 7), (16, 8), (16, 15)])
+@pytest.mark.parametrize("n", [1, 2, 4, 8])
+def test_small_domains_against_schoolbook_division(settings, n, D, q):
+    """n = 1, 2, 4, 8 - one lane to eight of one workgroup, M = 2 D n down to 4, up to 16 coefficients folded into one index - at
+    every D with D - 1 and D / 2 pieces: byte for byte the long division in Python integers (poly_arith_model.result), and
+    sum-of-products' bytes; a single-coefficient remainder at index 0 and at index n - 1 is refused by the call and by the division."""
+    sets, terms = small_case(n, D, q, 8600 + 64 * n + 4 * D + q)
+    want = A.result(sets, terms, v=n, piece=n)
+    L0 = D * n if q == D - 1 else q * n + 1
+    assert want is not None and len(want) == q
+    assert api.poly_coset_quotient_plan([len(f[0]) for f in sets], [facs for _, facs in terms], n)[:4] + (0,) == (L0, D, L0 - n, q, 0)
+    rng = random.Random(8700 + n)
+    resident = [api.Polys([raw_poly(p) for p in f], settings) for f in sets]
+    try:
+        got, ref = both(settings, resident, terms, n)
+        assert got == [raw_poly(p) for p in want], "the long division's bytes"
+        assert got == ref, "sum-of-products' bytes"
+        for k in sorted({0, n - 1}):
+            c = rng.randrange(1, R)
+            assert A.result(sets + [[[0] * k + [1]]], terms + [(c, [(len(sets), 0)])], v=n, piece=n) is None
+            with api.Polys([raw_poly([0] * k + [1])], settings) as mono:
+                rc, h, words = refused(settings, resident + [mono], terms + [(c, [(len(sets), 0)])], n)
+                assert (rc, h) == (1, 0x1234) and words.endswith(NOT_DIVISIBLE), (k, rc, h, words)
+        assert both(settings, resident, terms, n)[0] == got
+    finally:
+        for f in resident:
+            f.close()
+
+
+# ---------------------------------------------------------------- 10. input forms and extreme values at n = 2^10
+FORMS_N = 1 << 10
+
+
+def agree(s, resident, terms, n):
+    """the call, sum-of-products and the model (held to schoolbook division on the CPU) on the same resident sets -> the raw rows"""
+    got, ref = both(s, resident, terms, n)
+    assert got == ref, "sum-of-products' bytes"
+    want = M.quotient([ints(f.coeffs()) for f in resident], terms, n)
+    assert want is not None and got == [raw_poly(p) for p in want], "the model's bytes"
+    return got
+
+
+def reduced_on_the_domain(polys, n):
+    """prod polys mod X^n - 1, the factors of at most n coefficients: the product of their values on the domain, brought back"""
+    w = M.root(n)
+    ev = [1] * n
+    for p in polys:
+        ev = [x * y % R for x, y in zip(ev, M.ntt(list(p) + [0] * (n - len(p)), w))]
+    return M.intt(ev, w)
+
+
+def test_a_term_without_factors(settings):
+    """a b - 1 with b the pointwise inverse of a on the domain: the constant is a term of no factor.  a b - 2 leaves the remainder -1."""
+    n = FORMS_N
+    rng = random.Random(8800)
+    a = [rng.randrange(1, R) for _ in range(n)]
+    b = [pow(x, R - 2, R) for x in a]
+    with api.Polys.from_evals([raw_poly(a), raw_poly(b)], settings) as f:
+        terms = [(1, [(0, 0), (0, 1)]), (R - 1, [])]
+        assert api.poly_coset_quotient_plan([n], [facs for _, facs in terms], n)[:5] == (2 * n - 1, 2, n - 1, 1, 2)
+        agree(settings, [f], terms, n)
+        wrong = [(1, [(0, 0), (0, 1)]), (R - 2, [])]
+        rc, h, words = refused(settings, [f], wrong, n)
+        assert (rc, h) == (1, 0x1234) and words.endswith(NOT_DIVISIBLE), (rc, h, words)
+        assert M.quotient([ints(f.coeffs())], wrong, n) is None
+
+
+def test_polynomials_shorter_than_the_domain(settings):
+    """factors of 1, n / 2 + 3, n - 1 and n coefficients, each in a set of its own: the load pads the short ones with zeros (the
+    i >= np branch of cq_load_index), the constant for every index but 0.  L0 = 5 n / 2: four cosets, two pieces."""
+    n = FORMS_N
+    rng = random.Random(8810)
+    polys = [rand_poly(rng, k) for k in (1, n // 2 + 3, n - 1, n)]
+    red = reduced_on_the_domain(polys, n)
+    terms = [(1, [(0, 0), (1, 0), (2, 0), (3, 0)]), (R - 1, [(4, 0)])]
+    assert api.poly_coset_quotient_plan([1, n // 2 + 3, n - 1, n, n], [facs for _, facs in terms], n)[:5] == (5 * n // 2, 4, 3 * n // 2, 2, 5)
+    resident = [api.Polys([raw_poly(p)], settings) for p in polys + [red]]
+    try:
+        got = agree(settings, resident, terms, n)
+        assert identity_holds(got, n, lambda z: A.evaluate(polys[0], z) * A.evaluate(polys[1], z) * A.evaluate(polys[2], z) * A.evaluate(polys[3], z) - A.evaluate(red, z))
+    finally:
+        for f in resident:
+            f.close()
+
+
+def test_random_term_coefficients(settings):
+    """the gate of plonk_evals with term t scaled by alpha^t and the column e by beta: e = -(1 / beta) sum_t alpha^t (term t) on the
+    domain, so the sum vanishes there and no coefficient is 1 or r - 1"""
+    n = FORMS_N
+    rng = random.Random(8820)
+    evals, terms = plonk_evals(rng, n)
+    alpha, beta = rng.randrange(2, R - 1), rng.randrange(2, R - 1)
+    scaled = [(pow(alpha, t + 1, R), facs) for t, (_, facs) in enumerate(terms[:-1])]
+    e = [0] * n
+    for c, facs in scaled:
+        for i in range(n):
+            v = c
+            for _, k in facs:
+                v = v * evals[k][i] % R
+            e[i] = (e[i] + v) % R
+    minus_beta_inv = (R - pow(beta, R - 2, R)) % R
+    evals[12] = [x * minus_beta_inv % R for x in e]
+    terms = scaled + [(beta, [(0, 12)])]
+    assert all(c not in (0, 1, R - 1) for c, _ in terms)
+    with api.Polys.from_evals([raw_poly(row) for row in evals], settings) as f:
+        assert api.poly_coset_quotient_plan([n], [facs for _, facs in terms], n)[:5] == (4 * n - 3, 4, 3 * n - 3, 3, 13)
+        agree(settings, [f], terms, n)
+
+
+def test_extreme_values(settings):
+    n = FORMS_N
+    rng = random.Random(8830)
+    # every coefficient r - 1: a b = sum_k (min(k, 2 n - 2 - k) + 1) X^k, so red[i] = (i + 1) + (n - 1 - i) = n
+    top = [R - 1] * n
+    red = reduced_on_the_domain([top, top], n)
+    assert red == [n] * n
+    with api.Polys([raw_poly(top), raw_poly(top), raw_poly(red)], settings) as f:
+        got = agree(settings, [f], [(1, [(0, 0), (0, 1)]), (R - 1, [(0, 2)])], n)
+        assert got == [raw_poly([n - 1 - i for i in range(n)])], "t_i = the product's coefficient i + n = n - 1 - i"
+    a, b = rand_poly(rng, n), rand_poly(rng, n)
+    e = reduced_on_the_domain([a, b], n)
+    with api.Polys([raw_poly(a), raw_poly(b), raw_poly(e), raw_poly([0] * n)], settings) as f:
+        pair = [(1, [(0, 0), (0, 1)]), (R - 1, [(0, 2)])]
+        first = agree(settings, [f], pair, n)
+        # a zero factor: a b 0 0 is the zero polynomial of formal length 4 n - 3 - three pieces of zeros, no refusal
+        assert agree(settings, [f], [(1, [(0, 0), (0, 1), (0, 3), (0, 3)])], n) == [bytes(32 * n)] * 3
+        # a term of coefficient 0 beside the divisible sum: it lengthens the sum to 4 n - 3, the pieces above the first are zero
+        assert agree(settings, [f], pair + [(0, [(0, 0), (0, 0), (0, 1), (0, 1)])], n) == first + [bytes(32 * n)] * 2
+        # a term given twice, with c and r - c
+        c = rng.randrange(2, R - 1)
+        assert agree(settings, [f], pair + [(c, [(0, 0), (0, 1), (0, 0)]), (R - c, [(0, 0), (0, 1), (0, 0)])], n) == first + [bytes(32 * n)]
+
+
+# ---------------------------------------------------------------- 11. the largest root: M = 2 D n = 2^25
+def add_rows(x, y):
+    """x + y of two (k, 32) big-endian byte arrays whose sums stay below 2^256: four 64-bit limbs with carries"""
+    xl, yl = x.reshape(-1).view(">u8").reshape(-1, 4).astype(np.uint64), y.reshape(-1).view(">u8").reshape(-1, 4).astype(np.uint64)
+    out = np.zeros_like(xl)
+    carry = np.zeros(len(xl), dtype=np.uint64)
+    for j in (3, 2, 1, 0):
+        t = xl[:, j] + yl[:, j]
+        c1 = t < xl[:, j]
+        out[:, j] = t + carry
+        carry = (c1 | (out[:, j] < t)).astype(np.uint64)
+    assert not carry.any()
+    return out.astype(">u8").view(np.uint8).reshape(-1, 32)
+
+
+def test_largest_root_eight_cosets_at_full_size(settings):
+    """D = 8 at n = 2^20: M = 2^25, g is CQ_ROOT itself (cq_g squares nothing) and every exponent bound is tight.  a b^7 - red with
+    b = X^(n-1) and red = a X^(7n-7) mod X^n - 1 = a rotated down by seven places; L0 = 8 n - 7.
+    For i >= 7, with e = i - 7: a_i (X^(e+7n) - X^e) = a_i X^e (X^n - 1)(1 + X^n + .. + X^(6n)): a_i lands at place e of all seven pieces.
+    For i < 7, with e = i + n - 7: a_i (X^(e+6n) - X^e): a_i lands at place e of pieces 0 .. 5.
+    So T_0 .. T_5 = a rotated down by seven, T_6 = the same with its last seven places zero."""
+    n = 1 << 20
+    a = rand_rows(8900, n)
+    facs = [[(0, 0)] + [(0, 1)] * 7, [(0, 2)]]
+    assert api.poly_coset_quotient_plan([n], facs, n)[:4] + (0,) == (8 * n - 7, 8, 7 * n - 7, 7, 0)
+    terms = terms32([(1, facs[0]), (R - 1, facs[1])])
+    rot = np.roll(a, -7, axis=0)
+    with api.Polys([a.tobytes(), monomial(n, n - 1).tobytes(), rot.tobytes()], settings) as f:
+        with pytest.raises(api.KzgError, match="longer than 2\\^20"):
+            api.polys_sum_of_products([f], terms, settings, vanishing=n, piece_coeffs=n)
+        with api.polys_quotient([f], terms, settings, domain=n) as out:
+            assert (out.n_coeffs(), len(out)) == (n, 7)
+            got = raw_rows(out)
+    top = rot.copy()
+    top[n - 7:] = 0
+    want = rot.tobytes()
+    for m in range(6):
+        assert got[m] == want, m
+    assert got[6] == top.tobytes()
+
+
+def test_largest_root_sixteen_cosets_two_passes_folded_inputs(settings):
+    """D = 16 at n = 2^19: M = 2^25 again, with both passes of the recombination and inputs of 2 n coefficients folded by the load.
+    a b^7 - red with a of 2 n coefficients below 2^253, b = X^(2n-1), red[e] = a[(e + 7) mod n] + a[(e + 7) mod n + n] (below 2^254 < r:
+    no reduction); L0 = 16 n - 7, 15 pieces.  a_i X^s - a_i X^(s mod n) with s = i + 14 n - 7 lands at place s mod n of the pieces
+    0 .. floor(s / n) - 1, and floor(s / n) = 13 for i < 7, 14 for 7 <= i < n + 7, 15 above.  So T_0 .. T_12 = red; T_13 = red but
+    for the places n - 7 .. n - 1, where place e holds a[e + 7] alone (a_n .. a_(n+6)); T_14[e] = a[n + 7 + e] for e < n - 7 and 0 in
+    the last seven places.  Then X^k is added at k = 0 and k = n - 1: both refused."""
+    n = 1 << 19
+    a = rand_rows(8910, 2 * n)
+    a[:, 0] &= 0x1F
+    red = add_rows(np.roll(a[:n], -7, axis=0), np.roll(a[n:], -7, axis=0))
+    for e in (0, 1, n - 8, n - 7, n - 1):  # the limb arithmetic against Python integers
+        lo = (e + 7) % n
+        assert int.from_bytes(red[e].tobytes(), "big") == int.from_bytes(a[lo].tobytes(), "big") + int.from_bytes(a[lo + n].tobytes(), "big") < R
+    facs = [[(0, 0)] + [(0, 1)] * 7, [(1, 0)]]
+    assert api.poly_coset_quotient_plan([2 * n, n], facs, n)[:4] + (0,) == (16 * n - 7, 16, 15 * n - 7, 15, 0)
+    terms = [(1, facs[0]), (R - 1, facs[1])]
+    t13 = red.copy()
+    t13[n - 7:] = a[n: n + 7]
+    t14 = np.zeros((n, 32), dtype=np.uint8)
+    t14[: n - 7] = a[n + 7:]
+    with api.Polys([a.tobytes(), monomial(2 * n, 2 * n - 1).tobytes()], settings) as f, api.Polys([red.tobytes()], settings) as fr:
+        with api.polys_quotient([f, fr], terms32(terms), settings, domain=n) as out:
+            assert (out.n_coeffs(), len(out)) == (n, 15)
+            got = raw_rows(out)
+        want = red.tobytes()
+        for m in range(13):
+            assert got[m] == want, m
+        assert got[13] == t13.tobytes() and got[14] == t14.tobytes()
+        del got
+        for k in (0, n - 1):
+            with api.Polys([monomial(k + 1, k).tobytes()], settings) as mono:
+                rc, h, words = refused(settings, [f, fr, mono], terms + [(1, [(2, 0)])], n)
+                assert (rc, h) == (1, 0x1234) and words.endswith(NOT_DIVISIBLE), (k, rc, h, words)

@@ -91,3 +91,30 @@ def test_folded_factors(prog):
     for length in (10, 16, 25):
         line = prog("run", 8, 2, length, length, -1)[0]
         assert line.endswith("flag 0 want_flag 0 wrong 0"), line
+
+
+@pytest.mark.parametrize("p", range(1, 16))
+def test_every_piece_count_accepted_and_refused(prog, p):
+    """two factors of 4 (p + 1) coefficients on the domain of 8: L0 = 8 (p + 1) - 1, so `p` pieces on the smallest power of two
+    D >= p + 1 cosets - every (D, pieces) the plan can make, D = 16 with 8 .. 15 pieces among them.  The pieces from p on are the
+    remainder check: which registers of which pass they are depends on p.  A remainder c X^k at ONE index is seen only by the lane of
+    that index, and there only through the spare pieces: with p = D - 1 through the single register v[brp(D - 1)]."""
+    D = 2
+    while D < p + 1:
+        D *= 2
+    head = "D %d pieces %d " % (D, p)
+    line = prog("run", 8, 2, 4 * (p + 1), 9100 + p, -1)[0]
+    assert line.startswith(head) and line.endswith("flag 0 want_flag 0 wrong 0"), line
+    for k in (0, 3, 7):
+        line = prog("run", 8, 2, 4 * (p + 1), 9100 + p, k)[0]
+        assert line.startswith(head) and line.endswith("flag 1 want_flag 1 wrong 0"), (k, line)
+
+
+@pytest.mark.parametrize("rem_k", [-1, 255, 256, 511])
+def test_the_second_lane_step(prog, rem_k):
+    """n = 512: a lane owns the indices t and t + 256, so the step constants sigma_j^256, zeta^-256 and g^-256 - which no run at
+    n <= 32 uses - are held to schoolbook division; the remainders sit on the last index of step 0, the first and the last of step 1.
+    (The second tile, n = 2048, is left to the GPU tests: the program's transform is the naive quadratic one.)"""
+    line = prog("run", 512, 2, 512, 9200, rem_k)[0]
+    want = "flag 0 want_flag 0 wrong 0" if rem_k < 0 else "flag 1 want_flag 1 wrong 0"
+    assert line.startswith("D 2 pieces 1 ") and line.endswith(want), line
