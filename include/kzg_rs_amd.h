@@ -970,7 +970,7 @@ KzgRet kzg_debug_polys_arith_split(const KzgSettings *s, float out[5]);
  * as evaluations into the new set's buffer - and the inverse transform runs in place there.
  * kzg_last_timings: [4] the device stage, [6] the copies - the factor table; no coefficient crosses the bus (kzg_debug_polys_stats
  * counts the call as served from a resident set; its byte counters do not move).
- * NOT in this call: blinding terms (b2 X^2 + b1 X + b0) Z_H, which lengthen z beyond n coefficients.  logUp-style running SUMS of
+ * NOT in this call: blinding terms (b2 X^2 + b1 X + b0) Z_H, which lengthen z beyond n coefficients.  (They are kzg_polys_blind's, below.)  logUp-style running SUMS of
  * fractions are kzg_polys_fraction_sum's, below, which reuses the products-and-one-inverse scheme.
  * Measured (tools/prof/polys_grand_product_probe.py, profiles/polys_grand_product_probe.json; 10 warm calls each, median (min - max); 3 + 3
  * factors, one product, with shift): n = 2^20: 2.154 (2.105 - 2.248) ms, slot [4] 1.873 ms = pad 0.063 + forward transforms 0.881 + tile
@@ -1034,7 +1034,7 @@ KzgRet kzg_debug_polys_grand_product_split(const KzgSettings *s, float out[5]);
  * The host does no field arithmetic: the c_k go up as bytes and the device range-checks them.
  * kzg_last_timings: [4] the device stage, [6] the copies - the fraction table; no coefficient crosses the bus (kzg_debug_polys_stats
  * counts the call as served from a resident set; its byte counters do not move).
- * NOT in this call: blinding terms; a judgement of the total.
+ * NOT in this call: blinding terms; a judgement of the total.  (Blinding is kzg_polys_blind's, below.)
  * Measured (tools/prof/polys_fraction_sum_probe.py, profiles/polys_fraction_sum_probe.json; 10 warm calls each, median (min - max); one
  * sum of 4 fractions of 1 + 1 factors, with shift and steps): n = 2^20: 2.741 (2.598 - 3.063) ms, slot [4] 2.448 ms = pad 0.084 + forward
  * transforms 1.076 + tile products, carries and the inverse 0.454 + steps and tile sums 0.315 + apply 0.037 + inverse transforms 0.462 ms,
@@ -1093,7 +1093,8 @@ KzgRet kzg_debug_polys_fraction_sum_split(const KzgSettings *s, float out[6]);
  * D - pieces times, so the remainder check is exact; g is invisible in the result.  The host does no field arithmetic.
  * kzg_last_timings: [4] the device stage, [6] the copies - the term table and the coefficients; no coefficient of a polynomial crosses
  * the bus (kzg_debug_polys_stats counts the call as served from a resident set; its byte counters do not move).
- * NOT in this call: a vanishing polynomial other than X^n - 1, pieces of another length, blinding of the pieces.
+ * NOT in this call: a vanishing polynomial other than X^n - 1, pieces of another length, blinding of the pieces.  (The last is
+ * kzg_polys_blind_pieces', below.)
  * Measured (tools/prof/polys_quotient_probe.py, profiles/polys_quotient_probe.json): 13 polynomials, 9 terms of up to 4 factors, D = 4, 3
  * pieces; 10 warm calls each, median (min - max), interleaved with kzg_polys_sum_of_products on the same arguments in the same run.  n =
  * 2^20: 11.734 (11.324 - 11.882) ms, slot [4] 11.225 ms = load 1.053 + forward transforms 7.787 + k_poly_sop 1.000 + inverse transforms
@@ -1117,6 +1118,65 @@ KzgRet KZG_POLYS_API kzg_debug_poly_coset_quotient_plan(size_t out[8], const siz
 /* diagnostic: slot [4] of the handle's last kzg_polys_quotient split by events and summed over the cosets, ms - out = { load, forward
  * transforms, k_poly_sop, inverse transforms, coefficients + constants, pieces } */
 KzgRet kzg_debug_polys_quotient_split(const KzgSettings *s, float out[6]);
+/* BLINDING OF RESIDENT POLYNOMIALS (csrc/capi_polys_blind.hpp): what the calls above leave out for a ZERO-KNOWLEDGE proof - the
+ * multiples of Z_H = X^n - 1 added to the witness columns and to z, and the constants moved between the pieces of the quotient - as one
+ * small streaming call each, so that a hiding prover stays on its one upload like a plain one.  All arithmetic mod r; w = w_n is the
+ * root kzg_fr_ntt uses for n = domain_n.  Drawing the blinders is the caller's business; the host does no field arithmetic.
+ *   kzg_polys_blind: out_j = p_(first + j) + b_j(rho_j X) (X^n - 1), j < count, with b_j = sum_(i<k) b_(j,i) X^i, k = n_blinders, 1 <= k
+ *     <= KZG_POLYS_BLIND_MAX; blinders: count * k * 32 bytes big-endian canonical, row j = b_(j,0) .. b_(j,k-1); rho_j = w where rotate[j]
+ *     == 1 and 1 where it is 0 (rotate: count bytes, or NULL for none).  In coefficients, with beta_(j,i) = b_(j,i) rho_j^i:
+ *     out_(j,i) = p_(j,i) - [i < k] beta_(j,i) + [n <= i < n + k] beta_(j,i-n); for n < k both brackets hold at i = n .. k - 1 and the
+ *     coefficient takes both, as the product says.  The new set has count polynomials of max(n_coeffs, n + k) coefficients: a set
+ *     shorter than n is zero-padded, a longer one - an already blinded one - is accepted.  out_j agrees with p_j on the whole domain.
+ *     The rotation keeps a pair z, z(wX) - polynomials 2g and 2g + 1 of kzg_polys_grand_product and kzg_polys_fraction_sum with their
+ *     shift - consistent: (wX)^n = X^n, so the second row takes b(wX) (X^n - 1); pass the same b for both rows and rotate = 1 on the
+ *     second, and out_(2g+1)(X) = out_(2g)(wX) still holds.  This answers "(b2 X^2 + b1 X + b0) Z_H" of the grand product with k = 3 and
+ *     the blinded witness a + (b1 X + b0)(X^n - 1) of kzg_polys_quotient with k = 2.
+ *   kzg_polys_blind_pieces: the range is the pieces t_0 .. t_(count-1) of a quotient, n_coeffs <= n; out_j = t_j - b_(j-1) + b_j X^n with
+ *     b_(-1) = b_(count-1) = 0; blinders: (count - 1) * 32 bytes, NULL allowed for count == 1 (a zero-padded copy).  sum_j X^(j n) out_j =
+ *     sum_j X^(j n) t_j: PLONK's t_lo + b_10 X^n, t_mid - b_10 + b_11 X^n, t_hi - b_11.  The new set has count polynomials of n + 1
+ *     coefficients.
+ * The returned set is an ordinary KzgPolys: immutable, owned by `s`, freed with kzg_polys_free before the handle, accepted by every call
+ * that takes one - kzg_polys_quotient over blinded factors, the commitments and the openings included; its coefficients are canonical.
+ * The handle's lock is taken; the call runs on the set's device; the same call twice gives the same bytes.
+ * KZG_BADARGS - *out untouched, nothing kept, the handle usable afterwards - each with its own words in kzg_last_error(), the first of
+ * this order (csrc/poly_blind_plan.hpp, PbRefusal): a null pointer; a set uploaded on another handle ("the polynomial set was uploaded
+ * on another handle"); a range past the set ("the range runs past the set's polynomials"); count == 0 ("count is 0"); a set of n_coeffs
+ * == 0 ("the set has no coefficients"); domain_n zero, no power of two or above KZG_FR_NTT_MAX ("domain_n is not a power of two between
+ * 1 and 2^20"); k == 0 or above KZG_POLYS_BLIND_MAX ("n_blinders is not between 1 and 8"); pieces only, a set longer than domain_n ("a
+ * piece is longer than domain_n"); an output length above KZG_POLYS_MAX_COEFFS ("the blinded polynomials would have more than 2^20
+ * coefficients"); count times that length above KZG_POLYS_MAX_SCALARS ("more than 2^26 scalars in the blinded set"); a rotate byte
+ * other than 0 or 1 ("a rotate byte is neither 0 nor 1"); a blinder that is not below r ("a blinder is not below r"), found on the
+ * device.  An allocation the device refuses is KZG_MALLOC.
+ * n = 2^20 CANNOT be blinded: n + k coefficients exceed KZG_POLYS_MAX_COEFFS, and a set of more than KZG_G1_POINTS_MAX coefficients
+ * could not be committed either.  The largest domain is 2^19 (an input of 2^20 coefficients over it is accepted: the output has 2^20).
+ * On the device (csrc/poly_blind_plan.hpp, poly_blind_kernels.hpp) a call is TWO launches whatever count is: k_blind_prepare, a lane
+ * per blinder, compares it with r and forms beta - the only products of the call, at most k - 1 per rotated row - and k_poly_blind
+ * streams every row of the new set in one launch: an element is moved as its 32 bytes, or written as zero past the input's length, and
+ * the 2 k elements of a row's patch take one modular subtraction or addition.  No per-row copy, no memset, no transform.
+ * kzg_last_timings: [4] the device stage, [6] the copy of the blinders; no coefficient crosses the bus (kzg_debug_polys_stats counts the
+ * call as served from a resident set; its byte counters do not move).
+ * NOT in these calls: drawing the blinders; a vanishing polynomial other than X^n - 1; domains of 2^20 points.
+ * Measured (tools/prof/polys_blind_probe.py, profiles/polys_blind_probe.json): 13 polynomials with k = 2 in one call and the pair z, z(wX)
+ * with k = 3 in a second; 10 warm repetitions, median (min - max), interleaved in the same run with the route the library offered before
+ * - one kzg_polys_sum_of_products per polynomial over {p, b, X^n - 1}, 15 calls, the same bytes.  n = 2^19: 0.272 (0.268 - 0.492) ms
+ * against 71.835 (56.858 - 86.925) ms; n = 2^16: 0.180 (0.176 - 0.285) against 6.409 (6.234 - 6.508) ms; n = 2^12: 0.132 (0.129 - 0.153)
+ * against 2.724 (2.705 - 2.742) ms: below the route's minimum at every size.  Slot [4] of the 13-row call at 2^19 (both launches) is 0.079
+ * ms for the 436 MB it reads and writes, 5.5 TB/s - the 218 MB it reads were written just before and fit the 256 MB last-level cache, so
+ * this is no HBM rate; in the same run 13 k_poly_lincomb rows with the factor 1 over the same number of bytes take 0.150 ms (2.91 TB/s).
+ * Copies 0.008 ms. */
+#define KZG_POLYS_BLIND_MAX 8
+KzgRet KZG_POLYS_API kzg_polys_blind(KzgPolys **out, const KzgPolys *f, size_t first, size_t count,
+        size_t domain_n, size_t n_blinders, const uint8_t *blinders,
+        const uint8_t *rotate /* count bytes, 0 or 1, may be NULL */, const KzgSettings *s);
+KzgRet KZG_POLYS_API kzg_polys_blind_pieces(KzgPolys **out, const KzgPolys *f, size_t first, size_t count,
+        size_t domain_n, const uint8_t *blinders /* (count - 1) * 32 */, const KzgSettings *s);
+/* test hook: the host plan alone, no handle and no GPU - out = { output coefficients, grid x and grid y of k_poly_blind, elements per
+ * workgroup E, entries of the beta table, workgroups of k_blind_prepare, patch entries per side of a row, refusal code (0: none;
+ * otherwise the rest is 0) }; the set is given by its n_coeffs and n_polys; pieces != 0: kzg_polys_blind_pieces, which ignores
+ * n_blinders (csrc/poly_blind_plan.hpp) */
+KzgRet KZG_POLYS_API kzg_debug_poly_blind_plan(size_t out[8], size_t n_coeffs, size_t n_polys, size_t first, size_t count,
+        size_t domain_n, size_t n_blinders, int pieces);
 /* The number-theoretic transform over Fr for n_polys vectors of n elements, n a power of two <= KZG_FR_NTT_MAX (csrc/capi_fr_ntt.hpp):
  * out[k][i] = sum_t in[k][t] w_n^(i t) with w_n = 7^((r - 1) / n) (c-kzg-4844's SCALE2_ROOT_OF_UNITY: w_4096 is the blob domain's
  * root); inverse != 0: w_n^-1 and the factor 1 / n.  Elements are 32 bytes big-endian, canonical on the way out; host pointers; out

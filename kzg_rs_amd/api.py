@@ -212,6 +212,9 @@ def lib():
         L.kzg_polys_quotient.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, u8, szp, u32p, sz, sz, vp]
         L.kzg_debug_poly_coset_quotient_plan.argtypes = [szp, szp, sz, szp, u32p, sz, sz]
         L.kzg_debug_polys_quotient_split.argtypes = [vp, C.POINTER(C.c_float)]
+        L.kzg_polys_blind.argtypes = [C.POINTER(vp), vp, sz, sz, sz, sz, u8, u8, vp]
+        L.kzg_polys_blind_pieces.argtypes = [C.POINTER(vp), vp, sz, sz, sz, u8, vp]
+        L.kzg_debug_poly_blind_plan.argtypes = [szp, sz, sz, sz, sz, sz, sz, C.c_int]
         L.kzg_pairing_check.argtypes = [bp, u8, u8, vp]
         L.kzg_pairings_verify.argtypes = [bp, u8, u8, u8, u8, vp]
         L.kzg_g1_mul_generator.argtypes = [u8, u8, sz, vp]
@@ -1253,6 +1256,42 @@ class Polys:
         _chk(lib().kzg_polys_linear_combinations(C.byref(h), self._h, first, count, b"".join(r for r, _ in raws), len(raws), self._settings._h))
         return Polys._from_handle(h, self._settings)
 
+    def blind(self, domain, blinders, rotate=None, first=0, count=None):
+        """kzg_polys_blind: blinders[j] = the k 32-byte values b_(j,0) .. b_(j,k-1) of polynomial first + j (equal k, 1 .. 8, for all rows);
+        rotate = None or one 0 / 1 per polynomial -> a new resident set, out_j = p_(first + j) + b_j(rho_j X) (X^domain - 1) with rho_j the
+        domain's root where rotate[j] is set (the row that holds z(wX) beside z) and 1 otherwise; max(n_coeffs, domain + k) coefficients"""
+        first, count = self._range(first, count)
+        if not isinstance(domain, int) or domain < 0:
+            raise KzgError("BadArgs", "domain: an integer, not negative")
+        if isinstance(blinders, (bytes, bytearray, memoryview, str)):
+            raise TypeError("blinders: one row of 32-byte values per polynomial")
+        raws = [_points32(row, "blinders") for row in blinders]
+        if len(raws) != count or any(k != raws[0][1] for _, k in raws):
+            raise KzgError("InvalidBytesLength", "blinders: one row of equally many values per polynomial of the range")
+        rot = None
+        if rotate is not None:
+            if isinstance(rotate, (bytes, bytearray, memoryview, str)) or any(not isinstance(x, (int, bool)) for x in rotate):
+                raise TypeError("rotate: a list of 0 / 1, one per polynomial")
+            if len(rotate) != count or any(not 0 <= int(x) <= 255 for x in rotate):
+                raise KzgError("InvalidBytesLength", "rotate: one byte per polynomial of the range")
+            rot = bytes(int(x) for x in rotate) or bytes(1)
+        h = C.c_void_p()
+        _chk(lib().kzg_polys_blind(C.byref(h), self._h, first, count, domain, raws[0][1] if raws else 0, b"".join(r for r, _ in raws) or bytes(1), rot, self._settings._h))
+        return Polys._from_handle(h, self._settings)
+
+    def blind_pieces(self, domain, blinders, first=0, count=None):
+        """kzg_polys_blind_pieces: the range is the pieces of a quotient, blinders = count - 1 32-byte values -> a new resident set of
+        domain + 1 coefficients, out_j = t_j - b_(j-1) + b_j X^domain (b_(-1) = b_(count-1) = 0): sum_j X^(j domain) out_j is unchanged"""
+        first, count = self._range(first, count)
+        if not isinstance(domain, int) or domain < 0:
+            raise KzgError("BadArgs", "domain: an integer, not negative")
+        raw, nb = _points32(blinders, "blinders")
+        if nb != max(count, 1) - 1:
+            raise KzgError("InvalidBytesLength", "blinders: one value between every two pieces of the range")
+        h = C.c_void_p()
+        _chk(lib().kzg_polys_blind_pieces(C.byref(h), self._h, first, count, domain, raw or None, self._settings._h))
+        return Polys._from_handle(h, self._settings)
+
     def close(self):
         if getattr(self, "_h", None):
             if getattr(self._settings, "_h", None):  # (a set outliving its handle cannot be freed any more: the free takes the handle's lock)
@@ -1411,6 +1450,18 @@ def poly_coset_quotient_plan(set_coeffs, terms, domain):
     out = (C.c_size_t * 8)()
     _chk(lib().kzg_debug_poly_coset_quotient_plan(out, (C.c_size_t * max(len(set_coeffs), 1))(*set_coeffs), len(set_coeffs), (C.c_size_t * max(len(sizes), 1))(*sizes),
                                                   (C.c_uint32 * max(len(flat), 1))(*flat), len(sizes), domain))
+    return tuple(int(x) for x in out)
+
+
+POLYS_BLIND_MAX = 8
+
+
+def poly_blind_plan(n_coeffs, count, domain, n_blinders=1, pieces=False, n_polys=None, first=0):
+    """kzg_debug_poly_blind_plan: a set of n_polys (None: first + count) polynomials of n_coeffs coefficients, its range [first, first +
+    count) -> (output coefficients, grid x, grid y, elements per workgroup E, beta-table entries, workgroups of the prepare kernel, patch
+    entries per side of a row, refusal code); pieces: Polys.blind_pieces, which ignores n_blinders; host code"""
+    out = (C.c_size_t * 8)()
+    _chk(lib().kzg_debug_poly_blind_plan(out, n_coeffs, first + count if n_polys is None else n_polys, first, count, domain, n_blinders, 1 if pieces else 0))
     return tuple(int(x) for x in out)
 
 
