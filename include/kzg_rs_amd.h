@@ -1062,6 +1062,74 @@ KzgRet KZG_POLYS_API kzg_debug_poly_fraction_sum_plan(size_t out[8], const size_
 /* diagnostic: slot [4] of the handle's last kzg_polys_fraction_sum split by events, ms - out = { pad, forward transforms, tile products +
  * carries with the inverse, steps + tile sums + their carries, apply, inverse transforms } */
 KzgRet kzg_debug_polys_fraction_sum_split(const KzgSettings *s, float out[6]);
+/* RESIDENT LOOKUP MULTIPLICITIES (csrc/capi_polys_lookup.hpp): the multiplicity column m of a log-derivative lookup - sum_i 1 / (beta +
+ * f_i) = sum_j m_j / (beta + t_j), the identity kzg_polys_fraction_sum above closes - counted on the device over resident polynomials and
+ * returned as a NEW resident set.  m is no polynomial identity but a count, the one input of a lookup round that a caller had to make on
+ * the host from a copy of its columns; plookup's sorted column is "t with row j repeated 1 + m_j times".  w = w_n is the root kzg_fr_ntt
+ * uses for n = domain_n.
+ *   The TABLE has `width` polynomials t_1 .. t_w, 1 .. KZG_POLYS_LM_MAX_WIDTH; each of the n_lookups LOOKUPS, 0 ..
+ *   KZG_POLYS_LM_MAX_LOOKUPS, has `width` polynomials f_(l,1) .. f_(l,w).  `table` names the table's and `lookups` the lookups', lookup
+ *   after lookup, as kzg_polys_sum_of_products names a factor: per polynomial two uint32_t, the index into `sets` and the polynomial's
+ *   index in that set.  A polynomial may be named any number of times, in the table and in lookups alike.  The sets may differ in
+ *   n_coeffs, each at most domain_n (shorter ones are zero-padded) - kzg_polys_grand_product's rule.
+ *   T_j = (t_1(w^j), .., t_w(w^j)) is the table's tuple at row j and F_(l,i) = (f_(l,1)(w^i), .., f_(l,w)(w^i)) lookup l's at row i;
+ *   tuples are equal when their canonical residues are.  If j is the LOWEST row with T_j = T then m_j = #{(l, i) : F_(l,i) = T}; on every
+ *   later row of the same tuple m_j = 0; so sum_j m_j = n_lookups n.  The new set holds ONE polynomial of domain_n coefficients, the
+ *   polynomial of degree < n with m(w^j) = m_j.  n_lookups == 0 is accepted and gives m = 0.
+ *   A tuple F_(l,i) that is in no table row REFUSES the call with KZG_BADARGS: kzg_last_error() ends in
+ *   "a looked-up tuple is in no table row: lookup L, row I" for the lowest l n + i that misses, and missing_out, when not NULL, receives
+ *   { l, i }; it is written on this refusal alone.
+ * The returned set is an ordinary KzgPolys: immutable, owned by `s`, freed with kzg_polys_free before the handle, accepted by every call
+ * that takes one - kzg_polys_fraction_sum with m as a numerator factor first of all; its coefficients are canonical.  The handle's lock
+ * is taken; the call runs on the sets' device; the same call twice gives the same bytes, whatever the order the device's lanes ran in.
+ * KZG_BADARGS - *out untouched, nothing kept, the handle usable afterwards - each with its own words in kzg_last_error(), the first of
+ * this order (csrc/poly_lookup_plan.hpp, LmRefusal): a null pointer (missing_out may be NULL); width zero or above KZG_POLYS_LM_MAX_WIDTH
+ * ("width is not between 1 and 8"); n_lookups above KZG_POLYS_LM_MAX_LOOKUPS ("more than 16 lookups"); n_sets above
+ * KZG_POLYS_SOP_MAX_SETS; n_sets == 0 ("a column is named and there is no set"); a set uploaded on another handle; a set index out of
+ * range; a polynomial index out of range; a referenced set of n_coeffs == 0; domain_n zero, no power of two or above KZG_FR_NTT_MAX; a
+ * referenced set longer than domain_n; U * domain_n above KZG_POLYS_MAX_SCALARS for the U distinct polynomials named - the last eight in
+ * kzg_polys_grand_product's words; the miss above.  An allocation the device refuses is KZG_MALLOC.
+ * On the device (csrc/poly_lookup_plan.hpp, which holds the scheme and the bounds, poly_lookup_kernels.hpp): the U polynomials are padded
+ * into a workspace of U * domain_n scalars - the call's own, released on return - and transformed forward in place (the transform of
+ * kzg_fr_ntt, in its chunks), which leaves 32 canonical big-endian bytes per evaluation: tuples are compared and hashed as bytes, no
+ * field operation is needed.  An open-addressing hash table of C slots, C the power of two >= 2 domain_n, holds row indices: k_lm_insert
+ * (a lane per table row: compare-and-swap into an empty slot, atomic minimum on a slot of the same tuple - the lowest row wins whatever
+ * the interleaving), k_lm_count (a lane per lookup row: linear probing, one addition to the found row's counter per wavefront and row,
+ * an atomic minimum of l n + i on a miss), k_lm_store (the counters as 32-byte residues into the new set's buffer), and the inverse
+ * transform runs in place there.  Every probe walk is bounded by C steps in code; a walk that used them up would be KZG_ERROR ("a probe
+ * walk passed every slot") and is out of reach at a load of 1/2.  KZG_OPTIONS lookup_hash_bits=k masks the hash to its low k bits (k =
+ * 0: one chain through every distinct tuple) for the tests; the result does not change.  The host does no field arithmetic.
+ * kzg_last_timings: [4] the device stage, [6] the copies - the column table; no coefficient crosses the bus (kzg_debug_polys_stats
+ * counts the call as served from a resident set; its byte counters do not move).
+ * NOT in this call: plookup's sorted column (a prefix sum over m and an expansion); lookups under a selector q - form q f + (1 - q) t_0
+ * with kzg_polys_sum_of_products first and look that up; domains above KZG_FR_NTT_MAX.
+ * Measured (tools/prof/polys_lookup_probe.py, profiles/polys_lookup_probe.json; one MI355X, 10 warm calls each, median (min - max)).
+ * One lookup of width 1 into the range table t_j = j: n = 2^20: 1.038 (1.004 - 1.081) ms, slot [4] 0.728 ms = pad 0.025 + forward
+ * transforms 0.317 + memsets and table build 0.106 + count 0.089 + store 0.011 + inverse transform 0.181 ms, copies 0.008 ms; n = 2^16:
+ * 0.503 (0.497 - 0.513) ms, stage 0.192 ms; n = 2^12: 0.210 (0.208 - 0.238) ms, stage 0.145 ms.  Four lookups of width 3 into a random
+ * table (15 polynomials): n = 2^20: 3.770 (3.627 - 3.874) ms, stage 3.472 ms = pad 0.163 + forward transforms 2.289 + build 0.153 + count
+ * 0.652 + store 0.013 + inverse 0.201 ms; n = 2^16: 0.667 (0.659 - 0.922) ms; n = 2^12: 0.237 (0.234 - 0.249) ms.  Build + count + store
+ * against one k_poly_lincomb row over the bytes of the U rows in the same run: 0.206 against 0.034 ms (6.1 times) for the range shape
+ * at 2^20, 0.818 against 0.180 ms (4.6 times) for the random one - dependent random accesses against a stream.  The route of the calls
+ * that were there before - kzg_polys_coeffs, kzg_fr_ntt, a hash map over the 32-byte values, kzg_polys_upload_evals of m - with the count
+ * in INTERPRETED Python (2 repetitions at 2^20): 1 328 ms (range) and 5 342 ms (random) at 2^20, of which the copies and the transform,
+ * which a compiled hash map would keep, are 15.1 + 15.9 + 40.0 = 71 ms and 115.0 + 124.1 + 34.9 = 274 ms; 77.9 and 229.9 ms at 2^16 (copies
+ * and transform 24.9 and 17.2 ms); 3.1 and 11.0 ms at 2^12 (0.38 and 0.68 ms).  One value in every row, 16 lookups at n = 2^20 (the
+ * A/B library, lookup_wave_combine): k_lm_count 2.978 (2.977 - 2.979) ms with the wavefront combine against 190.151 ms without; a random
+ * column 0.891 (0.889 - 0.895) against 0.892 (0.890 - 0.894) ms. */
+#define KZG_POLYS_LM_MAX_WIDTH   8     /* polynomials of the table and of every lookup */
+#define KZG_POLYS_LM_MAX_LOOKUPS 16
+KzgRet KZG_POLYS_API kzg_polys_lookup_multiplicities(KzgPolys **out, size_t missing_out[2],
+        const KzgPolys *const *sets, size_t n_sets, const uint32_t *table, const uint32_t *lookups,
+        size_t width, size_t n_lookups, size_t domain_n, const KzgSettings *s);
+/* test hook: the host plan alone, no handle and no GPU - out = { U, workspace scalars, slots C, workspace bytes, lanes per workgroup,
+ * workgroups of the insert and of the store, workgroups of the count, refusal code (0: none; otherwise the rest is 0) }; the sets are
+ * given by their n_coeffs, so polynomial indices are not checked (csrc/poly_lookup_plan.hpp) */
+KzgRet KZG_POLYS_API kzg_debug_poly_lookup_plan(size_t out[8], const size_t *set_coeffs, size_t n_sets, const uint32_t *table,
+        const uint32_t *lookups, size_t width, size_t n_lookups, size_t domain_n);
+/* diagnostic: slot [4] of the handle's last kzg_polys_lookup_multiplicities split by events, ms - out = { pad, forward transforms,
+ * memsets + table build, count, store, inverse transform } */
+KzgRet kzg_debug_polys_lookup_split(const KzgSettings *s, float out[6]);
 /* THE QUOTIENT BY X^n - 1 ON COSETS (csrc/capi_polys_quotient.hpp): the quotient round of a PLONK-style prover for circuits of up to
  * KZG_FR_NTT_MAX rows.  kzg_polys_sum_of_products takes its product at full size, one transform of N >= L0 points, and a gate of four
  * factors has L0 = 4 n - 3: its largest circuit has n = 2^18 rows.  This call uses transforms of n points only, so the quotient no longer

@@ -209,6 +209,9 @@ def lib():
         L.kzg_polys_fraction_sum.argtypes = [C.POINTER(vp), u8, C.POINTER(vp), sz, szp, sz, u8, szp, szp, u32p, sz, C.c_uint, vp]
         L.kzg_debug_poly_fraction_sum_plan.argtypes = [szp, szp, sz, szp, sz, szp, szp, u32p, sz, C.c_uint]
         L.kzg_debug_polys_fraction_sum_split.argtypes = [vp, C.POINTER(C.c_float)]
+        L.kzg_polys_lookup_multiplicities.argtypes = [C.POINTER(vp), szp, C.POINTER(vp), sz, u32p, u32p, sz, sz, sz, vp]
+        L.kzg_debug_poly_lookup_plan.argtypes = [szp, szp, sz, u32p, u32p, sz, sz, sz]
+        L.kzg_debug_polys_lookup_split.argtypes = [vp, C.POINTER(C.c_float)]
         L.kzg_polys_quotient.argtypes = [C.POINTER(vp), C.POINTER(vp), sz, u8, szp, u32p, sz, sz, vp]
         L.kzg_debug_poly_coset_quotient_plan.argtypes = [szp, szp, sz, szp, u32p, sz, sz]
         L.kzg_debug_polys_quotient_split.argtypes = [vp, C.POINTER(C.c_float)]
@@ -1585,6 +1588,72 @@ def poly_fraction_sum_plan(set_coeffs, sums, domain, shift=False, steps=False):
     flags = (POLYS_FS_WITH_SHIFT if shift else 0) | (POLYS_FS_WITH_STEPS if steps else 0)
     _chk(lib().kzg_debug_poly_fraction_sum_plan(out, arr(set_coeffs), len(set_coeffs), arr(counts), len(counts), arr(nums), arr(dens), (C.c_uint32 * max(len(flat), 1))(*flat),
                                                 domain, flags))
+    return tuple(int(x) for x in out)
+
+
+POLYS_LM_MAX_WIDTH, POLYS_LM_MAX_LOOKUPS = 8, 16
+
+
+def _lm_columns(table, lookups):
+    """table = [(set_index, poly_index), ...], lookups = a list of such lists -> (width, the table's index pairs flat, the lookups' flat)"""
+    table, lookups = list(table), [list(lk) for lk in lookups]
+    if any(len(lk) != len(table) for lk in lookups):
+        raise KzgError("BadArgs", "lookups: every lookup has the table's number of polynomials")
+    flat = []
+    for cols in [table] + lookups:
+        for si, pi in cols:
+            if not isinstance(si, int) or not isinstance(pi, int) or not 0 <= si < 1 << 32 or not 0 <= pi < 1 << 32:
+                raise KzgError("BadArgs", "table, lookups: a polynomial is (set_index, poly_index), not negative")
+            flat += [si, pi]
+    return len(table), flat[:2 * len(table)], flat[2 * len(table):]
+
+
+def polys_lookup_multiplicities(sets, table, lookups, kzg_settings, domain=None):
+    """kzg_polys_lookup_multiplicities: sets = a list of Polys of the handle, table = [(set_index, poly_index), ...] the table's
+    polynomials, lookups = a list of such lists, each as long as the table -> a new resident Polys of ONE polynomial m on the domain of
+    `domain` points (None: the largest n_coeffs of the sets, rounded up to a power of two): m(w^j) = how many rows of all the lookups
+    hold the table's tuple of row j, counted at the LOWEST row of every distinct tuple and 0 at its later ones.  A looked-up tuple that is
+    in no table row raises KzgError of kind BadArgs whose attribute `missing` = (lookup, row) names the lowest miss."""
+    if not isinstance(kzg_settings, KzgSettings):
+        raise TypeError("kzg_settings: a KzgSettings")
+    sets = list(sets)
+    if any(not isinstance(f, Polys) for f in sets):
+        raise TypeError("sets: a list of Polys")
+    width, tflat, lflat = _lm_columns(table, lookups)
+    if domain is None:
+        domain = 1
+        while domain < max([f.n_coeffs() for f in sets] + [1]):
+            domain *= 2
+    if not isinstance(domain, int) or domain < 0:
+        raise KzgError("BadArgs", "domain: an integer, not negative")
+    hs = (C.c_void_p * max(len(sets), 1))(*[f._h for f in sets])
+    h, missing = C.c_void_p(), (C.c_size_t * 2)(2 ** 64 - 1, 2 ** 64 - 1)
+    u32 = lambda xs: (C.c_uint32 * max(len(xs), 1))(*xs)
+    rc = lib().kzg_polys_lookup_multiplicities(C.byref(h), missing, hs, len(sets), u32(tflat), u32(lflat), width, len(lflat) // (2 * width) if width else 0, domain,
+                                               kzg_settings._h)
+    if rc != KZG_OK:
+        err = KzgError(_KIND.get(rc, "InternalError"), lib().kzg_last_error().decode(errors="replace"))
+        if missing[0] != 2 ** 64 - 1:
+            err.missing = (int(missing[0]), int(missing[1]))
+        raise err
+    return Polys._from_handle(h, kzg_settings)
+
+
+def poly_lookup_plan(set_coeffs, width, n_lookups, domain, table=None, lookups=None):
+    """kzg_debug_poly_lookup_plan: set_coeffs = n_coeffs of every set, a table of `width` polynomials and n_lookups lookups (table, lookups
+    as polys_lookup_multiplicities takes them; None: polynomial k of set 0 for column k of the table, the next `width` for every lookup in
+    turn) -> (distinct polynomials, workspace scalars, slots, workspace bytes, lanes per workgroup, workgroups of the insert and of the
+    store, workgroups of the count, refusal code); host code"""
+    set_coeffs = list(set_coeffs)
+    if table is None:
+        table = [(0, k) for k in range(width)]
+    if lookups is None:
+        lookups = [[(0, width * (1 + l) + k) for k in range(width)] for l in range(n_lookups)]
+    tflat = [x for pair in table for x in pair]
+    lflat = [x for lk in lookups for pair in lk for x in pair]
+    out = (C.c_size_t * 8)()
+    u32 = lambda xs: (C.c_uint32 * max(len(xs), 1))(*xs)
+    _chk(lib().kzg_debug_poly_lookup_plan(out, (C.c_size_t * max(len(set_coeffs), 1))(*set_coeffs), len(set_coeffs), u32(tflat), u32(lflat), width, n_lookups, domain))
     return tuple(int(x) for x in out)
 
 

@@ -70,7 +70,7 @@ HOST_ONLY = ("capi_host_util.hpp", "capi_pieces.hpp", "capi_prover.hpp", "capi_c
              "capi_poly_batch.hpp", "poly_fold_plan.hpp", "fb_sum_plan.hpp", "capi_polys.hpp", "poly_eval_plan.hpp",
              "capi_polys_multiopen.hpp", "poly_multiopen_plan.hpp", "capi_polys_arith.hpp", "poly_arith_plan.hpp",
              "capi_polys_grand_product.hpp", "poly_grand_product_plan.hpp",
-             "capi_polys_fraction_sum.hpp", "poly_fraction_sum_plan.hpp", "capi_polys_quotient.hpp", "capi_polys_blind.hpp")
+             "capi_polys_fraction_sum.hpp", "poly_fraction_sum_plan.hpp", "capi_polys_quotient.hpp", "capi_polys_blind.hpp", "capi_polys_lookup.hpp")
 LLVM_BIN = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin")
 
 

@@ -148,6 +148,7 @@ struct KzgSettings {
     mutable float polys_arith_split[5] = {};   // kzg_debug_polys_arith_split (capi_polys_arith.hpp): slot [4] of the last product call, by stage
     mutable float polys_gp_split[5] = {};      // kzg_debug_polys_grand_product_split (capi_polys_grand_product.hpp): the same of the last grand product
     mutable float polys_fs_split[6] = {};      // kzg_debug_polys_fraction_sum_split (capi_polys_fraction_sum.hpp): the same of the last fraction sum
+    mutable float polys_lm_split[6] = {};      // kzg_debug_polys_lookup_split (capi_polys_lookup.hpp): the same of the last lookup multiplicities
     mutable float polys_cq_split[6] = {};      // kzg_debug_polys_quotient_split (capi_polys_quotient.hpp): the same of the last coset quotient
     mutable double clk_sum[2] = {};  // shader cycles | 100 MHz reference ticks of the throughput-form challenge kernel's waves
     // the kernels' own execution intervals (in-kernel stamps), ms: challenge | evaluate | decode + multiples | MSM window - of the

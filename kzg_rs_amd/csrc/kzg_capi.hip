@@ -41,6 +41,7 @@
 #include "poly_fraction_sum_kernels.hpp"
 #include "poly_coset_quotient_kernels.hpp"
 #include "poly_blind_kernels.hpp"
+#include "poly_lookup_kernels.hpp"
 #include "fr_ntt_kernels.hpp"
 
 using namespace kzg;
@@ -89,6 +90,7 @@ extern "C" const unsigned char kzg_slp_prep_begin[], kzg_slp_prep_end[], kzg_slp
 #include "capi_polys_fraction_sum.hpp"
 #include "capi_polys_quotient.hpp"
 #include "capi_polys_blind.hpp"
+#include "capi_polys_lookup.hpp"
 #include "capi_cells.hpp"
 #include "capi_cell_groups.hpp"
 #include "capi_cell_prover.hpp"
